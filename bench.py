@@ -2,7 +2,11 @@
 """Headline benchmark: frames/s of OccDepth.forward, SemanticKITTI stereo 1220x370 -> 256x256x32 voxels
 (BASELINE.json configs[1]: EfficientNet-B7, feature 64, FLoSP-Depth + CRP + cascade head, batch 1 per GPU).
 
-    python bench.py --gpus N --steps K --warmup W [--train [--bf16]] [--config 5] [--no-extras]
+    python bench.py --gpus N --steps K --warmup W [--train [--bf16]] [--config 5] [--dump-outputs DIR] [--full [--no-extras]]
+
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs if --dump-outputs is given, and prints
+the result line (metric, value, unit, ms_per_step, dtype, config, ...).  Everything else -- the roofline and per-stage
+passes, the parity check, the auxiliary legs (`extras`), the CPU baseline, the eager training step -- runs only with --full.
 
 N > 1: one rank per GPU over RCCL.  Under `torch.distributed.run` (WORLD_SIZE set) the ranks are the launcher's;
 a bare `python bench.py --gpus N` re-executes itself through `torch.distributed.run` on 127.0.0.1, so the printed
@@ -23,7 +27,7 @@ hipGraph on one rank; `--bf16` = the bf16-MFMA mode (configs[3]: hand-written bf
 and fp32 storage; `--autocast` adds torch autocast on top); OCCDEPTH_FORCE_DIST=1 drives SyncBatchNorm + buckets through a
 single-rank RCCL group on one GPU.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields; with --full also
   roofline       : dominant kernel (3x3x3 32->32 head convolution, 115.96 GFLOP per launch) timed live with HIP
                    events on the launch stream: issued bf16 MFMA flops (6 x algorithmic) against the dense bf16 peak
                    (2.5 PF) in the default mode, algorithmic flops against the fp32-MFMA peak (157.3 TF/s) in the exact
@@ -34,9 +38,14 @@ Rank 0 prints ONE JSON line with the contract fields plus
                    default convolution mode), run once untimed on the golden frame with the golden weights and compared
                    with the real reference's outputs (tests/golden/occdepth_kitti_a100.npz); max |delta| / max |ref| per
                    output, and `lift_kernels` = the lift launches an eager twin of that model makes;
-  extras         : (N = 1, default run) config 5, the all-exact-fp32 frame and the fp32 / bf16 training step, each a short
+  extras         : (N = 1, config 2) config 5, the all-exact-fp32 frame and the fp32 / bf16 training step, each a short
                    child run of this script.
 The oracle / golden machinery is used by the `cpu_baseline` and `parity_rel_err` legs only, as the checker.
+
+--dump-outputs DIR (rank 0) writes what the last timed step returned as DIR/<name>.npy, float32 (float64 stays float64):
+the forward's output dict (config 2 / 5) or the training step's loss (--train).  An array too large for the 64 MB budget is
+replaced by a fixed sample of its flattened elements (seeded, sorted indices; the same for every run of the same shape).
+Weights and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -59,10 +68,47 @@ STACK3D_GFLOP = 1068.3                 # conv 1059.74 + CRP bmm 8.5
 LIFT_MBYTES = 249.0                    # BASELINE.md / SURVEY.md 8(d) algorithmic HBM bytes of the lift
 LIFT_PROJ_MBYTES = 240.4               # the fused lift (occd_lift_proj_fwd): no 8.9 MB of int64 tables / masks; 67.1 written
 #                                        + 167.3 gathered + 6.0 depth volumes
+# `dtype` of the forward line when the head convolutions take the 3-way bf16 split (OCCDEPTH_BF16X3 head / 1, the default)
+HEAD_X3_DTYPE = ("f32 storage and accumulate; matrix arithmetic as 3x bf16 split (hi + mid + lo of both operands, six "
+                 "v_mfma_f32_32x32x16_bf16 per K step; error vs float64 tested within 1.5x of the exact-fp32 kernels', measured 0.8-1.1x) in the head convolutions "
+                 "(K2s3), the small-volume 3x3x3 convolutions and transposed-convolution phases of the 3-D stack (K2b) and "
+                 "the 2-D network's GEMMs (K16 / K16p); exact fp32 MFMA / VALU everywhere else (K2, K10, K11, K14, depthwise, lift). "
+                 " OCCDEPTH_BF16X3=0 OCCDEPTH_GEMM_X3=0 restores exact fp32 everywhere")
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 60 << 20           # --dump-outputs: array data of all files together (64 MB with room for the headers)
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(arrays, outdir, budget_bytes=DUMP_BUDGET_BYTES):
+    """{name: tensor} -> outdir/<name>.npy.  float64 stays float64, every other dtype is written as float32.  The budget is
+    shared out smallest array first; an array that does not fit its share is written as a sample of its flattened elements
+    (indices drawn without replacement from a generator seeded with DUMP_SAMPLE_SEED and the array's size, then sorted), so
+    the same shape gives the same sample in every run.  Returns {name: (elements written, elements in the array)}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(((k, v.detach()) for k, v in arrays.items()), key=lambda kv: (kv[1].numel(), kv[0]))
+    left, written = budget_bytes, {}
+    for i, (name, t) in enumerate(items):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        take = min(t.numel(), left // (len(items) - i) // item)
+        flat = t.reshape(-1)
+        if take < t.numel():
+            idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, t.numel()]).choice(t.numel(), take, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.to(dt).cpu().numpy()
+        else:
+            arr = flat.to(dt).cpu().numpy().reshape(tuple(t.shape))
+        left -= arr.nbytes
+        fname = "".join(c if c.isalnum() or c in "._-" else "_" for c in name)
+        np.save(os.path.join(outdir, fname + ".npy"), arr)
+        written[name] = (int(arr.size), int(t.numel()))
+    return written
 
 
 def model_flags():
@@ -271,10 +317,10 @@ def run_extras():
     for name, extra in legs.items():
         t0 = time.time()
         try:
-            lenv, flags = env, ["--no-cpu-baseline", "--no-parity", "--no-extras"]
+            lenv, flags = env, ["--full", "--no-cpu-baseline", "--no-parity", "--no-extras"]
             if name == "exact_fp32":        # exact-fp32 MFMA convolutions + the library's fp32 GEMMs; its own golden parity check
                 lenv = dict(env, OCCDEPTH_BF16X3="0", OCCDEPTH_GEMM_X3="0")
-                flags = ["--no-cpu-baseline", "--no-extras"]
+                flags = ["--full", "--no-cpu-baseline", "--no-extras"]
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1"] + flags + extra, env=lenv,
                                capture_output=True, text=True, timeout=420)
             line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -342,10 +388,17 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 5),
                     help="2: BASELINE configs[1] (the headline metric); 5: BASELINE configs[4], UNet3D alone on a synthetic "
                          "512x512x64 grid (auxiliary workload: 3-D-conv MFMA tiling + HBM footprint)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: roofline / stage / kernel-table passes, the parity check, "
+                         "the auxiliary legs (`extras`), the CPU baseline, the eager training step (off: set up, warm up, time "
+                         "the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity check")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the auxiliary legs of the default run (config 5, fp32 / bf16 training step: `extras` in the JSON line)")
+                    help="with --full: skip the auxiliary legs (config 5, fp32 / bf16 training step: `extras` in the JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all: a seeded sample of an array too large for its share)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 5 if args.train else 20
@@ -449,6 +502,24 @@ def _forward(args, world, rank, device, dist):
     graph_flags["lift_input"] = ("batch WITHOUT projected_pix_* / fov_mask_* (the kernel projects; INTEGRATION.md section 2: the "
                                  "one-line dataset edit) -- a batch from the reference's unmodified collate_fn carries the tables and "
                                  "takes the table lift (+ an 8.9 MB H2D copy, ~0.05 ms per frame; same parity)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs({k: v for k, v in out.items() if torch.is_tensor(v)}, args.dump_outputs)
+    res = {
+        "metric": "frames/sec forward, SemanticKITTI stereo->256x256x32 voxels",
+        "value": world * args.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": HEAD_X3_DTYPE if _fused.BF16X3 else "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: SemanticKITTI stereo 370x1220, tf_efficientnet_b7_ns, "
+                               "feature 64, flosp_depth + CRP + cascade head, 256x256x32 voxels, batch 1/GPU",
+                   "frames_per_step": world, "parallelism": f"dp{world} (frames sharded, no collective)",
+                   "ranks": dist.get_world_size() if dist is not None else 1, **graph_flags},
+    }
+    for attr in ("graph_2d_error", "graph_all_error"):
+        if getattr(model, attr, None):
+            res["config"][attr] = getattr(model, attr)
+    if not args.full:
+        res["cpu_baseline"] = None
+        return res if rank == 0 else None
 
     # ---- untimed diagnostic passes (the same model, the same frame), eager so that every launch can be bracketed:
     # (1) per-launch HIP events on the launch stream (occd_prof_*) -> roofline.achieved of the head convolution;
@@ -496,7 +567,6 @@ def _forward(args, world, rank, device, dist):
     if rank != 0:
         return None
 
-    fps = world * args.steps / elapsed
     head = [(k, v) for k, v in prof.rows.items() if HEAD_CONV_TAG in k and k.startswith("conv3d")]
     n_launch = sum(v["launches"] for _, v in head)
     ms = sum(v["ms"] for _, v in head)
@@ -517,15 +587,7 @@ def _forward(args, world, rank, device, dist):
                 traffic = json.load(f).get("bytes_per_launch")
             traffic_src = f"profiles/{name}: {what}"
             break
-    res = {
-        "metric": "frames/sec forward, SemanticKITTI stereo->256x256x32 voxels",
-        "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: SemanticKITTI stereo 370x1220, tf_efficientnet_b7_ns, "
-                               "feature 64, flosp_depth + CRP + cascade head, 256x256x32 voxels, batch 1/GPU",
-                   "frames_per_step": world, "parallelism": f"dp{world} (frames sharded, no collective)",
-                   "ranks": dist.get_world_size() if dist is not None else 1, **graph_flags},
+    res.update({
         "roofline": {"bound": "mfma", "kernel": "conv3d_c32_slide_kernel: 3x3x3 32->32 @256x256x32 (v_mfma_f32_32x32x2_f32)",
                      "achieved": ach, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": ach / FP32_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
@@ -544,18 +606,14 @@ def _forward(args, world, rank, device, dist):
                  "frac_of_8TBps": lift_mb / lift_ms / 8000.0 if lift_ms else 0.0, "algorithmic_mbytes": lift_mb,
                  "kernel": "lift_proj_kernel (projection + frustum sample + gather in one launch)" if lift_fused
                            else "lift_p1_kernel (tables from the batch) + flosp_sample_kernel"},
-    }
+    })
     res["roofline_2d"] = roofline_2d(prof2d.rows, 3)
     split_head = any(k.startswith(("conv3d_c32x3", "conv3d_bf16x3")) for k, _ in head)
+    res["dtype"] = HEAD_X3_DTYPE if split_head else "f32"          # (from the launches the profiled frames made)
     if split_head:
         # the head convolutions run on the bf16 matrix pipe (3-way split, six bf16 MFMAs per algorithmic MAC): the roofline is
         # priced against the instruction that is issued; the fp32-equivalent figures stay next to it
         x3_slide = any(k.startswith("conv3d_c32x3") for k, _ in head)
-        res["dtype"] = ("f32 storage and accumulate; matrix arithmetic as 3x bf16 split (hi + mid + lo of both operands, six "
-                        "v_mfma_f32_32x32x16_bf16 per K step; error vs float64 tested within 1.5x of the exact-fp32 kernels', measured 0.8-1.1x) in the head convolutions "
-                        "(K2s3), the small-volume 3x3x3 convolutions and transposed-convolution phases of the 3-D stack (K2b) and "
-                        "the 2-D network's GEMMs (K16 / K16p); exact fp32 MFMA / VALU everywhere else (K2, K10, K11, K14, depthwise, lift). "
-                        " OCCDEPTH_BF16X3=0 OCCDEPTH_GEMM_X3=0 restores exact fp32 everywhere")
         res["roofline"].update({
             "kernel": ("conv3d_c32_slide_x3_kernel" if x3_slide else "conv3d_bf16_kernel<SPLIT=3>") +
                       ": 3x3x3 32->32 @256x256x32 (6 x v_mfma_f32_32x32x16_bf16 per 16-channel K step)",
@@ -580,9 +638,6 @@ def _forward(args, world, rank, device, dist):
             res["roofline"]["isolated_random_data"] = isolated_head(device, split_head)
         except Exception as e:  # a report, never a reason to lose the measurement
             res["roofline"]["isolated_random_data"] = {"error": repr(e)}
-    for attr in ("graph_2d_error", "graph_all_error"):
-        if getattr(model, attr, None):
-            res["config"][attr] = getattr(model, attr)
     if not args.no_parity:
         log(f"[bench {time.strftime('%H:%M:%S')}] parity check against the real-reference golden")
         try:
@@ -690,6 +745,8 @@ def _config5(args, world, rank, device, dist):
     shard.fence(dist)
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist, device)
     assert out["ssc_logit"].shape == (1, 20, 512, 512, 64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs({k: v for k, v in out.items() if torch.is_tensor(v)}, args.dump_outputs)
     del out
     with hip.profile() as prof:
         step()
@@ -802,29 +859,26 @@ def _train(args, world, rank, device, dist):
     loss_value = float(loss.detach())
     if None in shard._SMALL:
         shard._SMALL[None].check()                 # a peer-memory exchange that gave up waiting fails the run, loudly
-    # the step a user of the UNMODIFIED scripts gets (Lightning's automatic optimisation: zero_grad, training_step, backward,
-    # optimizer.step, all eager -- ~4 500 launches, host-bound), timed the same way right after the replayed one
-    eager_ms = None
-    if graphed is not None:
-        step()
-        shard.fence(dist)
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"loss": loss}, args.dump_outputs)
+    eager_ms, prof = None, None
+    if args.full:
+        # the step a user of the UNMODIFIED scripts gets (Lightning's automatic optimisation: zero_grad, training_step, backward,
+        # optimizer.step, all eager -- ~4 500 launches, host-bound), timed the same way right after the replayed one
+        if graphed is not None:
             step()
-        shard.fence(dist)
-        eager_ms = 1e3 * shard.max_over_ranks(time.perf_counter() - t0, dist, device) / args.steps
-    with hip.profile() as prof:                    # kernel table: ONE eager step after the timed loop (HIP events per launch)
-        step()
-        torch.cuda.synchronize()
+            shard.fence(dist)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            shard.fence(dist)
+            eager_ms = 1e3 * shard.max_over_ranks(time.perf_counter() - t0, dist, device) / args.steps
+        with hip.profile() as prof:                # kernel table: ONE eager step after the timed loop (HIP events per launch)
+            step()
+            torch.cuda.synchronize()
     if rank != 0:
         return None
-    rows = sorted(prof.rows.items(), key=lambda kv: -kv[1]["ms"])[:8]
-    families = {}
-    for k, v in prof.rows.items():
-        fam = k.split(":")[0]
-        families[fam] = families.get(fam, 0.0) + v["ms"]
-    families = {k: round(v, 3) for k, v in sorted(families.items(), key=lambda kv: -kv[1])}
-    return {
+    res = {
         "metric": "frames/sec trained (fwd + losses + bwd + gradient exchange + AdamW), SemanticKITTI stereo->256x256x32 voxels",
         "value": world * args.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -841,11 +895,19 @@ def _train(args, world, rank, device, dist):
                                   ("peer-memory kernel csrc/ipc_allreduce.hip" if None in shard._SMALL else "process group") +
                                   f") + {len(buckets.buckets) if buckets else 0} gradient buckets ({buckets.algo if buckets else 'none'})"},
         "train_graph": graphed is not None, "train_graph_error": graph_error,
-        "eager_ms_per_step": eager_ms if graphed is not None else 1e3 * elapsed / args.steps,
         "loss": loss_value, "max_mem_GiB": torch.cuda.max_memory_allocated() / 2 ** 30,
-        "hip_kernels_ms_per_step": {k: v["ms"] for k, v in rows},
-        "hip_kernel_families_ms_per_step": families,
     }
+    if args.full:
+        rows = sorted(prof.rows.items(), key=lambda kv: -kv[1]["ms"])[:8]
+        families = {}
+        for k, v in prof.rows.items():
+            fam = k.split(":")[0]
+            families[fam] = families.get(fam, 0.0) + v["ms"]
+        families = {k: round(v, 3) for k, v in sorted(families.items(), key=lambda kv: -kv[1])}
+        res.update({"eager_ms_per_step": eager_ms if graphed is not None else 1e3 * elapsed / args.steps,
+                    "hip_kernels_ms_per_step": {k: v["ms"] for k, v in rows},
+                    "hip_kernel_families_ms_per_step": families})
+    return res
 
 
 if __name__ == "__main__":

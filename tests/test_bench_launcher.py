@@ -41,7 +41,7 @@ def _launch(bench_args, extra_env=None, timeout=600):
 
 
 def test_forward_bench_under_the_launcher():
-    t = _launch(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+    t = _launch(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"])
     assert t["n_gpus"] == 1 and t["steps"] == 2 and t["warmup"] == 1 and t["scaling"] == "weak"
     assert t["config"]["ranks"] == 1 and t["config"]["frames_per_step"] == 1
     assert t["config"]["graph_all"] is True and "graph_all_error" not in t["config"]
@@ -54,7 +54,7 @@ def test_forward_bench_under_the_launcher():
 def test_training_bench_under_the_launcher_on_a_forced_rccl_group(mode):
     """`--train` through a single-rank RCCL group (OCCDEPTH_FORCE_DIST=1): SyncBatchNorm + buckets wrap the model, their
     collectives are captured into the whole-step hipGraph (OCCDEPTH_TRAIN_GRAPH_DDP=1) and the replayed step trains."""
-    args = ["--train", "--steps", "2", "--warmup", "1"] + (["--bf16"] if mode == "bf16" else [])
+    args = ["--train", "--steps", "2", "--warmup", "1", "--full"] + (["--bf16"] if mode == "bf16" else [])
     t = _launch(args, {"OCCDEPTH_FORCE_DIST": "1", "OCCDEPTH_TRAIN_GRAPH_DDP": "1"}, timeout=900)
     assert t["n_gpus"] == 1 and t["config"]["ranks"] == 1 and t["config"]["global_batch"] == 1
     assert "SyncBatchNorm" in t["config"]["parallelism"] and "gradient buckets" in t["config"]["parallelism"]

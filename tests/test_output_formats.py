@@ -13,13 +13,13 @@ def _reference_recipe(logits):
 
 
 def test_inverse_label_map_matches_reference_yaml():
+    import json
     import os
-    import yaml
     from occdepth_amd.output import KITTI_LEARNING_MAP_INV, get_inv_map
-    ref = "/root/reference/occdepth/data/semantic_kitti/semantic-kitti.yaml"
-    if os.path.exists(ref):                                   # build container only; the table is also pinned below
-        cfg = yaml.safe_load(open(ref))
-        assert [cfg["learning_map_inv"][i] for i in range(20)] == list(KITTI_LEARNING_MAP_INV)
+    # learning_map_inv of the reference's occdepth/data/semantic_kitti/semantic-kitti.yaml, classes 0 .. 19
+    fixture = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "semantic_kitti_learning_map_inv.json")
+    with open(fixture) as f:
+        assert json.load(f)["learning_map_inv"] == list(KITTI_LEARNING_MAP_INV)
     assert get_inv_map().dtype == np.int32 and get_inv_map()[[0, 1, 9, 19]].tolist() == [0, 10, 40, 81]
 
 

@@ -733,6 +733,17 @@ int occd_pack_weights_bf16x3_gather(const float* w, const float* scale, void* wp
 int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk,
                              int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,
                              int32_t layout, void* stream);
+/* dtype 3 of occd_conv3d_bf16_fwd = float32 tensors, the two-term fp16 split (x = hi + 2^-11 lo', three fp16 MFMAs per K
+ * step: lo_w * hi_x, hs_w * lo'_x, hi_w * hi_x), fp32 accumulate; the full-resolution head convolutions only (K2s3h: 3x3x3,
+ * dilation = padding 1 / 2 / 3, <= 32 -> <= 32 channels on rows of >= 32 channels, Z a multiple of 32), anything else is
+ * OCCD_EINVAL.  Finite activations with |x| >= 32760 overflow the fp16 operand and make the outputs they reach non-finite.
+ * Its weight image (occd_packed_weight_f16x2_bytes() bytes, 16-byte aligned) comes from occd_pack_weights_f16x2: three fp16
+ * images hi | hs | lo of w' = 2^k[co] w (layout of occd_pack_weights_bf16) and 32 * ceil(cout / 32) float epilogue factors.
+ * Weights must be finite.                                                                                              */
+int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps);
+int occd_pack_weights_f16x2(const float* w, const float* scale, void* wpk,
+                            int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,
+                            int32_t layout, void* stream);
 int64_t occd_conv3d_wgrad_bf16_workspace_floats(const occd_conv3d_wgrad_args* a, int32_t dtype);
 int occd_conv3d_wgrad_bf16(const occd_conv3d_wgrad_args* a, int32_t dtype, void* stream);
 

@@ -19,7 +19,7 @@ struct ProfScope {
 // 1 = launched, 0 = geometry does not qualify (use the generic kernel), <0 = error.
 int try_conv3d_c32_persist(const occd_conv3d_args* a, hipStream_t stream);
 // K2s3: the same launches with the 3-way bf16 split (weights = the image of occd_pack_weights_bf16x3); same return convention.
-int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream);
+int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream, bool f16x2 = false);
 
 // occd_pack_weights*_gather: where element (co, ci, tap) of a packed operator lives in a dense source tensor
 constexpr int kMaxTaps = 27;

@@ -412,6 +412,56 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, const floa
     }
 }
 
+// K2s3h weight image (occd_pack_weights_f16x2): three fp16 images in the layout above -- hi | hs | lo of w' = 2^k[co] w,
+// hi = fp16(w'), hs = hi 2^-11, lo = fp16(w' - hi) -- followed by NT * 32 floats 2^-(k[co] + kF2XExp) (the epilogue factor;
+// kF2XExp = 1, the activation pre-scale of conv3d_c32p.hip).  k[co] puts max_{ci, tap} |w'| into [2^13, 2^14).
+__global__ void f16x2_scale_kernel(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ fac,
+                                   int cout, int cin, int taps, int NT, int layout) {
+    const int co = blockIdx.x * blockDim.x + threadIdx.x;
+    if (co >= NT * 32) return;
+    float m = 0.f;
+    if (co < cout) {
+        for (int ci = 0; ci < cin; ++ci)
+            for (int tap = 0; tap < taps; ++tap) {
+                float v = layout == 0 ? w[((size_t)co * cin + ci) * taps + tap] : layout == 1 ? w[((size_t)ci * cout + co) * taps + tap]
+                                                                                             : w[(size_t)ci * cout + co];
+                if (scale != nullptr) v *= scale[co];
+                m = fmaxf(m, fabsf(v));
+            }
+    }
+    int e = 0;
+    if (m > 0.f && m <= 3.0e38f) frexpf(m, &e);                  // m in [2^(e-1), 2^e)
+    const int k = m > 0.f && m <= 3.0e38f ? min(max(14 - e, -120), 120) : 0;   // (non-finite weights: the host keeps bf16x3)
+    fac[co] = ldexpf(1.f, -(k + 1));                              // 2^-(k + kF2XExp)
+}
+
+__global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, const float* __restrict__ scale,
+                                          const float* __restrict__ fac, uint16_t* __restrict__ wpk, int cout, int cin,
+                                          int taps, int K16, int NT, int layout, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int j = i & 7;
+    const int lane = (i >> 3) & 63;
+    long t = i >> 9;
+    const int nt = t % NT; t /= NT;
+    const int k16 = t % K16; t /= K16;
+    const int tap = (int)t;
+    const int co = nt * 32 + (lane & 31);
+    const int ci = k16 * 16 + (lane >> 5) * 8 + j;
+    float v = 0.f;
+    if (co < cout && ci < cin) {
+        if (layout == 0) v = w[((size_t)co * cin + ci) * taps + tap];
+        else if (layout == 1) v = w[((size_t)ci * cout + co) * taps + tap];
+        else v = w[(size_t)ci * cout + co];
+        if (scale != nullptr) v *= scale[co];
+        v *= 0.5f / fac[co];                                      // 2^k[co]: exact
+    }
+    const _Float16 hi = (_Float16)v;
+    wpk[i] = __builtin_bit_cast(uint16_t, hi);
+    wpk[i + total] = __builtin_bit_cast(uint16_t, (_Float16)((float)hi * (1.f / 2048.f)));
+    wpk[i + 2 * total] = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)hi));
+}
+
 struct VariantB {
     int MT, NT, WM, WN, KS;
     void (*kern[3])(const ConvBP);   // [0] fp32 in / fp32 out, [1] bf16 in / bf16 out, [2] fp32 with the 3-way split (or null)
@@ -520,6 +570,30 @@ static int pack_bf16(const float* w, const float* scale, void* wpk, int32_t cout
 static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t ntaps,
                             int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, int nsplit, void* stream);
 
+extern "C" int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps) {
+    const int64_t n = occd_packed_weight_bf16_elems(cout, cin, taps);
+    if (n <= 0) return OCCD_EINVAL;
+    return 3 * n * 2 + (int64_t)((cout + 31) / 32) * 32 * 4;
+}
+
+extern "C" int occd_pack_weights_f16x2(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
+                                       int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
+    if (!w || !wpk || layout < 0 || layout > 2 || (reinterpret_cast<uintptr_t>(wpk) & 15)) return OCCD_EINVAL;
+    const int taps = kx * ky * kz;
+    const int64_t total = occd_packed_weight_bf16_elems(cout, cin, taps);
+    if (total <= 0 || (layout == 2 && taps != 1)) return OCCD_EINVAL;
+    const int K16 = (cin + 15) / 16, NT = (cout + 31) / 32;
+    float* const fac = reinterpret_cast<float*>(static_cast<uint16_t*>(wpk) + 3 * total);
+    const int th = 256;
+    const long blocks = (total + th - 1) / th;
+    occd::ProfScope prof("pack_weights_f16x2", (hipStream_t)stream, 0.0, (double)total * 10);
+    hipLaunchKernelGGL(f16x2_scale_kernel, dim3((unsigned)NT), dim3(32), 0, (hipStream_t)stream, w, scale, fac, cout, cin, taps,
+                       NT, layout);
+    hipLaunchKernelGGL(pack_weights_f16x2_kernel, dim3((unsigned)blocks), dim3(th), 0, (hipStream_t)stream, w, scale, fac,
+                       (uint16_t*)wpk, cout, cin, taps, K16, NT, layout, (long)total);
+    return occd::check_launch();
+}
+
 extern "C" int occd_pack_weights_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
                                              int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs,
                                              void* stream) {
@@ -555,12 +629,14 @@ static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32
 // the same type --, `a->wpk` at the image of occd_pack_weights_bf16, `a->bias` at fp32.  *_cs / *_coff count ELEMENTS.
 // dtype 2 = float32 tensors with the 3-way bf16 split of both operands (wpk from occd_pack_weights_bf16x3): float32-level
 // accuracy on the bf16 matrix pipe, an opt-in experiment beside the exact-fp32 kernels.
+// dtype 3 = float32 tensors with the two-term fp16 split (wpk from occd_pack_weights_f16x2): the head convolutions on
+// K2s3h (conv3d_c32p.hip) only; any other geometry is rejected (OCCD_EINVAL), there is no generic form.
 namespace {
 
 int validate_b(const occd_conv3d_args* a, int32_t dtype) {
-    if (!a || !a->in || !a->wpk || !a->out || dtype < 0 || dtype > 2) return OCCD_EINVAL;
+    if (!a || !a->in || !a->wpk || !a->out || dtype < 0 || dtype > 3) return OCCD_EINVAL;
     const int ksel = dtype;                           // kernel table column
-    if (dtype == 2) dtype = 0;                        // storage: float32
+    if (dtype >= 2) dtype = 0;                        // storage: float32
     if (a->batch <= 0 || a->X <= 0 || a->Y <= 0 || a->Z <= 0 || a->cin <= 0 || a->cout <= 0) return OCCD_EINVAL;
     if (a->kx <= 0 || a->ky <= 0 || a->kz <= 0 || a->sx <= 0 || a->sy <= 0 || a->sz <= 0) return OCCD_EINVAL;
     if (a->Xo <= 0 || a->Yo <= 0 || a->Zo <= 0) return OCCD_EINVAL;
@@ -701,6 +777,10 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
 extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, void* stream) {
     const int bad = validate_b(a, dtype);
     if (bad != OCCD_OK) return bad;
+    if (dtype == 3) {   // K2s3h: the head launches only
+        const int r = occd::try_conv3d_c32_slide_x3(a, (hipStream_t)stream, true);
+        return r < 0 ? r : r == 0 ? OCCD_EINVAL : OCCD_OK;
+    }
     if (dtype == 2) {   // the full-resolution head launches: sliding-window form of the split (K2s3, conv3d_c32p.hip)
         const int r = occd::try_conv3d_c32_slide_x3(a, (hipStream_t)stream);
         if (r != 0) return r < 0 ? r : OCCD_OK;
@@ -711,7 +791,7 @@ extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, vo
 // The n in {1, 2, 4, 8} sub-pixel phases of ONE transposed convolution on K2b as one launch (the bf16-pipe twin of
 // occd_conv3d_fwd_phases, same contract: a[0..n) differ ONLY in wpk, kx / ky / kz and o_off_*).
 extern "C" int occd_conv3d_bf16_fwd_phases(const occd_conv3d_args* a, int32_t n, int32_t dtype, void* stream) {
-    if (!a || (n != 1 && n != 2 && n != 4 && n != 8)) return OCCD_EINVAL;
+    if (!a || (n != 1 && n != 2 && n != 4 && n != 8) || dtype == 3) return OCCD_EINVAL;
     for (int i = 0; i < n; ++i) {
         const int bad = validate_b(a + i, dtype);
         if (bad != OCCD_OK) return bad;

@@ -487,10 +487,28 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_kernel(const SlideP s
 //     waves 6 and 7 stage and synchronise but own no output row -- 3/4 of the matrix-pipe rate, still well ahead of the
 //     exact-fp32 K2s: 5.x against 7.8 ms per launch at 512 x 512 x 64).
 // Work per launch 115.96 GFLOP algorithmic = 695.8 GFLOP issued on the bf16 pipe.
+//
+// K2s3h -- the same skeleton (one device body, `F16`) with the two-term fp16 split: v_mfma_f32_32x32x16_f16, THREE per
+// 16-channel K step, 347.9 GFLOP issued per launch.
+//   * activations: x' = 2^kF2XExp x = hi + 2^-11 lo' with hi = fp16(x'), lo' = fp16((x' - hi) 2^11) (22 significant bits
+//     while |x'| >= 2^-13); two fp16 planes in LDS, rows of 2 x 32 B + 16 B pad = 5 sixteen-byte slots (odd: conflict-free);
+//   * weights (occd_pack_weights_f16x2): per output channel scaled by 2^k so that max |w'| lies in [2^13, 2^14) (exact);
+//     hi = fp16(w'), lo = fp16(w' - hi) at natural scale, hs = hi 2^-11 (exact while normal).  hi and hs stay in LDS (the
+//     two 55,296 B images K2s3 keeps), lo streams from L2 through the same two-step ring;
+//   * per sub-step acc += lo * hi_x + hs * lo'_x + hi * hi_x (smallest first; the dropped lo * lo'_x term is <= 2^-22
+//     relative); the epilogue multiplies by 2^-(k + kF2XExp) (per channel, exact) before the bias;
+//   * range: an activation with |x'| >= 65520 (|x| >= 32760) stages as +-Inf and poisons the outputs it reaches (never a
+//     plausible finite number); the 2^kF2XExp pre-scale moves the 22-bit window to 2^-14 <= |x| < 32760 (the accuracy
+//     tests scale the activations by 2^-16 .. 2^+8);
+//   * dilation 3 at Z > 32: six-row y tiles as in K2s3 (the 8-row tile fits LDS with 80-byte entries, 42.6 KB, but its
+//     third staging load per thread spills at NRES = 2).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kX3RowB = 112;              // bytes per slab entry: hi | mid | lo of 16 channels + 16 B pad
+constexpr int kF2RowB = 80;               // K2s3h: hi | lo' of 16 channels + 16 B pad
+constexpr int kF2XExp = 1;                // K2s3h: activations are staged as 2^kF2XExp x
 constexpr int kX3ZW = 33;                 // entries per y row: z = 0 .. 31 and the zero entry
 constexpr int kX3WImg = kWTaps * 2 * 64;  // u32x4 per split image of the weights: [tap][k16 2][lane 64]
 
@@ -510,22 +528,38 @@ __device__ __forceinline__ void split3_bf16(f32x4 a, f32x4 b, u32x4& hi, u32x4& 
     lo = __builtin_bit_cast(u32x4, l);
 }
 
+// K2s3h: x' = hi + 2^-11 lo' (fp16; hi | lo' are the first two planes of the slab entry)
+__device__ __forceinline__ void split2_f16(f32x4 a, f32x4 b, u32x4& hi, u32x4& lo) {
+    const float s = (float)(1 << kF2XExp);
+    float x[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
+    f16x8 h, l;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        h[j] = (_Float16)x[j];
+        l[j] = (_Float16)((x[j] - (float)h[j]) * 2048.f);
+    }
+    hi = __builtin_bit_cast(u32x4, h);
+    lo = __builtin_bit_cast(u32x4, l);
+}
+
 // NRES: residual operands compiled in (0: neither, 1: res1, 2: res1 and res2) -- their prefetch registers (16 per
-// operand) are what the 5 of 7 head launches without residuals do not pay for.
-template <int D, int NRES, bool ZH = false, int TYV = kTY>
-__global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const SlideP sp) {
+// operand) are what the 5 of 7 head launches without residuals do not pay for.  F16: the K2s3h numerics (see above).
+template <bool F16, int D, int NRES, bool ZH, int TYV>
+__device__ __forceinline__ void slide_split_body(const SlideP& sp) {
     static_assert(TYV >= 1 && TYV <= kTY, "output rows per y tile: one wave each");
     const PersistP& p = sp.base;
+    constexpr int RowB = F16 ? kF2RowB : kX3RowB; // bytes per slab entry
     constexpr int ZW = ZH ? kTZ + 2 * D : kX3ZW;  // entries per y row: the tile + its z halo (ZH), or the tile + the zero entry
     constexpr int ZST = ZH ? ZW : kTZ;            // entries per row that are (re)staged with every slab
     constexpr int YIN = TYV + 2 * D, ROWS = YIN * ZW;
     constexpr int NITEM = YIN * ZST * 2;          // staging items: (y row, z, 8-channel chunk of the 16-channel half)
     constexpr int NLOAD = (NITEM + 511) / 512;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    u32x4* const w4 = reinterpret_cast<u32x4*>(lds_raw);                 // hi image | mid image
+    u32x4* const w4 = reinterpret_cast<u32x4*>(lds_raw);                 // hi image | mid image (F16: hi | hs)
     unsigned char* const slab = lds_raw + 2 * kX3WImg * 16;
-    int* const mailbox = reinterpret_cast<int*>(slab + ROWS * kX3RowB);
-    f32x4* const bias4 = reinterpret_cast<f32x4*>(slab + ROWS * kX3RowB + 16);
+    int* const mailbox = reinterpret_cast<int*>(slab + ROWS * RowB);
+    f32x4* const bias4 = reinterpret_cast<f32x4*>(slab + ROWS * RowB + 16);
+    f32x4* const wsc4 = bias4 + 8;                                      // F16: per-channel 2^-(k + kF2XExp)
     // lo image: read through a buffer descriptor (voffset = lane * 16, soffset = a compile-time constant per fragment, so
     // the 54 fragment addresses cost no address VGPRs)
     const auto wlo_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -557,9 +591,10 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
             }
         }
         // the zero entry of every y row (never written again)
-        if (!ZH && tid < YIN * 7) {
-            const int yi = tid / 7, s16 = tid - yi * 7;
-            *reinterpret_cast<u32x4*>(slab + (yi * kX3ZW + kTZ) * kX3RowB + s16 * 16) = u32x4{0u, 0u, 0u, 0u};
+        constexpr int NS16 = RowB / 16;
+        if (!ZH && tid < YIN * NS16) {
+            const int yi = tid / NS16, s16 = tid - yi * NS16;
+            *reinterpret_cast<u32x4*>(slab + (yi * kX3ZW + kTZ) * RowB + s16 * 16) = u32x4{0u, 0u, 0u, 0u};
         }
     }
 
@@ -571,7 +606,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
         const bool live = f < NITEM;
         const int row = f >> 1, c8 = f & 1;
         const int yi = ZH ? row / ZST : row >> 5, z = ZH ? row - yi * ZST : row & 31;
-        sdst[i] = live ? (yi * ZW + z) * kX3RowB + c8 * 16 : -1;
+        sdst[i] = live ? (yi * ZW + z) * RowB + c8 * 16 : -1;
         syi[i] = yi;
         sz[i] = ZH ? z - D : z;                    // relative to the tile's first column
         sc8[i] = c8 * 8;
@@ -582,7 +617,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
 #pragma unroll
     for (int kz = 0; kz < 3; ++kz) {
         const int z = li + (kz - 1) * D;
-        abase[kz] = ((wave < TYV ? wave : 0) * ZW + (ZH ? z + D : (z >= 0 && z < kTZ) ? z : kTZ)) * kX3RowB + kk * 16;
+        abase[kz] = ((wave < TYV ? wave : 0) * ZW + (ZH ? z + D : (z >= 0 && z < kTZ) ? z : kTZ)) * RowB + kk * 16;
     }
     int z0 = 0;                                    // first column of the segment's z tile (ZH)
     const size_t plane_stride = (size_t)p.Y * p.Z * p.in_cs;
@@ -602,7 +637,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
             }
         }
     };
-    auto commit = [&]() {                    // registers -> split -> the three bf16 planes of the slab
+    auto commit = [&]() {                    // registers -> split -> the three bf16 (F16: two fp16) planes of the slab
 #pragma unroll
         for (int i = 0; i < NLOAD; ++i)
             if (sdst[i] >= 0) {
@@ -611,11 +646,18 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
                     a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
                     b.x = fmaxf(b.x, 0.f); b.y = fmaxf(b.y, 0.f); b.z = fmaxf(b.z, 0.f); b.w = fmaxf(b.w, 0.f);
                 }
-                u32x4 hi, mid, lo;
-                split3_bf16(a, b, hi, mid, lo);
-                *reinterpret_cast<u32x4*>(slab + sdst[i]) = hi;
-                *reinterpret_cast<u32x4*>(slab + sdst[i] + 32) = mid;
-                *reinterpret_cast<u32x4*>(slab + sdst[i] + 64) = lo;
+                if constexpr (F16) {
+                    u32x4 hi, lo;
+                    split2_f16(a, b, hi, lo);
+                    *reinterpret_cast<u32x4*>(slab + sdst[i]) = hi;
+                    *reinterpret_cast<u32x4*>(slab + sdst[i] + 32) = lo;
+                } else {
+                    u32x4 hi, mid, lo;
+                    split3_bf16(a, b, hi, mid, lo);
+                    *reinterpret_cast<u32x4*>(slab + sdst[i]) = hi;
+                    *reinterpret_cast<u32x4*>(slab + sdst[i] + 32) = mid;
+                    *reinterpret_cast<u32x4*>(slab + sdst[i] + 64) = lo;
+                }
             }
     };
 
@@ -635,6 +677,8 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
 
 #define OCCD_X3_MFMA(ACC, W, A) \
     ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, W), __builtin_bit_cast(bf16x8, A), ACC, 0, 0, 0)
+#define OCCD_F2_MFMA(ACC, W, A) \
+    ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, W), __builtin_bit_cast(f16x8, A), ACC, 0, 0, 0)
 
     // one staged slab (16-channel half H of a plane) into the accumulators whose output plane exists.  Sub-step =
     // (tap t = (ky, kz), kx): 6 MFMAs into acc[kx]; the hi / mid weight fragments of the next sub-step and the three
@@ -649,18 +693,24 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
         const u32x4* const wmid = whi + mid_img;   // its own base register: the ds_read offsets of both images stay below 64 KB
         auto aptr = [&](int t, int term) {
             const int ky = t / 3, kz = t - 3 * ky;
-            return reinterpret_cast<const u32x4*>(slab + abase[kz] + ky * D * ZW * kX3RowB + term * 32);
+            return reinterpret_cast<const u32x4*>(slab + abase[kz] + ky * D * ZW * RowB + term * 32);
         };
-        u32x4 an0 = *aptr(0, 0), an1 = *aptr(0, 1), an2 = *aptr(0, 2);
+        u32x4 an0 = *aptr(0, 0), an1 = *aptr(0, 1), an2;
+        if constexpr (!F16) an2 = *aptr(0, 2);
         u32x4 bhn = whi[(KXS[0] * 9 * 2) * 64], bmn = wmid[(KXS[0] * 9 * 2) * 64];
-        u32x4 a0 = an0, a1 = an1, a2 = an2;
+        u32x4 a0 = an0, a1 = an1, a2;
+        if constexpr (!F16) a2 = an2;
 #pragma unroll
         for (int i = 0; i < NSUB; ++i) {
             const int t = i / NA, kx = KXS[i % NA];
             const int par = (H * 9 + t) & 1;
             if (i % NA == 0) {
-                a0 = an0; a1 = an1; a2 = an2;
-                if (t < 8) { an0 = *aptr(t + 1, 0); an1 = *aptr(t + 1, 1); an2 = *aptr(t + 1, 2); }
+                a0 = an0; a1 = an1;
+                if constexpr (!F16) a2 = an2;
+                if (t < 8) {
+                    an0 = *aptr(t + 1, 0); an1 = *aptr(t + 1, 1);
+                    if constexpr (!F16) an2 = *aptr(t + 1, 2);
+                }
             }
             const u32x4 bh = bhn, bm = bmn;
             if (i + 1 < NSUB) {
@@ -670,7 +720,11 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
             }
             const u32x4 bl = ring[par][kx];
             __builtin_amdgcn_sched_barrier(0);
-            if (kx == 0) {
+            if constexpr (F16) {            // bh = hi, bm = hs = hi 2^-11, bl = lo of w'; a0 = hi, a1 = lo' of x'
+                if (kx == 0) { OCCD_F2_MFMA(acc0, bl, a0); OCCD_F2_MFMA(acc0, bm, a1); OCCD_F2_MFMA(acc0, bh, a0); }
+                else if (kx == 1) { OCCD_F2_MFMA(acc1, bl, a0); OCCD_F2_MFMA(acc1, bm, a1); OCCD_F2_MFMA(acc1, bh, a0); }
+                else { OCCD_F2_MFMA(acc2, bl, a0); OCCD_F2_MFMA(acc2, bm, a1); OCCD_F2_MFMA(acc2, bh, a0); }
+            } else if (kx == 0) {
                 OCCD_X3_MFMA(acc0, bm, a1); OCCD_X3_MFMA(acc0, bh, a2); OCCD_X3_MFMA(acc0, bl, a0);
                 OCCD_X3_MFMA(acc0, bh, a1); OCCD_X3_MFMA(acc0, bm, a0); OCCD_X3_MFMA(acc0, bh, a0);
             } else if (kx == 1) {
@@ -701,6 +755,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
         f32x4 bv = {0.f, 0.f, 0.f, 0.f};
         if (p.bias != nullptr && 4 * tid < p.cout_store) bv = *(const f32x4*)(p.bias + 4 * tid);
         bias4[tid] = bv;
+        if constexpr (F16) wsc4[tid] = reinterpret_cast<const f32x4*>(reinterpret_cast<const u32x4*>(p.wpk) + 3 * kX3WImg)[tid];
     }
     auto res_fetch = [&](int b, int yt, int x) {
         if (NRES == 0) return;
@@ -725,6 +780,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
                 const int c = 8 * g + 4 * kk;
                 if (c < p.cout_store) {
                     f32x4 o = {acc2[4 * g], acc2[4 * g + 1], acc2[4 * g + 2], acc2[4 * g + 3]};
+                    if constexpr (F16) o *= wsc4[2 * g + kk];                 // 2^-(k + kF2XExp): exact
                     o += bias4[2 * g + kk];
                     if (p.act_out == OCCD_ACT_RELU_PRE) {
                         o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
@@ -830,6 +886,17 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
         }
     }
 #undef OCCD_X3_MFMA
+#undef OCCD_F2_MFMA
+}
+
+template <int D, int NRES, bool ZH = false, int TYV = kTY>
+__global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const SlideP sp) {
+    slide_split_body<false, D, NRES, ZH, TYV>(sp);
+}
+
+template <int D, int NRES, bool ZH = false, int TYV = kTY>
+__global__ void __launch_bounds__(512, 2) conv3d_c32_slide_f16x2_kernel(const SlideP sp) {
+    slide_split_body<true, D, NRES, ZH, TYV>(sp);
 }
 
 // Per-DEVICE launch state (work-list counters live in that device's memory, CU count and the large-LDS function
@@ -841,7 +908,7 @@ struct DevState {
     int* counter = nullptr;
     int num_cu = 0;
     bool slide_attr[4] = {};
-    bool slide_x3_attr[4][3][3] = {};
+    bool slide_x3_attr[2][4][3][3] = {};   // [F16][D][NRES][form]
     bool attr_done[4] = {};
 };
 DevState g_dev[kMaxDevices];
@@ -917,7 +984,7 @@ int launch_slide(const PersistP& base, hipStream_t st, DevState* ds) {
     return occd::check_launch();
 }
 
-template <int D, int NRES, bool ZH, int TYV = kTY>
+template <int D, int NRES, bool ZH, int TYV = kTY, bool F16 = false>
 int launch_slide_x3(const PersistP& base0, hipStream_t st, DevState* ds) {
     PersistP base = base0;
     if (TYV != kTY) {                                     // the work list is cut in y tiles of TYV rows
@@ -925,16 +992,19 @@ int launch_slide_x3(const PersistP& base0, hipStream_t st, DevState* ds) {
         base.tiles_total = base.batch * base.X * base.ytiles * base.ztiles;
     }
     constexpr int ROWS = (TYV + 2 * D) * (ZH ? kTZ + 2 * D : kX3ZW);
-    constexpr size_t lds = (size_t)2 * kX3WImg * 16 + (size_t)ROWS * kX3RowB + 16 + 128;
+    // (F16: + the 32 per-channel factors of the epilogue)
+    constexpr size_t lds = (size_t)2 * kX3WImg * 16 + (size_t)ROWS * (F16 ? kF2RowB : kX3RowB) + 16 + 128 + (F16 ? 128 : 0);
     static_assert(lds <= 160 * 1024, "K2s3 LDS budget (Z > 32: D <= 2 only)");
+    const void* kern;
+    if constexpr (F16) kern = reinterpret_cast<const void*>(conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV>);
+    else kern = reinterpret_cast<const void*>(conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>);
     {
         std::lock_guard<std::mutex> lock(ds->mu);
         constexpr int VAR = ZH ? (TYV == kTY ? 1 : 2) : 0;
-        if (!ds->slide_x3_attr[D][NRES][VAR]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (!ds->slide_x3_attr[F16][D][NRES][VAR]) {
+            if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
                 return OCCD_ELAUNCH;
-            ds->slide_x3_attr[D][NRES][VAR] = true;
+            ds->slide_x3_attr[F16][D][NRES][VAR] = true;
         }
     }
     SlideP sp;
@@ -943,7 +1013,8 @@ int launch_slide_x3(const PersistP& base0, hipStream_t st, DevState* ds) {
     static const bool res_early = occd::env_flag("OCCD_C32X3_RES_EARLY", true);      // A/B switch (0: in front of the second half)
     sp.res_early = res_early ? 1 : 0;
     const int grid = ds->num_cu < sp.total_segs ? ds->num_cu : sp.total_segs;
-    hipLaunchKernelGGL((conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>), dim3((unsigned)grid), dim3(512), lds, st, sp);
+    if constexpr (F16) hipLaunchKernelGGL((conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV>), dim3((unsigned)grid), dim3(512), lds, st, sp);
+    else hipLaunchKernelGGL((conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>), dim3((unsigned)grid), dim3(512), lds, st, sp);
     return occd::check_launch();
 }
 
@@ -1026,11 +1097,13 @@ int try_conv3d_c32_persist(const occd_conv3d_args* a, hipStream_t stream) {
 // occd_pack_weights_bf16x3, float32 tensors).  Same return convention; Z == 32, or Z = 64, 96, ... through the z-halo form
 // (see the kernel header; dilation 3 of such volumes on six-row y tiles);
 // OCCD_C32X3_SLIDE=0 leaves every split launch to the generic K2b skeleton (A/B).
-int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream) {
+// f16x2: K2s3h, the two-term fp16 split (a->wpk = the image of occd_pack_weights_f16x2); it has no generic twin, so the
+// A/B switch does not apply and a launch outside its geometry returns 0 for the caller to reject.
+int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream, bool f16x2) {
     static const bool off = !env_flag("OCCD_C32X3_SLIDE", true);
     PersistP p;
     double flops, bytes;
-    if (off || !c32_geometry(a, &p, &flops, &bytes)) return 0;
+    if ((off && !f16x2) || !c32_geometry(a, &p, &flops, &bytes)) return 0;
     if ((a->in_cs & 3) || (a->in_coff & 3)) return 0;
     const int d = a->dx;
     ProfScope prof("conv3d_c32x3", stream, flops, bytes);
@@ -1041,12 +1114,20 @@ int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream) {
     }
     const int nres = (p.res1 != nullptr) + (p.res2 != nullptr);
     int rc;
-#define OCCD_X3_LAUNCH(DD, ZZ) \
-    (nres == 0 ? launch_slide_x3<DD, 0, ZZ>(p, stream, ds) : nres == 1 ? launch_slide_x3<DD, 1, ZZ>(p, stream, ds) : launch_slide_x3<DD, 2, ZZ>(p, stream, ds))
-    if (a->Z == kTZ) rc = d == 1 ? OCCD_X3_LAUNCH(1, false) : d == 2 ? OCCD_X3_LAUNCH(2, false) : OCCD_X3_LAUNCH(3, false);
-    else if (d < 3) rc = d == 1 ? OCCD_X3_LAUNCH(1, true) : OCCD_X3_LAUNCH(2, true);
-    else rc = nres == 0 ? launch_slide_x3<3, 0, true, 6>(p, stream, ds) : nres == 1 ? launch_slide_x3<3, 1, true, 6>(p, stream, ds)
-                                                                                    : launch_slide_x3<3, 2, true, 6>(p, stream, ds);
+#define OCCD_X3_LAUNCH(DD, ZZ, TT, FF)                                                                          \
+    (nres == 0 ? launch_slide_x3<DD, 0, ZZ, TT, FF>(p, stream, ds) : nres == 1 ? launch_slide_x3<DD, 1, ZZ, TT, FF>(p, stream, ds) \
+               : launch_slide_x3<DD, 2, ZZ, TT, FF>(p, stream, ds))
+    if (f16x2) {
+        // (dilation 3 at Z > 32: the 8-row y tile would fit LDS with 80-byte entries, but its third staging load per thread
+        //  spills at NRES = 2 -- the six-row tile of K2s3 it is)
+        if (a->Z == kTZ) rc = d == 1 ? OCCD_X3_LAUNCH(1, false, kTY, true) : d == 2 ? OCCD_X3_LAUNCH(2, false, kTY, true)
+                                                                          : OCCD_X3_LAUNCH(3, false, kTY, true);
+        else rc = d == 1 ? OCCD_X3_LAUNCH(1, true, kTY, true) : d == 2 ? OCCD_X3_LAUNCH(2, true, kTY, true)
+                                                                      : OCCD_X3_LAUNCH(3, true, 6, true);
+    } else if (a->Z == kTZ) rc = d == 1 ? OCCD_X3_LAUNCH(1, false, kTY, false) : d == 2 ? OCCD_X3_LAUNCH(2, false, kTY, false)
+                                                                                 : OCCD_X3_LAUNCH(3, false, kTY, false);
+    else if (d < 3) rc = d == 1 ? OCCD_X3_LAUNCH(1, true, kTY, false) : OCCD_X3_LAUNCH(2, true, kTY, false);
+    else rc = OCCD_X3_LAUNCH(3, true, 6, false);
 #undef OCCD_X3_LAUNCH
     return rc == OCCD_OK ? 1 : rc;
 }

@@ -98,7 +98,8 @@ def _pad_bias(bias, cout):
 
 # The 3-way bf16 split (x = hi + mid + lo, six bf16 MFMAs per K step, float32-level accuracy on the bf16 matrix pipe):
 #   OCCDEPTH_BF16X3=head  (default since round 4) the full-resolution head convolutions (<= 32 -> <= 32 channels, 3x3x3,
-#                         dilation 1 / 2 / 3, Z = 32) on K2s3, the sliding-window form of the split (csrc/conv3d_c32p.hip):
+#                         dilation 1 / 2 / 3, Z = 32) on K2s3, the sliding-window form of the split (csrc/conv3d_c32p.hip;
+#                         since ABI 15 by default on its fp16 two-term twin K2s3h instead, see OCCDEPTH_HEAD_SPLIT below):
 #                         0.51 ms per launch against 0.90 ms for the exact-fp32 K2s, error against float64 no larger than
 #                         K2s' own (tests/test_bf16_conv.py::test_conv3d_slide_x3_head_kernel, profiles/r04_head_x3_ab.txt);
 #                         also (see below) the long-K 3x3x3 convolutions of small volumes and the merged phase launches of the
@@ -126,12 +127,35 @@ def set_bf16x3(on):
     BF16X3 = "all" if on is True else _parse_bf16x3(str(on)) if on else False
 
 
+# Which split the full-resolution head launches (K2s3's geometry) take while the split is on (OCCDEPTH_BF16X3 != 0):
+#   OCCDEPTH_HEAD_SPLIT=f16x2   (default) K2s3h, the two-term fp16 split: x = hi + 2^-11 lo', three v_mfma_f32_32x32x16_f16
+#                               per K step instead of six bf16 ones; error against float64 within 2x of the exact-fp32 K2s
+#                               (tests/test_head_f16x2.py); finite activations |x| >= 32760 overflow to non-finite outputs
+#                               (INTEGRATION.md section 6); plans whose weights are not all finite keep bf16x3
+#   OCCDEPTH_HEAD_SPLIT=bf16x3  K2s3 as before (the bit-for-bit previous path)
+# Everything else -- the K2b split launches, the 2-D GEMMs, training (autograd3d.py) -- is unchanged by this switch.
+def _parse_head_split(v):
+    v = (v or "f16x2").strip().lower()
+    if v not in ("f16x2", "bf16x3"):
+        raise ValueError(f"OCCDEPTH_HEAD_SPLIT={v!r}: expected f16x2 or bf16x3")
+    return v
+
+
+HEAD_SPLIT = _parse_head_split(os.environ.get("OCCDEPTH_HEAD_SPLIT", "f16x2"))
+
+
+def set_head_split(v):
+    """'f16x2' / 'bf16x3'; plans re-pack their weights on the next call."""
+    global HEAD_SPLIT
+    HEAD_SPLIT = _parse_head_split(v)
+
+
 class _DualW:
     """Both weight images of a plan while the split is on: the hi | mid | lo one for the launches the split kernels take,
-    the exact-fp32 one for the rest."""
+    the exact-fp32 one for the rest; f16x2: K2s3h's image for the head launches (None: they take K2s3)."""
 
-    def __init__(self, f32, x3):
-        self.f32, self.x3 = f32, x3
+    def __init__(self, f32, x3, f16x2=None):
+        self.f32, self.x3, self.f16x2 = f32, x3, f16x2
 
 
 BF16X3_DILATED = os.environ.get("OCCDEPTH_BF16X3_DILATED", "0") == "1"
@@ -163,9 +187,20 @@ def _smallvol_weight(w, layout):
             and w.shape[1] % 16 == 0 and w.shape[0] % 128 == 0)
 
 
+def _f16x2_ok(w, scale):
+    """K2s3h's weight image needs finite weights (its per-channel power-of-two scale) on the GPU; otherwise the plan keeps
+    bf16x3 (CPU tensors: the emulated path of the host-logic tests, which has no K2s3h twin)."""
+    if not w.is_cuda:
+        return False
+    ws = w if scale is None else w * scale.view(-1, *([1] * (w.dim() - 1)))
+    return bool(torch.isfinite(ws).all())
+
+
 def _pack_w(w, scale=None, layout=0):
     if BF16X3 == "all" or (BF16X3 == "head" and (_head_weight(w, layout) or _smallvol_weight(w, layout))):
-        return _DualW(hip.pack_weights(w, scale, layout), hip.pack_weights_bf16(w, scale, layout, split3=True))
+        f16 = (hip.pack_weights_f16x2(w, scale, layout)
+               if HEAD_SPLIT == "f16x2" and _head_weight(w, layout) and _f16x2_ok(w, scale) else None)
+        return _DualW(hip.pack_weights(w, scale, layout), hip.pack_weights_bf16(w, scale, layout, split3=True), f16)
     return hip.pack_weights(w, scale, layout)
 
 
@@ -183,7 +218,9 @@ def _smallvol_eligible(x, wpk, cout, kernel, out, **kw):
 
 def _conv3d(x, wpk, bias, cout, kernel, out, **kw):
     if isinstance(wpk, _DualW):
-        if hip.c32x3_eligible(x, cout, kernel, out, **kw):        # K2s3 (all three dilations)
+        if hip.c32x3_eligible(x, cout, kernel, out, **kw):        # K2s3h / K2s3 (all three dilations)
+            if wpk.f16x2 is not None:
+                return hip.conv3d_f16x2(x, wpk.f16x2, bias, cout, kernel, out, **kw)
             return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
         if _smallvol_eligible(x, wpk, cout, kernel, out, **kw):   # K2b split form, in-workgroup split-K
             return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
@@ -211,7 +248,7 @@ class ConvPlan:
         return self.conv.out_channels
 
     def _prepare(self):
-        key = (_stamp(self.conv, self.bn), BF16X3)
+        key = (_stamp(self.conv, self.bn), BF16X3, HEAD_SPLIT)
         if key == self._key:
             return
         w = self.conv.weight.detach().float()
@@ -270,7 +307,7 @@ class DerivedConvPlan:
         self.cout = self.kernel = None
 
     def _prepare(self):
-        key = (_stamp(*self.modules), BF16X3)
+        key = (_stamp(*self.modules), BF16X3, HEAD_SPLIT)
         if key == self._key:
             return
         w, b = self.derive()

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 MAX_VIEWS = 4
 MAX_SCALES = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 14   # 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+ABI_VERSION = 15   # 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
 
 _c_float_p = POINTER(c_float)
 
@@ -210,6 +210,9 @@ EXPORTS = {
                                                 c_void_p, c_void_p]),
     "occd_pack_weights_bf16x3": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            c_int32, c_void_p]),
+    "occd_packed_weight_f16x2_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "occd_pack_weights_f16x2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p]),
     "occd_conv3d_wgrad_bf16_workspace_floats": (c_int64, [POINTER(WgradArgs), c_int32]),
     "occd_conv3d_wgrad_bf16": (c_int32, [POINTER(WgradArgs), c_int32, c_void_p]),
     "occd_bn_blocks": (c_int32, [POINTER(BnArgs)]),
@@ -524,6 +527,42 @@ def pack_weights_bf16(w, scale=None, layout=0, split3=False):
     fn = load().occd_pack_weights_bf16x3 if split3 else load().occd_pack_weights_bf16
     _check(fn(_f32(w, "w"), _f32(sc, "scale") if sc is not None else None, _ptr(out, "wpk"),
               cout, cin, k[0], k[1], k[2], layout, _stream()), "occd_pack_weights_bf16")
+    return out
+
+
+def pack_weights_f16x2(w, scale=None, layout=0):
+    """fp32 master weights -> the image of K2s3h, the two-term fp16 split of the head convolutions (conv3d_f16x2): three fp16
+    images hi | hs | lo of the per-channel power-of-two scaled weights plus the epilogue factors (a uint8 tensor of
+    occd_packed_weight_f16x2_bytes bytes).  The weights must be finite."""
+    if layout == 2:
+        cin, cout = w.shape
+        k = (1, 1, 1)
+    else:
+        cout, cin = w.shape[0], w.shape[1]
+        k = tuple(w.shape[2:])
+    w = w.detach().float().contiguous()
+    n = load().occd_packed_weight_f16x2_bytes(cout, cin, k[0] * k[1] * k[2])
+    if n <= 0:
+        raise RuntimeError("occd_packed_weight_f16x2_bytes: bad shape")
+    out = torch.empty(n, device=w.device, dtype=torch.uint8)
+    sc = scale.detach().float().contiguous() if scale is not None else None
+    _check(load().occd_pack_weights_f16x2(_f32(w, "w"), _f32(sc, "scale") if sc is not None else None, _ptr(out, "wpk"),
+                                          cout, cin, k[0], k[1], k[2], layout, _stream()), "occd_pack_weights_f16x2")
+    return out
+
+
+def conv3d_f16x2(x, wpk, bias, cout, kernel, out, **kw):
+    """K2s3h: `conv3d` of a full-resolution head convolution (`c32x3_eligible`) with the two-term fp16 split of both
+    operands (float32 tensors, wpk = pack_weights_f16x2(w)).  Other geometries are an error: there is no generic form."""
+    if wpk.dtype != torch.uint8:
+        raise RuntimeError("conv3d_f16x2 needs the image of pack_weights_f16x2")
+    if x.buf.dtype != torch.float32:
+        raise RuntimeError("the fp16 split takes float32 tensors")
+    a = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, kw.get("stride", (1, 1, 1)), kw.get("dilation", (1, 1, 1)),
+                     kw.get("padding", (0, 0, 0)), kw.get("res1"), kw.get("res2"), kw.get("act_in", ACT_NONE),
+                     kw.get("act_out", ACT_NONE), kw.get("out_pos"), kw.get("o_stride", (1, 1, 1)), kw.get("o_off", (0, 0, 0)),
+                     kw.get("cin"), kw.get("tile_hint", 0), _act_ptr(x.buf.dtype))
+    _check(load().occd_conv3d_bf16_fwd(ctypes.byref(a), 3, _stream()), "occd_conv3d_bf16_fwd (f16x2)")
     return out
 
 

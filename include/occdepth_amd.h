@@ -41,7 +41,8 @@ extern "C" {
 #define OCCD_ACT_SIGMOID 2
 #define OCCD_ACT_RELU_PRE 3 /* act_out only: relu(conv + bias) + res1 + res2 */
 
-/* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk). */
+/* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk;
+ * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -824,6 +825,46 @@ int occd_depth_bce_grad(const float* prob, const float* gt, const float* gscale,
  * OccDepth.py:523-526); exactly one of the two is non-NULL.  hist is NOT cleared (it accumulates).         */
 int occd_ssc_confusion(const float* logits, const uint8_t* labels, const uint8_t* target, int64_t* hist,
                        int64_t batch, int32_t C, int64_t S, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Training targets of the SemanticKITTI dataloader, built on the GPU (csrc/targets.hip).  All three are bit-exact
+ * restatements of the reference's numpy functions and capture-safe: calibration is read from device memory, the
+ * counters are zeroed by a fill kernel, nothing is allocated and nothing synchronises.
+ *
+ * occd_frustum_targets: compute_local_frustums (occdepth/data/utils/helpers.py:183-260, dataset "kitti") over the
+ * voxel -> pixel projection of occd_project_voxels (pattern point 0), for V = 1 or 2 views.  Voxel n = (x*Y + y)*Z + z
+ * lies in frustum f = j*s + i of a view when  (i/s)*W <= pix_x < ((i+1)/s)*W,  (j/s)*H <= pix_y < ((j+1)/s)*H  and
+ * cam_z > 0, all compared in float64 as helpers.py:172-180,216-224 does.
+ *   masks[b, f, n] = target[b, n] != 255 && (n in frustum f of any view)                    (B, F, N) uint8, F = s*s
+ *   dists[b, f, c] = #{n : masks[b, f, n] && target[b, n] == c}, c < n_classes               (B, F, C) float32
+ * Labels in [n_classes, 255) enter the masks but no count.  Requires 1 <= s <= 16 and F * n_classes <= 4096. */
+typedef struct occd_frustum_args {
+    const double* cam_E;       /* (B, V, 4, 4) device float64, row major (lidar -> camera)                   */
+    const double* cam_k;       /* (B, V, 3, 3) device float64 (fx, fy, cx, cy are rounded to float32)        */
+    const uint8_t* target;     /* (B, N) labels, 255 = unlabelled                                            */
+    uint8_t* masks;            /* (B, F, N)                                                                  */
+    float* dists;              /* (B, F, C); used as uint32 counters until the last launch converts them     */
+    double vox_origin[3];
+    double voxel_size;
+    int32_t batch, n_views, X, Y, Z;
+    int32_t img_w, img_h, frustum_size, n_classes;
+} occd_frustum_args;
+int occd_frustum_targets(const occd_frustum_args* a, void* stream);
+
+/* _downsample_label (occdepth/data/NYU/preprocess.py:102-143, used by data/semantic_kitti/preprocess.py for the
+ * 1:8 labels): every ds^3 block of `in` (B, X, Y, Z) uint8 -> one label of `out` (B, X/ds, Y/ds, Z/ds):
+ * zero = #0 + #255;  zero > 0.95 * ds^3 ? (#0 > #255 ? 0 : 255) : the most frequent label in 1..254 (smallest on a tie).
+ * X, Y and Z must be multiples of ds. */
+int occd_downsample_label(const uint8_t* in, uint8_t* out, int32_t batch, int32_t X, int32_t Y, int32_t Z, int32_t ds,
+                          void* stream);
+
+/* compute_CP_mega_matrix (occdepth/data/utils/helpers.py:6-91): `coarse` (B, X, Y, Z) uint8 labels ->
+ * out (B, R, N, M) uint8, N = X*Y*Z, M = (X/2)(Y/2)(Z/2) mega voxels (index (xx*(Y/2) + yy)*(Z/2) + zz, children
+ * (2xx+dx, 2yy+dy, 2zz+dz)); R = 4 (non-non same, non-non diff, empty-empty, nonempty-empty) or, with `binary`,
+ * R = 2 (diff, same).  Entry (r, n, m) depends on label[n] and the set of non-255 child labels of m only; rows
+ * labelled 255 are zero.  Every byte of `out` is written. */
+int occd_cp_mega_matrix(const uint8_t* coarse, uint8_t* out, int32_t batch, int32_t X, int32_t Y, int32_t Z,
+                        int32_t binary, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Small-message all-reduce over peer-mapped device memory (round 5; csrc/ipc_allreduce.hip): the latency-optimal form

@@ -13,6 +13,7 @@
 // occdepth/models/flosp_depth/flosp_depth.py:561-602, f2v/frustum_grid_generator.py:70-152,
 // f2v/utils/{transform_utils.py:5-26,depth_utils.py:24-26,grid_utils.py:4-19}, f2v/sampler.py:59-64.
 #include "common.h"
+#include "project.h"
 #include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -34,39 +35,6 @@ __device__ __forceinline__ float group_sum(float v) {
     if (LPV >= 32) v += __shfl_xor(v, 16, 64);
     if (LPV >= 64) v += __shfl_xor(v, 32, 64);
     return v;
-}
-
-// SURVEY.md 8(f) row N2, one voxel: occdepth/data/utils/helpers.py:94-169 with fusion.py:203-217 (vox2world: float32
-// origin, float64 arithmetic, float32 store), :518-522 (rigid transform in float64) and :336-337 (round(x * fx / z + cx),
-// float32 intrinsics, numpy round-half-even).  Every product / sum is an explicitly rounded IEEE double operation (no FMA
-// contraction) so the pixels are the ones numpy computes.  Returns the FOV flag.
-__device__ __forceinline__ bool project_one(const double* __restrict__ E, double fx, double fy, double cx, double cy,
-                                            double vox_size, const float* origin, int ix, int iy, int iz, int img_w,
-                                            int img_h, long& px, long& py, double& camz) {
-    const int idx[3] = {ix, iy, iz};
-    double pt[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double a = __dadd_rn((double)origin[j], __dmul_rn(vox_size, (double)(float)idx[j]));
-        pt[j] = (double)(float)__dadd_rn(a, __dmul_rn(vox_size, 0.5));
-    }
-    double cam[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double acc = __dmul_rn(E[r * 4 + 0], pt[0]);
-        acc = __dadd_rn(acc, __dmul_rn(E[r * 4 + 1], pt[1]));
-        acc = __dadd_rn(acc, __dmul_rn(E[r * 4 + 2], pt[2]));
-        cam[r] = __dadd_rn(acc, E[r * 4 + 3]);
-    }
-    double xr = rint(__dadd_rn(__ddiv_rn(__dmul_rn(cam[0], fx), cam[2]), cx));
-    double yr = rint(__dadd_rn(__ddiv_rn(__dmul_rn(cam[1], fy), cam[2]), cy));
-    // non-finite projections (z == 0) are clamped like oracle/inputs.py; they are out of the FOV anyway
-    xr = isnan(xr) ? -1e9 : fmin(fmax(xr, -1e9), 1e9);
-    yr = isnan(yr) ? -1e9 : fmin(fmax(yr, -1e9), 1e9);
-    px = (long)xr;
-    py = (long)yr;
-    camz = cam[2];
-    return px >= 0 && px < img_w && py >= 0 && py < img_h && cam[2] > 0.0;
 }
 
 struct LiftP {
@@ -620,7 +588,7 @@ __global__ void __launch_bounds__(256) lift_proj_kernel(const LiftProjP pp) {
                 const double* K = pp.cam_k + ((size_t)b * V + v) * 9;
                 long px, py;
                 double camz;
-                if (project_one(E, (double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5],
+                if (occd::project_one(E, (double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5],
                                 pp.vox_size, pp.origin, ix, iy, iz, pp.img_w, pp.img_h, px, py, camz))
                     code = (int)((py << 16) | px);
             }
@@ -1034,7 +1002,7 @@ __global__ void __launch_bounds__(256) project_voxels_kernel(const ProjP p) {
     const int iy = (int)(t % p.Y), ix = (int)(t / p.Y);
     long px, py;
     double camz;
-    const bool in = project_one(p.E, p.fx, p.fy, p.cx, p.cy, p.vox_size, p.origin, ix, iy, iz, p.img_w, p.img_h, px, py,
+    const bool in = occd::project_one(p.E, p.fx, p.fy, p.cx, p.cy, p.vox_size, p.origin, ix, iy, iz, p.img_w, p.img_h, px, py,
                                 camz);
     p.pix[n * 2] = px;
     p.pix[n * 2 + 1] = py;

@@ -87,6 +87,18 @@ class OccDepth(_Base):
         if env("OCCDEPTH_FAST_TRAIN", "0") == "1":
             self.enable_fast_train(bf16=env("OCCDEPTH_FAST_TRAIN_BF16", "0") == "1")
         self.fused_lift = True    # training on the GPU: HIP lift + one-launch backward (lift_autograd.py) where it applies
+        # Training targets built on the GPU (targets.py) instead of in the dataloader workers.  OCCDEPTH_GPU_TARGETS =
+        #   auto (default)  build the frustum masks / class counts and the relation matrices a batch does NOT bring (key
+        #                   absent, an empty list, or zero-element entries: what the hooked collate delivers); a batch
+        #                   that brings them is used as it is;
+        #   1               always build (the batch's targets are ignored) and rebind the reference dataset's two target
+        #                   functions to stubs (targets.defer_dataset_targets; reaches dataloader workers forked later);
+        #   0               never build.
+        self.gpu_targets = {"1": True, "0": False}.get(env("OCCDEPTH_GPU_TARGETS", "auto"), "auto")
+        self._dataset_hook = None
+        if self.gpu_targets is True:
+            from ..targets import defer_dataset_targets
+            self._dataset_hook = defer_dataset_targets()
         if infer_mode:
             self.context_prior = False
         assert not (config.use_stereo_depth_gt and config.use_lidar_depth_gt), "only with one depth data supported."
@@ -611,17 +623,27 @@ class OccDepth(_Base):
         ssc_pred = out_dict["ssc_logit"]
         dev = ssc_pred.device
         target = batch["target"].to(dev)
+        use_rel = self.context_prior and self.relation_loss
+        built_fp = built_cp = None
+        if self.fp_loss and step_type != "test" and self._build_target(batch, "frustums_masks"):
+            built_fp = self.frustum_targets_on_gpu(batch, target)
+        if use_rel and self._build_target(batch, "CP_mega_matrices"):
+            built_cp = self.relation_targets_on_gpu(target)
         loss = 0
-        if self.context_prior and self.relation_loss:
-            loss_rel_ce = compute_super_CP_multilabel_loss(out_dict["P_logits"], batch["CP_mega_matrices"])
+        if use_rel:
+            loss_rel_ce = compute_super_CP_multilabel_loss(out_dict["P_logits"],
+                                                           built_cp if built_cp is not None else batch["CP_mega_matrices"])
             loss = loss + loss_rel_ce
             self._log(step_type + "/loss_relation_ce_super", loss_rel_ce)
 
         use_fp = self.fp_loss and step_type != "test"
         masks = dists = None
         if use_fp:
-            masks = torch.stack(list(batch["frustums_masks"])).to(dev)
-            dists = torch.stack(list(batch["frustums_class_dists"])).float().to(dev)
+            if built_fp is not None:
+                masks, dists = built_fp
+            else:
+                masks = torch.stack(list(batch["frustums_masks"])).to(dev)
+                dists = torch.stack(list(batch["frustums_class_dists"])).float().to(dev)
         terms = ssc_loss.ssc_losses(ssc_pred, target, self._on_device("class_weights", dev), masks, dists,
                                     ce=self.CE_ssc_loss, sem_scal=self.sem_scal_loss, geo_scal=self.geo_scal_loss)
         if self.CE_ssc_loss:
@@ -674,6 +696,59 @@ class OccDepth(_Base):
                 metric.add_batch(ssc_pred.detach().argmax(1).cpu().numpy(), target.cpu().numpy())
         self._log(step_type + "/loss", loss)
         return loss
+
+    @staticmethod
+    def _targets():
+        from .. import targets
+        return targets
+
+    def _build_target(self, batch, key):
+        """OCCDEPTH_GPU_TARGETS: is target `key` built on the GPU for this batch?"""
+        if self.gpu_targets is True:
+            return True
+        if self.gpu_targets is False:
+            return False
+        v = batch.get(key)
+        if v is None:
+            return True
+        if torch.is_tensor(v):
+            return v.numel() == 0
+        return all(torch.is_tensor(t) and t.numel() == 0 for t in v)       # also True for an empty list
+
+    def frustum_targets_on_gpu(self, batch, target):
+        """(frustums_masks (B, F, X, Y, Z) bool, frustums_class_dists (B, F, C) float32) of kitti_dataset.py:315-333, built
+        on the GPU (targets.frustum_targets) from the batch's UNFLIPPED calibration -- the reference builds them before its
+        flip augmentation (:384), so the batch's (possibly flipped) projected_pix tables are never used.  Output scale
+        ceil(project_scale / 2) (kitti_dataset.py:83), SemanticKITTI origin (_kitti_origin)."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("frustum targets are built on the GPU for the SemanticKITTI geometry only; a %s batch "
+                                      "must bring frustums_masks / frustums_class_dists" % self.dataset)
+        scale = -(-int(self.project_scale) // 2)
+        dims = tuple(int(d) // scale for d in self.full_scene_size)
+        if target.dim() != 4 or tuple(target.shape[1:]) != dims:
+            raise NotImplementedError("frustum targets on the GPU: target grid %s does not match the output grid %s; the "
+                                      "batch must bring frustums_masks / frustums_class_dists" % (tuple(target.shape[1:]), dims))
+        dev = target.device
+        ext = batch.get("T_velo_2_cam_f64", batch.get("T_velo_2_cam"))
+        E = torch.stack([e.to(dev) for e in ext]).to(torch.float64)
+        k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64)
+        H, W = batch["img"].shape[-2:]
+        return self._targets().frustum_targets(E, k, target, vox_origin=self._kitti_origin(batch), voxel_size=0.2 * scale,
+                                               img_wh=(int(W), int(H)), frustum_size=self.frustum_size,
+                                               n_classes=self.n_classes)
+
+    def relation_targets_on_gpu(self, target):
+        """CP_mega_matrices (B, 4, N, M) uint8 of kitti_dataset.py:294-300, built on the GPU: the 4-way matrix
+        (targets.cp_mega_matrix) of the 1:8 labels, which the reference's preprocessing makes from the 1:1 labels with
+        _downsample_label (targets.downsample_label)."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("relation targets are built on the GPU for the SemanticKITTI geometry only (NYU's come "
+                                      "from a 1:16 label the batch does not carry); the batch must bring CP_mega_matrices")
+        if target.dim() != 4 or any(int(d) % 16 for d in target.shape[1:]):
+            raise NotImplementedError("relation targets on the GPU need a (B, X, Y, Z) target with X, Y, Z multiples of 16, "
+                                      "got %s; the batch must bring CP_mega_matrices" % (tuple(target.shape),))
+        t = self._targets()
+        return t.cp_mega_matrix(t.downsample_label(target, 8))
 
     def _on_device(self, name, dev):
         """float32 device copy of a host-side attribute tensor (class weights), cached: `.to(dev)` per step is a host

@@ -1,0 +1,158 @@
+"""Training targets of the SemanticKITTI dataloader, built on the GPU (csrc/targets.hip).
+
+The reference builds two supervision targets per sample in numpy inside its dataloader workers, ~3.8 s of CPU per
+sample and 142.6 MB shipped per sample at the shipped KITTI geometry (256 x 256 x 32, frustum_size 8):
+  * frustum masks and class counts  -- compute_local_frustums, occdepth/data/utils/helpers.py:183-260, called at
+    occdepth/data/semantic_kitti/kitti_dataset.py:315-333 (the frustum-proportion loss, `fp_loss`);
+  * the CRP relation matrix         -- compute_CP_mega_matrix, helpers.py:6-91, on the 1:8 labels that
+    `_downsample_label` (occdepth/data/NYU/preprocess.py:102-143) makes from the 1:1 labels, kitti_dataset.py:294-300
+    (the relation loss, `context_prior`).
+Both are pure functions of what a batch already carries (`target`, `cam_k`, `T_velo_2_cam`).  The builders here are
+bit-exact restatements, GPU only (no CPU path, like hip.py), and never synchronise the host, so they can sit inside a
+captured training step.  `OccDepth.step` calls them when a batch comes without the targets (OCCDEPTH_GPU_TARGETS);
+`defer_dataset_targets` takes the numpy work out of the reference's dataset.
+"""
+import ctypes
+import importlib
+
+import numpy as np
+import torch
+
+from . import hip
+
+KITTI_DATASET_MODULE = "occdepth.data.semantic_kitti.kitti_dataset"
+
+
+def _dev_stack(x, name, dtype=None):
+    t = torch.stack(list(x)) if isinstance(x, (list, tuple)) else x
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (the target builders have no CPU path)")
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    return t.contiguous()
+
+
+def frustum_targets(cam_E, cam_k, target, *, vox_origin, voxel_size, img_wh, frustum_size, n_classes):
+    """compute_local_frustums (helpers.py:183-260, dataset "kitti") for a batch, on the GPU.
+
+    cam_E (B, V, 4, 4) and cam_k (B, V, 3, 3): device tensors (or lists of per-sample (V, ., .) tensors), V = 1 or 2,
+    used in float64 (the dataloader's calibration is float64; float32 extrinsics move a few voxels by one pixel).
+    target (B, X, Y, Z) labels, 255 = unlabelled.  The projection is the dataloader's vox2pix (pattern point 0,
+    helpers.py:94-169; csrc/project.h) at `vox_origin` / `voxel_size` for an image of img_wh = (W, H).
+    Returns masks (B, F, X, Y, Z) bool and dists (B, F, n_classes) float32, F = frustum_size ** 2, frustum f = j * s + i
+    for x tile i and y tile j (helpers.py:219-220); a voxel is in a frustum when any view puts it there."""
+    E = _dev_stack(cam_E, "cam_E", torch.float64)
+    K = _dev_stack(cam_k, "cam_k", torch.float64)
+    tgt = _dev_stack(target, "target", torch.uint8)
+    if E.dim() != 4 or tuple(E.shape[2:]) != (4, 4) or tuple(K.shape) != tuple(E.shape[:2]) + (3, 3):
+        raise RuntimeError("frustum_targets: cam_E must be (B, V, 4, 4) and cam_k (B, V, 3, 3)")
+    if tgt.dim() != 4 or tgt.shape[0] != E.shape[0]:
+        raise RuntimeError("frustum_targets: target must be (B, X, Y, Z) with the batch of cam_E")
+    B, V = E.shape[:2]
+    X, Y, Z = (int(d) for d in tgt.shape[1:])
+    s, C = int(frustum_size), int(n_classes)
+    F = s * s
+    masks = torch.empty((B, F, X, Y, Z), dtype=torch.uint8, device=tgt.device)
+    dists = torch.empty((B, F, C), dtype=torch.float32, device=tgt.device)
+    a = hip.FrustumArgs()
+    a.cam_E, a.cam_k, a.target, a.masks, a.dists = E.data_ptr(), K.data_ptr(), tgt.data_ptr(), masks.data_ptr(), \
+        dists.data_ptr()
+    for j, o in enumerate(vox_origin):
+        a.vox_origin[j] = float(o)
+    a.voxel_size = float(voxel_size)
+    a.batch, a.n_views, a.X, a.Y, a.Z = B, V, X, Y, Z
+    a.img_w, a.img_h = int(img_wh[0]), int(img_wh[1])
+    a.frustum_size, a.n_classes = s, C
+    hip._check(hip.load().occd_frustum_targets(ctypes.byref(a), hip._stream()), "occd_frustum_targets")
+    return masks.view(torch.bool), dists
+
+
+def downsample_label(target, ds):
+    """_downsample_label (occdepth/data/NYU/preprocess.py:102-143) on the GPU: (B, X, Y, Z) or (X, Y, Z) labels ->
+    (B, X/ds, Y/ds, Z/ds) uint8.  Per ds^3 block: more than 95 % of 0 / 255 -> 0 if #0 > #255 else 255, otherwise the most
+    frequent label in 1..254 (the smallest on a tie, as np.argmax(np.bincount(...)))."""
+    tgt = _dev_stack(target, "target", torch.uint8)
+    squeeze = tgt.dim() == 3
+    if squeeze:
+        tgt = tgt.unsqueeze(0)
+    if tgt.dim() != 4:
+        raise RuntimeError("downsample_label: target must be (B, X, Y, Z) or (X, Y, Z)")
+    B, X, Y, Z = (int(d) for d in tgt.shape)
+    ds = int(ds)
+    out = torch.empty((B, X // max(ds, 1), Y // max(ds, 1), Z // max(ds, 1)), dtype=torch.uint8, device=tgt.device)
+    hip._check(hip.load().occd_downsample_label(tgt.data_ptr(), out.data_ptr(), B, X, Y, Z, ds, hip._stream()),
+               "occd_downsample_label")
+    return out[0] if squeeze else out
+
+
+def cp_mega_matrix(coarse, binary=False):
+    """compute_CP_mega_matrix (helpers.py:6-91) on the GPU: (B, X, Y, Z) or (X, Y, Z) labels -> (B, R, N, M) uint8 in
+    the reference's layout (R = 4, or 2 with `binary`; N = X*Y*Z rows; M = (X/2)(Y/2)(Z/2) mega voxels)."""
+    lab = _dev_stack(coarse, "coarse", torch.uint8)
+    squeeze = lab.dim() == 3
+    if squeeze:
+        lab = lab.unsqueeze(0)
+    if lab.dim() != 4:
+        raise RuntimeError("cp_mega_matrix: labels must be (B, X, Y, Z) or (X, Y, Z)")
+    B, X, Y, Z = (int(d) for d in lab.shape)
+    R = 2 if binary else 4
+    out = torch.empty((B, R, X * Y * Z, (X // 2) * (Y // 2) * (Z // 2)), dtype=torch.uint8, device=lab.device)
+    hip._check(hip.load().occd_cp_mega_matrix(lab.data_ptr(), out.data_ptr(), B, X, Y, Z, int(bool(binary)),
+                                              hip._stream()), "occd_cp_mega_matrix")
+    return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------------------------------------ dataset hook
+def _no_frustums(*args, **kwargs):
+    """Stands in for compute_local_frustums: no masks, so the reference collate skips them (collate.py:29-34)."""
+    return None, None
+
+
+def _no_cp_matrix(*args, **kwargs):
+    """Stands in for compute_CP_mega_matrix: a zero-size uint8 array (collate.py:59-60 still calls torch.from_numpy)."""
+    return np.zeros((0,), dtype=np.uint8)
+
+
+class DatasetTargetsHook:
+    """Undo handle of `defer_dataset_targets`: `undo()` restores the names it rebound (idempotent)."""
+
+    def __init__(self, module, saved):
+        self.module, self.saved = module, saved
+
+    @property
+    def active(self):
+        return self.module is not None and bool(self.saved)
+
+    def undo(self):
+        if self.module is not None:
+            for name, fn in self.saved.items():
+                setattr(self.module, name, fn)
+        self.saved = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.undo()
+
+
+def defer_dataset_targets(module=None):
+    """Rebind `compute_local_frustums` and `compute_CP_mega_matrix` inside the reference's SemanticKITTI dataset module
+    (occdepth.data.semantic_kitti.kitti_dataset, when importable; or `module`) to stubs, so its workers stop building the
+    frustum and relation targets; `OccDepth.step` then builds them on the GPU (OCCDEPTH_GPU_TARGETS).  Returns a
+    DatasetTargetsHook (inactive when the module cannot be imported).
+
+    Only the module's global names change, in this process: dataloader workers started by fork afterwards inherit them;
+    workers started before the call, or by spawn / forkserver, do not.  Install the hook before the first epoch's
+    workers start (OCCDEPTH_GPU_TARGETS=1 installs it when the model is constructed)."""
+    if module is None:
+        try:
+            module = importlib.import_module(KITTI_DATASET_MODULE)
+        except Exception:
+            return DatasetTargetsHook(None, {})
+    saved = {}
+    for name, stub in (("compute_local_frustums", _no_frustums), ("compute_CP_mega_matrix", _no_cp_matrix)):
+        if hasattr(module, name) and getattr(module, name) is not stub:
+            saved[name] = getattr(module, name)
+            setattr(module, name, stub)
+    return DatasetTargetsHook(module, saved)

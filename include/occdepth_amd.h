@@ -42,7 +42,8 @@ extern "C" {
 #define OCCD_ACT_RELU_PRE 3 /* act_out only: relu(conv + bias) + res1 + res2 */
 
 /* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk;
- * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix). */
+ * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix;
+ * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -328,6 +329,9 @@ typedef struct occd_lift_proj_args {
     float origin[3];        /* float32(vox_origin)                                                                    */
     int32_t img_w, img_h;
     occd_flosp_args frustum;
+    const float* ida;       /* DEVICE (B, V, 4, 4) float32 image-space transforms (the batch's ida_mats) or NULL: a view
+                               with ida[b][v][0][0] < 0 was flipped left-right, and every in-FOV pixel x is gathered at
+                               img_w - 1 - x (kitti_dataset.py:384-390; the FOV itself is decided unflipped)         */
 } occd_lift_proj_args;
 int occd_lift_proj_fwd(const occd_lift_proj_args* a, void* stream);
 
@@ -352,6 +356,26 @@ int occd_lift_bwd(const occd_lift_bwd_args* a, void* stream);
 int occd_project_voxels(const double* cam_E_host, const double* cam_k_host, const double* vox_origin_host,
                         double voxel_size, int32_t X, int32_t Y, int32_t Z, int32_t img_w, int32_t img_h,
                         int64_t* pix, uint8_t* fov, float* pix_z, void* stream);
+
+/* The same projection for a whole batch, calibration in DEVICE memory (capture-safe, no host sync): the tables the
+ * reference's SemanticKITTI dataset ships, flip included.  For every (b, v) and voxel n = (x*Y + y)*Z + z:
+ *   pix[b, v, n, 0, :], fov[b, v, n, 0], pix_z[b, v, n] = occd_project_voxels(cam_E[b, v], cam_k[b, v], ...)
+ * then, when ida != NULL and ida[b, v, 0, 0] < 0 (img_transform(crop, flip=True), kitti_dataset.py:20-37), every x, in
+ * the FOV or not, becomes img_w - 1 - x (kitti_dataset.py:388); the FOV is the unflipped one.  The rest of ida is
+ * ignored.  Arbitrary grid dims.  Invalid arguments return OCCD_EINVAL without a launch. */
+typedef struct occd_vox2pix_args {
+    const double* cam_E;       /* (B, V, 4, 4) device float64, row major (lidar -> camera)                   */
+    const double* cam_k;       /* (B, V, 3, 3) device float64 (fx, fy, cx, cy are rounded to float32)        */
+    const float* ida;          /* (B, V, 4, 4) device float32, or NULL (no flip)                             */
+    int64_t* pix;              /* (B, V, N, 1, 2) int64, 16-byte aligned                                     */
+    uint8_t* fov;              /* (B, V, N, 1) bool                                                          */
+    float* pix_z;              /* (B, V, N) float32 camera depth, or NULL                                    */
+    double vox_origin[3];      /* rounded to float32 as vox2world does                                       */
+    double voxel_size;
+    int32_t batch, n_views, X, Y, Z;
+    int32_t img_w, img_h;
+} occd_vox2pix_args;
+int occd_vox2pix(const occd_vox2pix_args* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Layout / small fused helpers around the two big kernels.

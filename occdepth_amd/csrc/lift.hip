@@ -552,6 +552,7 @@ struct LiftProjP {
     int img_w, img_h;
     FlospP fr;
     int has_frustum;
+    const float* ida;        // (B, V, 16) device floats or null: ida[0] < 0 marks a left-right flipped view
 };
 
 template <int LPV, int V, int U>   // U = voxels in flight per lane group (1, 2 or 4)
@@ -589,8 +590,11 @@ __global__ void __launch_bounds__(256) lift_proj_kernel(const LiftProjP pp) {
                 long px, py;
                 double camz;
                 if (occd::project_one(E, (double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5],
-                                pp.vox_size, pp.origin, ix, iy, iz, pp.img_w, pp.img_h, px, py, camz))
+                                pp.vox_size, pp.origin, ix, iy, iz, pp.img_w, pp.img_h, px, py, camz)) {
+                    // flip after the FOV decision, as kitti_dataset.py:384-390 flips its (unflipped) tables
+                    if (pp.ida && pp.ida[((size_t)b * V + v) * 16] < 0.f) px = pp.img_w - 1 - px;
                     code = (int)((py << 16) | px);
+                }
             }
             s_pix[i] = code;
         } else {
@@ -903,6 +907,7 @@ extern "C" int occd_lift_proj_fwd(const occd_lift_proj_args* q, void* stream) {
     p.vox_size = q->voxel_size;
     for (int j = 0; j < 3; ++j) p.origin[j] = q->origin[j];
     p.img_w = q->img_w; p.img_h = q->img_h;
+    p.ida = q->ida;
     p.has_frustum = q->frustum.depth != nullptr;
     if (p.has_frustum) {
         const occd_flosp_args* f = &q->frustum;
@@ -1032,5 +1037,88 @@ extern "C" int occd_project_voxels(const double* cam_E_host, const double* cam_k
     occd::ProfScope prof("project_voxels", (hipStream_t)stream, 0.0, 17.0 * total);
     hipLaunchKernelGGL(project_voxels_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        p);
+    return occd::check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The batched, device-calibrated, flip-aware form of occd_project_voxels: the projected_pix / fov_mask tables of the
+// reference's SemanticKITTI dataset (kitti_dataset.py:253-284, flipped at :384-390), built inside a captured step.
+// Store-bound: 17 (21 with pix_z) bytes written per voxel and view, the calibration is 25 doubles per (b, v).
+namespace {
+
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+struct Vox2PixP {
+    const double* cam_E;          // (B*V, 16)
+    const double* cam_k;          // (B*V, 9)
+    const float* ida;             // (B*V, 16) or nullptr
+    int64_t* pix;                 // (B*V, N, 2)
+    uint8_t* fov;                 // (B*V, N)
+    float* pix_z;                 // (B*V, N) or nullptr
+    double vox_size;
+    float origin[3];
+    int X, Y, Z, img_w, img_h;
+    long N;
+};
+
+// grid (ceil(N / 256), B * V): one voxel per lane, one (b, v) per grid row.  Each lane writes its (px, py) as one
+// 16-byte store (a wave covers 1 KB contiguous).  PACK (N % 4 == 0 and a 4-byte aligned fov): the workgroup's 256 fov
+// bytes go through LDS and out as 64 32-bit stores.
+template <bool PACK>
+__global__ void __launch_bounds__(256) vox2pix_kernel(const Vox2PixP p) {
+    __shared__ uint32_t s_fov[64];
+    const int bv = blockIdx.y;
+    const long n0 = (long)blockIdx.x * 256;
+    const long n = n0 + threadIdx.x;
+    const size_t o = (size_t)bv * p.N;
+    bool in = false;
+    if (n < p.N) {
+        const double* E = p.cam_E + (size_t)bv * 16;
+        const double* K = p.cam_k + (size_t)bv * 9;
+        const int iz = (int)(n % p.Z);
+        const long t = n / p.Z;
+        const int iy = (int)(t % p.Y), ix = (int)(t / p.Y);
+        long px, py;
+        double camz;
+        in = occd::project_one(E, (double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5],
+                               p.vox_size, p.origin, ix, iy, iz, p.img_w, p.img_h, px, py, camz);
+        // kitti_dataset.py:388: every x of a flipped view, in the FOV or not; the FOV above is the unflipped one
+        if (p.ida && p.ida[(size_t)bv * 16] < 0.f) px = p.img_w - 1 - px;
+        *(i64x2*)(p.pix + (o + n) * 2) = i64x2{(long long)px, (long long)py};
+        if (p.pix_z) p.pix_z[o + n] = (float)camz;
+        if (!PACK) p.fov[o + n] = in ? 1 : 0;
+    }
+    if (PACK) {
+        reinterpret_cast<uint8_t*>(s_fov)[threadIdx.x] = in ? 1 : 0;
+        __syncthreads();
+        const long q = n0 + 4 * (long)threadIdx.x;
+        if (threadIdx.x < 64 && q < p.N) *(uint32_t*)(p.fov + o + q) = s_fov[threadIdx.x];
+    }
+}
+
+}  // namespace
+
+extern "C" int occd_vox2pix(const occd_vox2pix_args* a, void* stream) {
+    if (!a || !a->cam_E || !a->cam_k || !a->pix || !a->fov) return OCCD_EINVAL;
+    if (a->batch <= 0 || a->n_views <= 0 || (long)a->batch * a->n_views > 65535) return OCCD_EINVAL;
+    if (a->X <= 0 || a->Y <= 0 || a->Z <= 0 || !(a->voxel_size > 0) || a->img_w <= 0 || a->img_h <= 0)
+        return OCCD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->pix) & 15) return OCCD_EINVAL;
+    const long N = (long)a->X * a->Y * a->Z;
+    if ((N + 255) / 256 > 0x7FFFFFFFL) return OCCD_EINVAL;
+    Vox2PixP p;
+    p.cam_E = a->cam_E; p.cam_k = a->cam_k; p.ida = a->ida;
+    p.pix = a->pix; p.fov = a->fov; p.pix_z = a->pix_z;
+    p.vox_size = a->voxel_size;
+    for (int j = 0; j < 3; ++j) p.origin[j] = (float)a->vox_origin[j];
+    p.X = a->X; p.Y = a->Y; p.Z = a->Z; p.img_w = a->img_w; p.img_h = a->img_h;
+    p.N = N;
+    const long bv = (long)a->batch * a->n_views;
+    occd::ProfScope prof("vox2pix", (hipStream_t)stream, 0.0, (double)bv * N * (a->pix_z ? 21.0 : 17.0));
+    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)bv);
+    if (N % 4 == 0 && !(reinterpret_cast<uintptr_t>(a->fov) & 3))
+        hipLaunchKernelGGL(vox2pix_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(vox2pix_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return occd::check_launch();
 }

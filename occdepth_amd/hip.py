@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 MAX_VIEWS = 4
 MAX_SCALES = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 16   # 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+ABI_VERSION = 17   # 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
 
 _c_float_p = POINTER(c_float)
 
@@ -81,7 +81,7 @@ class LiftArgs(Structure):
 class LiftProjArgs(Structure):
     _fields_ = [("lift", LiftArgs), ("cam_E", c_void_p), ("cam_k", c_void_p), ("voxel_size", ctypes.c_double),
                 ("origin", c_float * 3),
-                ("img_w", c_int32), ("img_h", c_int32), ("frustum", FlospArgs)]
+                ("img_w", c_int32), ("img_h", c_int32), ("frustum", FlospArgs), ("ida", c_void_p)]
 
 
 class FlospBwdArgs(Structure):
@@ -137,6 +137,12 @@ class FrustumArgs(Structure):
     _fields_ = [("cam_E", c_void_p), ("cam_k", c_void_p), ("target", c_void_p), ("masks", c_void_p), ("dists", c_void_p),
                 ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
         [(n, c_int32) for n in ("batch", "n_views", "X", "Y", "Z", "img_w", "img_h", "frustum_size", "n_classes")]
+
+
+class Vox2PixArgs(Structure):
+    _fields_ = [("cam_E", c_void_p), ("cam_k", c_void_p), ("ida", c_void_p), ("pix", c_void_p), ("fov", c_void_p),
+                ("pix_z", c_void_p), ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
+        [(n, c_int32) for n in ("batch", "n_views", "X", "Y", "Z", "img_w", "img_h")]
 
 
 class ProfRow(Structure):
@@ -278,6 +284,7 @@ EXPORTS = {
     "occd_se_gate_set_fused": (c_int32, [c_int32]),
     "occd_graph_replace_memsets": (c_int32, [c_void_p]),
     "occd_frustum_targets": (c_int32, [POINTER(FrustumArgs), c_void_p]),
+    "occd_vox2pix": (c_int32, [POINTER(Vox2PixArgs), c_void_p]),
     "occd_downsample_label": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "occd_cp_mega_matrix": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "occd_prof_set_tag": (c_int32, [c_char_p]),
@@ -1231,18 +1238,26 @@ def bottleneck3d(x, w, P, dilation, out=None):
     return out
 
 
+def _check_calibration(B, V, cam_E, cam_k, ida=None):
+    for t, shape, what, dt in ((cam_E, (4, 4), "cam_E", torch.float64), (cam_k, (3, 3), "cam_k", torch.float64),
+                               (ida, (4, 4), "ida", torch.float32)):
+        if t is None and what == "ida":
+            continue
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, V) + shape:
+            raise RuntimeError(f"{what} must be a contiguous (batch, views, {shape[0]}, {shape[1]}) {dt} GPU tensor")
+
+
 def lift_proj(feats, scale_divs, cam_E, cam_k, origin, voxel_size, img_wh, n_dims, row_strides, out, frustum=None,
-              scale_const=100.0, xcd_mode=None):
+              scale_const=100.0, xcd_mode=None, ida=None):
     """The eval lift without its tables (occd_lift_proj_fwd): cam_E (B, V, 4, 4) / cam_k (B, V, 3, 3) float64 device
     tensors (the batch's extrinsics and intrinsics), the voxel grid n_dims = (X, Y, Z) of `voxel_size` metres from
-    `origin`; frustum: a `Frustum` or None."""
+    `origin`; frustum: a `Frustum` or None; ida: the batch's (B, V, 4, 4) float32 device ida_mats or None -- a view with
+    ida[b, v, 0, 0] < 0 gathers its in-FOV pixels at x' = W - 1 - x (the reference's left-right flip)."""
     q = LiftProjArgs()
     _lift_args(q.lift, feats, scale_divs, None, None, n_dims, row_strides, out, None, scale_const, xcd_mode)
-    for t, shape, what in ((cam_E, (4, 4), "cam_E"), (cam_k, (3, 3), "cam_k")):
-        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or \
-                tuple(t.shape) != (q.lift.batch, q.lift.n_views) + shape:
-            raise RuntimeError(f"{what} must be a contiguous (batch, views, {shape[0]}, {shape[1]}) float64 GPU tensor")
+    _check_calibration(q.lift.batch, q.lift.n_views, cam_E, cam_k, ida)
     q.cam_E, q.cam_k = cam_E.data_ptr(), cam_k.data_ptr()
+    q.ida = ida.data_ptr() if ida is not None else None
     q.voxel_size = float(voxel_size)
     for j in range(3):
         q.origin[j] = float(origin[j])
@@ -1941,6 +1956,37 @@ def project_voxels(cam_E, cam_k, vox_origin, voxel_size, grid_dims, img_w, img_h
     _check(load().occd_project_voxels(e.ctypes.data, k.ctypes.data, o.ctypes.data, float(voxel_size), X, Y, Z,
                                       int(img_w), int(img_h), _ptr(pix, "pix"), _ptr(fov.view(torch.uint8), "fov"),
                                       _ptr(z, "pix_z") if z is not None else None, _stream()), "occd_project_voxels")
+    return (pix, fov, z) if with_z else (pix, fov)
+
+
+def vox2pix(cam_E, cam_k, ida, vox_origin, voxel_size, dims, img_wh, with_z=False):
+    """The reference dataset's voxel -> pixel tables for a whole batch, on the GPU (occd_vox2pix, pattern 0): cam_E
+    (B, V, 4, 4) / cam_k (B, V, 3, 3) float64 and ida (B, V, 4, 4) float32 (or None: no flip) device tensors, the grid
+    dims = (X, Y, Z) of `voxel_size` metres from `vox_origin`, an image of img_wh = (W, H).  Returns projected_pix
+    (B, V, N, 1, 2) int64 and fov_mask (B, V, N, 1) bool [, pix_z (B, V, N) float32]: per (b, v) exactly
+    `project_voxels`, then x' = W - 1 - x for every voxel of a view with ida[b, v, 0, 0] < 0 (kitti_dataset.py:388).
+    Capture-safe: the flip flag is read on the device."""
+    if cam_E.dim() != 4:
+        raise RuntimeError("cam_E must be (batch, views, 4, 4)")
+    B, V = (int(d) for d in cam_E.shape[:2])
+    _check_calibration(B, V, cam_E, cam_k, ida)
+    X, Y, Z = (int(d) for d in dims)
+    n = X * Y * Z
+    dev = cam_E.device
+    pix = torch.empty((B, V, n, 1, 2), dtype=torch.int64, device=dev)
+    fov = torch.empty((B, V, n, 1), dtype=torch.bool, device=dev)
+    z = torch.empty((B, V, n), dtype=torch.float32, device=dev) if with_z else None
+    a = Vox2PixArgs()
+    a.cam_E, a.cam_k = cam_E.data_ptr(), cam_k.data_ptr()
+    a.ida = ida.data_ptr() if ida is not None else None
+    a.pix, a.fov = pix.data_ptr(), fov.data_ptr()
+    a.pix_z = z.data_ptr() if z is not None else None
+    for j, o in enumerate(vox_origin):
+        a.vox_origin[j] = float(o)
+    a.voxel_size = float(voxel_size)
+    a.batch, a.n_views, a.X, a.Y, a.Z = B, V, X, Y, Z
+    a.img_w, a.img_h = int(img_wh[0]), int(img_wh[1])
+    _check(load().occd_vox2pix(ctypes.byref(a), _stream()), "occd_vox2pix")
     return (pix, fov, z) if with_z else (pix, fov)
 
 

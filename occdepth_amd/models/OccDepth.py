@@ -99,6 +99,16 @@ class OccDepth(_Base):
         if self.gpu_targets is True:
             from ..targets import defer_dataset_targets
             self._dataset_hook = defer_dataset_targets()
+        # OCCDEPTH_GPU_PROJECTION=1: also take the voxel -> pixel tables out of the loader (targets.defer_dataset_projection
+        # stubs its vox2pix); a batch without tables is projected on the GPU (occd_vox2pix), in training as in eval.  The
+        # stub also silences compute_local_frustums, so the frustum targets must then come from the GPU builders.
+        self._projection_hook = None
+        if env("OCCDEPTH_GPU_PROJECTION", "0") == "1":
+            if self.gpu_targets is False:
+                raise ValueError("OCCDEPTH_GPU_PROJECTION=1 stubs the loader's compute_local_frustums: it needs the GPU "
+                                 "training targets (OCCDEPTH_GPU_TARGETS=auto or 1), not OCCDEPTH_GPU_TARGETS=0")
+            from ..targets import defer_dataset_projection
+            self._projection_hook = defer_dataset_projection()
         if infer_mode:
             self.context_prior = False
         assert not (config.use_stereo_depth_gt and config.use_lidar_depth_gt), "only with one depth data supported."
@@ -367,12 +377,40 @@ class OccDepth(_Base):
     # OCCDEPTH_LIFT_PROJ = auto | 1 | 0.
     lift_in_kernel = {"1": True, "0": False}.get(os.environ.get("OCCDEPTH_LIFT_PROJ", "auto"), "auto")
 
+    @staticmethod
+    def _tables_absent(batch, key):
+        """A batch brings no `key` entry (a voxel -> pixel table or a training target) when the key is missing, the list
+        is empty, or every entry has zero elements (what a loader hooked by targets.defer_dataset_projection /
+        defer_dataset_targets delivers)."""
+        v = batch.get(key)
+        if v is None:
+            return True
+        if torch.is_tensor(v):
+            return v.numel() == 0
+        return all(torch.is_tensor(t) and t.numel() == 0 for t in v)
+
+    @staticmethod
+    def _flip_mats(batch, E):
+        """The batch's ida_mats as a (B, V, 4, 4) float32 tensor on E's device for the projection's flip flag
+        (ida[b, v, 0, 0] < 0), or None without them.  Host matrices without a flip give None (nothing to read)."""
+        ida = batch.get("ida_mats")
+        if ida is None:
+            return None
+        t = torch.stack(list(ida)) if isinstance(ida, (list, tuple)) else ida
+        if not t.is_cuda and not bool((t[..., 0, 0] < 0).any()):
+            return None
+        t = t.to(E.device, torch.float32).contiguous()
+        if tuple(t.shape) != tuple(E.shape[:2]) + (4, 4):
+            raise ValueError("ida_mats must be (batch, views, 4, 4) like the extrinsics, got %s" % (tuple(t.shape),))
+        return t
+
     def _lift_calibration(self, batch, img, key):
-        """(cam_E (B, V, 4, 4), cam_k (B, V, 3, 3)) float64 device tensors for hip.lift_proj, or None when the in-kernel
-        projection does not apply (NYU geometry, multi-point patterns, tables present and not vouched for)."""
+        """(cam_E (B, V, 4, 4), cam_k (B, V, 3, 3)) float64 and ida (B, V, 4, 4) float32 (or None) device tensors for
+        hip.lift_proj, or None when the in-kernel projection does not apply (NYU geometry, multi-point patterns, tables
+        present and not vouched for)."""
         if not self.lift_in_kernel or self.dataset != "kitti" or "cam_k" not in batch:
             return None
-        have_tables = key in batch
+        have_tables = not self._tables_absent(batch, key)
         if have_tables and (self.lift_in_kernel != True or "T_velo_2_cam_f64" not in batch):   # noqa: E712 ("auto" is truthy)
             return None
         ext = batch.get("T_velo_2_cam_f64", batch.get("T_velo_2_cam"))
@@ -388,7 +426,7 @@ class OccDepth(_Base):
         k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64)
         if E.shape[:2] != img.shape[:2] or E.shape[1] > 2 or k.shape[:2] != E.shape[:2]:
             return None
-        return E.contiguous(), k.contiguous()
+        return E.contiguous(), k.contiguous(), self._flip_mats(batch, E)
 
     def _forward_2d_to_3d(self, batch, x_rgb, img, bs, vox_origin):
         """eval: returns (Vox, depth_pred); training: ((B, C, X, Y, Z) tensor, depth_pred)."""
@@ -411,24 +449,24 @@ class OccDepth(_Base):
                 H, W = img.shape[-2:]
                 vox = lift_scales_proj(feats, scales, cam[0], cam[1], self._kitti_origin(batch), 0.2 * self.project_scale, (W, H),
                                        self.projects[str(scales[0])].scene_size, self.project_scale, self.dataset,
-                                       frustum=frustum, scale_const=100.0)
+                                       frustum=frustum, scale_const=100.0, ida=cam[2])
                 return vox, depth_pred
         if self.trans_2d_to_3d == "flosp_depth":
             depth_vol, depth_pred = self._depth_volume(batch, x_rgb, vox_origin)
+        if self._tables_absent(batch, key):
+            # the loader shipped no tables (or the zero-size stubs of targets.defer_dataset_projection): build them here,
+            # on the device, flip included -- in training too, and inside a captured step
+            pix_all, fov_all = self.project_voxels_on_gpu(batch, img)
+        else:
+            pix_all = torch.stack([p.to(device) for p in batch[key]])
+            fov_all = torch.stack([m.to(device) for m in batch[mkey]])
         if not needs_autograd(self):
-            if key in batch:
-                pix = torch.stack([p.to(device) for p in batch[key]])
-                fov = torch.stack([m.to(device) for m in batch[mkey]])
-            else:
-                pix, fov = self.project_voxels_on_gpu(batch, img)
             feats = [[x_rgb[v]["1_" + str(s)] for v in range(len(x_rgb))] for s in scales]
             flat = depth_vol.reshape(bs, -1).contiguous() if depth_vol is not None else None
-            vox = lift_scales(feats, scales, pix, fov, self.projects[str(scales[0])].scene_size,
+            vox = lift_scales(feats, scales, pix_all, fov_all, self.projects[str(scales[0])].scene_size,
                               self.project_scale, self.dataset, depth_scale=flat, scale_const=100.0)
             return vox, depth_pred
         from .. import lift_autograd
-        pix_all = torch.stack([p.to(device) for p in batch[key]])
-        fov_all = torch.stack([m.to(device) for m in batch[mkey]])
         feats = [[x_rgb[v]["1_" + str(s)] for v in range(len(x_rgb))] for s in scales]
         if self.fused_lift and lift_autograd.usable(feats, pix_all) and self.dataset == "kitti":
             # training on the GPU, single-point patterns: the fused HIP lift with its one-launch backward
@@ -482,25 +520,28 @@ class OccDepth(_Base):
 
     def project_voxels_on_gpu(self, batch, img):
         """when the batch carries no `projected_pix_{s}` / `fov_mask_{s}` (the dataloader's
-        numba `vox2pix`, kitti_dataset.py:253-273), compute them on the GPU from the calibration
-        (SemanticKITTI geometry: vox_origin (0, -25.6, -2), 0.2 m voxels x project_scale, pattern_id 0)."""
+        numba `vox2pix`, kitti_dataset.py:253-273), compute them on the GPU from the calibration (SemanticKITTI geometry:
+        vox_origin (0, -25.6, -2), 0.2 m voxels x project_scale, pattern_id 0) in ONE launch (hip.vox2pix): device
+        calibration, no host sync, capture-safe.  Views flipped by the loader (ida_mats[..., 0, 0] < 0) get the flipped
+        tables of kitti_dataset.py:384-390.  -> (B, V, N, 1, 2) int64, (B, V, N, 1) bool."""
         from .. import hip
         if self.dataset != "kitti":
-            raise NotImplementedError("on-GPU voxel projection is wired for the SemanticKITTI geometry only")
+            raise NotImplementedError("on-GPU voxel projection is wired for the SemanticKITTI geometry only; a %s batch "
+                                      "must bring projected_pix_%s / fov_mask_%s" % (self.dataset, self.project_scale,
+                                                                                    self.project_scale))
+        if not img.is_cuda:
+            raise RuntimeError("the voxel -> pixel tables are built on the GPU only (occd_vox2pix); a CPU batch must bring "
+                               "projected_pix_%s / fov_mask_%s" % (self.project_scale, self.project_scale))
         ps = self.project_scale
         dims = tuple(int(s) // ps for s in self.full_scene_size)
         H, W = img.shape[-2:]
-        pix, fov = [], []
-        for i in range(img.shape[0]):
-            # the dataloader projects with the calibration file's float64 extrinsics; the batch only carries their
-            # float32 copy.  `T_velo_2_cam_f64`, when present, reproduces the dataloader's tables bit for bit.
-            ext = batch.get("T_velo_2_cam_f64", batch["T_velo_2_cam"])
-            views = [hip.project_voxels(ext[i][v].detach().cpu().double().numpy(),
-                                        batch["cam_k"][i][v].detach().cpu().double().numpy(), self._kitti_origin(batch),
-                                        0.2 * ps, dims, W, H, device=img.device) for v in range(img.shape[1])]
-            pix.append(torch.stack([p for p, _ in views]))
-            fov.append(torch.stack([m for _, m in views]))
-        return torch.stack(pix), torch.stack(fov)
+        dev = img.device
+        # the dataloader projects with the calibration file's float64 extrinsics; the batch only carries their float32
+        # copy.  `T_velo_2_cam_f64`, when present, reproduces the dataloader's tables bit for bit.
+        ext = batch.get("T_velo_2_cam_f64", batch["T_velo_2_cam"])
+        E = torch.stack([e.to(dev) for e in ext]).to(torch.float64).contiguous()
+        k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64).contiguous()
+        return hip.vox2pix(E, k, self._flip_mats(batch, E), self._kitti_origin(batch), 0.2 * ps, dims, (int(W), int(H)))
 
     # ---------------------------------------------------------------- whole-forward hipGraph
     @staticmethod
@@ -708,12 +749,7 @@ class OccDepth(_Base):
             return True
         if self.gpu_targets is False:
             return False
-        v = batch.get(key)
-        if v is None:
-            return True
-        if torch.is_tensor(v):
-            return v.numel() == 0
-        return all(torch.is_tensor(t) and t.numel() == 0 for t in v)       # also True for an empty list
+        return self._tables_absent(batch, key)
 
     def frustum_targets_on_gpu(self, batch, target):
         """(frustums_masks (B, F, X, Y, Z) bool, frustums_class_dists (B, F, C) float32) of kitti_dataset.py:315-333, built

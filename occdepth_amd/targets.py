@@ -150,9 +150,36 @@ def defer_dataset_targets(module=None):
             module = importlib.import_module(KITTI_DATASET_MODULE)
         except Exception:
             return DatasetTargetsHook(None, {})
+    return _rebind(module, (("compute_local_frustums", _no_frustums), ("compute_CP_mega_matrix", _no_cp_matrix)))
+
+
+def _rebind(module, stubs):
     saved = {}
-    for name, stub in (("compute_local_frustums", _no_frustums), ("compute_CP_mega_matrix", _no_cp_matrix)):
+    for name, stub in stubs:
         if hasattr(module, name) and getattr(module, name) is not stub:
             saved[name] = getattr(module, name)
             setattr(module, name, stub)
     return DatasetTargetsHook(module, saved)
+
+
+def _no_vox2pix(*args, **kwargs):
+    """Stands in for vox2pix (helpers.py:94-169): zero-size tables of the real ranks and dtypes -- projected_pix (0, 1, 2)
+    int64, fov_mask (0, 1) bool, pix_z (0,) float64 -- which survive the dataset's flip line (kitti_dataset.py:388) and
+    the collate's torch.from_numpy; OccDepth treats zero-element tables as absent and projects on the GPU."""
+    return np.zeros((0, 1, 2), dtype=np.int64), np.zeros((0, 1), dtype=bool), np.zeros((0,), dtype=np.float64)
+
+
+def defer_dataset_projection(module=None):
+    """Rebind `vox2pix` and `compute_local_frustums` inside the reference's SemanticKITTI dataset module (when importable;
+    or `module`) to stubs, so its workers stop building and shipping the voxel -> pixel tables (about 80 MB per sample at
+    config 2); `OccDepth` then builds them on the GPU (occd_vox2pix, flip included).  compute_local_frustums reads those
+    tables, so it is stubbed as in `defer_dataset_targets` and the frustum targets come from the GPU builders
+    (OCCDEPTH_GPU_TARGETS must not be 0).  Returns a DatasetTargetsHook (undo, context manager; inactive when the module
+    cannot be imported).  The same process / fork caveats as `defer_dataset_targets` apply; OCCDEPTH_GPU_PROJECTION=1
+    installs it when the model is constructed."""
+    if module is None:
+        try:
+            module = importlib.import_module(KITTI_DATASET_MODULE)
+        except Exception:
+            return DatasetTargetsHook(None, {})
+    return _rebind(module, (("vox2pix", _no_vox2pix), ("compute_local_frustums", _no_frustums)))

@@ -43,7 +43,8 @@ extern "C" {
 
 /* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk;
  * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix;
- * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida). */
+ * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida;
+ * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -889,6 +890,58 @@ int occd_downsample_label(const uint8_t* in, uint8_t* out, int32_t batch, int32_
  * labelled 255 are zero.  Every byte of `out` is written. */
 int occd_cp_mega_matrix(const uint8_t* coarse, uint8_t* out, int32_t batch, int32_t X, int32_t Y, int32_t Z,
                         int32_t binary, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Global gradient-norm clipping fused with the AdamW update (csrc/optim.hip): the "grad-clip 35 -> AdamW" stage of the
+ * reference's training step (`gradient_clip_val: 35` in every yaml under occdepth/config/, handed to the Trainer at
+ * occdepth/scripts/train.py:188,204 = torch.nn.utils.clip_grad_norm_(params, 35) before torch.optim.AdamW.step()).
+ * Multi-tensor, float32 only: the kernels walk a table of chunk descriptors, one workgroup per descriptor, so any number
+ * of parameter tensors costs three launches.  A tensor of n elements contributes max(1, ceil(n / OCCD_OPTIM_CHUNK))
+ * consecutive descriptors (offset 0, CHUNK, 2 CHUNK, ...); tensors may start at any 4-byte alignment.
+ *
+ * The table is read BY THE KERNELS and must stay valid and unchanged for as long as a launch -- or a captured graph
+ * that holds one -- can run: device memory, or pinned host memory the device can address (hipHostMalloc; the kernels
+ * then fetch one 64-byte descriptor per workgroup across the bus, and no copy node enters a capture).  Pageable host
+ * memory is rejected.
+ *
+ *   occd_grad_sumsq   2 launches: per-chunk sum of squares of the gradients, accumulated in float64 into
+ *                     partials[chunk]; then one workgroup adds the partials in a fixed order and writes
+ *                       norm_out[0] = total_norm = sqrt(sum)                         (float32)
+ *                       norm_out[1] = clip_coef  = min(1, max_norm / (total_norm + 1e-6)), NaN if the norm is NaN, 0 if Inf
+ *                     No atomics, no counters, nothing to zero: bit-identical from run to run.
+ *   occd_clip_adamw   the same two launches -- the workgroup of every tensor's first chunk also advances that tensor's
+ *                     `step` by one -- and the update, one read of p, g, m, v and one write of p, m, v per element:
+ *                       g' = clip_coef g (in registers: the gradient in memory stays unscaled)
+ *                       p *= 1 - lr wd;  m = m + (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g'^2
+ *                       p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *                     torch.optim.AdamW's arithmetic in its order, evaluated in float64 and rounded once per stored value.
+ * lr is read from the device scalar `lr_dev` when it is not NULL (a scheduler's change reaches a captured launch),
+ * else from `lr`. */
+#define OCCD_OPTIM_CHUNK 8192
+typedef struct occd_optim_chunk {      /* 64 bytes: one fetch per workgroup                                          */
+    float* p;                          /* parameter tensor (first element)                                           */
+    const float* g;                    /* its gradient                                                               */
+    float* m;                          /* exp_avg                                                                    */
+    float* v;                          /* exp_avg_sq                                                                 */
+    float* step;                       /* the parameter's step counter, device float32 scalar                        */
+    int64_t offset;                    /* first element of this chunk inside the tensor                              */
+    int32_t count;                     /* elements of this chunk, 0 .. OCCD_OPTIM_CHUNK (0: an empty tensor)         */
+    int32_t reserved0;
+    int64_t reserved1;
+} occd_optim_chunk;
+
+typedef struct occd_clip_adamw_args {
+    const occd_optim_chunk* chunks;    /* n_chunks descriptors, see above                                            */
+    double* partials;                  /* n_chunks float64, device workspace                                         */
+    float* norm_out;                   /* 2 device floats: total_norm, clip_coef                                     */
+    const float* lr_dev;               /* device scalar learning rate, or NULL                                       */
+    int64_t n_chunks;
+    int64_t n_elems;                   /* elements over all chunks (profiling only)                                  */
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_norm;                   /* > 0                                                                        */
+} occd_clip_adamw_args;
+int occd_grad_sumsq(const occd_clip_adamw_args* a, void* stream);
+int occd_clip_adamw(const occd_clip_adamw_args* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Small-message all-reduce over peer-mapped device memory (round 5; csrc/ipc_allreduce.hip): the latency-optimal form

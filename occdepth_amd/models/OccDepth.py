@@ -79,11 +79,12 @@ class OccDepth(_Base):
         # training fast path, OFF by default (the default `training_step` returns the loss and the Trainer runs backward and
         # the optimizer, as in the reference).  `enable_fast_train()` -- or OCCDEPTH_FAST_TRAIN=1 in the environment of an
         # unmodified scripts/train.py run -- switches the module to manual optimisation: `training_step` then replays the
-        # WHOLE step (forward, losses, backward, gradient exchange, AdamW) from one hipGraph (train_graph.GraphedTrainStep,
+        # WHOLE step (forward, losses, backward, gradient exchange, [gradient-norm clip +] AdamW) from one hipGraph (train_graph.GraphedTrainStep,
         # the step bench.py --train times).  OCCDEPTH_FAST_TRAIN_BF16=1: the bf16-MFMA convolution mode of configs[3].
         self._fast_train = None
         self._opt = self._sched = None
         self.fast_train = False
+        self.fast_train_grad_clip = None
         if env("OCCDEPTH_FAST_TRAIN", "0") == "1":
             self.enable_fast_train(bf16=env("OCCDEPTH_FAST_TRAIN_BF16", "0") == "1")
         self.fused_lift = True    # training on the GPU: HIP lift + one-launch backward (lift_autograd.py) where it applies
@@ -200,10 +201,13 @@ class OccDepth(_Base):
         self._drop_graphs()
         return self
 
-    def enable_fast_train(self, bf16=False, autocast=False):
+    def enable_fast_train(self, bf16=False, autocast=False, grad_clip=None):
         """Manual optimisation + the whole training step as ONE replayed hipGraph (see `_fast_training_step`).  Call before
-        `trainer.fit` (Lightning reads `automatic_optimization` when the loop starts)."""
+        `trainer.fit` (Lightning reads `automatic_optimization` when the loop starts).  `grad_clip`: global gradient-norm
+        clip for callers without a Trainer (0 = none); left at None, the attached Trainer's `gradient_clip_val` is used
+        (`_grad_clip_value`) -- under manual optimisation Lightning itself no longer clips."""
         self.fast_train = True
+        self.fast_train_grad_clip = grad_clip
         self.fast_train_bf16, self.fast_train_autocast = bool(bf16), bool(autocast)
         self.automatic_optimization = False
         self._fast_train = None
@@ -826,6 +830,27 @@ class OccDepth(_Base):
         opt = opts[0] if isinstance(opts, (list, tuple)) else opts
         return getattr(opt, "optimizer", opt)
 
+    def _grad_clip_value(self):
+        """The global gradient-norm clip of the fast training step, first hit wins: `enable_fast_train(grad_clip=...)`, then
+        the attached Trainer's `gradient_clip_val` (every reference yaml: 35, scripts/train.py:188,204) -- with
+        `automatic_optimization = False` Lightning 1.4.9 skips its own clipping together with backward and optimizer.step.
+        None or 0: no clipping.  Clipping by value is not implemented and raises instead of being ignored."""
+        from .. import optim
+        if self.fast_train_grad_clip is not None:
+            return self.fast_train_grad_clip if optim.clipping_enabled(self.fast_train_grad_clip) else None
+        try:
+            trainer = getattr(self, "trainer", None)
+        except RuntimeError:                                 # newer Lightning: the property raises while no Trainer is attached
+            trainer = None
+        val = getattr(trainer, "gradient_clip_val", None)
+        if trainer is None or not optim.clipping_enabled(val):
+            return None
+        algo = getattr(trainer, "gradient_clip_algorithm", None)
+        if str(getattr(algo, "value", algo)).lower() == "value":
+            raise NotImplementedError("occdepth_amd: the fast training step clips gradients by global norm only "
+                                      "(Trainer(gradient_clip_algorithm='value') is not implemented)")
+        return float(val)
+
     def _fast_training_step(self, batch, batch_idx):
         """`training_step` under manual optimisation (`automatic_optimization = False`: Lightning 1.4.9 then calls neither
         backward nor optimizer.step, models/OccDepth.py:535-541 + scripts/train.py:208 otherwise drive them eagerly).
@@ -854,7 +879,7 @@ class OccDepth(_Base):
                 if self.fast_train_bf16:
                     autograd3d.set_bf16_mfma(True)
                 gs = train_graph.GraphedTrainStep(self, opt, static, bf16=self.fast_train_autocast, buckets=st["buckets"],
-                                                  warmup=2, batch_idx=batch_idx)
+                                                  warmup=2, batch_idx=batch_idx, grad_clip=self._grad_clip_value())
                 self.__dict__["_in_fast_step"] = True
                 try:
                     ok = gs.capture()
@@ -887,7 +912,8 @@ class OccDepth(_Base):
         return loss.detach()
 
     def _manual_eager_step(self, batch, batch_idx, opt, buckets=None):
-        """One manual-optimisation step without a graph: zero_grad, training_step, backward, [gradient average], optimizer."""
+        """One manual-optimisation step without a graph: zero_grad, training_step, backward, [gradient average], optimizer
+        -- with a clip value set (`_grad_clip_value`), `optim.clip_adamw_step`: clip_grad_norm_ + AdamW, norm logged."""
         if buckets is not None:
             buckets.zero_grad()
         else:
@@ -897,7 +923,12 @@ class OccDepth(_Base):
         loss.backward()
         if buckets is not None:
             buckets.finish()
-        opt.step()
+        clip = self._grad_clip_value()
+        if clip is None:
+            opt.step()
+        else:
+            from .. import optim
+            self._log("train/grad_norm", optim.clip_adamw_step(opt, clip))
         return loss
 
     def on_train_epoch_start(self, *args, **kwargs):

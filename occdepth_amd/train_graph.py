@@ -1,5 +1,5 @@
 """Whole-step hipGraph for training: forward + every loss term + backward + gradient exchange +
-optimizer update captured ONCE and replayed per step.
+optimizer update (with `grad_clip`: global-norm clipping fused into it, optim.py) captured ONCE and replayed per step.
 
 A config-2 training step is ~9600 kernel launches, most of them 4-6 us long (BatchNorm pieces, the elementwise glue of
 55 MBConv blocks x 2 views, gradient accumulation): the eager step is HOST-bound (GPU busy 189 ms of a 213 ms step,
@@ -118,8 +118,15 @@ def find_syncs():
 
 
 class GraphedTrainStep:
-    def __init__(self, model, opt, batch, bf16=False, buckets=None, warmup=3, batch_idx=0):
+    """`grad_clip`: the Trainer's `gradient_clip_val` (global 2-norm, every reference yaml sets 35).  None or 0: the step
+    ends in `opt.step()`.  Otherwise it ends in `optim.clip_adamw_step` -- the norm of the (averaged) gradients, the clip
+    coefficient and the AdamW update in three HIP launches -- and publishes the norm as the device scalar
+    `model.logged["train/grad_norm"]`, which replays keep up to date."""
+
+    def __init__(self, model, opt, batch, bf16=False, buckets=None, warmup=3, batch_idx=0, grad_clip=None):
         self.model, self.opt, self.batch, self.bf16, self.buckets, self.batch_idx = model, opt, batch, bf16, buckets, batch_idx
+        self.grad_clip = grad_clip
+        self._optim_tables = None
         make_capturable(opt)
         self.graph = None
         self.loss = None
@@ -137,8 +144,18 @@ class GraphedTrainStep:
         loss.backward()
         if self.buckets is not None:
             self.buckets.finish()
-        self.opt.step()
+        self._optimizer_step()
         return loss
+
+    def _optimizer_step(self):
+        from . import optim
+        if not optim.clipping_enabled(self.grad_clip):
+            self.opt.step()
+            return
+        norm = optim.clip_adamw_step(self.opt, self.grad_clip)       # after the gradient average: the norm DDP would clip
+        logged = getattr(self.model, "logged", None)
+        if isinstance(logged, dict):
+            logged["train/grad_norm"] = norm.detach()
 
     def _sync_decay(self):
         """`sem_step_decay_loss`: the decay factor is a function of the host counter `cur_batch`; the captured step reads
@@ -166,6 +183,9 @@ class GraphedTrainStep:
         graph = new_graph()
         if self.buckets is None:
             self.opt.zero_grad(set_to_none=True)            # gradients are (re)allocated inside the graph's pool
+        if self.grad_clip:
+            from . import optim
+            optim.prepare_capture(self.opt)                 # new gradient pointers -> a new descriptor table, built under capture
         ok = True
         try:
             with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
@@ -179,6 +199,8 @@ class GraphedTrainStep:
         torch.cuda.synchronize(dev)
         if ok:
             self.graph = graph
+            if self.grad_clip:
+                self._optim_tables = optim.live_tables(self.opt)    # what the captured launches read lives as long as the graph
         return ok
 
     recapture = capture

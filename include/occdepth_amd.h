@@ -44,7 +44,8 @@ extern "C" {
 /* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk;
  * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix;
  * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida;
- * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw). */
+ * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw;
+ * 19: occd_kitti_labels). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -890,6 +891,22 @@ int occd_downsample_label(const uint8_t* in, uint8_t* out, int32_t batch, int32_
  * labelled 255 are zero.  Every byte of `out` is written. */
 int occd_cp_mega_matrix(const uint8_t* coarse, uint8_t* out, int32_t batch, int32_t X, int32_t Y, int32_t Z,
                         int32_t binary, void* stream);
+
+/* The label decode of the reference's SemanticKITTI preprocessing pass (occdepth/data/semantic_kitti/preprocess.py:76-84
+ * over io_data.py:10-22,122-134,175-195) and the `.occluded` volume of kitti_dataset.py:312-313, for a whole batch of raw
+ * voxel files:
+ *   raw           (B, N) uint16, the `.label` file: N = X*Y*Z voxels in (X, Y, Z) row-major order; 2-byte aligned is enough
+ *   invalid_bits  (B, N/8) uint8, the `.invalid` file: voxel 8k + j is bit 7 - j of byte k (io_data.unpack, MSB first)
+ *   occluded_bits optional, the `.occluded` file, packed the same way; given exactly when `occluded` is
+ *   lut           uint8[lut_len], 1 <= lut_len <= 4096 (io_data.get_remap_lut: 359 entries)
+ *   target[b, n]   = invalid bit set or raw >= lut_len ? 255 : lut[raw[b, n]]                    (B, N) uint8, 8-byte aligned
+ *   occluded[b, n] = the occluded bit, 0 or 1                                                   (B, N) uint8, 8-byte aligned
+ *   *out_of_range  = #{(b, n) : raw[b, n] >= lut_len} (the reference raises IndexError there); device int32, set by every
+ *                    call (a fill kernel, not a memset node), never read back here.
+ * N must be a multiple of 8.  Nothing is allocated and nothing synchronises: capture-safe. */
+int occd_kitti_labels(const uint16_t* raw, const uint8_t* invalid_bits, const uint8_t* occluded_bits, const uint8_t* lut,
+                      int32_t lut_len, uint8_t* target, uint8_t* occluded, int32_t* out_of_range, int32_t batch, int64_t N,
+                      void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Global gradient-norm clipping fused with the AdamW update (csrc/optim.hip): the "grad-clip 35 -> AdamW" stage of the

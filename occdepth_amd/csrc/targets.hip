@@ -3,6 +3,8 @@
 //   frustum_targets_kernel   compute_local_frustums   occdepth/data/utils/helpers.py:183-260 (dataset "kitti")
 //   downsample_label_kernel  _downsample_label        occdepth/data/NYU/preprocess.py:102-143
 //   cp_mega_kernel           compute_CP_mega_matrix   occdepth/data/utils/helpers.py:6-91
+//   kitti_labels_kernel      the label decode of       occdepth/data/semantic_kitti/preprocess.py:76-84 (io_data.py:10-22,
+//                            the preprocessing pass    122-134,175-195) and the `.occluded` volume of kitti_dataset.py:312-313
 //
 // All three are bit-exact: projection through occd::project_one (the integers of the dataloader's vox2pix), frustum
 // bounds compared in float64 as numpy does, integer counters (LDS histograms flushed with integer atomics: deterministic).
@@ -297,6 +299,49 @@ __global__ void __launch_bounds__(256) cp_mega_kernel(const uint8_t* __restrict_
     }
 }
 
+// Raw SemanticKITTI voxel files -> labels.  The batch is one flat run of groups of 8 voxels (N % 8 == 0, so no group
+// straddles two samples): a lane reads the group's 8 uint16 labels (16 bytes; the address may be only 2-byte aligned, so
+// the load goes through memcpy and the compiler picks the instruction), one byte of each bit mask (MSB first: voxel 8g + j
+// is bit 7 - j, io_data.unpack) and stores 8 label bytes, and 8 bytes of 0 / 1 when the occluded mask is given.  The LUT
+// sits in LDS.  Raw values >= lut_len become 255 and are counted (the counter is zeroed by frustum_zero_kernel first).
+constexpr int kMaxLut = 4096;
+
+__global__ void __launch_bounds__(256) kitti_labels_kernel(const uint16_t* __restrict__ raw,
+                                                           const uint8_t* __restrict__ invalid_bits,
+                                                           const uint8_t* __restrict__ occluded_bits,
+                                                           const uint8_t* __restrict__ lut, int lut_len,
+                                                           uint2* __restrict__ target, uint2* __restrict__ occluded,
+                                                           uint32_t* __restrict__ bad, long groups) {
+    __shared__ uint8_t s_lut[kMaxLut];
+    for (int i = threadIdx.x; i < lut_len; i += 256) s_lut[i] = lut[i];
+    __syncthreads();
+    uint32_t nbad = 0u;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+        uint16_t v[8];
+        __builtin_memcpy(v, raw + g * 8, 16);
+        const uint32_t inv = invalid_bits[g];
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t r = v[j];
+            const bool known = r < (uint32_t)lut_len;
+            uint32_t lab = s_lut[known ? r : 0u];
+            nbad += known ? 0u : 1u;
+            if (!known || ((inv >> (7 - j)) & 1u)) lab = 255u;
+            w[j >> 2] |= lab << ((j & 3) * 8);
+        }
+        target[g] = make_uint2(w[0], w[1]);
+        if (occluded_bits) {
+            const uint32_t occ = occluded_bits[g];
+            uint32_t o[2] = {0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j >> 2] |= ((occ >> (7 - j)) & 1u) << ((j & 3) * 8);
+            occluded[g] = make_uint2(o[0], o[1]);
+        }
+    }
+    if (nbad) atomicAdd(bad, nbad);
+}
+
 }  // namespace
 
 extern "C" int occd_frustum_targets(const occd_frustum_args* a, void* stream) {
@@ -361,5 +406,27 @@ extern "C" int occd_cp_mega_matrix(const uint8_t* coarse, uint8_t* out, int32_t 
     occd::ProfScope prof("cp_mega_matrix", st, 0.0, (double)batch * R * N * M);
     hipLaunchKernelGGL(cp_mega_kernel, dim3((unsigned)gy, (unsigned)((M + kMegaTile - 1) / kMegaTile), (unsigned)batch),
                        dim3(256), 0, st, coarse, out, X, Y, Z, N, M, binary ? 1 : 0);
+    return occd::check_launch();
+}
+
+extern "C" int occd_kitti_labels(const uint16_t* raw, const uint8_t* invalid_bits, const uint8_t* occluded_bits,
+                                 const uint8_t* lut, int32_t lut_len, uint8_t* target, uint8_t* occluded,
+                                 int32_t* out_of_range, int32_t batch, int64_t N, void* stream) {
+    if (!raw || !invalid_bits || !lut || !target || !out_of_range || batch <= 0 || N <= 0 || (N & 7) || lut_len < 1 ||
+        lut_len > kMaxLut || (occluded_bits != nullptr) != (occluded != nullptr))
+        return OCCD_EINVAL;
+    // 2-byte labels and 8-byte stores: raw at an odd address or outputs off an 8-byte boundary are not supported
+    if (((uintptr_t)raw & 1u) || ((uintptr_t)target & 7u) || ((uintptr_t)occluded & 7u) || ((uintptr_t)out_of_range & 3u))
+        return OCCD_EINVAL;
+    if (N > (1LL << 40) / batch) return OCCD_EINVAL;
+    const long groups = (long)batch * (N / 8);
+    long blocks = (groups + 255) / 256;
+    if (blocks > 2048) blocks = 2048;                  // 8 workgroups per CU; the loop takes the rest
+    hipStream_t st = (hipStream_t)stream;
+    occd::ProfScope prof("kitti_labels", st, 0.0, (double)groups * (16.0 + 1.0 + 8.0 + (occluded ? 9.0 : 0.0)));
+    hipLaunchKernelGGL(frustum_zero_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<uint32_t*>(out_of_range), 1);
+    hipLaunchKernelGGL(kitti_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, invalid_bits, occluded_bits, lut,
+                       (int)lut_len, reinterpret_cast<uint2*>(target), reinterpret_cast<uint2*>(occluded),
+                       reinterpret_cast<uint32_t*>(out_of_range), groups);
     return occd::check_launch();
 }

@@ -667,7 +667,7 @@ class OccDepth(_Base):
         out_dict = self(batch)
         ssc_pred = out_dict["ssc_logit"]
         dev = ssc_pred.device
-        target = batch["target"].to(dev)
+        target, occluded = self._step_labels(batch, dev)
         use_rel = self.context_prior and self.relation_loss
         built_fp = built_cp = None
         if self.fp_loss and step_type != "test" and self._build_target(batch, "frustums_masks"):
@@ -698,8 +698,8 @@ class OccDepth(_Base):
                 loss_occ = ssc_loss.occ_ce_loss(out_dict["occ_logit"], target, self._on_device("class_weights_occ", dev))
                 loss = loss + loss_occ
                 self._log(step_type + "/loss_occ", loss_occ)
-            if self.occluded_cls and "occluded" in batch:
-                loss_occluded = ssc_loss.CE_ssc_loss(out_dict["occluded_logit"], batch["occluded"].to(dev),
+            if self.occluded_cls and occluded is not None:
+                loss_occluded = ssc_loss.CE_ssc_loss(out_dict["occluded_logit"], occluded,
                                                      torch.ones(2, device=dev))
                 loss = loss + loss_occluded
                 self._log(step_type + "/loss_occluded", loss_occluded)
@@ -754,6 +754,36 @@ class OccDepth(_Base):
         if self.gpu_targets is False:
             return False
         return self._tables_absent(batch, key)
+
+    def _step_labels(self, batch, dev):
+        """(target, occluded or None) of a step, on `dev`.  A batch that brings `target` is used as it is (with its
+        `occluded`, when it has one).  Without `target` (missing, empty list or zero elements: _tables_absent) the batch must
+        bring the dataset's raw voxel files -- `voxel_label_raw` (B, N) uint16 or int16, `voxel_invalid_bits` (B, N / 8)
+        uint8 and, for `occluded_cls`, `voxel_occluded_bits` -- which targets.kitti_labels decodes on the GPU, eagerly or
+        inside a captured step; the frustum and relation targets are then built from the decoded labels as for any batch
+        without them.  The batch itself is not changed (a captured step keeps its static keys)."""
+        if not self._tables_absent(batch, "target"):
+            occluded = batch.get("occluded") if self.occluded_cls else None
+            return batch["target"].to(dev), (occluded.to(dev) if occluded is not None else None)
+        if "voxel_label_raw" not in batch or "voxel_invalid_bits" not in batch:
+            raise KeyError("the batch brings neither `target` nor the raw voxel files (`voxel_label_raw`, "
+                           "`voxel_invalid_bits`) to decode it from")
+        if self.gpu_targets is False:
+            raise RuntimeError("the batch brings raw voxel files instead of `target`; decoding them is part of building the "
+                               "training targets on the GPU (OCCDEPTH_GPU_TARGETS=auto or 1), not OCCDEPTH_GPU_TARGETS=0")
+        if self.dataset != "kitti":
+            raise NotImplementedError("raw voxel labels are decoded on the GPU for SemanticKITTI only; a %s batch must "
+                                      "bring `target`" % self.dataset)
+        scale = -(-int(self.project_scale) // 2)
+        dims = tuple(int(d) // scale for d in self.full_scene_size)
+
+        def rows(key):
+            v = batch[key]
+            return [t.to(dev) for t in v] if isinstance(v, (list, tuple)) else v.to(dev)
+
+        occ_bits = rows("voxel_occluded_bits") if self.occluded_cls and "voxel_occluded_bits" in batch else None
+        out = self._targets().kitti_labels(rows("voxel_label_raw"), rows("voxel_invalid_bits"), occ_bits, scene_size=dims)
+        return out if occ_bits is not None else (out, None)
 
     def frustum_targets_on_gpu(self, batch, target):
         """(frustums_masks (B, F, X, Y, Z) bool, frustums_class_dists (B, F, C) float32) of kitti_dataset.py:315-333, built

@@ -11,9 +11,15 @@ Both are pure functions of what a batch already carries (`target`, `cam_k`, `T_v
 bit-exact restatements, GPU only (no CPU path, like hip.py), and never synchronise the host, so they can sit inside a
 captured training step.  `OccDepth.step` calls them when a batch comes without the targets (OCCDEPTH_GPU_TARGETS);
 `defer_dataset_targets` takes the numpy work out of the reference's dataset.
+
+`kitti_labels` goes one step further back: it makes `target` (and `occluded`) from the dataset's own raw voxel files
+(`voxels/<frame>.label`, `.invalid`, `.occluded`), which the reference only reads in a separate preprocessing pass over all
+sequences (occdepth/data/semantic_kitti/preprocess.py).  A batch that carries the raw files (`read_raw_kitti_voxels`) needs
+no `labels/` tree; tools/preprocess_kitti_gpu.py writes that tree with the same kernels for whoever wants it.
 """
 import ctypes
 import importlib
+import os
 
 import numpy as np
 import torch
@@ -100,6 +106,119 @@ def cp_mega_matrix(coarse, binary=False):
     hip._check(hip.load().occd_cp_mega_matrix(lab.data_ptr(), out.data_ptr(), B, X, Y, Z, int(bool(binary)),
                                               hip._stream()), "occd_cp_mega_matrix")
     return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------------------------------------ raw voxel labels
+# `learning_map` of the SemanticKITTI label definition (semantic-kitti.yaml): raw label -> training class.
+KITTI_LEARNING_MAP = ((0, 0), (1, 0), (10, 1), (11, 2), (13, 5), (15, 3), (16, 5), (18, 4), (20, 5), (30, 6), (31, 7),
+                      (32, 8), (40, 9), (44, 10), (48, 11), (49, 12), (50, 13), (51, 14), (52, 0), (60, 9), (70, 15),
+                      (71, 16), (72, 17), (80, 18), (81, 19), (99, 0), (252, 1), (253, 7), (254, 6), (255, 8), (256, 5),
+                      (257, 5), (258, 4), (259, 5))
+KITTI_LUT_LEN = 359               # the largest raw label + 100 (io_data.py:187)
+
+
+def kitti_remap_lut():
+    """The table of io_data.get_remap_lut (io_data.py:175-195) as uint8[359]: raw label -> training class; every raw label
+    that maps to class 0, and every label the map does not name, becomes 255 ("invalid"); only raw 0 ("empty") stays 0."""
+    lut = np.full(KITTI_LUT_LEN, 255, dtype=np.uint8)
+    for raw, cls in KITTI_LEARNING_MAP:
+        if cls != 0:
+            lut[raw] = cls
+    lut[0] = 0
+    return lut
+
+
+_LUT_CACHE = {}
+
+
+def _device_lut(device):
+    key = str(device)
+    if key not in _LUT_CACHE:
+        _LUT_CACHE[key] = torch.from_numpy(kitti_remap_lut()).to(device)
+    return _LUT_CACHE[key]
+
+
+def _raw_rows(x, name, dtypes, cols=None):
+    """(B, n) contiguous device tensor of one of `dtypes` from a tensor or a list of per-sample tensors; never converted
+    (the kernel reads the files' own bits)."""
+    t = x
+    if isinstance(x, (list, tuple)):
+        rows = [v.reshape(-1) for v in x]
+        if rows and all(v.dtype == torch.uint16 for v in rows):      # stacked as int16: the same bits, and every backend has it
+            t = torch.stack([v.view(torch.int16) for v in rows]).view(torch.uint16)
+        else:
+            t = torch.stack(rows)
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (the label decode has no CPU path)")
+    if t.dtype not in dtypes:
+        raise RuntimeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() == 1:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or (cols is not None and tuple(t.shape) != cols):
+        raise RuntimeError(f"{name} must be (B, n) with one flat row per sample"
+                           + (f", here {cols}" if cols is not None else "") + f"; got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def kitti_labels_counted(raw, invalid_bits, occluded_bits=None, *, scene_size, lut=None):
+    """`kitti_labels` with its device counter: -> (target, occluded or None, count); count is an int32[1] device tensor, the
+    number of raw values outside the table, set by every launch and not read here."""
+    X, Y, Z = (int(d) for d in scene_size)
+    N = X * Y * Z
+    if N <= 0 or N % 8:
+        raise RuntimeError(f"kitti_labels: the voxel count {N} of scene_size {tuple(scene_size)} must be a positive "
+                           "multiple of 8 (the masks are packed 8 voxels to the byte)")
+    r = _raw_rows(raw, "raw", (torch.uint16, torch.int16))
+    if r.shape[1] != N:
+        raise RuntimeError(f"kitti_labels: raw must be (B, {N}) for scene_size {(X, Y, Z)}, got {tuple(r.shape)}")
+    B = int(r.shape[0])
+    inv = _raw_rows(invalid_bits, "invalid_bits", (torch.uint8,), (B, N // 8))
+    occ = None if occluded_bits is None else _raw_rows(occluded_bits, "occluded_bits", (torch.uint8,), (B, N // 8))
+    if lut is None:
+        table = _device_lut(r.device)
+    else:
+        table = torch.as_tensor(lut)
+        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() < 1:
+            raise RuntimeError("kitti_labels: lut must be a non-empty 1-D uint8 table")
+        table = table.to(r.device).contiguous()
+    target = torch.empty((B, X, Y, Z), dtype=torch.uint8, device=r.device)
+    occluded = None if occ is None else torch.empty((B, X, Y, Z), dtype=torch.uint8, device=r.device)
+    count = torch.empty(1, dtype=torch.int32, device=r.device)
+    hip._check(hip.load().occd_kitti_labels(r.data_ptr(), inv.data_ptr(), None if occ is None else occ.data_ptr(),
+                                            table.data_ptr(), int(table.numel()), target.data_ptr(),
+                                            None if occluded is None else occluded.data_ptr(), count.data_ptr(), B, N,
+                                            hip._stream()), "occd_kitti_labels")
+    return target, occluded, count
+
+
+def kitti_labels(raw, invalid_bits, occluded_bits=None, *, scene_size, lut=None, check=False):
+    """Raw SemanticKITTI voxel files -> training labels on the GPU (occd_kitti_labels), one launch for the batch.
+
+    raw (B, N) uint16 -- or int16 holding the same bits -- the `.label` files, N = X * Y * Z of scene_size, flat in
+    (X, Y, Z) order; invalid_bits (B, N / 8) uint8, the `.invalid` files as stored (MSB first, io_data.unpack);
+    occluded_bits optional, the `.occluded` files.  Lists of per-sample tensors are stacked.  Returns
+    target (B, X, Y, Z) uint8 = lut[raw], 255 where the invalid bit is set -- the values of the reference's
+    `<frame>_1_1.npy` (preprocess.py:76-84) -- and, with occluded_bits, (target, occluded (B, X, Y, Z) uint8 of 0 / 1).
+    `lut` defaults to kitti_remap_lut().  A raw value outside the table gives 255 and is counted on the device; with
+    `check` the count is read back (a host synchronisation: tools only, never the training step) and a non-zero count
+    raises IndexError, as the reference's table lookup would."""
+    target, occluded, count = kitti_labels_counted(raw, invalid_bits, occluded_bits, scene_size=scene_size, lut=lut)
+    if check:
+        bad = int(count.item())
+        if bad:
+            raise IndexError(f"kitti_labels: {bad} raw label(s) lie outside the remap table")
+    return target if occluded is None else (target, occluded)
+
+
+def read_raw_kitti_voxels(voxel_dir, frame_id, occluded=False):
+    """The raw voxel files of one frame, undecoded, for a dataset's __getitem__: (`<frame>.label` as uint16[N],
+    `<frame>.invalid` as uint8[N / 8] [, `<frame>.occluded` as uint8[N / 8]]) numpy arrays -- the batch entries
+    `voxel_label_raw`, `voxel_invalid_bits` [, `voxel_occluded_bits`] that OccDepth.step decodes on the GPU."""
+    base = os.path.join(voxel_dir, frame_id)
+    out = (np.fromfile(base + ".label", dtype=np.uint16), np.fromfile(base + ".invalid", dtype=np.uint8))
+    if occluded:
+        out += (np.fromfile(base + ".occluded", dtype=np.uint8),)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ dataset hook

@@ -6,6 +6,7 @@ The shared object lands next to this file so it travels with the source tree
 (it is git-ignored, not gpurun-ignored).  No torch headers are involved: the
 library exposes the C ABI of include/occdepth_amd.h only.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -14,9 +15,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["conv3d_igemm.hip", "conv3d_c32p.hip", "lift.hip", "nchw2d.hip", "loss.hip", "conv3d_wgrad.hip", "conv3d_bf16.hip", "bn.hip", "bneck3d.hip", "rows_gemm.hip", "gemm_x3.hip", "wino2d.hip", "wino_conv2d.hip", "pw_gemm.hip", "se2d.hip", "ipc_allreduce.hip", "graph_fix.hip", "targets.hip", "optim.hip", "prof.cpp"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "project.h"), os.path.join(HERE, "..", "include", "occdepth_amd.h")]
+# every header under csrc/ (a new one cannot drop out of source_digest()) + the public C ABI
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "occdepth_amd.h")]
 LIB = os.path.join(HERE, "libocc_hip.so")
 ARCH = "gfx950"
+FLAGS = ["-O3", "-std=c++17", "-fPIC"]   # of every compile command, and part of source_digest()
 
 
 def _hipcc():
@@ -30,7 +33,7 @@ def source_digest():
     """sha256 over the names and CONTENTS of every source and header the library is built from (+ the compiler flags)."""
     import hashlib
     h = hashlib.sha256()
-    h.update(f"arch={ARCH};flags=-O3 -std=c++17 -fPIC".encode())
+    h.update(f"arch={ARCH};flags={' '.join(FLAGS)}".encode())
     for path in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
@@ -60,8 +63,7 @@ def build(force=False, verbose=True):
     procs = []
     for s in SOURCES:
         o = os.path.join(bdir, os.path.splitext(s)[0] + ".o")
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
-               "-c", os.path.join(CSRC, s), "-o", o]
+        cmd = [_hipcc(), f"--offload-arch={ARCH}"] + FLAGS + ["-x", "hip", "-c", os.path.join(CSRC, s), "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((subprocess.Popen(cmd), cmd))

@@ -13,11 +13,7 @@
 // Every partial sum is combined in a fixed order: results are deterministic.
 // Reference semantics replaced: torch.nn.BatchNorm{2,3}d / SyncBatchNorm in training mode as used by
 // occdepth/models/DDR.py:111-139, modules.py:40-46,158-175,278-296, unet2d.py:24-46, scripts/train.py:179 (sync_batchnorm).
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#include "device.h"
 
 namespace {
 
@@ -48,14 +44,7 @@ __device__ __forceinline__ void st4(void* p, size_t e, f32x4 v) {
     }
 }
 
-__device__ __forceinline__ float act_fwd(float v, int act, float slope) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return occd::swish_fast(v);
-    if (act == 3) return v > 0.f ? v : v * slope;
-    return v;
-}
-
-// d act / d pre-activation.  `pre` is the pre-activation, or (sign_only) any value with its sign (the saved output).
+// d act2d_fast (device.h) / d pre-activation.  `pre` is the pre-activation, or (sign_only) any value with its sign (the saved output).
 __device__ __forceinline__ float act_bwd(float pre, int act, float slope) {
     if (act == 1) return pre > 0.f ? 1.f : 0.f;
     if (act == 3) return pre > 0.f ? 1.f : slope;
@@ -226,7 +215,7 @@ __global__ void __launch_bounds__(256) bn_apply_rows_kernel(const BnP p) {
                 f32x4 v = xv * a + b;
                 if (p.res_first) v += second;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = act_fwd(v[j], p.act, p.slope);
+                for (int j = 0; j < 4; ++j) v[j] = act2d_fast(v[j], p.act, p.slope);
                 if (!p.res_first) v += second;
                 o = v * keep;
             } else {
@@ -381,7 +370,7 @@ __global__ void __launch_bounds__(256) bn_apply_planes_kernel(const BnP p) {
                 if (res != nullptr) rr = *(const f32x4*)(res + off + 4 * i);
                 if (p.res_first) v += rr;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = act_fwd(v[j], p.act, p.slope);
+                for (int j = 0; j < 4; ++j) v[j] = act2d_fast(v[j], p.act, p.slope);
                 if (!p.res_first) v += rr;
                 *(f32x4*)(out + off + 4 * i) = v;
             }
@@ -390,7 +379,7 @@ __global__ void __launch_bounds__(256) bn_apply_planes_kernel(const BnP p) {
                 float v = x[off + i] * a + b;
                 const float rr = res != nullptr ? res[off + i] : 0.f;
                 if (p.res_first) v += rr;
-                v = act_fwd(v, p.act, p.slope);
+                v = act2d_fast(v, p.act, p.slope);
                 if (!p.res_first) v += rr;
                 out[off + i] = v;
             }
@@ -770,7 +759,7 @@ __global__ void __launch_bounds__(256) bn_small_planes_kernel(const BnP p, float
                 if (res != nullptr) rr = *(const f32x4*)(res + off + 4 * i);
                 if (p.res_first) v += rr;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = act_fwd(v[j], p.act, p.slope);
+                for (int j = 0; j < 4; ++j) v[j] = act2d_fast(v[j], p.act, p.slope);
                 if (!p.res_first) v += rr;
                 *(f32x4*)(out + off + 4 * i) = v;
             } else {
@@ -790,7 +779,7 @@ __global__ void __launch_bounds__(256) bn_small_planes_kernel(const BnP p, float
                 float v = xv * c0 + c1;
                 const float rr = res != nullptr ? res[off + i] : 0.f;
                 if (p.res_first) v += rr;
-                v = act_fwd(v, p.act, p.slope);
+                v = act2d_fast(v, p.act, p.slope);
                 if (!p.res_first) v += rr;
                 out[off + i] = v;
             } else {

@@ -21,10 +21,8 @@
 // P = 32 / 64); the matrix pipe form below replaced it.
 // HBM bytes per voxel: read x (4C) + write o2 (4P) | read o2 (4P, +halo from L2) + read x (4C) + write y (4C)
 //   = 4 (3C + 2P) = 896 B at C = 64 (235 MB per block at 128x128x16) against 4 (3C + 8P) + launch tails before.
-#include "common.h"
+#include "device.h"
 #include <algorithm>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -43,10 +41,6 @@ struct BneckP {
     int TX, TY, xtiles, ytiles;
     long ncols;                           // batch * X * Y
 };
-
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-}
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -117,7 +111,7 @@ __global__ void __launch_bounds__(NT) bneck_a_kernel(const BneckP p) {
                 if (t0 + u < CT) mma_step<M>(acc, w1f + (size_t)(t0 + u) * M * 256, lane, d[u]);
         }
 #pragma unroll
-        for (int m = 0; m < M; ++m) *(f32x4*)(o1s + row * P + 16 * m + 4 * g) = relu4(acc[m] + b1v[m]);
+        for (int m = 0; m < M; ++m) *(f32x4*)(o1s + row * P + 16 * m + 4 * g) = act3d_x4(acc[m] + b1v[m], OCCD_ACT_RELU);
         __syncthreads();                                  // (uniform trip count; the tile's columns are complete)
         const int z = row % p.Z;
         f32x4 o2[M];
@@ -198,7 +192,7 @@ __global__ void __launch_bounds__(NT) bneck_b_kernel(const BneckP p) {
 #pragma unroll
         for (int k = 0; k < 3; ++k)
 #pragma unroll
-            for (int t = 0; t < M; ++t) mma_step<M>(o3, w3f + (size_t)(k * M + t) * M * 256, lane, relu4(d[k][t]));
+            for (int t = 0; t < M; ++t) mma_step<M>(o3, w3f + (size_t)(k * M + t) * M * 256, lane, act3d_x4(d[k][t], OCCD_ACT_RELU));
         const bool centre = xr >= p.d2 && xr < p.d2 + p.TX;
 #pragma unroll
         for (int m = 0; m < M; ++m) {
@@ -225,9 +219,9 @@ __global__ void __launch_bounds__(NT) bneck_b_kernel(const BneckP p) {
 #pragma unroll
             for (int t = 0; t < M; ++t)
                 mma_step<M>(o4, w4f + (size_t)(k * M + t) * M * 256, lane,
-                            relu4(*(const f32x4*)(o3s + (size_t)(tv + k * p.d2 * TYZ) * P + 16 * t + 4 * g)));
+                            act3d_x4(*(const f32x4*)(o3s + (size_t)(tv + k * p.d2 * TYZ) * P + 16 * t + 4 * g), OCCD_ACT_RELU));
 #pragma unroll
-        for (int m = 0; m < M; ++m) o4[m] = relu4(o4[m]);
+        for (int m = 0; m < M; ++m) o4[m] = act3d_x4(o4[m], OCCD_ACT_RELU);
         float* yrow = p.y + vrow * p.y_cs + p.y_coff + 4 * g;
         for (int mo = 0; mo < CT; mo += 4) {               // 4 output tiles (64 channels) per round, residual loads first
             f32x4 res[4], bias[4], acc[4];
@@ -251,7 +245,7 @@ __global__ void __launch_bounds__(NT) bneck_b_kernel(const BneckP p) {
             if (live) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (mo + u < CT) *(f32x4*)(yrow + 16 * (mo + u)) = relu4(acc[u] + bias[u] + res[u]);
+                    if (mo + u < CT) *(f32x4*)(yrow + 16 * (mo + u)) = act3d_x4(acc[u] + bias[u] + res[u], OCCD_ACT_RELU);
             }
         }
     }

@@ -15,7 +15,7 @@
 //
 // Reference semantics replaced (training step, N1): occdepth/models/DDR.py:111-139, modules.py:40-46,158-175,278-296,
 // CRP3D.py:54-97, unet2d.py:24-46 -- forward and, on dL/dy with flipped weights, the data gradient.
-#include "common.h"
+#include "device.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -23,13 +23,6 @@
 #include <cstring>
 
 using occd::FastDiv;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -60,22 +53,6 @@ struct ConvBP {
     PhaseBP ph[kMaxPhasesB];
 };
 
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    return v;
-}
-// (the expf + IEEE division form of K2's apply_act, csrc/conv3d_igemm.hip: same values)
-__device__ __forceinline__ f32x4 sigmoid4(f32x4 v) {
-    v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y));
-    v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-    return v;
-}
-
-__device__ __forceinline__ u32x4 pack_bf16x8(f32x4 a, f32x4 b) {
-    bf16x8 r = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w, (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
-    return __builtin_bit_cast(u32x4, r);
-}
-
 __device__ __forceinline__ f32x4 unpack_lo(u32x2 v) {       // 4 bf16 -> 4 floats
     f32x4 r;
     r.x = __builtin_bit_cast(float, v.x << 16);
@@ -88,22 +65,7 @@ __device__ __forceinline__ f32x4 unpack_lo(u32x2 v) {       // 4 bf16 -> 4 float
 constexpr int kRSB = 80;   // LDS row stride in bytes: 32 bf16 channels + 16 B pad
 constexpr int kRSB3 = 208; // SPLIT = 3: three bf16 planes (hi, mid, lo) of the 32 channels + 16 B pad (13 slots: odd)
 
-// x = hi + mid + lo exactly (each bf16, 8 significant bits: 24 together) for every float32 x whose low parts do not
-// underflow; the six products hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid then reproduce x*w to ~2^-24 relative.
-__device__ __forceinline__ void split3(f32x4 a, f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    bf16x8 h = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w, (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
-    float r[8] = {a.x - (float)h[0], a.y - (float)h[1], a.z - (float)h[2], a.w - (float)h[3],
-                  b.x - (float)h[4], b.y - (float)h[5], b.z - (float)h[6], b.w - (float)h[7]};
-    bf16x8 m, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        m[j] = (__bf16)r[j];
-        l[j] = (__bf16)(r[j] - (float)m[j]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    mid = __builtin_bit_cast(u32x4, m);
-    lo = __builtin_bit_cast(u32x4, l);
-}
+// (activations act3d_x4, pack_bf16x8 and the three-term split split3_bf16x8: device.h)
 
 // SPLIT = 1: plain bf16 operands.  SPLIT = 3 (opt-in experiment): float32 activations and weights as
 // three bf16 terms each, six MFMAs per K step instead of one -- float32-level accuracy at 6/16 of the fp32-MFMA time.
@@ -127,11 +89,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
     const int li = lane & 31;
     const int h = lane >> 5;
 
-    uint32_t bid = blockIdx.x;   // XCD-aware bijective remap (see K2): an XCD walks a contiguous run of tiles
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    uint32_t bid = xcd_remap(blockIdx.x, p.nwg);   // an XCD walks a contiguous run of tiles
     // phase of a merged transposed-convolution launch: the low bits of the (remapped) linear id when ph_fast -- the phases of
     // one output tile run next to each other on one XCD, so their interleaved voxel rows meet in its L2 and the input tile is
     // fetched once -- else the low bits of blockIdx.y (phase-major dispatch, heaviest tap subset first)
@@ -248,9 +206,11 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
                     } else {
                         f32x4 lo = *(const f32x4*)((const float*)p.in + e);
                         f32x4 hi = *(const f32x4*)((const float*)p.in + e + 4);
-                        if (p.act_in == OCCD_ACT_RELU) { lo = relu4(lo); hi = relu4(hi); }
-                        else if (SPLIT == 3 && p.act_in == OCCD_ACT_SIGMOID) { lo = sigmoid4(lo); hi = sigmoid4(hi); }
-                        if (SPLIT == 3) split3(lo, hi, w[0], w[SPLIT == 3 ? 1 : 0], w[SPLIT == 3 ? 2 : 0]);
+                        if (p.act_in == OCCD_ACT_RELU) { lo = act3d_x4(lo, OCCD_ACT_RELU); hi = act3d_x4(hi, OCCD_ACT_RELU); }
+                        else if (SPLIT == 3 && p.act_in == OCCD_ACT_SIGMOID) {
+                            lo = act3d_x4(lo, OCCD_ACT_SIGMOID); hi = act3d_x4(hi, OCCD_ACT_SIGMOID);
+                        }
+                        if (SPLIT == 3) split3_bf16x8(lo, hi, w[0], w[SPLIT == 3 ? 1 : 0], w[SPLIT == 3 ? 2 : 0]);
                         else w[0] = pack_bf16x8(lo, hi);
                     }
 #pragma unroll
@@ -355,7 +315,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
                     f32x4 v = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2],
                                acc[mt][nt][4 * g + 3]};
                     if (p.bias != nullptr) v += *(const f32x4*)(p.bias + c);
-                    if (p.act_out == OCCD_ACT_RELU_PRE) v = relu4(v);
+                    if (p.act_out == OCCD_ACT_RELU_PRE) v = act3d_x4(v, OCCD_ACT_RELU);
                     if (OUT_BF16) {
                         if (p.res1 != nullptr)
                             v += unpack_lo(*(const u32x2*)((const uint16_t*)p.res1 + vox * p.res1_cs + p.res1_coff + c));
@@ -365,7 +325,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
                         if (p.res1 != nullptr) v += *(const f32x4*)((const float*)p.res1 + vox * p.res1_cs + p.res1_coff + c);
                         if (p.res2 != nullptr) v += *(const f32x4*)((const float*)p.res2 + vox * p.res2_cs + p.res2_coff + c);
                     }
-                    if (p.act_out == OCCD_ACT_RELU) v = relu4(v);
+                    if (p.act_out == OCCD_ACT_RELU) v = act3d_x4(v, OCCD_ACT_RELU);
                     if (OUT_BF16) {
                         bf16x4 o = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
                         *(u32x2*)((uint16_t*)p.out + vox * p.out_cs + p.out_coff + c) = __builtin_bit_cast(u32x2, o);
@@ -380,7 +340,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
 
 // ---------------------------------------------------------------- weight packing (fp32 master weights -> bf16 fragments)
 // wpk[tap][k16][nt][lane][j]: cout = nt * 32 + (lane & 31), cin = k16 * 16 + (lane >> 5) * 8 + j
-// nsplit = 3: three consecutive images hi | mid | lo of the float32 weight (see split3)
+// nsplit = 3: three consecutive images hi | mid | lo of the float32 weight (see split3_bf16x8, device.h)
 __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, const float* __restrict__ scale,
                                          uint16_t* __restrict__ wpk, int cout, int cin, int taps, int K16, int NT,
                                          int layout, long total, int nsplit, const occd::TapMap tm) {
@@ -414,7 +374,7 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, const floa
 
 // K2s3h weight image (occd_pack_weights_f16x2): three fp16 images in the layout above -- hi | hs | lo of w' = 2^k[co] w,
 // hi = fp16(w'), hs = hi 2^-11, lo = fp16(w' - hi) -- followed by NT * 32 floats 2^-(k[co] + kF2XExp) (the epilogue factor;
-// kF2XExp = 1, the activation pre-scale of conv3d_c32p.hip).  k[co] puts max_{ci, tap} |w'| into [2^13, 2^14).
+// kF2XExp: the activation pre-scale of split2_f16x8, device.h).  k[co] puts max_{ci, tap} |w'| into [2^13, 2^14).
 __global__ void f16x2_scale_kernel(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ fac,
                                    int cout, int cin, int taps, int NT, int layout) {
     const int co = blockIdx.x * blockDim.x + threadIdx.x;
@@ -432,7 +392,7 @@ __global__ void f16x2_scale_kernel(const float* __restrict__ w, const float* __r
     int e = 0;
     if (m > 0.f && m <= 3.0e38f) frexpf(m, &e);                  // m in [2^(e-1), 2^e)
     const int k = m > 0.f && m <= 3.0e38f ? min(max(14 - e, -120), 120) : 0;   // (non-finite weights: the host keeps bf16x3)
-    fac[co] = ldexpf(1.f, -(k + 1));                              // 2^-(k + kF2XExp)
+    fac[co] = ldexpf(1.f, -(k + kF2XExp));
 }
 
 __global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, const float* __restrict__ scale,

@@ -21,10 +21,7 @@
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "device.h"
 
 namespace {
 
@@ -502,45 +499,12 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_kernel(const SlideP s
 //     tests scale the activations by 2^-16 .. 2^+8);
 //   * dilation 3 at Z > 32: six-row y tiles as in K2s3 (the 8-row tile fits LDS with 80-byte entries, 42.6 KB, but its
 //     third staging load per thread spills at NRES = 2).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kX3RowB = 112;              // bytes per slab entry: hi | mid | lo of 16 channels + 16 B pad
 constexpr int kF2RowB = 80;               // K2s3h: hi | lo' of 16 channels + 16 B pad
-constexpr int kF2XExp = 1;                // K2s3h: activations are staged as 2^kF2XExp x
 constexpr int kX3ZW = 33;                 // entries per y row: z = 0 .. 31 and the zero entry
 constexpr int kX3WImg = kWTaps * 2 * 64;  // u32x4 per split image of the weights: [tap][k16 2][lane 64]
 
-// x = hi + mid + lo (round-to-nearest at every step; exact for every float32 whose low parts do not underflow)
-__device__ __forceinline__ void split3_bf16(f32x4 a, f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    bf16x8 h = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w, (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
-    float r[8] = {a.x - (float)h[0], a.y - (float)h[1], a.z - (float)h[2], a.w - (float)h[3],
-                  b.x - (float)h[4], b.y - (float)h[5], b.z - (float)h[6], b.w - (float)h[7]};
-    bf16x8 m, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        m[j] = (__bf16)r[j];
-        l[j] = (__bf16)(r[j] - (float)m[j]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    mid = __builtin_bit_cast(u32x4, m);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
-// K2s3h: x' = hi + 2^-11 lo' (fp16; hi | lo' are the first two planes of the slab entry)
-__device__ __forceinline__ void split2_f16(f32x4 a, f32x4 b, u32x4& hi, u32x4& lo) {
-    const float s = (float)(1 << kF2XExp);
-    float x[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
-    f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        h[j] = (_Float16)x[j];
-        l[j] = (_Float16)((x[j] - (float)h[j]) * 2048.f);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
+// The splits themselves -- split3_bf16x8, and split2_f16x8 with its pre-scale exponent kF2XExp -- live in device.h.
 
 // NRES: residual operands compiled in (0: neither, 1: res1, 2: res1 and res2) -- their prefetch registers (16 per
 // operand) are what the 5 of 7 head launches without residuals do not pay for.  F16: the K2s3h numerics (see above).
@@ -648,12 +612,12 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
                 }
                 if constexpr (F16) {
                     u32x4 hi, lo;
-                    split2_f16(a, b, hi, lo);
+                    split2_f16x8(a, b, hi, lo);
                     *reinterpret_cast<u32x4*>(slab + sdst[i]) = hi;
                     *reinterpret_cast<u32x4*>(slab + sdst[i] + 32) = lo;
                 } else {
                     u32x4 hi, mid, lo;
-                    split3_bf16(a, b, hi, mid, lo);
+                    split3_bf16x8(a, b, hi, mid, lo);
                     *reinterpret_cast<u32x4*>(slab + sdst[i]) = hi;
                     *reinterpret_cast<u32x4*>(slab + sdst[i] + 32) = mid;
                     *reinterpret_cast<u32x4*>(slab + sdst[i] + 64) = lo;

@@ -19,7 +19,7 @@
 //
 // Reference semantics replaced: occdepth/models/DDR.py:111-139,
 // occdepth/models/modules.py:40-46,158-175,278-296, occdepth/models/CRP3D.py:54-97.
-#include "common.h"
+#include "device.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -27,9 +27,6 @@
 #include <cstring>
 
 using occd::FastDiv;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -62,16 +59,6 @@ struct ConvP {
     PhaseP ph[kMaxPhases];
 };
 
-__device__ __forceinline__ f32x4 apply_act(f32x4 v, int act) {
-    if (act == OCCD_ACT_RELU) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    } else if (act == OCCD_ACT_SIGMOID) {
-        v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y));
-        v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-    }
-    return v;
-}
-
 // KS > 1: in-workgroup split-K.  The KS wave groups take interleaved cin chunks (each with its own LDS slab),
 // and their accumulators are summed through LDS before the epilogue.  It multiplies the waves per SIMD for
 // layers with few output tiles and a long K (the 32x32x4 ASPP / CRP level: 4096 voxels, K = 27 x 256).
@@ -95,11 +82,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64) conv3d_igemm_kernel(const Con
     // XCD-aware bijective remap: the dispatcher round-robins workgroups over
     // the 8 XCDs; give each XCD a contiguous run of tiles so the kx halo
     // (the same input planes are used by 3 neighbouring xo) hits its own L2.
-    uint32_t bid = blockIdx.x;
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
     // phase of a merged transposed-convolution launch: the low bits of the (remapped) linear id when ph_fast -- the phases of
     // one output tile run next to each other on one XCD, so their interleaved voxel rows meet in its L2 and the input tile is
     // fetched once -- else the low bits of blockIdx.y (phase-major dispatch, heaviest tap subset first)
@@ -197,7 +180,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64) conv3d_igemm_kernel(const Con
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const f32x4 a = apply_act(v[u], p.act_in);
+                    const f32x4 a = act3d_x4(v[u], p.act_in);
                     if (dst[u] >= 0) slab4[dst[u]] = okv[u] ? a : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }

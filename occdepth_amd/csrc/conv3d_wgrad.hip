@@ -13,11 +13,10 @@
 // The loads of step s+1 (8 output voxels) are issued before the MFMAs of step s (two register sets).
 // Each wave writes its partial (tap, 32, 32) tiles to a workspace; a second kernel sums the partials in a fixed
 // order, so the result is deterministic (no float atomics).
-#include "common.h"
+#include "device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kTPW = 7;            // accumulator sets per wave in the row-split mode; 4 when the 8 waves split the taps
 
 struct WgradP {
@@ -247,12 +246,6 @@ int plan(const occd_conv3d_wgrad_args* a, WgradP& p) {
 //   COSPLIT  (NCO = 128; <= 9 taps, the 2-D decoder's 3x3 convolutions as X = 1 volumes): wave w owns the 32 couts
 //            co0 + 32 w and every tap (<= 9 accumulators); the staged input rows serve 128 couts.
 // Partial (tap, 32 co, 32 ci) tiles go to the workspace layout of K8 and through the same deterministic reduction.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
 struct WgradBP {
     const void* x;
     const void* gy;
@@ -264,24 +257,13 @@ struct WgradBP {
     occd::FastDiv div_zin, div_ztiles, div_yo, div_xo;
 };
 
-__device__ __forceinline__ u32x4 wg_pack8(f32x4 a, f32x4 b) {
-    bf16x8 r = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w, (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
-    return __builtin_bit_cast(u32x4, r);
-}
-
 // 8 channels (16 B of bf16) of one voxel row from fp32 or bf16 storage; `e` = element index of the first channel
 template <bool IN_BF16>
 __device__ __forceinline__ u32x4 wg_load8(const void* base, size_t e) {
     if (IN_BF16) return *(const u32x4*)((const uint16_t*)base + e);
     const f32x4 lo = *(const f32x4*)((const float*)base + e);
     const f32x4 hi = *(const f32x4*)((const float*)base + e + 4);
-    return wg_pack8(lo, hi);
-}
-
-__device__ __forceinline__ bf16x8 wg_tr_frag(const unsigned char* p0, int step_bytes) {
-    const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p0);
-    const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p0 + step_bytes));
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+    return pack_bf16x8(lo, hi);
 }
 
 template <int TPW, bool COSPLIT, bool IN_BF16>
@@ -375,12 +357,12 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(const WgradBP p) {
         __syncthreads();
 
         for (int kg = 0; kg < kgroups; ++kg) {
-            const bf16x8 a = wg_tr_frag(gyt + a_lane + kg * 16 * p.grs, a_step);
+            const bf16x8 a = tr_frag_bf16x8(gyt + a_lane + kg * 16 * p.grs, a_step);
             const unsigned char* xb = xt + b_lane + kg * 16 * p.sz * 64;
 #pragma unroll
             for (int i = 0; i < TPW; ++i)
                 if (i < n_mine) {
-                    const bf16x8 bv = wg_tr_frag(xb + xoff[i], b_step);
+                    const bf16x8 bv = tr_frag_bf16x8(xb + xoff[i], b_step);
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv, acc[i], 0, 0, 0);
                 }
         }

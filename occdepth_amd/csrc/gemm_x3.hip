@@ -21,16 +21,9 @@
 // (through the tap-GEMM / Winograd-domain forms of this repo's unet2d.py) and the geffnet MBConv expand convolutions.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // rows of odd length: dword-aligned 16-byte loads
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;   // (as K8b, csrc/conv3d_wgrad.hip)
 
 namespace {
 
@@ -55,40 +48,7 @@ struct GemmP {
 
 constexpr int kARow = 208;              // bytes per A row in LDS: 3 x 64 B (32 k of one term) + 16 B pad
 
-__device__ __forceinline__ void split8(f32x4 a, f32x4 b, u32x4& hi, u32x4& mid, u32x4& lo) {
-    bf16x8 h = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w, (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
-    float r[8] = {a.x - (float)h[0], a.y - (float)h[1], a.z - (float)h[2], a.w - (float)h[3],
-                  b.x - (float)h[4], b.y - (float)h[5], b.z - (float)h[6], b.w - (float)h[7]};
-    bf16x8 m, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        m[j] = (__bf16)r[j];
-        l[j] = (__bf16)(r[j] - (float)m[j]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    mid = __builtin_bit_cast(u32x4, m);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
-__device__ __forceinline__ void split4(f32x4 a, u32x2& hi, u32x2& mid, u32x2& lo) {
-    bf16x4 h = {(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w};
-    float r[4] = {a.x - (float)h[0], a.y - (float)h[1], a.z - (float)h[2], a.w - (float)h[3]};
-    bf16x4 m, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        m[j] = (__bf16)r[j];
-        l[j] = (__bf16)(r[j] - (float)m[j]);
-    }
-    hi = __builtin_bit_cast(u32x2, h);
-    mid = __builtin_bit_cast(u32x2, m);
-    lo = __builtin_bit_cast(u32x2, l);
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, int step_bytes) {
-    const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)p0);
-    const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(p0 + step_bytes));
-    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// (the splits split3_bf16x8 / split3_bf16x4 and the transposed fragment read tr_frag_bf16x8: device.h)
 
 // PRE: 0 = both operands float32 in memory (split while staged); 1 = A is the pre-split fragment image of
 // occd_gemm_x3_pack (weights: [row tile 32][k16][term][lane][8 bf16], read straight from L2 like K2b's weights -- no LDS,
@@ -127,11 +87,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
     const int wm = wave / WN, wn = wave - wm * WN;
     const int li = lane & 31, h = lane >> 5, i16 = lane & 15, g1 = (lane >> 4) & 1;
 
-    uint32_t bid = blockIdx.x;   // XCD-aware bijective remap: an XCD walks a contiguous run of tiles
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);   // an XCD walks a contiguous run of tiles
     int mt_i, nt_i;
     if (p.n_fast) { nt_i = bid % p.ntiles; mt_i = bid / p.ntiles; }
     else { mt_i = bid % p.mtiles; nt_i = bid / p.mtiles; }
@@ -205,7 +161,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
                     a1[j] = 1.f / (1.f + __expf(-a1[j]));
                 }
             }
-            split8(ok ? a0 : z, ok ? a1 : z, hi, mid, lo);
+            split3_bf16x8(ok ? a0 : z, ok ? a1 : z, hi, mid, lo);
             *(u32x4*)(lA + a_dst[i]) = hi;
             if (TERMS == 3) {
                 *(u32x4*)(lA + a_dst[i] + 64) = mid;
@@ -228,7 +184,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
                 v.w = sh == 0 ? w.w : 0.f;
             }
             u32x2 hi, mid, lo;
-            split4(v, hi, mid, lo);
+            split3_bf16x4(v, hi, mid, lo);
             *(u32x2*)(lB + b_dst[i]) = hi;
             if (TERMS == 3) {
                 *(u32x2*)(lB + BTERM + b_dst[i]) = mid;
@@ -334,7 +290,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                    for (int t = 0; t < TERMS; ++t) bf[nt][t] = tr_frag(lB + t * BTERM + b_lane[nt] + ks * 16 * SB, 4 * SB);
+                    for (int t = 0; t < TERMS; ++t) bf[nt][t] = tr_frag_bf16x8(lB + t * BTERM + b_lane[nt] + ks * 16 * SB, 4 * SB);
             }
             if (PRE != 0) fetch_pk(ks, s * 2 + ks + 2);
             if (TERMS == 3) {
@@ -461,11 +417,7 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_ws_kernel(const GemmP p) {
     const bool loader = wave >= 4;                   // waves 0-3 multiply, 4-7 load (one of each per SIMD)
     const int li = lane & 31, h = lane >> 5, i16 = lane & 15, g1 = (lane >> 4) & 1;
 
-    uint32_t bid = blockIdx.x;
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
     int mt_i, nt_i;
     if (p.n_fast) { nt_i = bid % p.ntiles; mt_i = bid / p.ntiles; }
     else { mt_i = bid % p.mtiles; nt_i = bid / p.mtiles; }
@@ -525,7 +477,7 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_ws_kernel(const GemmP p) {
                                __builtin_amdgcn_perm(__float_as_uint(x1.w), __float_as_uint(x1.z), 0x07060302u)};
                     mid = hi; lo = hi;
                 } else {
-                    split8(oka ? ra[set][i][0] : z, oka ? ra[set][i][1] : z, hi, mid, lo);
+                    split3_bf16x8(oka ? ra[set][i][0] : z, oka ? ra[set][i][1] : z, hi, mid, lo);
                 }
                 *(u32x4*)(buf + a_dst[i]) = hi;
                 *(u32x4*)(buf + a_dst[i] + 32) = mid;
@@ -547,7 +499,7 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_ws_kernel(const GemmP p) {
                                __builtin_amdgcn_perm(__float_as_uint(w.w), __float_as_uint(w.z), 0x07060302u)};
                     m2 = h2; l2 = h2;
                 } else {
-                    split4(v, h2, m2, l2);
+                    split3_bf16x4(v, h2, m2, l2);
                 }
                 *(u32x2*)(lB + b_dst[i]) = h2;
                 *(u32x2*)(lB + kWsBTerm + b_dst[i]) = m2;
@@ -617,7 +569,7 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_ws_kernel(const GemmP p) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) bf[nt][t] = tr_frag(buf + t * kWsBTerm + b_lane[nt], 4 * kWsSB);
+                for (int t = 0; t < 3; ++t) bf[nt][t] = tr_frag_bf16x8(buf + t * kWsBTerm + b_lane[nt], 4 * kWsSB);
         }
         OCCD_WS(1, 1);
         OCCD_WS(0, 2);
@@ -709,11 +661,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
     const int li = lane & 31, h = lane >> 5, i16 = lane & 15, g1 = (lane >> 4) & 1;
     const int K16tot = (p.K + 15) >> 4, KP = K16tot * 16;
 
-    uint32_t bid = blockIdx.x;
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
     const int nt_i = bid % p.ntiles, mr_i = bid / p.ntiles;       // column panel fastest: an XCD shares the row range's weights
     const int bz = blockIdx.y;
     const int n0 = nt_i * TN;
@@ -774,7 +722,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
                     w.w = sh == 0 ? u.w : 0.f;
                 }
                 u32x2 hi, mid, lo;
-                split4(w, hi, mid, lo);
+                split3_bf16x4(w, hi, mid, lo);
                 unsigned char* dst = glds + k * SB + c4 * 8;
                 *(u32x2*)dst = hi;
                 *(u32x2*)(dst + TB) = mid;
@@ -803,7 +751,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
+                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
         };
         fetch_b(0);
 #define OCCD_GP(WT, XT)                                                                                              \
@@ -923,11 +871,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
     const int nst = min(q.k16_per_z, K16tot - ks0);             // its steps (>= 1 by construction of the grid)
     const int kbase = ks0 * 16;
 
-    uint32_t bid = blockIdx.x;
-    {
-        const uint32_t nwg = p.nwg, qq = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
     const int nt_i = bid % p.ntiles, mr_i = bid / p.ntiles;
     const int bz = blockIdx.y;
     const int n0 = nt_i * TN;
@@ -981,7 +925,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
                     w.w = sh == 0 ? u.w : 0.f;
                 }
                 u32x2 hi, mid, lo;
-                split4(w, hi, mid, lo);
+                split3_bf16x4(w, hi, mid, lo);
                 unsigned char* dst = glds + k * SB + c4 * 8;
                 *(u32x2*)dst = hi;
                 *(u32x2*)(dst + TB) = mid;
@@ -1006,7 +950,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
+                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
         };
         fetch_b(0);
 #define OCCD_GP(WT, XT)                                                                                              \
@@ -1158,7 +1102,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_x3_nt_kernel(const GemmP p) 
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             u32x4 hi, mid, lo;
-            split8(ra[i][0], ra[i][1], hi, mid, lo);
+            split3_bf16x8(ra[i][0], ra[i][1], hi, mid, lo);
             *(u32x4*)(lA + a_dst[i]) = hi;
             if (TERMS == 3) {
                 *(u32x4*)(lA + a_dst[i] + 64) = mid;
@@ -1168,7 +1112,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_x3_nt_kernel(const GemmP p) 
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             u32x4 hi, mid, lo;
-            split8(rb[i][0], rb[i][1], hi, mid, lo);
+            split3_bf16x8(rb[i][0], rb[i][1], hi, mid, lo);
             *(u32x4*)(lB + b_dst[i]) = hi;
             if (TERMS == 3) {
                 *(u32x4*)(lB + b_dst[i] + 64) = mid;

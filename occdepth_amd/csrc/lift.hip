@@ -12,13 +12,18 @@
 // Reference semantics: occdepth/models/SFA.py:12-106, occdepth/models/OccDepth.py:266-298,339;
 // occdepth/models/flosp_depth/flosp_depth.py:561-602, f2v/frustum_grid_generator.py:70-152,
 // f2v/utils/{transform_utils.py:5-26,depth_utils.py:24-26,grid_utils.py:4-19}, f2v/sampler.py:59-64.
-#include "common.h"
+#include "device.h"
 #include "project.h"
 #include <stdlib.h>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+// xcd_mode 2, plane-interleaved: every a-slab of `wps` workgroups (a multiple of 8) is shared out over the 8 XCDs in
+// contiguous runs, slab after slab (xcd_mode 1 is xcd_remap, device.h: one run per XCD over the whole grid)
+__device__ __forceinline__ uint32_t xcd_slab_interleave(uint32_t bid, uint32_t wps) {
+    const uint32_t per = wps >> 3, xcd = bid & 7, idx = bid >> 3;
+    return (idx / per) * wps + xcd * per + idx % per;
+}
 
 // ---- sum over the LPV lanes of a voxel group; result in every lane ---------
 template <int CTRL>
@@ -98,14 +103,8 @@ __global__ void __launch_bounds__(256) lift_p1_kernel(const LiftP pp) {
     // own L2).  A pixel row is re-read by the y / z neighbours of a voxel at the coarse scales and by the voxels further
     // along the same camera ray; which voxels share an L2 decides the HBM fetch (PMC numbers in DESIGN.md).
     uint32_t bid = blockIdx.x;
-    if (a.xcd_mode == 1) {
-        const uint32_t nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    } else if (a.xcd_mode == 2) {
-        const uint32_t wps = (uint32_t)((long)a.dimB * a.dimC * LPV / 256);      // workgroups per a-slab (multiple of 8)
-        const uint32_t per = wps >> 3, xcd = bid & 7, idx = bid >> 3;
-        bid = (idx / per) * wps + xcd * per + idx % per;
-    }
+    if (a.xcd_mode == 1) bid = xcd_remap(bid, gridDim.x);
+    else if (a.xcd_mode == 2) bid = xcd_slab_interleave(bid, (uint32_t)((long)a.dimB * a.dimC * LPV / 256));
     const long n = ((long)bid * 256 + tid) / LPV;
     const int b = blockIdx.y;
     const bool vox_ok = n < a.N;
@@ -563,14 +562,8 @@ __global__ void __launch_bounds__(256) lift_proj_kernel(const LiftProjP pp) {
     __shared__ float s_ds[T];
     const int tid = threadIdx.x;
     uint32_t bid = blockIdx.x;
-    if (a.xcd_mode == 1) {
-        const uint32_t nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    } else if (a.xcd_mode == 2) {
-        const uint32_t wps = (uint32_t)(((long)a.dimB * a.dimC) / T);       // workgroups per a-slab (multiple of 8)
-        const uint32_t per = wps >> 3, xcd = bid & 7, idx = bid >> 3;
-        bid = (idx / per) * wps + xcd * per + idx % per;
-    }
+    if (a.xcd_mode == 1) bid = xcd_remap(bid, gridDim.x);
+    else if (a.xcd_mode == 2) bid = xcd_slab_interleave(bid, (uint32_t)(((long)a.dimB * a.dimC) / T));
     const long n0 = (long)bid * T;
     const int b = blockIdx.y;
 

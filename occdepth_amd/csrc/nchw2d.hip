@@ -12,19 +12,9 @@
 //
 // Reference semantics: occdepth/models/unet2d.py:24-46 and the geffnet EfficientNet blocks (third party).
 #include <cstdlib>
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "device.h"
 
 namespace {
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == 1) return fmaxf(v, 0.f);                    // relu
-    if (act == 2) return occd::swish_fast(v);              // swish / silu
-    if (act == 3) return v > 0.f ? v : v * slope;          // leaky relu
-    return v;
-}
 
 // one (b, c) plane per blockIdx.y, grid-stride over the plane; float4 when the plane size allows
 __global__ void __launch_bounds__(256) affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res,
@@ -42,8 +32,8 @@ __global__ void __launch_bounds__(256) affine_act_kernel(const float* __restrict
         f32x4 r = {0.f, 0.f, 0.f, 0.f};
         if (res) r = *(const f32x4*)(res + off + i * 4);
         if (res_first) v += r;
-        v.x = act_apply(v.x, act, slope); v.y = act_apply(v.y, act, slope);
-        v.z = act_apply(v.z, act, slope); v.w = act_apply(v.w, act, slope);
+        v.x = act2d_fast(v.x, act, slope); v.y = act2d_fast(v.y, act, slope);
+        v.z = act2d_fast(v.z, act, slope); v.w = act2d_fast(v.w, act, slope);
         if (!res_first) v += r;
         *(f32x4*)(y + off + i * 4) = v;
     }
@@ -51,7 +41,7 @@ __global__ void __launch_bounds__(256) affine_act_kernel(const float* __restrict
         float v = x[off + i] * s + t;
         const float r = res ? res[off + i] : 0.f;
         if (res_first) v += r;
-        v = act_apply(v, act, slope);
+        v = act2d_fast(v, act, slope);
         if (!res_first) v += r;
         y[off + i] = v;
     }
@@ -113,7 +103,7 @@ __global__ void __launch_bounds__(256) dwconv2d_direct_kernel(const float* __res
 #pragma unroll
     for (int o = 0; o < NX; ++o)
         if (live && ox0 + o < Wo) {
-            const float v = act_apply(acc[o] * s + t, act, 0.f);
+            const float v = act2d_fast(acc[o] * s + t, act, 0.f);
             yp[o] = v;
             part += v;
         }
@@ -193,7 +183,7 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
 #pragma unroll
     for (int o = 0; o < NX; ++o)
         if (live && ox0 + o < Wo) {
-            const float v = act_apply(acc[o] * s + t, act, 0.f);
+            const float v = act2d_fast(acc[o] * s + t, act, 0.f);
             yp[o] = v;
             part += v;
         }
@@ -525,11 +515,7 @@ __global__ void __launch_bounds__(256) upconv_gather_kernel(const float* __restr
     // those rows came back from HBM twice (PMC: 2.2x the z tensor fetched).  XCD-aware bijective remap of the linear id,
     // then column-major tiles inside a plane: every XCD walks a contiguous run of vertically adjacent tiles.
     const uint32_t gx = gridDim.x, gy = gridDim.y, per_plane = gx * gy;
-    uint32_t bid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    {
-        const uint32_t nwg = per_plane * gridDim.z, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), per_plane * gridDim.z);
     const int plane = bid / per_plane;            // b * Cout + co
     const uint32_t local = bid - plane * per_plane;
     const int bx = local / gy, by = local - bx * gy;
@@ -1010,7 +996,7 @@ __global__ void __launch_bounds__(256, 2) stem_conv3x3_kernel(const float* __res
                 const int co = c0 + 4 * q + j;
                 if (co < Cout) {
                     const float o = acc[j] + (shift != nullptr ? shift[co] : 0.f);
-                    y[(((size_t)b * Cout + co) * Ho + oy) * Wo + ox] = act_apply(o, act, 0.f);
+                    y[(((size_t)b * Cout + co) * Ho + oy) * Wo + ox] = act2d_fast(o, act, 0.f);
                 }
             }
         }

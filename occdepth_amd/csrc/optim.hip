@@ -13,7 +13,7 @@
 // Deterministic: no atomics, no arrival counters, nothing to zero -- a captured launch needs no memset node.
 // The descriptor table is read through the pointer the caller gives (device memory or device-addressable pinned host
 // memory); each workgroup fetches its 64-byte descriptor once, into LDS.
-#include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -25,7 +25,6 @@ static_assert(sizeof(occd_optim_chunk) == 64, "one descriptor = one 64-byte fetc
 // flat_ accesses (which also tick the LDS counter); the address-space qualifier makes them global_load / global_store.
 typedef __attribute__((address_space(1))) float gfloat;
 typedef __attribute__((address_space(1))) const float gcfloat;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) f32x4 gf32x4;
 typedef __attribute__((address_space(1))) const f32x4 gcf32x4;
 

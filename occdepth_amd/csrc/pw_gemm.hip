@@ -23,10 +23,7 @@
 // Reference semantics replaced: the conv_pw / conv_pwl / conv_head 1x1 convolutions + BatchNorm + Swish + SE gate
 // + skip of the geffnet EfficientNet blocks behind occdepth/models/unet2d.py:175-190, and the `resize_output_1_s`
 // 1x1 convolutions of DecoderBN (unet2d.py:137-165), DepthNet.depth_pred (flosp_depth.py:225-227).
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "device.h"
 
 namespace {
 
@@ -46,13 +43,6 @@ struct PwP {
     int ntiles, mtiles;
     int out_cs;                 // NHWC output: floats per pixel row
 };
-
-__device__ __forceinline__ float pw_act(float v, int act, float slope) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return occd::swish_fast(v);
-    if (act == 3) return v > 0.f ? v : v * slope;
-    return v;
-}
 
 // (second launch bound = workgroups per CU = waves per SIMD: 128 accumulator registers leave room for 2, 64 for 3)
 // NHWC: the output is written pixel-major, y[b][n][co] (rows of out_cs floats) -- what the 2D->3D lift gathers from.
@@ -170,7 +160,7 @@ __global__ void __launch_bounds__(256, (MT * NT > 4 ? 2 : 3)) pw_gemm_kernel(con
                 for (int r = 0; r < 16; ++r) {
                     const long n = n0 + nt * 32 + 8 * (r >> 2) + 4 * kk + (r & 3);
                     if (n >= p.N) continue;
-                    const float v = pw_act(acc[mt][nt][r] + sh, p.act, p.slope);
+                    const float v = act2d_fast(acc[mt][nt][r] + sh, p.act, p.slope);
                     p.y[((size_t)b * p.N + n) * p.out_cs + co] = real ? v : 0.f;     // (channel pad written as zeros)
                 }
         }
@@ -190,7 +180,7 @@ __global__ void __launch_bounds__(256, (MT * NT > 4 ? 2 : 3)) pw_gemm_kernel(con
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (!colok[nt]) continue;
-                float v = pw_act(acc[mt][nt][r] + sh, p.act, p.slope);
+                float v = act2d_fast(acc[mt][nt][r] + sh, p.act, p.slope);
                 if (p.res != nullptr) v += p.res[row + col[nt]];
                 p.y[row + col[nt]] = v;
             }
@@ -325,14 +315,14 @@ __global__ void __launch_bounds__(KS * 64) pw_gemm_splitk_kernel(const PwP p) {
             const long n = n0 + nt * 32 + sub;
             if (mb0 + mt >= p.mblocks || co >= p.out_cs || n >= p.N) continue;
             const bool real = co < p.Cout;
-            v = pw_act(v + (real && p.shift != nullptr ? p.shift[co] : 0.f), p.act, p.slope);
+            v = act2d_fast(v + (real && p.shift != nullptr ? p.shift[co] : 0.f), p.act, p.slope);
             p.y[((size_t)b * p.N + n) * p.out_cs + co] = real ? v : 0.f;             // (channel pad written as zeros)
         } else {
             const int co = (mb0 + mt) * 32 + sub;
             const long n = n0 + nt * 32 + li;
             if (mb0 + mt >= p.mblocks || co >= p.Cout || n >= p.N) continue;
             const size_t o = ((size_t)b * p.Cout + co) * p.N + n;
-            v = pw_act(v + (p.shift != nullptr ? p.shift[co] : 0.f), p.act, p.slope);
+            v = act2d_fast(v + (p.shift != nullptr ? p.shift[co] : 0.f), p.act, p.slope);
             if (p.res != nullptr) v += p.res[o];
             p.y[o] = v;
         }

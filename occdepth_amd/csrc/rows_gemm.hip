@@ -11,9 +11,7 @@
 // Only the weights go through LDS (fragment order, double buffered, 32 k x 128 n per stage).
 // A workgroup = 4 waves x 16 rows x 128 columns.  Reference call sites: occdepth/models/CRP3D.py:54-97 (context_prior_logits,
 // the bmm, resize), DDR.py:33,42 (conv1 / conv5 of the strided bottlenecks).
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "device.h"
 
 namespace {
 
@@ -25,16 +23,6 @@ struct RowsP {
     int act_in, act_out;
     int ntiles;               // ceil(N / 128)
 };
-
-__device__ __forceinline__ f32x4 act4(f32x4 v, int act) {
-    if (act == OCCD_ACT_RELU) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    } else if (act == OCCD_ACT_SIGMOID) {      // the same expression as K2's apply_act: bit-identical operands
-        v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y));
-        v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-    }
-    return v;
-}
 
 constexpr int kStageK = 32;                    // k per weight stage (2 super-steps)
 constexpr int kTileN = 128;                    // columns per workgroup (8 MFMA row blocks of the transposed product)
@@ -80,7 +68,7 @@ __global__ void __launch_bounds__(256) rows_gemm_kernel(const RowsP p) {
         const bool more = s + 1 < stages;
         f32x4 d[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) d[t] = act4(dn[t], p.act_in);
+        for (int t = 0; t < 2; ++t) d[t] = act3d_x4(dn[t], p.act_in);
         if (p.act_in != OCCD_ACT_NONE) {                   // act(0) of the masked lanes must stay 0 (sigmoid(0) = 0.5)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -114,9 +102,9 @@ __global__ void __launch_bounds__(256) rows_gemm_kernel(const RowsP p) {
         if (n >= p.N) continue;
         f32x4 v = acc[m];
         if (p.bias) v += *(const f32x4*)(p.bias + n);
-        if (p.act_out == OCCD_ACT_RELU_PRE) v = act4(v, OCCD_ACT_RELU);
+        if (p.act_out == OCCD_ACT_RELU_PRE) v = act3d_x4(v, OCCD_ACT_RELU);
         if (p.res) v += *(const f32x4*)(p.res + (size_t)row * p.res_cs + p.res_coff + n);
-        if (p.act_out == OCCD_ACT_RELU) v = act4(v, OCCD_ACT_RELU);
+        if (p.act_out == OCCD_ACT_RELU) v = act3d_x4(v, OCCD_ACT_RELU);
         *(f32x4*)(p.out + (size_t)row * p.out_cs + p.out_coff + n) = v;
     }
 }

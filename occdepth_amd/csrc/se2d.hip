@@ -6,7 +6,7 @@
 //   se_expand_kernel : gate[b][c] = sigmoid(sum_i We[c][i] r[b][i] + be[c])
 // Both are tiny GEMVs (C <= 3840, Cr <= 160) spread over enough workgroups that no single CU streams the weights.
 // Reference: geffnet SqueezeExcite behind occdepth/models/unet2d.py:175-190.
-#include "common.h"
+#include "device.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -93,7 +93,6 @@ __global__ void __launch_bounds__(256) se_expand_kernel(const float* __restrict_
 // the weight row (the 4 lanes of a channel read 64 consecutive bytes per step), ALL of its <= kEPre chunk loads are
 // issued before the first is used (one memory round trip instead of Cr / 4 dependent ones), quad reduction on DPP.
 constexpr int kEPre = 12;                                  // float4 chunks a lane preloads: Cr <= 16 * kEPre = 192
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(256) se_expand4_kernel(const float* __restrict__ r, const float* __restrict__ we,
                                                          const float* __restrict__ be, float* __restrict__ gate, int C,
                                                          int Cr) {

@@ -13,20 +13,13 @@
 // high-resolution levels the V / M round trip costs more than it saves and MIOpen stays.
 //
 // Reference semantics: nn.Conv2d(k=3, s=1, p=1) + BatchNorm2d (eval) + LeakyReLU of occdepth/models/unet2d.py:24-46.
-#include "common.h"
+#include "device.h"
 
 namespace {
 
 constexpr int kTilesX = 32;                 // tiles per workgroup along x (64 output columns)
 constexpr int kCh = 32;                     // channels per workgroup
 constexpr int kCols = 2 * kTilesX + 2;      // staged input columns (one halo column each side)
-
-__device__ __forceinline__ float act_apply2(float v, int act, float slope) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return v / (1.f + expf(-v));
-    if (act == 3) return v > 0.f ? v : v * slope;
-    return v;
-}
 
 // grid: (ceil(tw / 32), th, B * ceil(Cin / 32)); 256 threads
 // (ty0, ths): the tile rows [ty0, ty0 + ths) of every image form the T = B * ths * tw rows of this call's V (a strip)
@@ -132,7 +125,7 @@ __global__ void __launch_bounds__(256) wino_output_kernel(const float* __restric
         float v = tile[cc][r * 2 * kTilesX + col];
         v = v * (scale != nullptr ? scale[ch] : 1.f) + (shift != nullptr ? shift[ch] : 0.f);
         if (res != nullptr && res_first) v += res[idx];
-        v = act_apply2(v, act, slope);
+        v = act2d_exact(v, act, slope);
         if (res != nullptr && !res_first) v += res[idx];
         y[idx] = v;
     }

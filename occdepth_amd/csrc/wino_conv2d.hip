@@ -28,11 +28,7 @@
 // occdepth/models/unet2d.py:24-46 (UpSampleBN), and the 3x3 convolutions of DepthNet / BasicBlock
 // (occdepth/models/flosp_depth/flosp_depth.py:201-257).
 #include <type_traits>
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "device.h"
 
 namespace {
 
@@ -47,13 +43,6 @@ struct WinoP {
     int act, res_first;
     float slope;
 };
-
-__device__ __forceinline__ float wino_act(float v, int act, float slope) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return v / (1.f + expf(-v));
-    if (act == 3) return v > 0.f ? v : v * slope;
-    return v;
-}
 
 // TWV: tiles per wave pair along x.  16 -> a pair is 2 x 16 tiles (4 x 32 pixels), a workgroup 8 x 16 tiles;
 //                                    32 -> a pair is 1 x 32 tiles (2 x 64 pixels), a workgroup 4 x 32 tiles.
@@ -108,11 +97,7 @@ __global__ void __launch_bounds__(512, 2) wino3x3_kernel(const WinoP p) {
     const int li = lane & 31, kk = lane >> 5;
 
     // XCD-aware bijective remap (cout blocks of one tile block stay on one XCD's L2: they re-read the same patch)
-    uint32_t bid = blockIdx.x;
-    {
-        const uint32_t nwg = p.nwg, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
     const int nb = bid % p.nblk;
     uint32_t t = bid / p.nblk;
     const int bx = t % p.wg_tx;
@@ -327,8 +312,8 @@ __global__ void __launch_bounds__(512, 2) wino3x3_kernel(const WinoP p) {
                 if (ox + 1 < p.W) r1 = p.res[o + 1];
             }
             if (p.res_first) { y0 += r0; y1 += r1; }
-            y0 = wino_act(y0, p.act, p.slope);
-            y1 = wino_act(y1, p.act, p.slope);
+            y0 = act2d_exact(y0, p.act, p.slope);
+            y1 = act2d_exact(y1, p.act, p.slope);
             if (!p.res_first) { y0 += r0; y1 += r1; }
             if (pair) {
                 *(f32x2*)(p.y + o) = f32x2{y0, y1};

@@ -45,7 +45,8 @@ extern "C" {
  * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix;
  * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida;
  * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw;
- * 19: occd_kitti_labels). */
+ * 19: occd_kitti_labels;
+ * 20: occd_optim_chunk.acc, occd_accum_adamw_args, occd_accum_clip_adamw). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -944,7 +945,7 @@ typedef struct occd_optim_chunk {      /* 64 bytes: one fetch per workgroup     
     int64_t offset;                    /* first element of this chunk inside the tensor                              */
     int32_t count;                     /* elements of this chunk, 0 .. OCCD_OPTIM_CHUNK (0: an empty tensor)         */
     int32_t reserved0;
-    int64_t reserved1;
+    float* acc;                        /* gradient accumulator of a window of micro-batches (occd_accum_clip_adamw), or NULL */
 } occd_optim_chunk;
 
 typedef struct occd_clip_adamw_args {
@@ -959,6 +960,41 @@ typedef struct occd_clip_adamw_args {
 } occd_clip_adamw_args;
 int occd_grad_sumsq(const occd_clip_adamw_args* a, void* stream);
 int occd_clip_adamw(const occd_clip_adamw_args* a, void* stream);
+
+/* Gradient accumulation over a window of N micro-batches, fused into the clip + AdamW above (what
+ * `Trainer(accumulate_grad_batches=N)` does under automatic optimisation: backward of loss / N into p.grad N times, then
+ * clip_grad_norm_ and AdamW.step() once).  Called once per micro-batch with the micro-batch's position in its window:
+ *
+ *   every micro-batch   1 launch, one workgroup per descriptor: acc = scale g when `first` (an overwrite: accumulators are
+ *                       never zeroed and never read before they are written), else acc = acc + scale g; float64
+ *                       arithmetic, each stored value rounded once; 4 + 8 bytes per element (4 + 4 when `first`).
+ *   when `last`         the same workgroups also leave the sum of squares of the acc values they stored in partials[chunk]
+ *                       (max_norm > 0 only) and advance every tensor's `step`; then the norm finalise of occd_grad_sumsq
+ *                       (max_norm > 0 only) and the update of occd_clip_adamw with acc in place of g.  max_norm <= 0: no
+ *                       clipping -- no norm is computed, norm_out is not touched and the coefficient is exactly 1.
+ *   when not `last`     p, m, v, step and norm_out keep their bits.
+ *
+ * The position comes from `flags_dev` (two device int32: first, last) when it is not NULL -- then all three launches are
+ * always enqueued and leave early by themselves, which is what a captured graph needs: one capture serves every position
+ * and the caller rewrites the two ints before a replay -- else from the host ints `first` / `last`, and the launches a
+ * non-closing micro-batch does not need are not made.  Every descriptor's `acc` must be set, n elements like its tensor,
+ * with the same offset to a 16-byte boundary as `p`; `g` may sit at any 4-byte alignment and is never written.  No
+ * atomics, nothing to zero, bit-identical from run to run; with scale = 1 and first = last = 1 the results are those of
+ * occd_clip_adamw. */
+typedef struct occd_accum_adamw_args {
+    const occd_optim_chunk* chunks;    /* n_chunks descriptors with `acc` set                                        */
+    double* partials;                  /* n_chunks float64, device workspace (max_norm > 0)                          */
+    float* norm_out;                   /* 2 device floats: total_norm, clip_coef of the last closed window (max_norm > 0) */
+    const float* lr_dev;               /* device scalar learning rate, or NULL                                       */
+    const int32_t* flags_dev;          /* 2 device ints {first, last}, or NULL: the host ints below                  */
+    int64_t n_chunks;
+    int64_t n_elems;                   /* elements over all chunks (profiling only)                                  */
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_norm;                   /* <= 0: no clipping                                                          */
+    double scale;                      /* 1 / N, in (0, 1]                                                           */
+    int32_t first, last;               /* read when flags_dev is NULL                                                */
+} occd_accum_adamw_args;
+int occd_accum_clip_adamw(const occd_accum_adamw_args* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Small-message all-reduce over peer-mapped device memory (round 5; csrc/ipc_allreduce.hip): the latency-optimal form

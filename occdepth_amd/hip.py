@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 MAX_VIEWS = 4
 MAX_SCALES = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 19   # 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+ABI_VERSION = 20   # 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
 
 _c_float_p = POINTER(c_float)
 
@@ -150,13 +150,20 @@ OPTIM_CHUNK = 8192   # OCCD_OPTIM_CHUNK: elements per chunk descriptor
 
 class OptimChunk(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("step", c_void_p),
-                ("offset", c_int64), ("count", c_int32), ("reserved0", c_int32), ("reserved1", c_int64)]
+                ("offset", c_int64), ("count", c_int32), ("reserved0", c_int32), ("acc", c_void_p)]
 
 
 class ClipAdamWArgs(Structure):
     _fields_ = [("chunks", c_void_p), ("partials", c_void_p), ("norm_out", c_void_p), ("lr_dev", c_void_p),
                 ("n_chunks", c_int64), ("n_elems", c_int64)] + \
         [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
+
+
+class AccumAdamWArgs(Structure):
+    _fields_ = [("chunks", c_void_p), ("partials", c_void_p), ("norm_out", c_void_p), ("lr_dev", c_void_p),
+                ("flags_dev", c_void_p), ("n_chunks", c_int64), ("n_elems", c_int64)] + \
+        [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "scale")] + \
+        [("first", c_int32), ("last", c_int32)]
 
 
 class ProfRow(Structure):
@@ -304,6 +311,7 @@ EXPORTS = {
     "occd_kitti_labels": (c_int32, [c_void_p] * 4 + [c_int32] + [c_void_p] * 3 + [c_int32, c_int64, c_void_p]),
     "occd_grad_sumsq": (c_int32, [POINTER(ClipAdamWArgs), c_void_p]),
     "occd_clip_adamw": (c_int32, [POINTER(ClipAdamWArgs), c_void_p]),
+    "occd_accum_clip_adamw": (c_int32, [POINTER(AccumAdamWArgs), c_void_p]),
     "occd_prof_set_tag": (c_int32, [c_char_p]),
     "occd_prof_report": (c_int32, [POINTER(ProfRow), c_int32]),
 }

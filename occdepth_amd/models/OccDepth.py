@@ -81,10 +81,12 @@ class OccDepth(_Base):
         # unmodified scripts/train.py run -- switches the module to manual optimisation: `training_step` then replays the
         # WHOLE step (forward, losses, backward, gradient exchange, [gradient-norm clip +] AdamW) from one hipGraph (train_graph.GraphedTrainStep,
         # the step bench.py --train times).  OCCDEPTH_FAST_TRAIN_BF16=1: the bf16-MFMA convolution mode of configs[3].
+        # OCCDEPTH_FAST_TRAIN_ACCUM=N: gradient accumulation over N micro-batches (`_accumulate_value`).
         self._fast_train = None
         self._opt = self._sched = None
         self.fast_train = False
         self.fast_train_grad_clip = None
+        self.fast_train_accumulate = None
         if env("OCCDEPTH_FAST_TRAIN", "0") == "1":
             self.enable_fast_train(bf16=env("OCCDEPTH_FAST_TRAIN_BF16", "0") == "1")
         self.fused_lift = True    # training on the GPU: HIP lift + one-launch backward (lift_autograd.py) where it applies
@@ -201,13 +203,18 @@ class OccDepth(_Base):
         self._drop_graphs()
         return self
 
-    def enable_fast_train(self, bf16=False, autocast=False, grad_clip=None):
+    def enable_fast_train(self, bf16=False, autocast=False, grad_clip=None, accumulate=None):
         """Manual optimisation + the whole training step as ONE replayed hipGraph (see `_fast_training_step`).  Call before
         `trainer.fit` (Lightning reads `automatic_optimization` when the loop starts).  `grad_clip`: global gradient-norm
         clip for callers without a Trainer (0 = none); left at None, the attached Trainer's `gradient_clip_val` is used
-        (`_grad_clip_value`) -- under manual optimisation Lightning itself no longer clips."""
+        (`_grad_clip_value`) -- under manual optimisation Lightning itself no longer clips.  `accumulate`: gradient
+        accumulation over N micro-batches; left at None, OCCDEPTH_FAST_TRAIN_ACCUM, then the Trainer's
+        `accumulate_grad_batches` (`_accumulate_value`) -- which Lightning skips too under manual optimisation."""
+        if accumulate is not None:
+            self._check_accumulate(accumulate, "enable_fast_train(accumulate=...)")
         self.fast_train = True
         self.fast_train_grad_clip = grad_clip
+        self.fast_train_accumulate = accumulate
         self.fast_train_bf16, self.fast_train_autocast = bool(bf16), bool(autocast)
         self.automatic_optimization = False
         self._fast_train = None
@@ -881,6 +888,54 @@ class OccDepth(_Base):
                                       "(Trainer(gradient_clip_algorithm='value') is not implemented)")
         return float(val)
 
+    @staticmethod
+    def _check_accumulate(n, where):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"occdepth_amd: {where} must be an int >= 1, got {n!r}")
+        return n
+
+    def _accumulate_value(self):
+        """N of the fast training step's gradient accumulation, first hit wins: `enable_fast_train(accumulate=...)`, then
+        OCCDEPTH_FAST_TRAIN_ACCUM in the environment (the route for an unmodified scripts/train.py, whose Trainer(...) call
+        passes no `accumulate_grad_batches`), then the attached Trainer's `accumulate_grad_batches`, else 1.  With
+        `automatic_optimization = False` Lightning 1.4.9 skips accumulation together with backward, clipping and
+        optimizer.step.  Anything but an int >= 1 (a per-epoch schedule dict among them) raises ValueError."""
+        if self.fast_train_accumulate is not None:
+            return self._check_accumulate(self.fast_train_accumulate, "enable_fast_train(accumulate=...)")
+        env = os.environ.get("OCCDEPTH_FAST_TRAIN_ACCUM")
+        if env is not None and env.strip() != "":
+            try:
+                n = int(env.strip())
+            except ValueError:
+                raise ValueError(f"occdepth_amd: OCCDEPTH_FAST_TRAIN_ACCUM must be an int >= 1, got {env!r}") from None
+            return self._check_accumulate(n, "OCCDEPTH_FAST_TRAIN_ACCUM")
+        try:
+            trainer = getattr(self, "trainer", None)
+        except RuntimeError:                                 # newer Lightning: the property raises while no Trainer is attached
+            trainer = None
+        if trainer is None:
+            return 1
+        return self._check_accumulate(getattr(trainer, "accumulate_grad_batches", 1), "Trainer(accumulate_grad_batches=...)")
+
+    def _window_position(self, st, batch_idx):
+        """pytorch-lightning 1.4.9's rule under automatic optimisation (TrainingBatchLoop.should_accumulate): the window
+        closes when (batch_idx + 1) % N == 0 or with the epoch's last batch; the scale stays 1/N for an epoch's short last
+        window.  It opens at batch_idx % N == 0 -- or wherever no window is open on the host (a run resumed in the middle
+        of a window must not read accumulators nobody wrote)."""
+        n = self._accumulate_value()
+        if n != st["accumulate"]:
+            raise ValueError(f"occdepth_amd: gradient accumulation changed from {st['accumulate']} to {n} after the first fast "
+                             "training step; call enable_fast_train() again to start over")
+        w = st["window"]
+        if w is None:
+            return
+        try:
+            trainer = getattr(self, "trainer", None)
+        except RuntimeError:
+            trainer = None
+        last = (batch_idx + 1) % n == 0 or batch_idx + 1 == getattr(trainer, "num_training_batches", None)
+        w.set(batch_idx % n == 0 or not w.is_open, last)
+
     def _fast_training_step(self, batch, batch_idx):
         """`training_step` under manual optimisation (`automatic_optimization = False`: Lightning 1.4.9 then calls neither
         backward nor optimizer.step, models/OccDepth.py:535-541 + scripts/train.py:208 otherwise drive them eagerly).
@@ -891,14 +946,20 @@ class OccDepth(_Base):
         `shard.GradBuckets` (captured with the step) and DDP's hooks stay idle.  What the replay cannot do is done here:
         `self.log` of the step's loss terms (device scalars the graph writes), the host counters (GraphedTrainStep.__call__).
         Falls back to the eager manual step with a warning when the capture fails, on the CPU, or for a batch whose
-        keys / shapes differ from the captured one (that batch alone runs eagerly)."""
+        keys / shapes differ from the captured one (that batch alone runs eagerly).
+        Gradient accumulation (`_accumulate_value` = N > 1): every call is one micro-batch of a window of N
+        (`_window_position`); replayed and eager micro-batches share ONE `optim.GradWindow` of the optimizer, so a window
+        may mix them.  With `GradBuckets` the all-reduce runs every micro-batch -- correct, averaging is linear; skipping it
+        on the micro-batches that do not close a window is not done."""
         import warnings
-        from .. import autograd3d, shard, train_graph
+        from .. import autograd3d, optim, shard, train_graph
         on_gpu = next(self.parameters()).is_cuda
         opt = self._fast_optimizer()
         st = self._fast_train
         if st is None:
-            st = self._fast_train = {"graph": None, "sig": None, "buckets": None, "warned": False, "logged": None}
+            n_acc = self._accumulate_value()
+            st = self._fast_train = {"graph": None, "sig": None, "buckets": None, "warned": False, "logged": None,
+                                     "accumulate": n_acc, "window": optim.GradWindow(opt, n_acc) if n_acc > 1 else None}
             if on_gpu:
                 import torch.distributed as dist
                 if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -909,7 +970,8 @@ class OccDepth(_Base):
                 if self.fast_train_bf16:
                     autograd3d.set_bf16_mfma(True)
                 gs = train_graph.GraphedTrainStep(self, opt, static, bf16=self.fast_train_autocast, buckets=st["buckets"],
-                                                  warmup=2, batch_idx=batch_idx, grad_clip=self._grad_clip_value())
+                                                  warmup=2, batch_idx=batch_idx, grad_clip=self._grad_clip_value(),
+                                                  accumulate=n_acc, window=st["window"])
                 self.__dict__["_in_fast_step"] = True
                 try:
                     ok = gs.capture()
@@ -922,6 +984,7 @@ class OccDepth(_Base):
             else:
                 warnings.warn("occdepth_amd: OCCDEPTH_FAST_TRAIN needs the model on the GPU; running the eager manual step")
         gs = st["graph"]
+        self._window_position(st, batch_idx)
         self.__dict__["_in_fast_step"] = True
         try:
             if gs is not None and self._batch_signature(batch) == st["sig"]:
@@ -943,7 +1006,8 @@ class OccDepth(_Base):
 
     def _manual_eager_step(self, batch, batch_idx, opt, buckets=None):
         """One manual-optimisation step without a graph: zero_grad, training_step, backward, [gradient average], optimizer
-        -- with a clip value set (`_grad_clip_value`), `optim.clip_adamw_step`: clip_grad_norm_ + AdamW, norm logged."""
+        -- with a clip value set (`_grad_clip_value`), `optim.clip_adamw_step`: clip_grad_norm_ + AdamW, norm logged.
+        With gradient accumulation the optimizer stage is one micro-batch of the step's window (`_fast_training_step`)."""
         if buckets is not None:
             buckets.zero_grad()
         else:
@@ -954,7 +1018,13 @@ class OccDepth(_Base):
         if buckets is not None:
             buckets.finish()
         clip = self._grad_clip_value()
-        if clip is None:
+        window = (self._fast_train or {}).get("window")
+        if window is not None:
+            from .. import optim
+            norm = optim.clip_adamw_step(opt, clip, window=window)
+            if norm is not None:                             # the last closed window's
+                self._log("train/grad_norm", norm)
+        elif clip is None:
             opt.step()
         else:
             from .. import optim

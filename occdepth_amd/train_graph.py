@@ -22,6 +22,9 @@ What a replay does and does not advance (the captured Python code does not run a
 Warm-up: capture needs the optimizer state allocated and the libraries' solvers chosen, which takes real eager steps.
 They run on a SNAPSHOT: parameters, buffers, optimizer state, metric counts and `cur_batch` are restored afterwards, so
 capturing (or re-capturing) trains nothing -- the reference's eager Lightning loop has no such extra steps.
+Gradient accumulation (`accumulate=N`, the Trainer's `accumulate_grad_batches`): every replay is one MICRO-batch; its
+position in the window of N is fed through two device ints (`gs.window.set(first, last)` before `gs()`), so the one
+captured graph accumulates on every replay and clips + updates only on the closing one (optim.GradWindow).
 Reference: scripts/train.py:176-206 drives the same step through PyTorch-Lightning, eagerly.
 """
 import contextlib
@@ -72,8 +75,9 @@ def make_capturable(opt):
 class _Snapshot:
     """Everything a warm-up step mutates, restored in place (same tensors, same pointers)."""
 
-    def __init__(self, model, opt):
-        self.model, self.opt = model, opt
+    def __init__(self, model, opt, window=None):
+        self.model, self.opt, self.window = model, opt, window
+        self.window_state = None if window is None else window.state()     # accumulators, norm, position
         self.tensors = [(t, t.detach().clone()) for t in list(model.parameters()) + list(model.buffers())]
         self.opt_state = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                           for p, st in opt.state.items()}
@@ -103,6 +107,8 @@ class _Snapshot:
                     else:
                         m.hist.zero_()
                 m.count = count
+            if self.window is not None:
+                self.window.restore(self.window_state)
         if self.cur_batch is not None:
             self.model.cur_batch = self.cur_batch
 
@@ -121,11 +127,28 @@ class GraphedTrainStep:
     """`grad_clip`: the Trainer's `gradient_clip_val` (global 2-norm, every reference yaml sets 35).  None or 0: the step
     ends in `opt.step()`.  Otherwise it ends in `optim.clip_adamw_step` -- the norm of the (averaged) gradients, the clip
     coefficient and the AdamW update in three HIP launches -- and publishes the norm as the device scalar
-    `model.logged["train/grad_norm"]`, which replays keep up to date."""
+    `model.logged["train/grad_norm"]`, which replays keep up to date.
 
-    def __init__(self, model, opt, batch, bf16=False, buckets=None, warmup=3, batch_idx=0, grad_clip=None):
+    `accumulate`: N > 1 makes every call one micro-batch of a window of N (optim.GradWindow, exposed as `.window`; a
+    window made elsewhere for the same optimizer may be handed in as `window`).  The step then ends in
+    `optim.clip_adamw_step(..., window=...)` with or without a clip: the gradient, times 1/N, goes into the window's
+    accumulators, and the micro-batch that closes the window clips and updates.  Set the position with
+    `gs.window.set(first, last)` before `gs()`; host counters advance per micro-batch, `train/grad_norm` is the last
+    closed window's.  With `buckets` the gradient average runs every micro-batch (averaging is linear, so the result is
+    right; skipping it on non-closing micro-batches is not done).  accumulate=1 builds no window and captures the graph it captures without the argument."""
+
+    def __init__(self, model, opt, batch, bf16=False, buckets=None, warmup=3, batch_idx=0, grad_clip=None, accumulate=1,
+                 window=None):
         self.model, self.opt, self.batch, self.bf16, self.buckets, self.batch_idx = model, opt, batch, bf16, buckets, batch_idx
         self.grad_clip = grad_clip
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f"GraphedTrainStep: accumulate must be an int >= 1, got {accumulate!r}")
+        if window is not None and (window.n != accumulate or window.opt is not opt):
+            raise ValueError("GraphedTrainStep: `window` belongs to another optimizer or has another length than `accumulate`")
+        if window is None and accumulate > 1:
+            from . import optim
+            window = optim.GradWindow(opt, accumulate)
+        self.accumulate, self.window = accumulate, window
         self._optim_tables = None
         make_capturable(opt)
         self.graph = None
@@ -149,10 +172,15 @@ class GraphedTrainStep:
 
     def _optimizer_step(self):
         from . import optim
-        if not optim.clipping_enabled(self.grad_clip):
+        if self.window is not None:
+            norm = optim.clip_adamw_step(self.opt, self.grad_clip, window=self.window)
+            if norm is None:                                # no clipping (or, on the torch path, no window closed yet)
+                return
+        elif not optim.clipping_enabled(self.grad_clip):
             self.opt.step()
             return
-        norm = optim.clip_adamw_step(self.opt, self.grad_clip)       # after the gradient average: the norm DDP would clip
+        else:
+            norm = optim.clip_adamw_step(self.opt, self.grad_clip)   # after the gradient average: the norm DDP would clip
         logged = getattr(self.model, "logged", None)
         if isinstance(logged, dict):
             logged["train/grad_norm"] = norm.detach()
@@ -170,9 +198,12 @@ class GraphedTrainStep:
     def capture(self):
         dev = next(self.model.parameters()).device
         torch.cuda.synchronize(dev)
-        snap = _Snapshot(self.model, self.opt)
+        snap = _Snapshot(self.model, self.opt, self.window)
         self.model.cur_batch = getattr(self.model, "cur_batch", 0)
         self._sync_decay()
+        if self.window is not None:
+            self.window.set(True, True)                     # warm-up steps close their window: every kernel runs, the optimizer
+                                                            # state exists before the capture (the snapshot restores the position)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -183,9 +214,9 @@ class GraphedTrainStep:
         graph = new_graph()
         if self.buckets is None:
             self.opt.zero_grad(set_to_none=True)            # gradients are (re)allocated inside the graph's pool
-        if self.grad_clip:
+        if self.grad_clip or self.window is not None:
             from . import optim
-            optim.prepare_capture(self.opt)                 # new gradient pointers -> a new descriptor table, built under capture
+            optim.prepare_capture(self.opt, self.window)    # new gradient pointers -> a new descriptor table, built under capture
         ok = True
         try:
             with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
@@ -199,8 +230,8 @@ class GraphedTrainStep:
         torch.cuda.synchronize(dev)
         if ok:
             self.graph = graph
-            if self.grad_clip:
-                self._optim_tables = optim.live_tables(self.opt)    # what the captured launches read lives as long as the graph
+            if self.grad_clip or self.window is not None:
+                self._optim_tables = optim.live_tables(self.opt, self.window)    # what the captured launches read lives as long as the graph
         return ok
 
     recapture = capture

@@ -46,7 +46,8 @@ extern "C" {
  * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida;
  * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw;
  * 19: occd_kitti_labels;
- * 20: occd_optim_chunk.acc, occd_accum_adamw_args, occd_accum_clip_adamw). */
+ * 20: occd_optim_chunk.acc, occd_accum_adamw_args, occd_accum_clip_adamw;
+ * 21: occd_wino_packed_f16x2_bytes, occd_wino_pack_weights_f16x2, occd_wino_conv3x3_f16x2_fwd). */
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 
@@ -511,6 +512,18 @@ typedef struct occd_wino_args {
 int64_t occd_wino_packed_floats(int32_t cout, int32_t cin);
 int occd_wino_pack_weights(const float* w, const float* scale, float* upk, int32_t cout, int32_t cin, void* stream);
 int occd_wino_conv3x3_fwd(const occd_wino_args* a, void* stream);
+
+/* K10h: the same convolution (same arguments, checks, epilogue and tile hints) on the f16 matrix pipe with the two-term
+ * fp16 split of both operands -- three v_mfma_f32_32x32x16_f16 per Winograd position and 16 input channels, float32
+ * accumulation; error against float64 within 2x of K10's (tests/test_wino_f16x2.py).  Finite activations with
+ * |x| >= 8190 may give non-finite outputs (the transformed patch, |V| <= 4 max|x|, is staged as fp16(2 V)).
+ * a->upk: the image of occd_wino_pack_weights_f16x2 (occd_wino_packed_f16x2_bytes(Cout, Cin) bytes, 16-byte aligned):
+ *      fp16 [ceil(Cin/16)][16 positions][hi, lo][ceil(Cout/32)][64 lanes][8] of U' = 2^k[co] G g G^T scale (max |U'| of a
+ *      cout in [2^13, 2^14)), A-fragment order, then ceil(Cout/32) * 32 floats 2^-(k[co] + 1).  The pack synchronises
+ *      the stream and returns OCCD_EINVAL when a weight (times scale) is not finite (keep K10's image then).        */
+int64_t occd_wino_packed_f16x2_bytes(int32_t cout, int32_t cin);
+int occd_wino_pack_weights_f16x2(const float* w, const float* scale, void* upk, int32_t cout, int32_t cin, void* stream);
+int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream);
 
 /* Backward of the depthwise convolution (autograd of the geffnet conv_dw layers in training_step):
  *   data  : dx (B, C, H, W) from gy (B, C, Ho, Wo) and w (C, 1, k, k), same geometry arguments as the forward;

@@ -28,6 +28,7 @@
 // occdepth/models/unet2d.py:24-46 (UpSampleBN), and the 3x3 convolutions of DepthNet / BasicBlock
 // (occdepth/models/flosp_depth/flosp_depth.py:201-257).
 #include <type_traits>
+#include <vector>
 #include "device.h"
 
 namespace {
@@ -43,6 +44,95 @@ struct WinoP {
     int act, res_first;
     float slope;
 };
+
+// The pair exchange and the epilogue of K10 and K10h (FAC: K10h's per-cout factor in front of the shift).
+// ---------------- pair exchange: wave half h finishes the cout registers r in [8h, 8h + 8) and needs the partner's 8 xi for
+// them.  xchg[pair][writer half][k * 8 + (r & 7)][lane]  (the staging buffers are dead: the caller's last barrier)
+// Both are instantiated once per domain half, like the K loop: with a run-time `h` the accumulator registers are picked by a
+// wave-uniform but DYNAMIC index, which hipcc lowers to s_set_gpr_idx moves through a 16-register VGPR copy of each tile --
+// that copy was the kernel's 16 - 50 spilled VGPRs.  Only the register selection is specialised; the
+// barrier between the exchange write and the exchange read is ONE instruction that every wave of the workgroup reaches on the
+// same path (the two halves used to meet at two different s_barrier instructions, which works on gfx950's
+// arrival-counting barrier but is not defined behaviour).
+// ---------------- epilogue: Y = A^T m A (A^T = [1 1 1 0; 0 1 -1 -1]), (factor,) shift, activation, residual, NCHW store.
+// D = U^T-rows x tile-columns: the lane is tile `lane & 31` of the pair and register r is cout 8 (r >> 2) + 4 (lane >> 5) + (r & 3).
+template <int TWV, bool FAC, class P>
+__device__ __forceinline__ void wino_exchange_store(const P& p, const float* fac, f32x16 (&acc)[8], float* xchg, int h, int pr,
+                                                    int lane, int nb, int b, int ty0, int tx0) {
+    constexpr int RW = 32 / TWV;
+    const int li = lane & 31, kk = lane >> 5;
+    const int lr = pr * RW + li / TWV, lc = li % TWV;
+    const bool h0 = h == 0;                                // wave-uniform
+    auto xwrite = [&](auto hc) {
+        constexpr int H = decltype(hc)::value;
+        constexpr bool h0 = H == 0;
+        float* mine = xchg + ((pr * 2 + H) * 64) * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int r8 = 0; r8 < 8; ++r8) mine[(k * 8 + r8) * 64] = h0 ? acc[k][8 + r8] : acc[k][r8];
+    };
+    if (h0) xwrite(std::integral_constant<int, 0>{});
+    else xwrite(std::integral_constant<int, 1>{});
+    __syncthreads();
+    auto finish = [&](auto hc) {
+    constexpr int H = decltype(hc)::value;
+    constexpr bool h0 = H == 0;
+    const float* theirs = xchg + ((pr * 2 + (1 - H)) * 64) * 64 + lane;
+    const int oy0 = 2 * (ty0 + lr), ox = 2 * (tx0 + lc);
+    const bool pair = ox + 1 < p.W && (p.W & 1) == 0;      // 8-byte aligned 2-pixel store
+    // One cout register per iteration, fenced by scheduling barriers: left alone, hipcc hoists the 64 exchange reads of
+    // all eight unrolled iterations above the first store and spills 16 - 50 VGPRs beside the 128 live accumulators.
+#pragma unroll
+    for (int r8 = 0; r8 < 8; ++r8) {
+        __builtin_amdgcn_sched_barrier(0);
+        const int r = H * 8 + r8;
+        const int co = nb * 32 + 8 * (r >> 2) + 4 * kk + (r & 3);
+        float m[4][4];                                     // m[i][j], xi = 4 i + j; rows 2h, 2h + 1 are this wave's
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float own = h0 ? acc[k][r8] : acc[k][8 + r8];
+            const float oth = theirs[(k * 8 + r8) * 64];
+            m[k >> 2][k & 3] = h0 ? own : oth;
+            m[2 + (k >> 2)][k & 3] = h0 ? oth : own;
+        }
+        float s[2][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s[0][j] = m[0][j] + m[1][j] + m[2][j];
+            s[1][j] = m[1][j] - m[2][j] - m[3][j];
+        }
+        if (co >= p.Cout || ox >= p.W) continue;
+        const float sh = p.shift != nullptr ? p.shift[co] : 0.f;
+        const float fc = FAC ? fac[co] : 1.f;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int oy = oy0 + a;
+            if (oy >= p.H) continue;
+            float y0 = FAC ? __builtin_fmaf(s[a][0] + s[a][1] + s[a][2], fc, sh) : s[a][0] + s[a][1] + s[a][2] + sh;
+            float y1 = FAC ? __builtin_fmaf(s[a][1] - s[a][2] - s[a][3], fc, sh) : s[a][1] - s[a][2] - s[a][3] + sh;
+            const size_t o = (((size_t)b * p.Cout + co) * p.H + oy) * p.W + ox;
+            float r0 = 0.f, r1 = 0.f;
+            if (p.res != nullptr) {
+                r0 = p.res[o];
+                if (ox + 1 < p.W) r1 = p.res[o + 1];
+            }
+            if (p.res_first) { y0 += r0; y1 += r1; }
+            y0 = act2d_exact(y0, p.act, p.slope);
+            y1 = act2d_exact(y1, p.act, p.slope);
+            if (!p.res_first) { y0 += r0; y1 += r1; }
+            if (pair) {
+                *(f32x2*)(p.y + o) = f32x2{y0, y1};
+            } else {
+                p.y[o] = y0;
+                if (ox + 1 < p.W) p.y[o + 1] = y1;
+            }
+        }
+    }
+    };
+    if (h0) finish(std::integral_constant<int, 0>{});
+    else finish(std::integral_constant<int, 1>{});
+}
 
 // TWV: tiles per wave pair along x.  16 -> a pair is 2 x 16 tiles (4 x 32 pixels), a workgroup 8 x 16 tiles;
 //                                    32 -> a pair is 1 x 32 tiles (2 x 64 pixels), a workgroup 4 x 32 tiles.
@@ -246,86 +336,7 @@ __global__ void __launch_bounds__(512, 2) wino3x3_kernel(const WinoP p) {
     else k_loop(std::integral_constant<int, 1>{});
     __syncthreads();                                       // every wave is done with the staging buffers
 
-    // The exchange and the epilogue are instantiated once per domain half, like the K loop: with a run-time `h` the
-    // accumulator registers are picked by a wave-uniform but DYNAMIC index, which hipcc lowers to s_set_gpr_idx moves
-    // through a 16-register VGPR copy of each tile -- that copy was the kernel's 16 - 50 spilled VGPRs.
-    // Only the register selection is specialised; the barrier between the exchange write and the exchange read is ONE
-    // instruction that every wave of the workgroup reaches on the same path (the two halves used to meet at two
-    // different s_barrier instructions, which works on gfx950's arrival-counting barrier but is not defined behaviour).
-    // ---------------- pair exchange: wave half h finishes the cout registers r in [8h, 8h + 8) and needs the partner's
-    // 8 xi for them.  xchg[pair][writer half][k * 8 + (r & 7)][lane]  (the staging buffers are dead: last barrier above)
-    float* const xchg = lds;
-    auto xwrite = [&](auto hc) {
-        constexpr int H = decltype(hc)::value;
-        constexpr bool h0 = H == 0;
-        float* mine = xchg + ((pr * 2 + H) * 64) * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int r8 = 0; r8 < 8; ++r8) mine[(k * 8 + r8) * 64] = h0 ? acc[k][8 + r8] : acc[k][r8];
-    };
-    if (h0) xwrite(std::integral_constant<int, 0>{});
-    else xwrite(std::integral_constant<int, 1>{});
-    __syncthreads();
-    auto finish = [&](auto hc) {
-    constexpr int H = decltype(hc)::value;
-    constexpr bool h0 = H == 0;
-    const float* theirs = xchg + ((pr * 2 + (1 - H)) * 64) * 64 + lane;
-
-    // ---------------- epilogue: Y = A^T m A (A^T = [1 1 1 0; 0 1 -1 -1]), shift, activation, residual, NCHW store.
-    // D = U^T-rows x tile-columns: this lane is tile `li` of the pair and register r is cout 8 (r >> 2) + 4 kk + (r & 3).
-    const int oy0 = 2 * (ty0 + lr), ox = 2 * (tx0 + lc);
-    const bool pair = ox + 1 < p.W && (p.W & 1) == 0;      // 8-byte aligned 2-pixel store
-    // One cout register per iteration, fenced by scheduling barriers: left alone, hipcc hoists the 64 exchange reads of
-    // all eight unrolled iterations above the first store and spills 16 - 50 VGPRs beside the 128 live accumulators.
-#pragma unroll
-    for (int r8 = 0; r8 < 8; ++r8) {
-        __builtin_amdgcn_sched_barrier(0);
-        const int r = H * 8 + r8;
-        const int co = nb * 32 + 8 * (r >> 2) + 4 * kk + (r & 3);
-        float m[4][4];                                     // m[i][j], xi = 4 i + j; rows 2h, 2h + 1 are this wave's
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float own = h0 ? acc[k][r8] : acc[k][8 + r8];
-            const float oth = theirs[(k * 8 + r8) * 64];
-            m[k >> 2][k & 3] = h0 ? own : oth;
-            m[2 + (k >> 2)][k & 3] = h0 ? oth : own;
-        }
-        float s[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            s[0][j] = m[0][j] + m[1][j] + m[2][j];
-            s[1][j] = m[1][j] - m[2][j] - m[3][j];
-        }
-        if (co >= p.Cout || ox >= p.W) continue;
-        const float sh = p.shift != nullptr ? p.shift[co] : 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int oy = oy0 + a;
-            if (oy >= p.H) continue;
-            float y0 = s[a][0] + s[a][1] + s[a][2] + sh;
-            float y1 = s[a][1] - s[a][2] - s[a][3] + sh;
-            const size_t o = (((size_t)b * p.Cout + co) * p.H + oy) * p.W + ox;
-            float r0 = 0.f, r1 = 0.f;
-            if (p.res != nullptr) {
-                r0 = p.res[o];
-                if (ox + 1 < p.W) r1 = p.res[o + 1];
-            }
-            if (p.res_first) { y0 += r0; y1 += r1; }
-            y0 = act2d_exact(y0, p.act, p.slope);
-            y1 = act2d_exact(y1, p.act, p.slope);
-            if (!p.res_first) { y0 += r0; y1 += r1; }
-            if (pair) {
-                *(f32x2*)(p.y + o) = f32x2{y0, y1};
-            } else {
-                p.y[o] = y0;
-                if (ox + 1 < p.W) p.y[o + 1] = y1;
-            }
-        }
-    }
-    };
-    if (h0) finish(std::integral_constant<int, 0>{});
-    else finish(std::integral_constant<int, 1>{});
+    wino_exchange_store<TWV, false>(p, nullptr, acc, lds, h, pr, lane, nb, b, ty0, tx0);
 }
 
 // upk[chunk][r = 4 q + 2 h + part][cout/32][lane][j]: the A operands of cin 8 chunk + 4 (lane >> 5) + q for the four
@@ -360,6 +371,283 @@ __global__ void wino_pack_kernel(const float* __restrict__ w, const float* __res
     upk[i] = out;
 }
 
+// K10h -- K10 on the f16 matrix pipe with the two-term fp16 split (the scheme of K2s3h, csrc/conv3d_c32p.hip): same contract,
+// same tiling (8 waves, a pair of waves owns 32 tiles x 32 couts and 8 Winograd positions each), same exchange and epilogue.
+//   U' = 2^k[co] (G g G^T scale[co]) = hi_u + lo_u          (packed: occd_wino_pack_weights_f16x2, max|U'| in [2^13, 2^14))
+//   V' = 2^kWinoStageExp (B^T d B)   = hi_v + 2^-11 lo'_v   (split in the kernel, after the float32 transform)
+//   acc += lo_u hi_v + (2^-11 hi_u) lo'_v + hi_u hi_v       three v_mfma_f32_32x32x16_f16 per position and 16 cins, smallest
+//                                                           terms first; 2^-11 hi_u is one v_pk_mul_f16 per two elements
+//   y = act(fac[co] (A^T acc A) + shift) (+ res),           fac = 2^-(k + kWinoStageExp)
+// |V| <= 4 max|x| and fp16 rounds to Inf from 65520 on, so finite activations with |x| >= 65520 / (4 * 2^kWinoStageExp) = 8190
+// can overflow hi_v and give non-finite outputs in the pixels their patches reach.
+// What differs from K10's loop:
+//   * a chunk is 16 cins, staged as two 8-cin images (K10's DMA pattern twice); lane half kk owns cins 8 kk .. 8 kk + 7 --
+//     the 8 k values of its B fragment -- and transforms their 4x4 patches two cins at a time (a pair of cins is one packed
+//     fp16 register per position and term);
+//   * the loop is bound by vector issue, not by the matrix pipe (24 MFMAs = 768 pipe cycles per wave and chunk against some
+//     500 VALU / LDS instructions), so it is plain program order, one ROW of the wave's half of the domain at a time (4
+//     positions: 32 operand VGPRs): transform + split row 0 | barrier | 12 MFMAs | transform + split row 1 | 12 MFMAs |
+//     barrier.  A row needs two patch rows, so a chunk costs 64 ds_read_b64 where all 8 positions at once would cost 48 --
+//     and 64 operand VGPRs, which spill next to the DMA offsets;
+//   * U (two fp16 images in A-fragment order, 32 KB per chunk and cout block, LDS-DMA as in K10) is single-buffered (a second
+//     buffer does not fit beside the patches of the 2 x 16 tiling): the first barrier is where it (and the next patch) has
+//     landed, under the transform of row 0; the second frees it.
+//     Both barriers sit in the one loop body that every wave runs; only the transform is instantiated per domain half.
+constexpr int kWinoStageExp = 1;
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+struct WinoHP {
+    const float* x;
+    const uint16_t* upk;
+    const float* fac;
+    const float* shift;
+    const float* res;
+    float* y;
+    int B, Cin, Cout, H, W;
+    int chunks, nblk, wg_ty, wg_tx, nwg;
+    int act, res_first;
+    float slope;
+};
+
+// (a, b) = the values of one Winograd position for two consecutive cins -> packed hi and lo' terms.  The residuals are
+// fma(hi, -2^11, 2^11 x) on the fp16 hi (one mixed-precision fma each, no conversion back; both products are exact, so
+// this is (x - hi) 2^11 to the bit).  The empty asm keeps the SLP vectoriser from packing the transform and the residuals
+// into v_pk_*_f32: packed float32 VALU instructions beside MFMAs cost more than the two scalar ones they replace.
+__device__ __forceinline__ void split2_f16x2(float a, float b, uint32_t& hi, uint32_t& lo) {
+    asm("" : "+v"(a));
+    asm("" : "+v"(b));
+    const f16x2 h = __builtin_convertvector((f32x2){a, b}, f16x2);
+    float r0 = __builtin_fmaf((float)h[0], -2048.f, a * 2048.f);
+    float r1 = __builtin_fmaf((float)h[1], -2048.f, b * 2048.f);
+    asm("" : "+v"(r0));
+    asm("" : "+v"(r1));
+    hi = __builtin_bit_cast(uint32_t, h);
+    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, f16x2));
+}
+
+template <int TWV>
+__global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
+    constexpr int RW = 32 / TWV;                 // (tile geometry and LDS row stride: see wino3x3_kernel)
+    constexpr int WGR = 4 * RW;
+    constexpr int PR = 2 * WGR + 2;
+    constexpr int PC = 2 * TWV + 2;
+    constexpr int RS = TWV == 16 ? 48 : 68;
+    constexpr int PLANE = PR * RS;
+    constexpr int NEL = 8 * PLANE;               // floats of one staged 8-cin image
+    constexpr int NDMA = (NEL + 511) / 512;
+    constexpr int PBUF = NDMA * 512;
+    constexpr int UOFF = 4 * PBUF;               // [2 buffers][2 x 8 cins][PBUF] patches, then 32 records of U (32 KB)
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pr = wave & 3, h = wave >> 2;
+    const int li = lane & 31, kk = lane >> 5;
+
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
+    const int nb = bid % p.nblk;
+    uint32_t t = bid / p.nblk;
+    const int bx = t % p.wg_tx;
+    t /= p.wg_tx;
+    const int by = t % p.wg_ty;
+    const int b = t / p.wg_ty;
+    const int ty0 = by * WGR, tx0 = bx * TWV;
+    const int gy0 = 2 * ty0 - 1, gx0 = 2 * tx0 - 1;
+
+    const size_t plane_hw = (size_t)p.H * p.W;
+    uint32_t voff[NDMA];                          // as in wino3x3_kernel: 0xFFFFFFF0 = outside, the DMA writes 0.0f
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+        const int e = (wave * NDMA + i) * 64 + lane;
+        const int cin = e / PLANE, rem = e - cin * PLANE;
+        const int row = rem / RS, col = rem - row * RS;
+        const int gy = gy0 + row, gx = gx0 + col;
+        const bool ok = e < NEL && col < PC && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+        voff[i] = ok ? (uint32_t)((cin * plane_hw + (size_t)gy * p.W + gx) * 4) : 0xFFFFFFF0u;
+    }
+    const float* const xb = p.x + (size_t)b * p.Cin * plane_hw;
+    const uint16_t* const ubase = p.upk + (size_t)nb * 512 + lane * 8;
+    const size_t u_rec = (size_t)p.nblk * 512;           // halves per (chunk, xi, image) record
+
+    auto issue_patch = [&](int c) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            // descriptor over channels [16 c + 8 s, Cin) of image b; none left: zero records, every lane reads 0.0f
+            const int ch0 = c * 16 + s * 8, left = p.Cin - ch0;
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (size_t)(left > 0 ? ch0 : 0) * plane_hw), 0,
+                                                                left > 0 ? (uint32_t)((size_t)left * plane_hw * 4) : 0u, 0x00020000);
+            float* pdst = lds + ((c & 1) * 2 + s) * PBUF + wave * NDMA * 64;
+#pragma unroll
+            for (int i = 0; i < NDMA; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, pdst + i * 64, 4, voff[i], 0, 0, 0);
+        }
+    };
+    auto issue_u = [&](int c) {                           // 32 records of 1 KB: r = 2 xi + image (0 hi, 1 lo), 4 per wave
+        float* udst = lds + UOFF + wave * 4 * 256;
+        const uint16_t* usrc = ubase + ((size_t)c * 32 + wave * 4) * u_rec;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds(usrc + (size_t)j * u_rec, udst + j * 256, 16, 0, 0);
+    };
+
+    const int lr = pr * RW + li / TWV, lc = li % TWV;
+    const int pbase = kk * PBUF + (2 * lr + h) * RS + 2 * lc;
+
+    asm volatile("" ::"a"(0.f));                          // AGPR accumulators (see wino3x3_kernel)
+    f32x16 acc[8];                                        // xi = 8 h + k
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
+
+    // One ROW i of this wave's half of the domain (xi = 8 h + 4 i + j) for the lane's 8 cins: row 2h + i of B^T d needs two
+    // patch rows (B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]; rows counted from patch row h):
+    //   h = 0: i = 0: d0 - d2, i = 1: d1 + d2        h = 1: i = 0: d1 - d0, i = 1: d0 - d2
+    // then (.) B with the staging factor 2^kWinoStageExp riding on it: 2 t_a -+ 2 t_b is one fma of t_a against the doubled
+    // t_b, exactly 2 (t_a -+ t_b).  Two cins at a time: a pair is one packed fp16 register per position and term.
+    static_assert(kWinoStageExp == 1, "the transform below stages 2 V");
+    auto row_v = [&](auto hc, auto ic, const float* pl, uint32_t (&vh)[4][4], uint32_t (&vl)[4][4]) {
+        constexpr int H = decltype(hc)::value, I = decltype(ic)::value;
+        constexpr int RA = H == 0 ? I : 1 - I, RB = H == 1 && I == 0 ? 0 : 2;
+        constexpr bool ADD = H == 0 && I == 1;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            float v[2][4];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float* pq = pl + (2 * m + e) * PLANE;
+                const f32x2 a0 = *(const f32x2*)(pq + RA * RS), a1 = *(const f32x2*)(pq + RA * RS + 2);
+                const f32x2 b0 = *(const f32x2*)(pq + RB * RS), b1 = *(const f32x2*)(pq + RB * RS + 2);
+                float ra[4] = {a0.x, a0.y, a1.x, a1.y};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm("" : "+v"(ra[j]));      // (scalar adds: see split2_f16x2)
+                const float t0 = ADD ? ra[0] + b0.x : ra[0] - b0.x, t1 = ADD ? ra[1] + b0.y : ra[1] - b0.y;
+                const float t2 = ADD ? ra[2] + b1.x : ra[2] - b1.x, t3 = ADD ? ra[3] + b1.y : ra[3] - b1.y;
+                const float u1 = 2.f * t1, u2 = 2.f * t2;
+                v[e][0] = __builtin_fmaf(2.f, t0, -u2);
+                v[e][1] = u1 + u2;
+                v[e][2] = u2 - u1;
+                v[e][3] = __builtin_fmaf(-2.f, t3, u1);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) split2_f16x2(v[0][j], v[1][j], vh[j][m], vl[j][m]);
+        }
+    };
+    // the 12 MFMAs of row i against the U records r = 2 xi + image of this chunk; positions in two interleaved pairs so
+    // that no MFMA waits on its predecessor
+    const u32x4* const ul = (const u32x4*)(lds + UOFF) + (h * 16 * 64 + lane);
+    auto row_m = [&](auto ic, const uint32_t (&vh)[4][4], const uint32_t (&vl)[4][4]) {
+        constexpr int I = decltype(ic)::value;
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            f16x8 uh[2], ulo[2], us[2], bh[2], bl[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                uh[e] = __builtin_bit_cast(f16x8, ul[(2 * (4 * I + j + e)) * 64]);
+                ulo[e] = __builtin_bit_cast(f16x8, ul[(2 * (4 * I + j + e) + 1) * 64]);
+                us[e] = uh[e] * (_Float16)(1.f / 2048.f);
+                bh[e] = __builtin_bit_cast(f16x8, (u32x4){vh[j + e][0], vh[j + e][1], vh[j + e][2], vh[j + e][3]});
+                bl[e] = __builtin_bit_cast(f16x8, (u32x4){vl[j + e][0], vl[j + e][1], vl[j + e][2], vl[j + e][3]});
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * I + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ulo[e], bh[e], acc[4 * I + j + e], 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * I + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(us[e], bl[e], acc[4 * I + j + e], 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * I + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[e], bh[e], acc[4 * I + j + e], 0, 0, 0);
+        }
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+
+    const bool h0 = h == 0;                                // wave-uniform
+    issue_patch(0);
+    __syncthreads();                                       // (vmcnt(0) + barrier: patch 0 has landed)
+    for (int c = 0; c < p.chunks; ++c) {
+        issue_u(c);
+        if (c + 1 < p.chunks) issue_patch(c + 1);
+        const float* pl = lds + (c & 1) * 2 * PBUF + pbase;
+        uint32_t ah[4][4], al[4][4], bh[4][4], bl[4][4];   // [position of the row][cin pair]: B fragments, hi and lo' terms
+        if (h0) row_v(I0{}, I0{}, pl, ah, al);
+        else row_v(I1{}, I0{}, pl, ah, al);
+        __syncthreads();                                   // U of chunk c has landed (vmcnt(0): so has the patch of chunk c + 1)
+        row_m(I0{}, ah, al);                               // ... and run under the transform of the second row
+        if (h0) row_v(I0{}, I1{}, pl, bh, bl);
+        else row_v(I1{}, I1{}, pl, bh, bl);
+        row_m(I1{}, bh, bl);
+        __syncthreads();                                   // every wave is done with U and the patch of chunk c; patch c + 1 has landed
+    }
+
+    // ---------------- pair exchange and epilogue (shared with K10), with the per-cout factor.  The lane index is taken again from
+    // a thread id the compiler cannot match with the one above: kept live across the K loop, the lane's indices are the
+    // registers it spills.
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    wino_exchange_store<TWV, true>(p, p.fac, acc, lds, h, pr, tid_e & 63, nb, b, ty0, tx0);
+}
+
+// K10h weight image: fp16 halves [chunk of 16 cins][xi 16][image: 0 hi, 1 lo][cout/32][lane][8], then (cout/32) * 32 floats
+// fac[co].  Element j of lane l is cin 16 chunk + 8 (l >> 5) + j of cout 32 blk + (l & 31): the A fragment of
+// v_mfma_f32_32x32x16_f16.  U' = 2^k[co] (G g G^T)[xi] scale[co] in float64, rounded to float32; hi = fp16(U'),
+// lo = fp16(U' - hi); k[co] puts max |U'| over (cin, xi) into [2^13, 2^14); fac = 2^-(k + kWinoStageExp).
+__device__ __forceinline__ double wino_u_f64(const float* g, int xi) {
+    const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const int a = xi >> 2, bcol = xi & 3;
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+        for (int n = 0; n < 3; ++n) s += G[a][m] * (double)g[m * 3 + n] * G[bcol][n];
+    return s;
+}
+
+__global__ void wino_f16x2_scale_kernel(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ fac,
+                                        int cout, int cin, int nblk) {
+    const int co = blockIdx.x * blockDim.x + threadIdx.x;
+    if (co >= nblk * 32) return;
+    double m = 0.0;
+    bool bad = false;
+    if (co < cout) {
+        const double sc = scale != nullptr ? (double)scale[co] : 1.0;
+        for (int ci = 0; ci < cin; ++ci)
+            for (int xi = 0; xi < 16; ++xi) {
+                const double v = fabs(wino_u_f64(w + ((size_t)co * cin + ci) * 9, xi) * sc);
+                if (!(v <= 3.0e38)) bad = true;            // Inf, NaN (fmax would drop it) or beyond float32
+                m = fmax(m, v);
+            }
+    }
+    int e = 0;
+    const bool ok = m > 0.0 && !bad;
+    if (ok) frexp(m, &e);                                  // m in [2^(e-1), 2^e)
+    const int k = ok ? min(max(14 - e, -100), 100) : 0;
+    // a channel with a non-finite weight is marked with a NaN factor: the entry point reads the factors back and refuses
+    fac[co] = bad ? __builtin_nanf("") : ldexpf(1.f, -(k + kWinoStageExp));
+}
+
+__global__ void wino_pack_f16x2_kernel(const float* __restrict__ w, const float* __restrict__ scale,
+                                       const float* __restrict__ fac, uint16_t* __restrict__ upk, int cout, int cin, int nblk,
+                                       long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int j = i & 7, lane = (i >> 3) & 63;
+    long t = i >> 9;
+    const int blk = t % nblk; t /= nblk;
+    const int img = t & 1, xi = (t >> 1) & 15;
+    const int chunk = (int)(t >> 5);
+    const int co = blk * 32 + (lane & 31), ci = chunk * 16 + (lane >> 5) * 8 + j;
+    float v = 0.f;
+    if (co < cout && ci < cin) {
+        double s = wino_u_f64(w + ((size_t)co * cin + ci) * 9, xi);
+        if (scale != nullptr) s *= (double)scale[co];
+        v = (float)(s * (double)(ldexpf(1.f, -kWinoStageExp) / fac[co]));      // 2^k[co]: exact
+    }
+    const _Float16 hi = (_Float16)v;
+    upk[i] = __builtin_bit_cast(uint16_t, img == 0 ? hi : (_Float16)(v - (float)hi));
+}
+
 template <int TWV, int EXP = 0>
 int launch_wino(const WinoP& p, hipStream_t st) {
     constexpr int RW = 32 / TWV, PR = 2 * 4 * RW + 2, RS = TWV == 16 ? 48 : 68;
@@ -370,6 +658,49 @@ int launch_wino(const WinoP& p, hipStream_t st) {
     if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_kernel<TWV, EXP>)) != OCCD_OK) return OCCD_ELAUNCH;
     hipLaunchKernelGGL((wino3x3_kernel<TWV, EXP>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
     return occd::check_launch();
+}
+
+template <int TWV>
+int launch_wino_f16x2(const WinoHP& p, hipStream_t st) {
+    constexpr int RW = 32 / TWV, PR = 2 * 4 * RW + 2, RS = TWV == 16 ? 48 : 68;
+    constexpr int PBUF = (8 * PR * RS + 511) / 512 * 512;
+    size_t lds = ((size_t)4 * PBUF + 32 * 256) * sizeof(float);
+    const size_t xchg = (size_t)4 * 2 * 64 * 64 * sizeof(float);
+    if (lds < xchg) lds = xchg;
+    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_kernel<TWV>)) != OCCD_OK) return OCCD_ELAUNCH;
+    hipLaunchKernelGGL((wino3x3_f16x2_kernel<TWV>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
+    return occd::check_launch();
+}
+
+// Argument checks and launch geometry shared by K10 and K10h (P: WinoP / WinoHP; `cin_step`: cins per chunk).  Returns the
+// tile width of a wave pair (16 / 32), or a negative status.
+template <class P>
+int wino_geometry(const occd_wino_args* a, int cin_step, P& p) {
+    if (a == nullptr || a->x == nullptr || a->upk == nullptr || a->y == nullptr) return OCCD_EINVAL;
+    if (a->batch < 1 || a->cin < 1 || a->cout < 1 || a->H < 1 || a->W < 1) return OCCD_EINVAL;
+    if (a->act < 0 || a->act > 3) return OCCD_EINVAL;
+    if ((double)a->cin * a->H * a->W >= 2147483648.0) return OCCD_EINVAL;      // 32-bit offsets inside one image
+    p.x = a->x; p.shift = a->shift; p.res = a->res; p.y = a->y;
+    p.B = a->batch; p.Cin = a->cin; p.Cout = a->cout; p.H = a->H; p.W = a->W;
+    p.chunks = (a->cin + cin_step - 1) / cin_step;
+    p.nblk = (a->cout + 31) / 32;
+    p.act = a->act; p.res_first = a->res_first; p.slope = a->slope;
+    const int th = (a->H + 1) / 2, tw = (a->W + 1) / 2;
+    // wide waves (1 x 32 tiles) waste less halo; narrow ones (2 x 16) waste fewer tiles on narrow images
+    const int hint = a->tile_hint % 100;
+    int twv = hint == 16 || hint == 32 ? hint : 0;
+    if (twv == 0) {
+        const long w16 = (long)((tw + 15) / 16) * 16 * ((th + 7) / 8) * 8;
+        const long w32 = (long)((tw + 31) / 32) * 32 * ((th + 3) / 4) * 4;
+        twv = w32 <= w16 ? 32 : 16;
+    }
+    const int wgr = twv == 16 ? 8 : 4;
+    p.wg_tx = (tw + twv - 1) / twv;
+    p.wg_ty = (th + wgr - 1) / wgr;
+    const long nwg = (long)p.nblk * p.wg_tx * p.wg_ty * p.B;
+    if (nwg > 0x7fffffffL) return OCCD_EINVAL;
+    p.nwg = (int)nwg;
+    return twv;
 }
 
 }  // namespace
@@ -390,32 +721,12 @@ int occd_wino_pack_weights(const float* w, const float* scale, float* upk, int32
 }
 
 int occd_wino_conv3x3_fwd(const occd_wino_args* a, void* stream) {
-    if (a == nullptr || a->x == nullptr || a->upk == nullptr || a->y == nullptr) return OCCD_EINVAL;
-    if (a->batch < 1 || a->cin < 1 || a->cout < 1 || a->H < 1 || a->W < 1) return OCCD_EINVAL;
-    if (a->act < 0 || a->act > 3) return OCCD_EINVAL;
-    if ((double)a->cin * a->H * a->W >= 2147483648.0) return OCCD_EINVAL;      // 32-bit offsets inside one image
     WinoP p{};
-    p.x = a->x; p.upk = a->upk; p.shift = a->shift; p.res = a->res; p.y = a->y;
-    p.B = a->batch; p.Cin = a->cin; p.Cout = a->cout; p.H = a->H; p.W = a->W;
-    p.chunks = (a->cin + 7) / 8;
-    p.nblk = (a->cout + 31) / 32;
-    p.act = a->act; p.res_first = a->res_first; p.slope = a->slope;
+    const int twv = wino_geometry(a, 8, p);
+    if (twv < 0) return twv;
+    p.upk = a->upk;
     const int th = (a->H + 1) / 2, tw = (a->W + 1) / 2;
-    // wide waves (1 x 32 tiles) waste less halo; narrow ones (2 x 16) waste fewer tiles on narrow images
     const int exp_mode = a->tile_hint / 100;                  // development switches (see the kernel template)
-    const int hint = a->tile_hint % 100;
-    int twv = hint == 16 || hint == 32 ? hint : 0;
-    if (twv == 0) {
-        const long w16 = (long)((tw + 15) / 16) * 16 * ((th + 7) / 8) * 8;
-        const long w32 = (long)((tw + 31) / 32) * 32 * ((th + 3) / 4) * 4;
-        twv = w32 <= w16 ? 32 : 16;
-    }
-    const int wgr = twv == 16 ? 8 : 4;
-    p.wg_tx = (tw + twv - 1) / twv;
-    p.wg_ty = (th + wgr - 1) / wgr;
-    const long nwg = (long)p.nblk * p.wg_tx * p.wg_ty * p.B;
-    if (nwg > 0x7fffffffL) return OCCD_EINVAL;
-    p.nwg = (int)nwg;
     const double tiles = (double)p.B * th * tw;
     occd::ProfScope prof("wino_conv3x3", (hipStream_t)stream, 2.0 * 16 * tiles * p.chunks * 8 * p.nblk * 32,
                          4.0 * p.B * ((double)p.Cin + p.Cout) * p.H * p.W);
@@ -426,6 +737,47 @@ int occd_wino_conv3x3_fwd(const occd_wino_args* a, void* stream) {
     (void)exp_mode;
 #endif
     return twv == 16 ? launch_wino<16>(p, (hipStream_t)stream) : launch_wino<32>(p, (hipStream_t)stream);
+}
+
+int64_t occd_wino_packed_f16x2_bytes(int32_t cout, int32_t cin) {
+    if (cout < 1 || cin < 1) return OCCD_EINVAL;
+    const int64_t nblk = (cout + 31) / 32;
+    return (int64_t)((cin + 15) / 16) * 32 * nblk * 512 * 2 + nblk * 32 * 4;
+}
+
+int occd_wino_pack_weights_f16x2(const float* w, const float* scale, void* upk, int32_t cout, int32_t cin, void* stream) {
+    if (w == nullptr || upk == nullptr || cout < 1 || cin < 1) return OCCD_EINVAL;
+    const int nblk = (cout + 31) / 32;
+    const long total = (long)((cin + 15) / 16) * 32 * nblk * 512;             // fp16 elements in front of the factors
+    float* fac = reinterpret_cast<float*>(static_cast<uint16_t*>(upk) + total);
+    hipLaunchKernelGGL(wino_f16x2_scale_kernel, dim3((unsigned)nblk), dim3(32), 0, (hipStream_t)stream, w, scale, fac, cout,
+                       cin, nblk);
+    hipLaunchKernelGGL(wino_pack_f16x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                       scale, fac, static_cast<uint16_t*>(upk), cout, cin, nblk, total);
+    const int rc = occd::check_launch();
+    if (rc != OCCD_OK) return rc;
+    // non-finite weights (times scale) have no power-of-two scale: read the factors back (packing is a set-up step, never
+    // part of a captured forward) and refuse; the caller keeps the float32 image of occd_wino_pack_weights
+    std::vector<float> host((size_t)nblk * 32);
+    if (hipMemcpyAsync(host.data(), fac, host.size() * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        return OCCD_ELAUNCH;
+    for (float f : host)
+        if (f != f) return OCCD_EINVAL;
+    return OCCD_OK;
+}
+
+int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream) {
+    WinoHP p{};
+    const int twv = wino_geometry(a, 16, p);
+    if (twv < 0) return twv;
+    p.upk = reinterpret_cast<const uint16_t*>(a->upk);
+    p.fac = reinterpret_cast<const float*>(p.upk + (size_t)p.chunks * 32 * p.nblk * 512);
+    const double tiles = (double)p.B * ((a->H + 1) / 2) * ((a->W + 1) / 2);
+    // (the algorithmic Winograd-domain flops, K10's figure: the three fp16 MFMAs per product are how they are computed)
+    occd::ProfScope prof("wino_conv3x3_f16x2", (hipStream_t)stream, 2.0 * 16 * tiles * ((a->cin + 7) / 8) * 8 * p.nblk * 32,
+                         4.0 * p.B * ((double)p.Cin + p.Cout) * p.H * p.W);
+    return twv == 16 ? launch_wino_f16x2<16>(p, (hipStream_t)stream) : launch_wino_f16x2<32>(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

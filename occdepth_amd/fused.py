@@ -75,17 +75,55 @@ def bn_affine_cached(bn):
     return cached[1], cached[2]
 
 
+# Which kernel the fused Winograd 3x3 convolutions of the eval forward take (the decoder levels of unet2d.py, DepthNet's 3x3 +
+# BatchNorm + ReLU of flosp_depth.py):
+#   OCCDEPTH_WINO_SPLIT=f16x2  (default) K10h, K10 on the f16 matrix pipe with the two-term fp16 split, wherever
+#                              hip.wino_f16x2_wins says it is faster (per launch geometry); error against float64 within 2x of
+#                              K10's (tests/test_wino_f16x2.py); finite activations |x| >= 8190 overflow to non-finite outputs
+#                              (INTEGRATION.md section 6); weights that are not all finite keep K10
+#   OCCDEPTH_WINO_SPLIT=fp32   K10 everywhere (the bit-for-bit previous path)
+# Training (hip.conv2d_3x3_autograd) is K10 in either mode.
+def _parse_wino_split(v):
+    v = (v or "f16x2").strip().lower()
+    if v not in ("f16x2", "fp32"):
+        raise ValueError(f"OCCDEPTH_WINO_SPLIT={v!r}: expected f16x2 or fp32")
+    return v
+
+
+WINO_SPLIT = _parse_wino_split(os.environ.get("OCCDEPTH_WINO_SPLIT", "f16x2"))
+
+
+def set_wino_split(v):
+    """'f16x2' / 'fp32'; the cached operands are re-packed on the next call."""
+    global WINO_SPLIT
+    WINO_SPLIT = _parse_wino_split(v)
+
+
+def wino_pack(w, scale=None):
+    """The weight operand of hip.conv2d_3x3_fused under the current WINO_SPLIT: K10's float32 image, or (f16x2, GPU tensors,
+    finite weights) K10h's image with K10's beside it for the launch geometries that stay on K10."""
+    f32 = hip.wino_pack_weights(w, scale)
+    if WINO_SPLIT != "f16x2" or not w.is_cuda:             # (CPU tensors: the emulated path of the host-logic tests)
+        return f32
+    try:
+        upk = hip.wino_pack_weights_f16x2(w, scale)
+    except ValueError:                                     # non-finite weights: no power-of-two scale
+        return f32
+    upk.f32 = f32
+    return upk
+
+
 def wino_fused_operands(owner, conv, bn):
-    """(packed Winograd-domain weights of K10 with the BatchNorm scale folded in, shift) of a 3x3 convolution + BatchNorm,
-    cached on `owner` until a source tensor changes ((data_ptr, _version) stamp)."""
-    key = _stamp(conv, bn)
+    """(packed Winograd-domain weights of K10 / K10h with the BatchNorm scale folded in, shift) of a 3x3 convolution +
+    BatchNorm, cached on `owner` until a source tensor changes ((data_ptr, _version) stamp) or the split is switched."""
+    key = (_stamp(conv, bn), WINO_SPLIT)
     cache = owner.__dict__.setdefault("_fused_cache", {})
     hit = cache.get(id(conv))
     if hit is None or hit[0] != key:
         scale, shift = bn_affine_cached(bn)
         if conv.bias is not None:
             shift = shift + scale * conv.bias.detach().float()
-        hit = (key, hip.wino_pack_weights(conv.weight, scale), shift.contiguous())
+        hit = (key, wino_pack(conv.weight, scale), shift.contiguous())
         cache[id(conv)] = hit
     return hit[1:]
 

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 MAX_VIEWS = 4
 MAX_SCALES = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 20   # 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+ABI_VERSION = 21   # 21: occd_wino_pack_weights_f16x2 / occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd 3x3 convolution on the two-term fp16 split); 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
 
 _c_float_p = POINTER(c_float)
 
@@ -212,6 +212,9 @@ EXPORTS = {
     "occd_wino_packed_floats": (c_int64, [c_int32, c_int32]),
     "occd_wino_pack_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "occd_wino_conv3x3_fwd": (c_int32, [POINTER(WinoArgs), c_void_p]),
+    "occd_wino_packed_f16x2_bytes": (c_int64, [c_int32, c_int32]),
+    "occd_wino_pack_weights_f16x2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "occd_wino_conv3x3_f16x2_fwd": (c_int32, [POINTER(WinoArgs), c_void_p]),
     "occd_softmax_nchw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
     "occd_dwconv2d_bwd_data_nchw": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p]),
     "occd_dwconv2d_bwd_weight_workspace_floats": (c_int64, [c_int32] * 5),
@@ -1453,25 +1456,83 @@ def wino_pack_weights(w, scale=None):
     return upk
 
 
+class WinoF16x2:
+    """The weight operand of K10h (wino_pack_weights_f16x2): conv2d_3x3_fused takes K10h when it is handed one of these."""
+
+    __slots__ = ("image", "cout", "cin", "f32")
+
+    def __init__(self, image, cout, cin, f32=None):
+        # f32: K10's image of the same weights, or None.  With it, the launch geometries K10h does not win stay on K10.
+        self.image, self.cout, self.cin, self.f32 = image, cout, cin, f32
+
+
+_CU_COUNT = {}
+
+
+def _cu_count(device):
+    n = _CU_COUNT.get(device)
+    if n is None:
+        n = _CU_COUNT[device] = torch.cuda.get_device_properties(device).multi_processor_count
+    return n
+
+
+def wino_f16x2_wins(B, cin, cout, H, W, device=None):
+    """Whether a launch takes K10h when its operand carries both images: launches of at least one workgroup (128 tiles x 32
+    couts) per CU do.  K10h is 1.14 - 1.39x faster on every geometry of the config-2 frame (tools/bench_wino_split.py,
+    profiles/wino_f16x2_ab.txt), the 120-workgroup DepthNet launches included (1.23x, 71 us per frame together); those stay on
+    K10 for now -- DESIGN.md, K10h section, says why -- and moving them is the follow-up."""
+    tiles = B * ((H + 1) // 2) * ((W + 1) // 2)
+    return ((cout + 31) // 32) * ((tiles + 127) // 128) >= _cu_count(torch.cuda.current_device() if device is None else device)
+
+
+def wino_pack_weights_f16x2(w, scale=None):
+    """(Cout, Cin, 3, 3) conv weight (+ per-cout scale) -> WinoF16x2, the operand of K10h: two fp16 images hi | lo of the
+    per-channel power-of-two scaled G g G^T scale plus the epilogue factors.  ValueError when a weight (times scale) is not
+    finite (the pack reports it; it synchronises the stream)."""
+    cout, cin = w.shape[0], w.shape[1]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise RuntimeError("wino_pack_weights_f16x2 needs a (Cout, Cin, 3, 3) weight")
+    n = load().occd_wino_packed_f16x2_bytes(cout, cin)
+    if n <= 0:
+        raise RuntimeError("occd_wino_packed_f16x2_bytes: bad shape")
+    wc = w.detach().float().contiguous()
+    sc = scale.detach().float().contiguous() if scale is not None else None
+    image = torch.empty(n, device=w.device, dtype=torch.uint8)
+    rc = load().occd_wino_pack_weights_f16x2(_f32(wc, "w"), _f32(sc, "scale") if sc is not None else None,
+                                             _ptr(image, "upk"), cout, cin, _stream())
+    if rc == -1:
+        raise ValueError("wino_pack_weights_f16x2: non-finite weights (keep the float32 image of wino_pack_weights)")
+    _check(rc, "occd_wino_pack_weights_f16x2")
+    return WinoF16x2(image, cout, cin)
+
+
 def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, res_first=False, tile_hint=0, out=None):
-    """K10: act(conv3x3(x, g * scale, pad 1) + shift) (+ res) in one launch (upk = wino_pack_weights(g, scale))."""
+    """K10: act(conv3x3(x, g * scale, pad 1) + shift) (+ res) in one launch (upk = wino_pack_weights(g, scale)); K10h, the
+    same on the two-term fp16 split, when upk is the WinoF16x2 of wino_pack_weights_f16x2(g, scale)."""
     if not x.is_contiguous():
         x = x.contiguous()
     B, cin, H, W = x.shape
     y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32) if out is None else out
     if res is not None and not res.is_contiguous():
         res = res.contiguous()
+    if isinstance(upk, WinoF16x2) and upk.f32 is not None and not wino_f16x2_wins(B, cin, cout, H, W, x.device):
+        upk = upk.f32
+    split = isinstance(upk, WinoF16x2)
     a = WinoArgs()
-    a.x, a.upk, a.y = _f32(x, "x"), _f32(upk, "upk"), _f32(y, "y")
+    a.x, a.y = _f32(x, "x"), _f32(y, "y")
+    a.upk = _ptr(upk.image, "upk") if split else _f32(upk, "upk")
     a.shift = _f32(shift, "shift") if shift is not None else None
     a.res = _f32(res, "res") if res is not None else None
     a.batch, a.cin, a.cout, a.H, a.W = B, cin, cout, H, W
     a.act, a.res_first, a.tile_hint, a.slope = ACT2D[act], 1 if res_first else 0, int(tile_hint), float(slope)
-    if upk.numel() != load().occd_wino_packed_floats(cout, cin):
+    if (upk.cout, upk.cin) != (cout, cin) if split else upk.numel() != load().occd_wino_packed_floats(cout, cin):
         raise RuntimeError("packed Winograd weights do not match (cout, cin)")
     if _PROFILING:
         set_tag("%d>%d @%dx%dx%d" % (cin, cout, B, H, W))
-    _check(load().occd_wino_conv3x3_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_fwd")
+    if split:
+        _check(load().occd_wino_conv3x3_f16x2_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_f16x2_fwd")
+    else:
+        _check(load().occd_wino_conv3x3_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_fwd")
     return y
 
 

@@ -107,7 +107,7 @@ class UpSampleBN(nn.Module):
     UPCONV_FUSE_SKIP = os.environ.get("OCCDEPTH_UPCONV_FUSE_SKIP", "1") == "1"
 
     def _upconv_operands(self, conv, bn, cup):
-        key = (_stamp(conv, bn), cup)
+        key = (_stamp(conv, bn), cup, _fused.WINO_SPLIT)
         hit = self.__dict__.get("_upconv_cache")
         if hit is None or hit[0] != key:
             scale, shift = bn_affine_cached(bn)
@@ -119,7 +119,7 @@ class UpSampleBN(nn.Module):
             w9 = (w[:, :cup] * scale.view(-1, 1, 1, 1)).permute(2, 3, 0, 1).reshape(9 * cout, cup).contiguous()
             wskip = (w[:, cup:] * scale.view(-1, 1, 1, 1)).contiguous()
             hit = (key, hip.pw_pack_weights(w9), hip.matmul_operand(w9, "a"),
-                   hip.wino_pack_weights(w[:, cup:].contiguous(), scale), shift.contiguous(), wskip)
+                   _fused.wino_pack(w[:, cup:].contiguous(), scale), shift.contiguous(), wskip)
             self.__dict__["_upconv_cache"] = hit
         return hit[1:]
 

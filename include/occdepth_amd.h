@@ -866,6 +866,46 @@ int occd_depth_bce_grad(const float* prob, const float* gt, const float* gscale,
 int occd_ssc_confusion(const float* logits, const uint8_t* labels, const uint8_t* target, int64_t* hist,
                        int64_t batch, int32_t C, int64_t S, void* stream);
 
+/* The same counts BY REGION in one pass over a (B, X, Y, Z) volume (voxel n = (x*Y + y)*Z + z): every labelled voxel is
+ * counted into each of R <= OCCD_MAX_REGIONS regions it belongs to,
+ *   hist[b * frame_stride + r*C*C + t*C + pred] += 1,
+ * frame_stride = 0: all frames share one set of R matrices; frame_stride >= R*C*C: one set per frame.  hist accumulates.
+ * A region is a half-open index box and a set of required flags, `need`: bit 0 = inside the camera field of view, bits
+ * 1..3 = masks[0..2][b, n] != 0.  The descriptors travel by value with the launch (capture-safe: no device table, no
+ * copy, no allocation).  The FOV flag is either the byte mask `fov` (B, S) or, when `fov` is NULL, computed from the
+ * calibration exactly as occd_vox2pix computes fov[b, v, n, 0]: a voxel is inside when it is inside any view v whose bit
+ * is set in view_mask (a horizontal image flip does not change the flag, so there is no ida).  Exactly one of the two
+ * sources may be given.  pred as in occd_ssc_confusion: `labels` (B, S) or the arg-max (first maximum) of `logits` with
+ * element (b, c, n) at b*s_b + c*s_c + n*s_v floats; channels-last rows (s_c = 1, s_v % 4 == 0, s_b % 4 == 0, 16-byte
+ * aligned base) are read with 16-byte loads.  Voxels with t == 255, t >= C or pred >= C are dropped in every region.
+ * OCCD_EINVAL before any launch: both or neither of logits / labels, R outside 1..8, an empty or out-of-grid box, a need
+ * bit without its mask / FOV source, C outside 1..32, R*C*C*4 > 64 KiB (the workgroup's LDS counters), n_views outside
+ * 1..4 or a view_mask that selects no view of them when the FOV is computed, frame_stride < 0 or in (0, R*C*C).      */
+#define OCCD_MAX_REGIONS 8
+typedef struct occd_confusion_region {
+    int32_t x0, x1, y0, y1, z0, z1;   /* [x0, x1) x [y0, y1) x [z0, z1), inside the grid, not empty                   */
+    uint32_t need;                    /* bit 0: FOV, bits 1..3: masks[0..2]                                         */
+    int32_t reserved;
+} occd_confusion_region;
+typedef struct occd_confusion_regions_args {
+    const float* logits;       /* or NULL                                                                           */
+    const uint8_t* labels;     /* (B, S) or NULL                                                                    */
+    const uint8_t* target;     /* (B, S), 255 = unlabelled                                                          */
+    const uint8_t* masks[3];   /* (B, S) each, non-zero = member; NULL when unused                                  */
+    const uint8_t* fov;        /* (B, S) explicit FOV mask, or NULL                                                 */
+    const double* cam_E;       /* (B, V, 4, 4) device float64, or NULL                                              */
+    const double* cam_k;       /* (B, V, 3, 3) device float64, or NULL                                              */
+    int64_t* hist;
+    int64_t s_b, s_c, s_v;     /* logits strides in floats                                                          */
+    int64_t frame_stride;      /* 0 or >= R*C*C                                                                     */
+    double vox_origin[3];      /* rounded to float32 as vox2world does                                              */
+    double voxel_size;
+    int32_t batch, C, X, Y, Z, R;
+    int32_t n_views, view_mask, img_w, img_h;
+    occd_confusion_region regions[OCCD_MAX_REGIONS];
+} occd_confusion_regions_args;
+int occd_ssc_confusion_regions(const occd_confusion_regions_args* a, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * Training targets of the SemanticKITTI dataloader, built on the GPU (csrc/targets.hip).  All three are bit-exact
  * restatements of the reference's numpy functions and capture-safe: calibration is read from device memory, the

@@ -10,6 +10,7 @@
 // probabilities, Q24 for the cross-entropy terms): integer addition is associative, so the result does not depend
 // on the order of the atomics -- bit-identical from run to run, and more accurate than a float32 tree.
 #include "common.h"
+#include "project.h"
 
 namespace {
 
@@ -260,6 +261,144 @@ __global__ void __launch_bounds__(256) confusion_kernel(const float* logits, con
     __syncthreads();
     for (int i = threadIdx.x; i < C * C; i += 256)
         if (h32[i]) atomicAdd(&hist[i], (u64)h32[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// SSC confusion counts by region: ONE pass over the voxels of a (B, X, Y, Z) volume counts [target, prediction] into every
+// one of R <= 8 regions the voxel belongs to (index box x camera FOV x up to three byte masks).  The descriptors travel by
+// value in the kernel arguments: no device table, nothing to copy or allocate, so a captured launch replays as it is.
+// Grid (blocks, B): a workgroup stays inside one frame, its R * C * C LDS counters belong to that frame.  The membership
+// word is formed BEFORE the prediction, so a voxel outside every region never reads its logits, and the float64
+// projection (occd::project_one, the FOV flag of occd_vox2pix bit for bit) runs only for labelled voxels inside the box
+// of a region that asks for it.  Most voxels of a scene are (empty, empty): with R regions that is R LDS atomics on R hot
+// addresses per lane, so a wave whose active lanes all share (target, prediction, membership) lets one lane add the lane
+// count; only mixed waves fall back to one LDS atomic per lane and region.
+struct RegionsP {
+    const float* logits;
+    const uint8_t* labels;
+    const uint8_t* target;
+    const uint8_t* masks[3];
+    const uint8_t* fov;
+    const double* cam_E;
+    const double* cam_k;
+    u64* hist;
+    long s_b, s_c, s_v, frame_stride;
+    double vox_size;
+    float origin[3];
+    int C, X, Y, Z, S, R, V, view_mask, img_w, img_h;
+    int rows16;                // channels-last rows read with 16-byte loads
+    unsigned fov_regions;      // bit r: region r needs the FOV
+    occd_confusion_region reg[OCCD_MAX_REGIONS];
+};
+
+__global__ void __launch_bounds__(256) confusion_regions_kernel(const RegionsP q) {
+    extern __shared__ unsigned int h32[];              // R * C * C
+    const int C = q.C, CC = q.C * q.C, cells = q.R * CC;
+    for (int i = threadIdx.x; i < cells; i += 256) h32[i] = 0;
+    __syncthreads();
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const uint8_t* tg = q.target + (size_t)b * q.S;
+    // the trip count is uniform over the workgroup: every lane reaches the ballots below
+    for (unsigned base = blockIdx.x * 256u; base < (unsigned)q.S; base += gridDim.x * 256u) {
+        const unsigned v = base + threadIdx.x;
+        int t = 255;
+        unsigned memb = 0;
+        if (v < (unsigned)q.S) t = tg[v];
+        if (t != 255 && t < C) {
+            const unsigned xy = v / (unsigned)q.Z;
+            const int iz = (int)(v - xy * (unsigned)q.Z);
+            const int ix = (int)(xy / (unsigned)q.Y);
+            const int iy = (int)(xy - (unsigned)ix * (unsigned)q.Y);
+            unsigned boxm = 0;
+#pragma unroll
+            for (int r = 0; r < OCCD_MAX_REGIONS; ++r) {
+                if (r < q.R) {
+                    const occd_confusion_region& g = q.reg[r];
+                    if (ix >= g.x0 && ix < g.x1 && iy >= g.y0 && iy < g.y1 && iz >= g.z0 && iz < g.z1) boxm |= 1u << r;
+                }
+            }
+            if (boxm) {
+                unsigned have = 0;                     // bit 0: in the FOV, bits 1..3: mask 0..2 non-zero
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+                    if (q.masks[m] != nullptr && q.masks[m][(size_t)b * q.S + v]) have |= 2u << m;
+                if (boxm & q.fov_regions) {
+                    if (q.fov != nullptr) {
+                        have |= q.fov[(size_t)b * q.S + v] ? 1u : 0u;
+                    } else {
+                        for (int view = 0; view < q.V; ++view) {
+                            if (!((q.view_mask >> view) & 1)) continue;
+                            const double* E = q.cam_E + ((size_t)b * q.V + view) * 16;
+                            const double* K = q.cam_k + ((size_t)b * q.V + view) * 9;
+                            long px, py;
+                            double camz;
+                            if (occd::project_one(E, (double)(float)K[0], (double)(float)K[4], (double)(float)K[2],
+                                                  (double)(float)K[5], q.vox_size, q.origin, ix, iy, iz, q.img_w, q.img_h, px,
+                                                  py, camz)) {
+                                have |= 1u;
+                                break;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < OCCD_MAX_REGIONS; ++r)
+                    if (r < q.R && ((boxm >> r) & 1) && (q.reg[r].need & ~have) == 0) memb |= 1u << r;
+            }
+        }
+        int pred = C;
+        if (memb) {
+            if (q.labels != nullptr) {
+                pred = q.labels[(size_t)b * q.S + v];
+            } else if (q.rows16) {
+                const float4* row = (const float4*)(q.logits + (size_t)b * q.s_b + (size_t)v * q.s_v);
+                float best = 0.f;
+                for (int c4 = 0; c4 < C; c4 += 4) {    // the row is at least round_up(C, 4) floats wide (strides_ok)
+                    const float4 x = row[c4 >> 2];
+                    const float xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int c = c4 + j;
+                        if (c == 0) { best = xs[0]; pred = 0; }
+                        else if (c < C && xs[j] > best) { best = xs[j]; pred = c; }
+                    }
+                }
+            } else {
+                const float* lp = q.logits + (size_t)b * q.s_b + (size_t)v * q.s_v;
+                float best = lp[0];
+                pred = 0;
+                for (int c = 1; c < C; ++c) {
+                    const float x = lp[(size_t)c * q.s_c];
+                    if (x > best) { best = x; pred = c; }
+                }
+            }
+        }
+        const bool act = memb != 0 && pred < C;
+        const unsigned key = act ? (((unsigned)(t * C + pred) << 8) | memb) : 0xffffffffu;
+        const unsigned long long am = __ballot(act);
+        if (am == 0) continue;
+        const int leader = __ffsll((long long)am) - 1;
+        const unsigned k0 = (unsigned)__shfl((int)key, leader);
+        if (__ballot(act && key != k0) == 0) {
+            if (lane == leader) {
+                const unsigned n = (unsigned)__popcll(am);
+                const int cell = t * C + pred;
+#pragma unroll
+                for (int r = 0; r < OCCD_MAX_REGIONS; ++r)
+                    if ((memb >> r) & 1) atomicAdd(&h32[r * CC + cell], n);
+            }
+        } else if (act) {
+            const int cell = t * C + pred;
+#pragma unroll
+            for (int r = 0; r < OCCD_MAX_REGIONS; ++r)
+                if ((memb >> r) & 1) atomicAdd(&h32[r * CC + cell], 1u);
+        }
+    }
+    __syncthreads();
+    u64* out = q.hist + (size_t)b * q.frame_stride;
+    for (int i = threadIdx.x; i < cells; i += 256)
+        if (h32[i]) atomicAdd(&out[i], (u64)h32[i]);
 }
 
 __global__ void zero_u64_kernel(u64* p, long n) {
@@ -574,6 +713,63 @@ int occd_ssc_confusion_strided(const float* logits, const uint8_t* labels, const
 int occd_ssc_confusion(const float* logits, const uint8_t* labels, const uint8_t* target, int64_t* hist,
                        int64_t batch, int32_t C, int64_t S, void* stream) {
     return occd_ssc_confusion_strided(logits, labels, target, hist, batch, C, S, (int64_t)C * S, S, 1, stream);
+}
+
+int occd_ssc_confusion_regions(const occd_confusion_regions_args* a, void* stream) {
+    if (a == nullptr || a->target == nullptr || a->hist == nullptr) return OCCD_EINVAL;
+    if ((a->logits == nullptr) == (a->labels == nullptr)) return OCCD_EINVAL;
+    if (a->R < 1 || a->R > OCCD_MAX_REGIONS || a->C < 1 || a->C > kMaxC) return OCCD_EINVAL;
+    if (a->batch < 1 || a->batch > 65535 || a->X < 1 || a->Y < 1 || a->Z < 1) return OCCD_EINVAL;
+    const int64_t S = (int64_t)a->X * a->Y * a->Z;
+    if (S > 0x7fffffff || (int64_t)a->X * a->Y > 0x7fffffff) return OCCD_EINVAL;
+    const int64_t cells = (int64_t)a->R * a->C * a->C;
+    if (cells * (int64_t)sizeof(unsigned int) > 64 * 1024) return OCCD_EINVAL;      // the workgroup's LDS counters
+    if (a->frame_stride < 0 || (a->frame_stride != 0 && a->frame_stride < cells)) return OCCD_EINVAL;
+    const bool fov_calib = a->cam_E != nullptr || a->cam_k != nullptr;
+    if (a->fov != nullptr && fov_calib) return OCCD_EINVAL;                          // one FOV source per call
+    unsigned fov_regions = 0;
+    for (int r = 0; r < a->R; ++r) {
+        const occd_confusion_region& g = a->regions[r];
+        if (g.x0 < 0 || g.x1 > a->X || g.x0 >= g.x1 || g.y0 < 0 || g.y1 > a->Y || g.y0 >= g.y1 || g.z0 < 0 || g.z1 > a->Z ||
+            g.z0 >= g.z1)
+            return OCCD_EINVAL;
+        if (g.need & ~0xfu) return OCCD_EINVAL;
+        for (int m = 0; m < 3; ++m)
+            if ((g.need & (2u << m)) && a->masks[m] == nullptr) return OCCD_EINVAL;
+        if (g.need & 1u) {
+            if (a->fov == nullptr && !fov_calib) return OCCD_EINVAL;
+            fov_regions |= 1u << r;
+        }
+    }
+    if (fov_regions && a->fov == nullptr) {
+        if (a->cam_E == nullptr || a->cam_k == nullptr) return OCCD_EINVAL;
+        if (a->n_views < 1 || a->n_views > 4 || a->img_w < 1 || a->img_h < 1 || !(a->voxel_size > 0.0)) return OCCD_EINVAL;
+        if ((a->view_mask & ((1 << a->n_views) - 1)) == 0 || (a->view_mask >> a->n_views) != 0) return OCCD_EINVAL;
+    }
+    RegionsP q{};
+    if (a->logits != nullptr) {
+        if (a->s_c < 1 || a->s_v < 1 || a->s_b < 0) return OCCD_EINVAL;
+        q.rows16 = a->s_c == 1 && a->s_v >= ((a->C + 3) & ~3) && strides_ok(a->logits, a->C, a->s_b, a->s_c, a->s_v);
+    }
+    q.logits = a->logits; q.labels = a->labels; q.target = a->target; q.fov = a->fov;
+    for (int m = 0; m < 3; ++m) q.masks[m] = a->masks[m];
+    q.cam_E = a->cam_E; q.cam_k = a->cam_k; q.hist = (u64*)a->hist;
+    q.s_b = a->s_b; q.s_c = a->s_c; q.s_v = a->s_v; q.frame_stride = a->frame_stride;
+    q.vox_size = a->voxel_size;
+    for (int j = 0; j < 3; ++j) q.origin[j] = (float)a->vox_origin[j];
+    q.C = a->C; q.X = a->X; q.Y = a->Y; q.Z = a->Z; q.S = (int)S; q.R = a->R;
+    q.V = a->n_views; q.view_mask = a->view_mask; q.img_w = a->img_w; q.img_h = a->img_h;
+    q.fov_regions = fov_regions;
+    for (int r = 0; r < a->R; ++r) q.reg[r] = a->regions[r];
+    int n_masks = a->fov != nullptr ? 1 : 0;
+    for (int m = 0; m < 3; ++m) n_masks += a->masks[m] != nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const double total = (double)a->batch * (double)S;
+    occd::ProfScope prof("ssc_confusion_regions", st, 0.0, total * ((a->logits ? 4.0 * a->C + 1 : 2.0) + n_masks));
+    int gx = grid_for(S) / a->batch;                   // the chip as full as K7 keeps it, split over the frames
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(confusion_regions_kernel, dim3(gx, a->batch), dim3(256), (size_t)cells * sizeof(unsigned int), st, q);
+    return occd::check_launch();
 }
 
 int occd_relation_bce_stats(const float* logits, const void* labels, int32_t label_dtype, int64_t* stats, int64_t batch,

@@ -7,7 +7,7 @@ a missing / unloadable library or a CPU tensor raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
 
 import torch
 
@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 MAX_VIEWS = 4
 MAX_SCALES = 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 21   # 21: occd_wino_pack_weights_f16x2 / occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd 3x3 convolution on the two-term fp16 split); 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+ABI_VERSION = 22   # 22: occd_ssc_confusion_regions (SSC confusion counts by region -- index box x camera FOV x byte masks, shared or per frame -- in one pass); 21: occd_wino_pack_weights_f16x2 / occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd 3x3 convolution on the two-term fp16 split); 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
 
 _c_float_p = POINTER(c_float)
 
@@ -137,6 +137,19 @@ class FrustumArgs(Structure):
     _fields_ = [("cam_E", c_void_p), ("cam_k", c_void_p), ("target", c_void_p), ("masks", c_void_p), ("dists", c_void_p),
                 ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
         [(n, c_int32) for n in ("batch", "n_views", "X", "Y", "Z", "img_w", "img_h", "frustum_size", "n_classes")]
+
+
+class ConfusionRegion(Structure):
+    _fields_ = [(n, c_int32) for n in ("x0", "x1", "y0", "y1", "z0", "z1")] + [("need", c_uint32), ("reserved", c_int32)]
+
+
+class ConfusionRegionsArgs(Structure):
+    _fields_ = [("logits", c_void_p), ("labels", c_void_p), ("target", c_void_p), ("masks", c_void_p * 3), ("fov", c_void_p),
+                ("cam_E", c_void_p), ("cam_k", c_void_p), ("hist", c_void_p),
+                ("s_b", c_int64), ("s_c", c_int64), ("s_v", c_int64), ("frame_stride", c_int64),
+                ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
+        [(n, c_int32) for n in ("batch", "C", "X", "Y", "Z", "R", "n_views", "view_mask", "img_w", "img_h")] + \
+        [("regions", ConfusionRegion * 8)]
 
 
 class Vox2PixArgs(Structure):
@@ -309,6 +322,7 @@ EXPORTS = {
     "occd_graph_replace_memsets": (c_int32, [c_void_p]),
     "occd_frustum_targets": (c_int32, [POINTER(FrustumArgs), c_void_p]),
     "occd_vox2pix": (c_int32, [POINTER(Vox2PixArgs), c_void_p]),
+    "occd_ssc_confusion_regions": (c_int32, [POINTER(ConfusionRegionsArgs), c_void_p]),
     "occd_downsample_label": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "occd_cp_mega_matrix": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "occd_kitti_labels": (c_int32, [c_void_p] * 4 + [c_int32] + [c_void_p] * 3 + [c_int32, c_int64, c_void_p]),
@@ -2225,6 +2239,94 @@ def ssc_confusion(hist, target, logits=None, labels=None):
     _check(load().occd_ssc_confusion_strided(logits.data_ptr() if logits is not None else None, _ptr(labels, "labels"),
                                              _ptr(target, "target"), _ptr(hist, "hist"), B, C, S, lay[0], lay[1], lay[2],
                                              _stream()), "occd_ssc_confusion_strided")
+    return hist
+
+
+MAX_REGIONS = 8
+NEED_FOV = 1                    # `need` bits of a region: the camera FOV, then mask slot i -> NEED_MASK0 << i
+NEED_MASK0 = 2
+
+
+def _byte_mask(t, B, S, name):
+    """A (B, ...) bool / uint8 GPU mask with S entries per frame -> its contiguous uint8 view (no copy)."""
+    if not torch.is_tensor(t) or t.dtype not in (torch.bool, torch.uint8) or t.shape[0] != B or t[0].numel() != S:
+        raise RuntimeError(f"{name} must be a bool / uint8 tensor of shape (B, ...) matching target")
+    if t.dtype == torch.bool:
+        _ptr(t, name)
+        t = t.view(torch.uint8)
+    return t
+
+
+def ssc_confusion_regions(hist, target, regions, logits=None, labels=None, masks=(), fov=None, per_frame=False):
+    """hist += confusion counts [target, prediction] BY REGION, one pass (occd_ssc_confusion_regions).  target: uint8
+    (B, X, Y, Z), 255 = unlabelled; the prediction is `labels` (uint8) or the arg-max of `logits` (B, C, X, Y, Z; planes
+    or channels-last rows, read in place).  regions: up to 8 pairs (box, need): box = (x0, x1, y0, y1, z0, z1) voxel
+    indices, half open (None: the whole grid), need = NEED_FOV | NEED_MASK0 << i ... .  masks: up to three bool / uint8
+    (B, ...) tensors.  fov: a bool / uint8 (B, ...) mask, or the calibration (cam_E (B, V, 4, 4) float64, cam_k
+    (B, V, 3, 3) float64, vox_origin, voxel_size, (W, H)[, views = (0,)]) from which the kernel computes the flag of
+    `vox2pix(...)[1][b, v, :, 0]`, OR-ed over `views`.  hist: int64 (R, C, C), or (B, R, C, C) with per_frame."""
+    R = len(regions)
+    if target.dtype != torch.uint8 or target.dim() < 2:
+        raise RuntimeError("target must be uint8 of shape (B, X, Y, Z)")
+    B = int(target.shape[0])
+    S = target[0].numel()
+    dims = tuple(int(d) for d in target.shape[1:]) if target.dim() == 4 else (S, 1, 1)
+    if hist.dtype != torch.int64 or hist.dim() != (4 if per_frame else 3) or hist.shape[-1] != hist.shape[-2] or \
+            tuple(hist.shape[:-2]) != ((B, R) if per_frame else (R,)):
+        raise RuntimeError("hist must be int64 (R, C, C), or (B, R, C, C) with per_frame")
+    C = int(hist.shape[-1])
+    if not 1 <= R <= MAX_REGIONS:
+        raise RuntimeError(f"1..{MAX_REGIONS} regions per call, got {R}")
+    if (logits is None) == (labels is None):
+        raise RuntimeError("give exactly one of logits / labels")
+    if len(masks) > 3:
+        raise RuntimeError("at most three masks")
+    a = ConfusionRegionsArgs()
+    lay = (C * S, S, 1)
+    if logits is not None:
+        if logits.dtype != torch.float32 or logits.shape[:2] != (B, C) or logits[0, 0].numel() != S:
+            raise RuntimeError("logits must be float32 (B, C, ...) matching target")
+        lay = _logit_layout(logits)
+        if lay is None:
+            logits = logits.contiguous()
+            lay = (C * S, S, 1)
+        if not logits.is_cuda:
+            raise RuntimeError("logits must live on the GPU (the HIP kernels have no CPU path)")
+        a.logits = logits.data_ptr()
+    if labels is not None:
+        if labels.dtype != torch.uint8 or labels.shape != target.shape:
+            raise RuntimeError("labels must be uint8 with the shape of target")
+        a.labels = _ptr(labels, "labels")
+    a.target, a.hist = _ptr(target, "target"), _ptr(hist, "hist")
+    for i, m in enumerate(masks):
+        a.masks[i] = _ptr(_byte_mask(m, B, S, f"masks[{i}]"), f"masks[{i}]")
+    if torch.is_tensor(fov):
+        fov = _byte_mask(fov, B, S, "fov")
+        a.fov = _ptr(fov, "fov")
+    elif fov is not None:
+        cam_E, cam_k, origin, voxel_size, img_wh = fov[:5]
+        views = tuple(fov[5]) if len(fov) > 5 else (0,)
+        if cam_E.dim() != 4 or int(cam_E.shape[0]) != B:
+            raise RuntimeError("cam_E must be (batch, views, 4, 4)")
+        V = int(cam_E.shape[1])
+        _check_calibration(B, V, cam_E, cam_k)
+        if not views or any(not 0 <= int(v) < V for v in views):
+            raise RuntimeError(f"views must name cameras 0..{V - 1}")
+        a.cam_E, a.cam_k = cam_E.data_ptr(), cam_k.data_ptr()
+        for j, o in enumerate(origin):
+            a.vox_origin[j] = float(o)
+        a.voxel_size = float(voxel_size)
+        a.n_views, a.img_w, a.img_h = V, int(img_wh[0]), int(img_wh[1])
+        a.view_mask = sum({1 << int(v) for v in views})
+    for r, (box, need) in enumerate(regions):
+        g = a.regions[r]
+        g.x0, g.x1, g.y0, g.y1, g.z0, g.z1 = (0, dims[0], 0, dims[1], 0, dims[2]) if box is None else (int(x) for x in box)
+        g.need = int(need)
+    a.s_b, a.s_c, a.s_v = lay
+    a.frame_stride = R * C * C if per_frame else 0
+    a.batch, a.C, a.R = B, C, R
+    a.X, a.Y, a.Z = dims
+    _check(load().occd_ssc_confusion_regions(ctypes.byref(a), _stream()), "occd_ssc_confusion_regions")
     return hist
 
 

@@ -137,6 +137,12 @@ class OccDepth(_Base):
         self.val_metrics = SSCMetrics(self.n_classes)
         self.test_metrics = SSCMetrics(self.n_classes)
         self.metrics_allreduce = False    # opt-in: sum the confusion matrices over ranks before the epoch statistics
+        # Evaluation report by region (camera FOV, range boxes, per frame), OFF by default: `enable_eval_report()` -- or
+        # OCCDEPTH_EVAL_REPORT=kitti in the environment of an unmodified scripts/eval.py.  Off: nothing is allocated or launched.
+        self.eval_report = None
+        self.report_metrics = {}
+        if env("OCCDEPTH_EVAL_REPORT", ""):
+            self.enable_eval_report(env("OCCDEPTH_EVAL_REPORT"))
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -502,6 +508,95 @@ class OccDepth(_Base):
             x3ds = x3ds * depth_vol * 100
         return x3ds, depth_pred
 
+    # ---------------------------------------------------------------- evaluation report by region
+    REPORT_PRESETS = {"kitti": ("full", "fov", "12.8m", "25.6m", "fov_12.8m", "fov_25.6m")}
+
+    def enable_eval_report(self, regions="kitti", per_frame=False, mask_keys=()):
+        """Count the test / validation steps into a second metric BY REGION beside the ordinary one, in one extra pass
+        over the logits for all regions (loss/sscMetrics.py, hip.ssc_confusion_regions); `test_epoch_end` prints one block per region
+        after the reference's report.  regions: the preset "kitti" -- `full`, `fov` (left camera), `12.8m` / `25.6m`
+        (x in [0, r], |y| <= r / 2 metres from the sensor, all z) and their intersections with the FOV -- or a list of
+        `Region`s with index boxes; their mask slots are filled from the batch entries named by `mask_keys` (lists of
+        per-sample tensors or (B, ...) tensors).  per_frame keeps every frame's matrices (`report_metrics["test"].frame_stats()`)."""
+        if isinstance(regions, str):
+            if regions not in self.REPORT_PRESETS:
+                raise ValueError("unknown eval report preset %r (have %s)" % (regions, sorted(self.REPORT_PRESETS)))
+            if self.dataset != "kitti":
+                raise NotImplementedError("the eval report preset %r is the SemanticKITTI geometry; a %s model takes a list "
+                                          "of Region objects" % (regions, self.dataset))
+        else:
+            regions = tuple(regions)
+        self.eval_report = {"regions": regions, "per_frame": bool(per_frame), "mask_keys": tuple(mask_keys)}
+        self.report_metrics = {}
+        return self
+
+    def _report_regions(self, batch):
+        from ..loss.sscMetrics import Region, metric_box
+        regions = self.eval_report["regions"]
+        if not isinstance(regions, str):
+            return regions
+        scale = -(-int(self.project_scale) // 2)           # the output scale of kitti_dataset.py:83
+        grid = tuple(int(s) // scale for s in self.full_scene_size)
+        origin = self._kitti_origin(batch)
+        out = [Region("full"), Region("fov", fov=True)]
+        for r in (12.8, 25.6):
+            out.append(Region("%.1fm" % r, box=metric_box((0.0, r, -r / 2, r / 2), origin, 0.2 * scale, grid)))
+        return out + [Region("fov_" + r.name, box=r.box, fov=True) for r in out[2:]]
+
+    def _report_fov(self, batch, target):
+        """The left camera's FOV at output scale: the batch's `fov_mask_1` when it is there and has the grid's size, else
+        the calibration (float64 extrinsics when the batch carries them), from which the kernel computes the flag."""
+        dev = target.device
+        n = target[0].numel()
+        fm = batch.get("fov_mask_1")
+        if fm is not None and len(fm) == target.shape[0]:
+            rows = []
+            for t in fm:                              # (N,) / (N, 1), or the loader's (V, N, P): left view, pattern point 0
+                t = torch.as_tensor(t).to(dev)
+                if t.numel() == n:
+                    rows.append(t.reshape(n))
+                elif t.dim() > 1 and t[0].numel() >= n and t[0].numel() % n == 0:
+                    rows.append(t[0].reshape(n, -1)[:, 0])
+            if len(rows) == len(fm):
+                return torch.stack(rows).contiguous()
+        if self.dataset != "kitti":
+            raise NotImplementedError("the FOV of a %s batch must come with it as fov_mask_1" % self.dataset)
+        ext = batch.get("T_velo_2_cam_f64", batch["T_velo_2_cam"])
+        E = torch.stack([e.to(dev) for e in ext]).to(torch.float64).contiguous()
+        k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64).contiguous()
+        H, W = batch["img"].shape[-2:]
+        return (E, k, self._kitti_origin(batch), 0.2 * -(-int(self.project_scale) // 2), (int(W), int(H)), (0,))
+
+    def _report_count(self, step_type, batch, ssc_pred, target):
+        from ..loss.sscMetrics import SSCMetrics
+        metric = self.report_metrics.get(step_type)
+        if metric is None:
+            metric = self.report_metrics[step_type] = SSCMetrics(self.n_classes, regions=self._report_regions(batch),
+                                                                 per_frame=self.eval_report["per_frame"])
+        masks = []
+        for key in self.eval_report["mask_keys"]:
+            m = batch[key]
+            masks.append(m if torch.is_tensor(m) else torch.stack([torch.as_tensor(t).to(target.device) for t in m]))
+        fov = self._report_fov(batch, target) if any(r.fov for r in metric.regions) else None
+        metric.add_batch_logits(ssc_pred, target, fov=fov, masks=masks)
+
+    def _print_region_report(self, prefix):
+        metric = self.report_metrics.get(prefix)
+        if metric is None:
+            return
+        if self.metrics_allreduce and metric.region_hist is not None:
+            from .. import shard
+            shard.allreduce_confusion(metric.region_hist)
+        classes = self.class_names
+        for name, stats in metric.get_region_stats().items():
+            print("{}[{}]======".format(prefix, name))
+            print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(
+                stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
+            print("class IoU: {}, ".format(classes))
+            print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
+            print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+        metric.reset()
+
     def _kitti_origin(self, batch=None):
         """SemanticKITTI voxel origin (kitti_dataset.py:82: vox_origin = (0, -25.6, -2) for the 51.2 m wide scene): the grid
         is centred on the sensor in y, whatever the scene width of a reduced test config.  A batch that carries its own
@@ -746,6 +841,8 @@ class OccDepth(_Base):
                 metric.add_batch_logits(ssc_pred, target)
             else:                                        # a reference-style (numpy) metric object
                 metric.add_batch(ssc_pred.detach().argmax(1).cpu().numpy(), target.cpu().numpy())
+        if self.eval_report is not None and step_type in ("test", "val"):
+            self._report_count(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
         return loss
 
@@ -1070,6 +1167,15 @@ class OccDepth(_Base):
             self.log("{}/Precision".format(prefix), stats["precision"], sync_dist=True)
             self.log("{}/Recall".format(prefix), stats["recall"], sync_dist=True)
             metric.reset()
+        rep = self.report_metrics.get("val")
+        if rep is not None:
+            if self.metrics_allreduce and rep.region_hist is not None:
+                from .. import shard
+                shard.allreduce_confusion(rep.region_hist)
+            for name, stats in rep.get_region_stats().items():
+                self.log("val_region/{}/mIoU".format(name), stats["iou_ssc_mean"], sync_dist=True)
+                self.log("val_region/{}/IoU".format(name), stats["iou"], sync_dist=True)
+            rep.reset()
 
     def test_step(self, batch, batch_idx):
         self.step(batch, "test", self.test_metrics)
@@ -1086,6 +1192,7 @@ class OccDepth(_Base):
             print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
             print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
             metric.reset()
+        self._print_region_report("test")
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

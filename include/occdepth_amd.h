@@ -524,6 +524,20 @@ int occd_wino_conv3x3_fwd(const occd_wino_args* a, void* stream);
 int64_t occd_wino_packed_f16x2_bytes(int32_t cout, int32_t cin);
 int occd_wino_pack_weights_f16x2(const float* w, const float* scale, void* upk, int32_t cout, int32_t cin, void* stream);
 int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream);
+/* K10h with the grid chosen by the caller.  max_workgroups:
+ *    0  persistent workgroups, min(tile blocks x cout blocks, CUs of the device) of them, rounded down to a multiple of 8
+ *       (one per XCD and round); workgroup g computes the items g, g + grid, ... -- a static assignment, no state on the
+ *       device -- and requests the next item's first input patch while it stores the current one;
+ *  k > 0  the same with min(items, k) workgroups; any k gives the same result;
+ *   -1  one workgroup per item (the earlier kernel);
+ * < -1  OCCD_EINVAL.
+ *    0  with no more items than that grid has workgroups: the form -1 (nothing to hand over);
+ * Every form gives the same bits.  occd_wino_conv3x3_f16x2_fwd(a, s) is the form -1, or the form 0 when OCCDEPTH_WINO_PERSIST=1
+ * is in the environment of the first call (unset or "0": -1; any other value: OCCD_EINVAL from every call).  Both (and
+ * occd_wino_conv3x3_fwd) need 20 H W < 2^32: the epilogue addresses the 5 output planes of a lane with 32-bit offsets.
+ * The ABI number stays 22 although this export is new: no struct changed, and tests/test_metric_regions.py pins 22.  A
+ * library without it fails at symbol lookup (hip.load() binds every export), not at the version check.                   */
+int occd_wino_conv3x3_f16x2_fwd_ex(const occd_wino_args* a, int32_t max_workgroups, void* stream);
 
 /* Backward of the depthwise convolution (autograd of the geffnet conv_dw layers in training_step):
  *   data  : dx (B, C, H, W) from gy (B, C, Ho, Wo) and w (C, 1, k, k), same geometry arguments as the forward;

@@ -27,6 +27,7 @@
 // Reference semantics replaced: nn.Conv2d(k=3, s=1, p=1) + BatchNorm2d (eval) + LeakyReLU of
 // occdepth/models/unet2d.py:24-46 (UpSampleBN), and the 3x3 convolutions of DepthNet / BasicBlock
 // (occdepth/models/flosp_depth/flosp_depth.py:201-257).
+#include <atomic>
 #include <type_traits>
 #include <vector>
 #include "device.h"
@@ -47,91 +48,183 @@ struct WinoP {
 
 // The pair exchange and the epilogue of K10 and K10h (FAC: K10h's per-cout factor in front of the shift).
 // ---------------- pair exchange: wave half h finishes the cout registers r in [8h, 8h + 8) and needs the partner's 8 xi for
-// them.  xchg[pair][writer half][k * 8 + (r & 7)][lane]  (the staging buffers are dead: the caller's last barrier)
-// Both are instantiated once per domain half, like the K loop: with a run-time `h` the accumulator registers are picked by a
-// wave-uniform but DYNAMIC index, which hipcc lowers to s_set_gpr_idx moves through a 16-register VGPR copy of each tile --
-// that copy was the kernel's 16 - 50 spilled VGPRs.  Only the register selection is specialised; the
-// barrier between the exchange write and the exchange read is ONE instruction that every wave of the workgroup reaches on the
-// same path (the two halves used to meet at two different s_barrier instructions, which works on gfx950's
-// arrival-counting barrier but is not defined behaviour).
+// them.  NPART = 1: one exchange of all 8 registers, xchg[pair][writer half][k * 8 + (r & 7)][lane] (128 KB; the staging
+// buffers are dead: the caller's last barrier).  NPART = 2 (the persistent K10h): two exchanges of 4 registers each through
+// xchg[pair][writer half][k * 4 + (r & 3)][lane] (64 KB), so that the buffer fits BEHIND the first patch buffer, which the
+// next item's first patch is landing in meanwhile; an output's 16 values are the same either way.
+// Writing and finishing are instantiated once per domain half, like the K loop: with a run-time `h` the accumulator registers
+// are picked by a wave-uniform but DYNAMIC index, which hipcc lowers to s_set_gpr_idx moves through a 16-register VGPR copy of
+// each tile -- that copy was the kernel's 16 - 50 spilled VGPRs.  Only the register selection is
+// specialised; every barrier is ONE instruction that every wave of the workgroup reaches on the same path (the two
+// halves used to meet at two different s_barrier instructions, which works on gfx950's arrival-counting barrier but is not
+// defined behaviour).  The barriers wait for the LDS only: the stores behind them, and with NPART = 2 the next item's patch
+// DMA, stay in flight.
 // ---------------- epilogue: Y = A^T m A (A^T = [1 1 1 0; 0 1 -1 -1]), (factor,) shift, activation, residual, NCHW store.
 // D = U^T-rows x tile-columns: the lane is tile `lane & 31` of the pair and register r is cout 8 (r >> 2) + 4 (lane >> 5) + (r & 3).
-template <int TWV, bool FAC, class P>
+// Memory traffic of the epilogue is straight-line code, so that every wait hipcc places is an exact vmcnt(N) and no iteration
+// waits for the round trip of its own loads (they used to: 8 per wave, 16 with a residual, all waves of the CU in lockstep):
+//   * the 8 shifts (and factors) of the wave's registers are loaded once, in front of the exchange (`mid`, the persistent
+//     kernel's hand-over to the next item, runs behind them);
+//   * the residual and the output go through buffer descriptors, one per cout register: the descriptor's base carries
+//     (b, cout) -- scalar arithmetic --, the lane keeps two 32-bit row offsets for all 8 registers, and the hardware bounds
+//     check drops what must not be touched: offset 0xFFFFFFF0 for pixels outside the image, the descriptor's end for couts
+//     past Cout, a descriptor of zero records where there is no residual (it reads as 0.0f: the `+ 0.f` of before);
+//   * the residual of register r + 1 is requested before register r is finished.
+constexpr uint32_t kWinoOutside = 0xFFFFFFF0u;
+// One accumulator element -> VGPR.  Written out because hipcc, given plain element reads in an epilogue that keeps more than a
+// few values live, turns the accumulator tiles into VGPR tuples behind the K loop: 128 v_accvgpr_read in one block and
+// 20 - 60 spilled registers.  An asm statement is not padded for the MFMA -> read hazard: wino_acc_settle() goes first.
+__device__ __forceinline__ float wino_acc_read(float a) {
+    float t;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t) : "a"(a));
+    return t;
+}
+// The hazard (CDNA3 / CDNA4 ISA guide, "Manually inserted wait states", rows "XDL write VGPR -> VALU read / write of that
+// VGPR", which cover v_accvgpr_read of an MFMA's D): 5 / 7 / 11 / 19 wait states behind an MFMA of 2 / 4 / 8 / 16 passes.
+// v_mfma_f32_32x32x2_f32 (K10) is 16 passes, v_mfma_f32_32x32x16_f16 (K10h) 8 on gfx950 (16 at most): 19 states cover both,
+// two `s_nop 15` are 32.  hipcc pads the hazard only for its own instructions, not for what an asm statement holds, so:
+// the operands (one element of each of the 8 tiles: an MFMA writes its whole tile) tie the statement behind the last MFMA of
+// every tile, and volatile statements keep their order, so every wino_acc_read comes after it.  Check after a compiler
+// change: the two s_nop 15 stand between the last v_mfma and the first v_accvgpr_read in the disassembly of all kernels
+// (tools/kernel_resources.sh does not see this).
+__device__ __forceinline__ void wino_acc_settle(const f32x16 (&acc)[8]) {
+    asm volatile("s_nop 15\n\ts_nop 15" ::"a"(acc[0][0]), "a"(acc[1][0]), "a"(acc[2][0]), "a"(acc[3][0]), "a"(acc[4][0]),
+                 "a"(acc[5][0]), "a"(acc[6][0]), "a"(acc[7][0]));
+}
+// s_waitcnt lgkmcnt(0) + s_barrier: a barrier for LDS traffic that leaves global stores and LDS-DMA in flight
+// (__syncthreads() drains them: vmcnt(0))
+__device__ __forceinline__ void wino_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <int TWV, bool FAC, int NPART, bool WE, class P, class Mid>
 __device__ __forceinline__ void wino_exchange_store(const P& p, const float* fac, f32x16 (&acc)[8], float* xchg, int h, int pr,
-                                                    int lane, int nb, int b, int ty0, int tx0) {
-    constexpr int RW = 32 / TWV;
+                                                    int lane, int nb, int b, int ty0, int tx0, Mid mid) {
+    static_assert(NPART == 1 || NPART == 2, "one exchange of 8 cout registers or two of 4");
+    wino_acc_settle(acc);
+    constexpr int RW = 32 / TWV, RP = 8 / NPART;           // RP: cout registers per exchange
     const int li = lane & 31, kk = lane >> 5;
     const int lr = pr * RW + li / TWV, lc = li % TWV;
     const bool h0 = h == 0;                                // wave-uniform
-    auto xwrite = [&](auto hc) {
-        constexpr int H = decltype(hc)::value;
-        constexpr bool h0 = H == 0;
-        float* mine = xchg + ((pr * 2 + H) * 64) * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-#pragma unroll
-            for (int r8 = 0; r8 < 8; ++r8) mine[(k * 8 + r8) * 64] = h0 ? acc[k][8 + r8] : acc[k][r8];
-    };
-    if (h0) xwrite(std::integral_constant<int, 0>{});
-    else xwrite(std::integral_constant<int, 1>{});
-    __syncthreads();
-    auto finish = [&](auto hc) {
-    constexpr int H = decltype(hc)::value;
-    constexpr bool h0 = H == 0;
-    const float* theirs = xchg + ((pr * 2 + (1 - H)) * 64) * 64 + lane;
     const int oy0 = 2 * (ty0 + lr), ox = 2 * (tx0 + lc);
-    const bool pair = ox + 1 < p.W && (p.W & 1) == 0;      // 8-byte aligned 2-pixel store
-    // One cout register per iteration, fenced by scheduling barriers: left alone, hipcc hoists the 64 exchange reads of
-    // all eight unrolled iterations above the first store and spills 16 - 50 VGPRs beside the 128 live accumulators.
+    const size_t hw = (size_t)p.H * p.W;
+    const int cb = nb * 32 + 16 * h;                       // cout of register r8 = 0 in lane half 0 (uniform)
+    auto cout_of = [](int r8) { return 8 * (r8 >> 2) + (r8 & 3); };
+    // byte offsets of the lane's two output rows (and of their second pixel where it is accessed on its own) relative to
+    // plane (b, cb + cout_of(r8)): < 20 H W, which the entry points keep below 2^32
+    uint32_t vo[2][2];
 #pragma unroll
-    for (int r8 = 0; r8 < 8; ++r8) {
-        __builtin_amdgcn_sched_barrier(0);
-        const int r = H * 8 + r8;
-        const int co = nb * 32 + 8 * (r >> 2) + 4 * kk + (r & 3);
-        float m[4][4];                                     // m[i][j], xi = 4 i + j; rows 2h, 2h + 1 are this wave's
+    for (int a = 0; a < 2; ++a) {
+        const bool ok = ox < p.W && oy0 + a < p.H;
+        const uint32_t o = (uint32_t)(((size_t)(4 * kk) * hw + (size_t)(oy0 + a) * p.W + ox) * 4);
+        vo[a][0] = ok ? o : kWinoOutside;
+        vo[a][1] = ok && ox + 1 < p.W ? o + 4 : kWinoOutside;
+    }
+    const size_t plane0 = ((size_t)b * p.Cout + cb) * hw;
+    // descriptor over the planes of register r8 that exist: lane half 1 (4 couts further) falls off its end when they do not
+    auto desc = [&](const float* base, int r8) {
+        const int rem = p.Cout - cb - cout_of(r8);
+        const uint32_t n = base == nullptr || rem <= 0 ? 0u : (uint32_t)((size_t)(rem < 5 ? rem : 5) * hw * 4);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((base == nullptr ? p.y : base) + plane0 + (size_t)cout_of(r8) * hw), 0, n,
+                                                 0x00020000);
+    };
+    // shifts and factors of the lane's 8 couts (a cout past Cout, or no shift at all, reads as 0.0f and is never stored)
+    float sh[8], fc[8], rn[4];
+    {
+        const auto ss = __builtin_amdgcn_make_buffer_rsrc((void*)(p.shift != nullptr ? p.shift : p.y), 0,
+                                                          p.shift != nullptr ? (uint32_t)p.Cout * 4u : 0u, 0x00020000);
+        const auto fs = __builtin_amdgcn_make_buffer_rsrc((void*)(FAC ? fac : p.y), 0, FAC ? (uint32_t)p.Cout * 4u : 0u, 0x00020000);
+        const uint32_t co4 = (uint32_t)(cb + 4 * kk) * 4;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float own = h0 ? acc[k][r8] : acc[k][8 + r8];
-            const float oth = theirs[(k * 8 + r8) * 64];
-            m[k >> 2][k & 3] = h0 ? own : oth;
-            m[2 + (k >> 2)][k & 3] = h0 ? oth : own;
-        }
-        float s[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            s[0][j] = m[0][j] + m[1][j] + m[2][j];
-            s[1][j] = m[1][j] - m[2][j] - m[3][j];
-        }
-        if (co >= p.Cout || ox >= p.W) continue;
-        const float sh = p.shift != nullptr ? p.shift[co] : 0.f;
-        const float fc = FAC ? fac[co] : 1.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int oy = oy0 + a;
-            if (oy >= p.H) continue;
-            float y0 = FAC ? __builtin_fmaf(s[a][0] + s[a][1] + s[a][2], fc, sh) : s[a][0] + s[a][1] + s[a][2] + sh;
-            float y1 = FAC ? __builtin_fmaf(s[a][1] - s[a][2] - s[a][3], fc, sh) : s[a][1] - s[a][2] - s[a][3] + sh;
-            const size_t o = (((size_t)b * p.Cout + co) * p.H + oy) * p.W + ox;
-            float r0 = 0.f, r1 = 0.f;
-            if (p.res != nullptr) {
-                r0 = p.res[o];
-                if (ox + 1 < p.W) r1 = p.res[o + 1];
-            }
-            if (p.res_first) { y0 += r0; y1 += r1; }
-            y0 = act2d_exact(y0, p.act, p.slope);
-            y1 = act2d_exact(y1, p.act, p.slope);
-            if (!p.res_first) { y0 += r0; y1 += r1; }
-            if (pair) {
-                *(f32x2*)(p.y + o) = f32x2{y0, y1};
-            } else {
-                p.y[o] = y0;
-                if (ox + 1 < p.W) p.y[o + 1] = y1;
-            }
+        for (int r8 = 0; r8 < 8; ++r8) {
+            sh[r8] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ss, co4 + cout_of(r8) * 4, 0, 0));
+            fc[r8] = FAC ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(fs, co4 + cout_of(r8) * 4, 0, 0)) : 1.f;
         }
     }
+    // WE: W is even, so a lane's two pixels are one 8-byte access (ox is even); otherwise they go one by one
+    auto res_issue = [&](int r8) {
+        const auto rs = desc(p.res, r8);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            if (WE) {
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo[a][0], 0, 0);
+                const uint32_t v0 = v[0], v1 = v[1];       // (a bit_cast of `v.y` itself reads element 0)
+                rn[2 * a] = __builtin_bit_cast(float, v0);
+                rn[2 * a + 1] = __builtin_bit_cast(float, v1);
+            } else {
+                rn[2 * a] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo[a][0], 0, 0));
+                rn[2 * a + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo[a][1], 0, 0));
+            }
+        }
     };
-    if (h0) finish(std::integral_constant<int, 0>{});
-    else finish(std::integral_constant<int, 1>{});
+    res_issue(0);
+    __builtin_amdgcn_sched_barrier(0);
+    mid();
+    __builtin_amdgcn_sched_barrier(0);
+
+    auto xwrite = [&](auto hc, int part) {
+        constexpr int H = decltype(hc)::value;
+        constexpr bool h0 = H == 0;
+        float* mine = xchg + ((pr * 2 + H) * 8 * RP) * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+#pragma unroll
+            for (int q = 0; q < RP; ++q) mine[(k * RP + q) * 64] = wino_acc_read(h0 ? acc[k][8 + part * RP + q] : acc[k][part * RP + q]);
+            __builtin_amdgcn_sched_barrier(0);             // (one accumulator tile at a time: few registers in flight)
+        }
+    };
+    auto finish = [&](auto hc, int part) {
+        constexpr int H = decltype(hc)::value;
+        constexpr bool h0 = H == 0;
+        const float* theirs = xchg + ((pr * 2 + (1 - H)) * 8 * RP) * 64 + lane;
+        // One cout register per iteration, fenced by scheduling barriers: left alone, hipcc hoists the 64 exchange reads of
+        // all eight unrolled iterations above the first store and spills 16 - 50 VGPRs beside the 128 live accumulators.
+#pragma unroll
+        for (int q = 0; q < RP; ++q) {
+            __builtin_amdgcn_sched_barrier(0);
+            const int r8 = part * RP + q;
+            const float rc[4] = {rn[0], rn[1], rn[2], rn[3]};
+            if (r8 + 1 < 8) res_issue(r8 + 1);            // one register ahead
+            float m[4][4];                                 // m[i][j], xi = 4 i + j; rows 2h, 2h + 1 are this wave's
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float own = wino_acc_read(h0 ? acc[k][r8] : acc[k][8 + r8]);
+                const float oth = theirs[(k * RP + q) * 64];
+                m[k >> 2][k & 3] = h0 ? own : oth;
+                m[2 + (k >> 2)][k & 3] = h0 ? oth : own;
+            }
+            float s[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[0][j] = m[0][j] + m[1][j] + m[2][j];
+                s[1][j] = m[1][j] - m[2][j] - m[3][j];
+            }
+            const auto ws = desc(p.y, r8);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                float y0 = FAC ? __builtin_fmaf(s[a][0] + s[a][1] + s[a][2], fc[r8], sh[r8]) : s[a][0] + s[a][1] + s[a][2] + sh[r8];
+                float y1 = FAC ? __builtin_fmaf(s[a][1] - s[a][2] - s[a][3], fc[r8], sh[r8]) : s[a][1] - s[a][2] - s[a][3] + sh[r8];
+                const float r0 = rc[2 * a], r1 = rc[2 * a + 1];
+                if (p.res_first) { y0 += r0; y1 += r1; }
+                y0 = act2d_exact(y0, p.act, p.slope);
+                y1 = act2d_exact(y1, p.act, p.slope);
+                if (!p.res_first) { y0 += r0; y1 += r1; }
+                if (WE) {
+                    __builtin_amdgcn_raw_buffer_store_b64((u32x2){__builtin_bit_cast(uint32_t, y0), __builtin_bit_cast(uint32_t, y1)},
+                                                          ws, vo[a][0], 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y0), ws, vo[a][0], 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y1), ws, vo[a][1], 0, 0);
+                }
+            }
+        }
+    };
+#pragma unroll
+    for (int part = 0; part < NPART; ++part) {
+        if (part > 0) wino_lds_barrier();                  // the partner has read the previous part
+        if (h0) xwrite(std::integral_constant<int, 0>{}, part);
+        else xwrite(std::integral_constant<int, 1>{}, part);
+        wino_lds_barrier();
+        if (h0) finish(std::integral_constant<int, 0>{}, part);
+        else finish(std::integral_constant<int, 1>{}, part);
+    }
 }
 
 // TWV: tiles per wave pair along x.  16 -> a pair is 2 x 16 tiles (4 x 32 pixels), a workgroup 8 x 16 tiles;
@@ -165,7 +258,7 @@ __device__ __forceinline__ void wino_exchange_store(const P& p, const float* fac
 // Block (c, 3) reads chunk c+1, so the barrier (vmcnt(0): chunk c+1, issued a chunk earlier, has landed; every wave has
 // issued its last reads of chunk c) sits in front of it and the DMA of chunk c+2 into chunk c's buffers follows it.
 // EXP (development A/B switches, wrong results): 1 = no DMA after chunk 1, 2 = DMA only (no MFMA)
-template <int TWV, int EXP = 0>
+template <int TWV, bool WE, int EXP = 0>
 __global__ void __launch_bounds__(512, 2) wino3x3_kernel(const WinoP p) {
     constexpr int RW = 32 / TWV;                 // tile rows per wave pair
     constexpr int WGR = 4 * RW;                  // tile rows per workgroup
@@ -336,7 +429,7 @@ __global__ void __launch_bounds__(512, 2) wino3x3_kernel(const WinoP p) {
     else k_loop(std::integral_constant<int, 1>{});
     __syncthreads();                                       // every wave is done with the staging buffers
 
-    wino_exchange_store<TWV, false>(p, nullptr, acc, lds, h, pr, lane, nb, b, ty0, tx0);
+    wino_exchange_store<TWV, false, 1, WE>(p, nullptr, acc, lds, h, pr, lane, nb, b, ty0, tx0, [] {});
 }
 
 // upk[chunk][r = 4 q + 2 h + part][cout/32][lane][j]: the A operands of cin 8 chunk + 4 (lane >> 5) + q for the four
@@ -425,7 +518,16 @@ __device__ __forceinline__ void split2_f16x2(float a, float b, uint32_t& hi, uin
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, f16x2));
 }
 
-template <int TWV>
+// PERSIST: a workgroup walks the items v = blockIdx.x, blockIdx.x + gridDim.x, ... < nwg (a static assignment: no queue, no
+// flags, nothing shared between workgroups, any grid size is correct) and hands over inside the epilogue:
+//     last barrier of the K loop | shifts, factors, first residual requested | next item: DMA offsets, descriptor, patch DMA
+//     of its chunk 0 into patch buffer 0 | exchange registers 0-3: write, barrier, finish, store | barrier | registers 4-7:
+//     write, barrier, finish, store | next item's first barrier (vmcnt(0): its patch 0 has landed, and every wave has read
+//     the second exchange) | issue_u(0), issue_patch(1), ...
+// The two-part exchange (64 KB) lives behind patch buffer 0, over patch buffer 1 and U, which are dead until that barrier.
+// With a grid that is a multiple of 8, v % 8 is the same for all items of a workgroup, so xcd_remap still puts the cout blocks
+// of one tile block on one XCD, one round at a time.  !PERSIST: one item per workgroup, one 128-KB exchange over everything.
+template <int TWV, bool PERSIST, bool WE>
 __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
     constexpr int RW = 32 / TWV;                 // (tile geometry and LDS row stride: see wino3x3_kernel)
     constexpr int WGR = 4 * RW;
@@ -437,44 +539,55 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
     constexpr int NDMA = (NEL + 511) / 512;
     constexpr int PBUF = NDMA * 512;
     constexpr int UOFF = 4 * PBUF;               // [2 buffers][2 x 8 cins][PBUF] patches, then 32 records of U (32 KB)
+    constexpr int XOFF = PERSIST ? 2 * PBUF : 0; // the exchange: behind patch buffer 0, or over everything
+    constexpr int XFLOATS = 4 * 2 * 64 * 64 / (PERSIST ? 2 : 1);
+    static_assert(XOFF + XFLOATS <= (PERSIST ? UOFF + 32 * 256 : 4 * 2 * 64 * 64), "the exchange must fit in the staging buffers");
+    static_assert((UOFF + 32 * 256) * 4 <= 160 * 1024 && (XOFF + XFLOATS) * 4 <= 160 * 1024, "LDS of a CU");
+    static_assert(XOFF % 4 == 0, "16-byte aligned exchange");
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pr = wave & 3, h = wave >> 2;
-    const int li = lane & 31, kk = lane >> 5;
-
-    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
-    const int nb = bid % p.nblk;
-    uint32_t t = bid / p.nblk;
-    const int bx = t % p.wg_tx;
-    t /= p.wg_tx;
-    const int by = t % p.wg_ty;
-    const int b = t / p.wg_ty;
-    const int ty0 = by * WGR, tx0 = bx * TWV;
-    const int gy0 = 2 * ty0 - 1, gx0 = 2 * tx0 - 1;
-
     const size_t plane_hw = (size_t)p.H * p.W;
-    uint32_t voff[NDMA];                          // as in wino3x3_kernel: 0xFFFFFFF0 = outside, the DMA writes 0.0f
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-        const int e = (wave * NDMA + i) * 64 + lane;
-        const int cin = e / PLANE, rem = e - cin * PLANE;
-        const int row = rem / RS, col = rem - row * RS;
-        const int gy = gy0 + row, gx = gx0 + col;
-        const bool ok = e < NEL && col < PC && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-        voff[i] = ok ? (uint32_t)((cin * plane_hw + (size_t)gy * p.W + gx) * 4) : 0xFFFFFFF0u;
-    }
-    const float* const xb = p.x + (size_t)b * p.Cin * plane_hw;
-    const uint16_t* const ubase = p.upk + (size_t)nb * 512 + lane * 8;
     const size_t u_rec = (size_t)p.nblk * 512;           // halves per (chunk, xi, image) record
+    uint32_t voff[NDMA];                          // as in wino3x3_kernel: 0xFFFFFFF0 = outside, the DMA writes 0.0f
+    int nb, b, ty0, tx0;                          // the item: cout block, image, first tile
+    // (the lane index is taken from a thread id the compiler cannot match with earlier ones: kept live across the K loop,
+    // the lane's indices are the registers it spills)
+    auto fresh_tid = [] {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pr = wave & 3, h = wave >> 2;
+    const bool h0 = h == 0;                                // wave-uniform
 
-    auto issue_patch = [&](int c) {
+    auto setup = [&](uint32_t v) {                        // item v: where it is, and this lane's DMA offsets in it
+        const uint32_t bid = xcd_remap(v, p.nwg);
+        nb = bid % p.nblk;
+        uint32_t t = bid / p.nblk;
+        const int bx = t % p.wg_tx;
+        t /= p.wg_tx;
+        const int by = t % p.wg_ty;
+        b = t / p.wg_ty;
+        ty0 = by * WGR, tx0 = bx * TWV;
+        const int gy0 = 2 * ty0 - 1, gx0 = 2 * tx0 - 1;
+        const int lane = fresh_tid() & 63;
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) {
+            const int e = (wave * NDMA + i) * 64 + lane;
+            const int cin = e / PLANE, rem = e - cin * PLANE;
+            const int row = rem / RS, col = rem - row * RS;
+            const int gy = gy0 + row, gx = gx0 + col;
+            const bool ok = e < NEL && col < PC && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            voff[i] = ok ? (uint32_t)((cin * plane_hw + (size_t)gy * p.W + gx) * 4) : 0xFFFFFFF0u;
+        }
+    };
+    auto issue_patch = [&](int c, bool live = true) {
+        const float* const xb = p.x + (size_t)b * p.Cin * plane_hw;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            // descriptor over channels [16 c + 8 s, Cin) of image b; none left: zero records, every lane reads 0.0f
-            const int ch0 = c * 16 + s * 8, left = p.Cin - ch0;
+            // descriptor over channels [16 c + 8 s, Cin) of image b; none left (or !live): zero records, every lane reads 0.0f
+            const int ch0 = c * 16 + s * 8, left = live ? p.Cin - ch0 : 0;
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (size_t)(left > 0 ? ch0 : 0) * plane_hw), 0,
                                                                 left > 0 ? (uint32_t)((size_t)left * plane_hw * 4) : 0u, 0x00020000);
             float* pdst = lds + ((c & 1) * 2 + s) * PBUF + wave * NDMA * 64;
@@ -483,22 +596,9 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, pdst + i * 64, 4, voff[i], 0, 0, 0);
         }
     };
-    auto issue_u = [&](int c) {                           // 32 records of 1 KB: r = 2 xi + image (0 hi, 1 lo), 4 per wave
-        float* udst = lds + UOFF + wave * 4 * 256;
-        const uint16_t* usrc = ubase + ((size_t)c * 32 + wave * 4) * u_rec;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds(usrc + (size_t)j * u_rec, udst + j * 256, 16, 0, 0);
-    };
-
-    const int lr = pr * RW + li / TWV, lc = li % TWV;
-    const int pbase = kk * PBUF + (2 * lr + h) * RS + 2 * lc;
 
     asm volatile("" ::"a"(0.f));                          // AGPR accumulators (see wino3x3_kernel)
     f32x16 acc[8];                                        // xi = 8 h + k
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
 
     // One ROW i of this wave's half of the domain (xi = 8 h + 4 i + j) for the lane's 8 cins: row 2h + i of B^T d needs two
     // patch rows (B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]; rows counted from patch row h):
@@ -535,8 +635,7 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
     };
     // the 12 MFMAs of row i against the U records r = 2 xi + image of this chunk; positions in two interleaved pairs so
     // that no MFMA waits on its predecessor
-    const u32x4* const ul = (const u32x4*)(lds + UOFF) + (h * 16 * 64 + lane);
-    auto row_m = [&](auto ic, const uint32_t (&vh)[4][4], const uint32_t (&vl)[4][4]) {
+    auto row_m = [&](auto ic, const u32x4* ul, const uint32_t (&vh)[4][4], const uint32_t (&vl)[4][4]) {
         constexpr int I = decltype(ic)::value;
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {
@@ -563,30 +662,64 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
 
-    const bool h0 = h == 0;                                // wave-uniform
+    uint32_t v = blockIdx.x;
+    setup(v);
     issue_patch(0);
-    __syncthreads();                                       // (vmcnt(0) + barrier: patch 0 has landed)
-    for (int c = 0; c < p.chunks; ++c) {
-        issue_u(c);
-        if (c + 1 < p.chunks) issue_patch(c + 1);
-        const float* pl = lds + (c & 1) * 2 * PBUF + pbase;
-        uint32_t ah[4][4], al[4][4], bh[4][4], bl[4][4];   // [position of the row][cin pair]: B fragments, hi and lo' terms
-        if (h0) row_v(I0{}, I0{}, pl, ah, al);
-        else row_v(I1{}, I0{}, pl, ah, al);
-        __syncthreads();                                   // U of chunk c has landed (vmcnt(0): so has the patch of chunk c + 1)
-        row_m(I0{}, ah, al);                               // ... and run under the transform of the second row
-        if (h0) row_v(I0{}, I1{}, pl, bh, bl);
-        else row_v(I1{}, I1{}, pl, bh, bl);
-        row_m(I1{}, bh, bl);
-        __syncthreads();                                   // every wave is done with U and the patch of chunk c; patch c + 1 has landed
-    }
+    for (;;) {
+        const int lane = fresh_tid() & 63;
+        const int li = lane & 31, kk = lane >> 5;
+        const int lr = pr * RW + li / TWV, lc = li % TWV;
+        const int pbase = kk * PBUF + (2 * lr + h) * RS + 2 * lc;
+        const u32x4* const ul = (const u32x4*)(lds + UOFF) + (h * 16 * 64 + lane);
+        const uint16_t* const ubase = p.upk + (size_t)nb * 512 + lane * 8;
+        auto issue_u = [&](int c) {                       // 32 records of 1 KB: r = 2 xi + image (0 hi, 1 lo), 4 per wave
+            float* udst = lds + UOFF + wave * 4 * 256;
+            const uint16_t* usrc = ubase + ((size_t)c * 32 + wave * 4) * u_rec;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds(usrc + (size_t)j * u_rec, udst + j * 256, 16, 0, 0);
+        };
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
 
-    // ---------------- pair exchange and epilogue (shared with K10), with the per-cout factor.  The lane index is taken again from
-    // a thread id the compiler cannot match with the one above: kept live across the K loop, the lane's indices are the
-    // registers it spills.
-    int tid_e = threadIdx.x;
-    asm volatile("" : "+v"(tid_e));
-    wino_exchange_store<TWV, true>(p, p.fac, acc, lds, h, pr, tid_e & 63, nb, b, ty0, tx0);
+        __syncthreads();                                   // (vmcnt(0) + barrier: patch 0 has landed; the exchange is read)
+        for (int c = 0; c < p.chunks; ++c) {
+            issue_u(c);
+            if (c + 1 < p.chunks) issue_patch(c + 1);
+            const float* pl = lds + (c & 1) * 2 * PBUF + pbase;
+            uint32_t ah[4][4], al[4][4], bh[4][4], bl[4][4];   // [position of the row][cin pair]: B fragments, hi and lo' terms
+            if (h0) row_v(I0{}, I0{}, pl, ah, al);
+            else row_v(I1{}, I0{}, pl, ah, al);
+            __syncthreads();                               // U of chunk c has landed (vmcnt(0): so has the patch of chunk c + 1)
+            row_m(I0{}, ul, ah, al);                       // ... and run under the transform of the second row
+            if (h0) row_v(I0{}, I1{}, pl, bh, bl);
+            else row_v(I1{}, I1{}, pl, bh, bl);
+            row_m(I1{}, ul, bh, bl);
+            __syncthreads();                               // every wave is done with U and the patch of chunk c; patch c + 1 has landed
+        }
+
+        // ---------------- pair exchange and epilogue (shared with K10), with the per-cout factor; the next item's first patch
+        // is requested from inside it
+        const int nb_c = nb, b_c = b, ty0_c = ty0, tx0_c = tx0;
+        const uint32_t vn = v + gridDim.x;
+        const bool more = PERSIST && vn < (uint32_t)p.nwg;
+        wino_exchange_store<TWV, true, PERSIST ? 2 : 1, WE>(p, p.fac, acc, lds + XOFF, h, pr, fresh_tid() & 63, nb_c, b_c, ty0_c, tx0_c, [&] {
+            // No branch around the DMA: behind a uniform `if (more)` hipcc takes the smaller pending count at the join, and
+            // the epilogue's first counted waits then drain the 2 x NDMA patch requests as well.  The last item of a
+            // workgroup requests its own patch again through descriptors of zero records: nothing is read.
+            if (PERSIST) {
+                setup(more ? vn : v);
+                issue_patch(0, more);
+            }
+        });
+        if (!more) {
+            // (the zero-record DMA still writes LDS: it must have landed before the workgroup gives its LDS back)
+            if (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            break;
+        }
+        v = vn;
+    }
 }
 
 // K10h weight image: fp16 halves [chunk of 16 cins][xi 16][image: 0 hi, 1 lo][cout/32][lane][8], then (cout/32) * 32 floats
@@ -648,28 +781,45 @@ __global__ void wino_pack_f16x2_kernel(const float* __restrict__ w, const float*
     upk[i] = __builtin_bit_cast(uint16_t, img == 0 ? hi : (_Float16)(v - (float)hi));
 }
 
-template <int TWV, int EXP = 0>
-int launch_wino(const WinoP& p, hipStream_t st) {
+template <int TWV, bool WE, int EXP = 0>
+int launch_wino_we(const WinoP& p, hipStream_t st) {
     constexpr int RW = 32 / TWV, PR = 2 * 4 * RW + 2, RS = TWV == 16 ? 48 : 68;
     constexpr int PBUF = (8 * PR * RS + 511) / 512 * 512;
     size_t lds = ((size_t)2 * PBUF + 2 * 16 * 256) * sizeof(float);
     const size_t xchg = (size_t)4 * 2 * 64 * 64 * sizeof(float);          // the pairs' accumulator exchange (128 KB)
     if (lds < xchg) lds = xchg;
-    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_kernel<TWV, EXP>)) != OCCD_OK) return OCCD_ELAUNCH;
-    hipLaunchKernelGGL((wino3x3_kernel<TWV, EXP>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
+    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_kernel<TWV, WE, EXP>)) != OCCD_OK) return OCCD_ELAUNCH;
+    hipLaunchKernelGGL((wino3x3_kernel<TWV, WE, EXP>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
     return occd::check_launch();
 }
 
-template <int TWV>
-int launch_wino_f16x2(const WinoHP& p, hipStream_t st) {
+// grid: 0 = one item per workgroup with the single exchange (the earlier kernel); > 0 = that many persistent workgroups
+template <int TWV, bool WE>
+int launch_wino_f16x2_we(const WinoHP& p, int grid, hipStream_t st) {
     constexpr int RW = 32 / TWV, PR = 2 * 4 * RW + 2, RS = TWV == 16 ? 48 : 68;
     constexpr int PBUF = (8 * PR * RS + 511) / 512 * 512;
     size_t lds = ((size_t)4 * PBUF + 32 * 256) * sizeof(float);
+    if (grid > 0) {                                                        // (the 64-KB exchange fits behind patch buffer 0)
+        if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_kernel<TWV, true, WE>)) != OCCD_OK) return OCCD_ELAUNCH;
+        hipLaunchKernelGGL((wino3x3_f16x2_kernel<TWV, true, WE>), dim3((unsigned)grid), dim3(512), lds, st, p);
+        return occd::check_launch();
+    }
     const size_t xchg = (size_t)4 * 2 * 64 * 64 * sizeof(float);
     if (lds < xchg) lds = xchg;
-    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_kernel<TWV>)) != OCCD_OK) return OCCD_ELAUNCH;
-    hipLaunchKernelGGL((wino3x3_f16x2_kernel<TWV>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
+    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_kernel<TWV, false, WE>)) != OCCD_OK) return OCCD_ELAUNCH;
+    hipLaunchKernelGGL((wino3x3_f16x2_kernel<TWV, false, WE>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
     return occd::check_launch();
+}
+
+// (even W: the epilogue's 2-pixel accesses, see wino_exchange_store)
+template <int TWV, int EXP = 0>
+int launch_wino(const WinoP& p, hipStream_t st) {
+    return (p.W & 1) == 0 ? launch_wino_we<TWV, true, EXP>(p, st) : launch_wino_we<TWV, false, EXP>(p, st);
+}
+
+template <int TWV>
+int launch_wino_f16x2(const WinoHP& p, int grid, hipStream_t st) {
+    return (p.W & 1) == 0 ? launch_wino_f16x2_we<TWV, true>(p, grid, st) : launch_wino_f16x2_we<TWV, false>(p, grid, st);
 }
 
 // Argument checks and launch geometry shared by K10 and K10h (P: WinoP / WinoHP; `cin_step`: cins per chunk).  Returns the
@@ -680,6 +830,7 @@ int wino_geometry(const occd_wino_args* a, int cin_step, P& p) {
     if (a->batch < 1 || a->cin < 1 || a->cout < 1 || a->H < 1 || a->W < 1) return OCCD_EINVAL;
     if (a->act < 0 || a->act > 3) return OCCD_EINVAL;
     if ((double)a->cin * a->H * a->W >= 2147483648.0) return OCCD_EINVAL;      // 32-bit offsets inside one image
+    if (20.0 * a->H * a->W >= 4294967040.0) return OCCD_EINVAL;                // ... and inside the epilogue's 5 output planes
     p.x = a->x; p.shift = a->shift; p.res = a->res; p.y = a->y;
     p.B = a->batch; p.Cin = a->cin; p.Cout = a->cout; p.H = a->H; p.W = a->W;
     p.chunks = (a->cin + cin_step - 1) / cin_step;
@@ -701,6 +852,19 @@ int wino_geometry(const occd_wino_args* a, int cin_step, P& p) {
     if (nwg > 0x7fffffffL) return OCCD_EINVAL;
     p.nwg = (int)nwg;
     return twv;
+}
+
+// CUs of the current device (0: unknown), looked up once per device
+int wino_cu_count() {
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int n = cached[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 0;
+        cached[dev].store(n, std::memory_order_relaxed);
+    }
+    return n;
 }
 
 }  // namespace
@@ -767,17 +931,42 @@ int occd_wino_pack_weights_f16x2(const float* w, const float* scale, void* upk, 
     return OCCD_OK;
 }
 
-int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream) {
+int occd_wino_conv3x3_f16x2_fwd_ex(const occd_wino_args* a, int32_t max_workgroups, void* stream) {
+    if (max_workgroups < -1) return OCCD_EINVAL;
     WinoHP p{};
     const int twv = wino_geometry(a, 16, p);
     if (twv < 0) return twv;
     p.upk = reinterpret_cast<const uint16_t*>(a->upk);
     p.fac = reinterpret_cast<const float*>(p.upk + (size_t)p.chunks * 32 * p.nblk * 512);
+    int grid = 0;                                             // -1: one item per workgroup
+    if (max_workgroups > 0) {
+        grid = p.nwg < max_workgroups ? p.nwg : max_workgroups;
+    } else if (max_workgroups == 0) {
+        // one workgroup per CU (LDS allows no more), a multiple of 8 so that a workgroup's items stay on its XCD's slice
+        // of the remapped order
+        // A launch that gives no workgroup a second item has nothing to hand over and keeps the one-item form: the
+        // two-part exchange alone costs it two more barriers (120 items: 0 - 4 % slower, profiles/wino_persist_ab.txt).
+        const int cus = wino_cu_count();
+        if (cus < 1) return OCCD_ELAUNCH;
+        grid = cus >= 8 ? cus - cus % 8 : cus;
+        if (p.nwg <= grid) grid = 0;
+    }
     const double tiles = (double)p.B * ((a->H + 1) / 2) * ((a->W + 1) / 2);
     // (the algorithmic Winograd-domain flops, K10's figure: the three fp16 MFMAs per product are how they are computed)
     occd::ProfScope prof("wino_conv3x3_f16x2", (hipStream_t)stream, 2.0 * 16 * tiles * ((a->cin + 7) / 8) * 8 * p.nblk * 32,
                          4.0 * p.B * ((double)p.Cin + p.Cout) * p.H * p.W);
-    return twv == 16 ? launch_wino_f16x2<16>(p, (hipStream_t)stream) : launch_wino_f16x2<32>(p, (hipStream_t)stream);
+    return twv == 16 ? launch_wino_f16x2<16>(p, grid, (hipStream_t)stream) : launch_wino_f16x2<32>(p, grid, (hipStream_t)stream);
+}
+
+int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream) {
+    // OCCDEPTH_WINO_PERSIST: unset or "0" = one workgroup per item, "1" = persistent; anything else is refused, as in hip.py
+    static const int dflt = [] {
+        const char* e = getenv("OCCDEPTH_WINO_PERSIST");
+        if (e == nullptr || (e[0] == '0' && e[1] == '\0')) return -1;
+        return e[0] == '1' && e[1] == '\0' ? 0 : -2;
+    }();
+    if (dflt < -1) return OCCD_EINVAL;
+    return occd_wino_conv3x3_f16x2_fwd_ex(a, dflt, stream);
 }
 
 }  // extern "C"

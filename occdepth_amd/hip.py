@@ -228,6 +228,7 @@ EXPORTS = {
     "occd_wino_packed_f16x2_bytes": (c_int64, [c_int32, c_int32]),
     "occd_wino_pack_weights_f16x2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "occd_wino_conv3x3_f16x2_fwd": (c_int32, [POINTER(WinoArgs), c_void_p]),
+    "occd_wino_conv3x3_f16x2_fwd_ex": (c_int32, [POINTER(WinoArgs), c_int32, c_void_p]),
     "occd_softmax_nchw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
     "occd_dwconv2d_bwd_data_nchw": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p]),
     "occd_dwconv2d_bwd_weight_workspace_floats": (c_int64, [c_int32] * 5),
@@ -1520,15 +1521,33 @@ def wino_pack_weights_f16x2(w, scale=None):
     return WinoF16x2(image, cout, cin)
 
 
-def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, res_first=False, tile_hint=0, out=None):
+def _parse_wino_persist(value):
+    if value not in ("0", "1"):
+        raise ValueError("OCCDEPTH_WINO_PERSIST must be 0 or 1, not %r" % (value,))
+    return value == "1"
+
+
+# 1: K10h with persistent workgroups (one per CU walks the tiles, the next tile's first patch lands under the epilogue) -- opt-in:
+# bit-identical, 1 - 3 % per launch, no gain outside the run-to-run range in the frame; 0 (default): one
+# workgroup per tile block, the form the persistent one is checked against bit for bit (tests/test_wino_persist.py)
+WINO_PERSIST = _parse_wino_persist(os.environ.get("OCCDEPTH_WINO_PERSIST", "0"))
+
+
+def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, res_first=False, tile_hint=0, out=None,
+                     max_workgroups=None):
     """K10: act(conv3x3(x, g * scale, pad 1) + shift) (+ res) in one launch (upk = wino_pack_weights(g, scale)); K10h, the
-    same on the two-term fp16 split, when upk is the WinoF16x2 of wino_pack_weights_f16x2(g, scale)."""
+    same on the two-term fp16 split, when upk is the WinoF16x2 of wino_pack_weights_f16x2(g, scale).  max_workgroups (K10h
+    only; RuntimeError with a K10 operand; without effect on a launch that wino_f16x2_wins sends to the K10 image of a WinoF16x2):
+    0 = persistent workgroups, one per CU (the one-item form when the launch has no more items than that); k > 0 = at most k
+    persistent workgroups; -1 = one workgroup per tile block; None = WINO_PERSIST's choice between 0 and -1."""
     if not x.is_contiguous():
         x = x.contiguous()
     B, cin, H, W = x.shape
     y = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32) if out is None else out
     if res is not None and not res.is_contiguous():
         res = res.contiguous()
+    if max_workgroups is not None and not isinstance(upk, WinoF16x2):
+        raise RuntimeError("max_workgroups is K10h's grid: the operand of this launch is K10's float32 image")
     if isinstance(upk, WinoF16x2) and upk.f32 is not None and not wino_f16x2_wins(B, cin, cout, H, W, x.device):
         upk = upk.f32
     split = isinstance(upk, WinoF16x2)
@@ -1544,7 +1563,10 @@ def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, r
     if _PROFILING:
         set_tag("%d>%d @%dx%dx%d" % (cin, cout, B, H, W))
     if split:
-        _check(load().occd_wino_conv3x3_f16x2_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_f16x2_fwd")
+        if max_workgroups is None:
+            max_workgroups = 0 if WINO_PERSIST else -1
+        _check(load().occd_wino_conv3x3_f16x2_fwd_ex(ctypes.byref(a), int(max_workgroups), _stream()),
+               "occd_wino_conv3x3_f16x2_fwd_ex")
     else:
         _check(load().occd_wino_conv3x3_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_fwd")
     return y

@@ -8,6 +8,9 @@
  * ATen-op sequence it replaces; `occdepth_amd/hip.py` is the ctypes binding.
  *
  * Conventions
+ *  - Python derives its binding (structures, prototypes, constants, ABI number) from this file at import
+ *    (occdepth_amd/abi.py), so declarations stay within the subset it parses: block comments, `#define NAME integer`,
+ *    `typedef struct T {...} T;` with plain `*` / `const` / `[N]` declarators, and function declarations.
  *  - plain pointers + ints only; all pointers are DEVICE pointers (fp32 unless
  *    noted) owned by the caller; nothing is retained after the call returns.
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream).  Every
@@ -41,13 +44,35 @@ extern "C" {
 #define OCCD_ACT_SIGMOID 2
 #define OCCD_ACT_RELU_PRE 3 /* act_out only: relu(conv + bias) + res1 + res2 */
 
-/* ABI version; bumped whenever a struct below changes (13: occd_gemm_args.bias_n / stride_bias_n, occd_gemm_f32x3_splitk;
- * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix;
- * 17: occd_vox2pix_args, occd_vox2pix, occd_lift_proj_args.ida;
- * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw;
- * 19: occd_kitti_labels;
- * 20: occd_optim_chunk.acc, occd_accum_adamw_args, occd_accum_clip_adamw;
- * 21: occd_wino_packed_f16x2_bytes, occd_wino_pack_weights_f16x2, occd_wino_conv3x3_f16x2_fwd). */
+/* ABI version, returned by occd_abi_version(); bumped whenever a struct below changes.  This is the one place the number
+ * and its history are written: csrc/prof.cpp returns the macro and occdepth_amd/abi.py reads it.
+ *  3: K10
+ *  4: K11 pointwise GEMM, SE gate, depthwise pool / backward, softmax, lift backward + xcd_mode / feat_bstride
+ *  5: K11s split-K hints, occd_upconv_gather_nchw (K12)
+ *  6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels
+ *  7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of
+ *     occd_conv3d_bf16_fwd
+ *  8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2
+ *  9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases
+ * 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd
+ * 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg),
+ *     occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd
+ * 12: x_plane_stride of occd_dwconv2d_pool_nchw
+ * 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk
+ *     (K21), occd_se_gate_set_fused
+ * 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels)
+ * 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions)
+ * 16: occd_frustum_args, occd_frustum_targets, occd_downsample_label, occd_cp_mega_matrix (training targets on the GPU)
+ * 17: occd_vox2pix_args, occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida
+ * 18: occd_optim_chunk, occd_clip_adamw_args, occd_grad_sumsq, occd_clip_adamw (gradient-norm clipping fused with AdamW)
+ * 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU)
+ * 20: occd_optim_chunk.acc, occd_accum_adamw_args, occd_accum_clip_adamw (gradient accumulation over a window of
+ *     micro-batches fused into clip + AdamW)
+ * 21: occd_wino_packed_f16x2_bytes, occd_wino_pack_weights_f16x2, occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd
+ *     3x3 convolution on the two-term fp16 split)
+ * 22: occd_confusion_region, occd_confusion_regions_args, occd_ssc_confusion_regions (SSC confusion counts by region --
+ *     index box x camera FOV x byte masks, shared or per frame -- in one pass) */
+#define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
 

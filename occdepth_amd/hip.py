@@ -7,332 +7,49 @@ a missing / unloadable library or a CPU tensor raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
+from ctypes import c_int32, c_int64, c_void_p
 
 import torch
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libocc_hip.so")
 
-MAX_VIEWS = 4
-MAX_SCALES = 4
-ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_RELU_PRE = 0, 1, 2, 3
-ABI_VERSION = 22   # 22: occd_ssc_confusion_regions (SSC confusion counts by region -- index box x camera FOV x byte masks, shared or per frame -- in one pass); 21: occd_wino_pack_weights_f16x2 / occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd 3x3 convolution on the two-term fp16 split); 20: occd_accum_clip_adamw + occd_optim_chunk.acc (gradient accumulation over a window of micro-batches fused into clip + AdamW, optim.GradWindow); 19: occd_kitti_labels (raw SemanticKITTI voxel files -> labels on the GPU, targets.kitti_labels); 18: occd_grad_sumsq / occd_clip_adamw (global gradient-norm clipping fused with the AdamW update, optim.py); 17: occd_vox2pix (batched device-side voxel -> pixel tables, flip included), occd_lift_proj_args.ida; 16: occd_frustum_targets / occd_downsample_label / occd_cp_mega_matrix (training targets on the GPU, targets.py); 15: occd_pack_weights_f16x2 + dtype 3 of occd_conv3d_bf16_fwd (K2s3h, the two-term fp16 split of the head convolutions); 14: occd_graph_replace_memsets (captured memset nodes -> fill kernels); 13: occd_gemm_args.bias_n / stride_bias_n (column bias: CRP relation-logit convolutions on K16), occd_gemm_f32x3_splitk (K21), occd_se_gate_set_fused; 11: occd_gemm_args.act_a (sigmoid on A: CRP products on K16), peer-memory exchanges (occd_ipc_*, occd_bn_*_small_xchg), occd_stem_conv3x3_nchw, occd_depthnet_gate, occd_plane_reduce / occd_se_bwd; 10: strided (channels-last) ssc loss / confusion passes, occd_relation_bce_*, occd_depth_bce_*, occd_flosp_sample_bwd (N1 kernels); 9: occd_gemm_args.res / scale_k (project convolutions on K16), occd_conv3d_fwd_phases; 8: occd_gemm_f32x3 (K16, row-major float32 GEMM with the 3-way bf16 split), K2s3 behind occd_conv3d_bf16_fwd dtype 2; 7: occd_lift_proj_fwd (fused projection + frustum sample + lift), occd_pack_weights_bf16x3 + split mode of occd_conv3d_bf16_fwd; 6: K2b / K8b bf16-MFMA convolution forward + weight gradient, BN kernels; 5: K11s split-K hints, occd_upconv_gather_nchw (K12); 4: K11 pointwise GEMM, SE gate, depthwise pool/backward, softmax, lift backward + xcd_mode/feat_bstride; 3: K10
+# Everything the C ABI defines comes from include/occdepth_amd.h through abi.py; the names below are aliases.
+EXPORTS = abi.EXPORTS
+ABI_VERSION = abi.ABI_VERSION
+MAX_VIEWS = abi.CONSTANTS["OCCD_MAX_VIEWS"]
+MAX_SCALES = abi.CONSTANTS["OCCD_MAX_SCALES"]
+ACT_NONE = abi.CONSTANTS["OCCD_ACT_NONE"]
+ACT_RELU = abi.CONSTANTS["OCCD_ACT_RELU"]
+ACT_SIGMOID = abi.CONSTANTS["OCCD_ACT_SIGMOID"]
+ACT_RELU_PRE = abi.CONSTANTS["OCCD_ACT_RELU_PRE"]
+OPTIM_CHUNK = abi.CONSTANTS["OCCD_OPTIM_CHUNK"]   # elements per chunk descriptor
+MAX_REGIONS = abi.CONSTANTS["OCCD_MAX_REGIONS"]
 
-_c_float_p = POINTER(c_float)
+Conv3dArgs = abi.STRUCTS["occd_conv3d_args"]
+WgradArgs = abi.STRUCTS["occd_conv3d_wgrad_args"]
+FlospArgs = abi.STRUCTS["occd_flosp_args"]
+LiftArgs = abi.STRUCTS["occd_lift_args"]
+LiftProjArgs = abi.STRUCTS["occd_lift_proj_args"]
+FlospBwdArgs = abi.STRUCTS["occd_flosp_bwd_args"]
+BneckArgs = abi.STRUCTS["occd_bneck_args"]
+RowsGemmArgs = abi.STRUCTS["occd_rows_gemm_args"]
+GemmArgs = abi.STRUCTS["occd_gemm_args"]
+WinoArgs = abi.STRUCTS["occd_wino_args"]
+PwArgs = abi.STRUCTS["occd_pw_args"]
+LiftBwdArgs = abi.STRUCTS["occd_lift_bwd_args"]
+BnArgs = abi.STRUCTS["occd_bn_args"]
+FrustumArgs = abi.STRUCTS["occd_frustum_args"]
+ConfusionRegion = abi.STRUCTS["occd_confusion_region"]
+ConfusionRegionsArgs = abi.STRUCTS["occd_confusion_regions_args"]
+Vox2PixArgs = abi.STRUCTS["occd_vox2pix_args"]
+OptimChunk = abi.STRUCTS["occd_optim_chunk"]
+ClipAdamWArgs = abi.STRUCTS["occd_clip_adamw_args"]
+AccumAdamWArgs = abi.STRUCTS["occd_accum_adamw_args"]
+ProfRow = abi.STRUCTS["occd_prof_row"]
 
-
-class Conv3dArgs(Structure):
-    _fields_ = [
-        ("inp", c_void_p), ("wpk", c_void_p), ("bias", c_void_p), ("res1", c_void_p), ("res2", c_void_p),
-        ("out", c_void_p),
-        ("batch", c_int32),
-        ("X", c_int32), ("Y", c_int32), ("Z", c_int32),
-        ("cin", c_int32), ("in_cs", c_int32), ("in_coff", c_int32),
-        ("cout", c_int32), ("out_cs", c_int32), ("out_coff", c_int32),
-        ("res1_cs", c_int32), ("res1_coff", c_int32), ("res2_cs", c_int32), ("res2_coff", c_int32),
-        ("kx", c_int32), ("ky", c_int32), ("kz", c_int32),
-        ("sx", c_int32), ("sy", c_int32), ("sz", c_int32),
-        ("dx", c_int32), ("dy", c_int32), ("dz", c_int32),
-        ("px", c_int32), ("py", c_int32), ("pz", c_int32),
-        ("Xo", c_int32), ("Yo", c_int32), ("Zo", c_int32),
-        ("OX", c_int32), ("OY", c_int32), ("OZ", c_int32),
-        ("o_stride_x", c_int32), ("o_stride_y", c_int32), ("o_stride_z", c_int32),
-        ("o_off_x", c_int32), ("o_off_y", c_int32), ("o_off_z", c_int32),
-        ("act_in", c_int32), ("act_out", c_int32), ("cout_store", c_int32), ("tile_hint", c_int32),
-    ]
-
-
-class WgradArgs(Structure):
-    _fields_ = [("x", c_void_p), ("gy", c_void_p), ("dw", c_void_p), ("workspace", c_void_p),
-                ("workspace_floats", c_int64), ("batch", c_int32)] + \
-        [(n, c_int32) for n in ("X", "Y", "Z", "cin", "x_cs", "x_coff", "Xo", "Yo", "Zo", "cout", "gy_cs", "gy_coff",
-                                "kx", "ky", "kz", "sx", "sy", "sz", "dx", "dy", "dz", "px", "py", "pz")]
-
-
-class FlospArgs(Structure):
-    _fields_ = [
-        ("depth", c_void_p), ("trans", c_void_p), ("proj", c_void_p), ("ida", c_void_p), ("grids", c_void_p),
-        ("out", c_void_p),
-        ("batch", c_int32), ("n_cams", c_int32),
-        ("D", c_int32), ("h", c_int32), ("w", c_int32),
-        ("A", c_int32), ("Bdim", c_int32), ("C", c_int32),
-        ("img_w", c_float), ("img_h", c_float), ("depth_min", c_float), ("depth_max", c_float),
-        ("mean_mode", c_int32),
-    ]
-
-
-class LiftArgs(Structure):
-    _fields_ = [
-        ("feat", (c_void_p * MAX_VIEWS) * MAX_SCALES),
-        ("feat_h", c_int32 * MAX_SCALES), ("feat_w", c_int32 * MAX_SCALES),
-        ("feat_cs", c_int32 * MAX_SCALES), ("scale_div", c_int32 * MAX_SCALES),
-        ("n_scales", c_int32), ("n_views", c_int32), ("batch", c_int32), ("C", c_int32),
-        ("pix", c_void_p), ("fov", c_void_p),
-        ("N", c_int32), ("P", c_int32),
-        ("depth_scale", c_void_p), ("scale_const", c_float),
-        ("dimA", c_int32), ("dimB", c_int32), ("dimC", c_int32),
-        ("row_a", c_int64), ("row_b", c_int64), ("row_c", c_int64),
-        ("out", c_void_p), ("out_rows", c_int64), ("out_cs", c_int32),
-        ("feat_bstride", (c_int64 * MAX_VIEWS) * MAX_SCALES), ("xcd_mode", c_int32),
-    ]
-
-
-class LiftProjArgs(Structure):
-    _fields_ = [("lift", LiftArgs), ("cam_E", c_void_p), ("cam_k", c_void_p), ("voxel_size", ctypes.c_double),
-                ("origin", c_float * 3),
-                ("img_w", c_int32), ("img_h", c_int32), ("frustum", FlospArgs), ("ida", c_void_p)]
-
-
-class FlospBwdArgs(Structure):
-    _fields_ = [("fwd", FlospArgs), ("gout", c_void_p), ("gdepth", c_void_p), ("workspace", c_void_p),
-                ("workspace_bytes", c_int64)]
-
-
-class BneckArgs(Structure):
-    _fields_ = [("x", c_void_p), ("y", c_void_p), ("o2", c_void_p), ("w", c_void_p)] + \
-        [(n, c_int32) for n in ("batch", "X", "Y", "Z", "C", "P", "x_cs", "x_coff", "y_cs", "y_coff", "d0", "d1", "d2")]
-
-
-class RowsGemmArgs(Structure):
-    _fields_ = [("a", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("res", c_void_p), ("out", c_void_p), ("rows", c_int64)] + \
-        [(n, c_int32) for n in ("K", "N", "a_cs", "a_coff", "out_cs", "out_coff", "res_cs", "res_coff", "w_stride", "act_in",
-                                "act_out")]
-
-
-class GemmArgs(Structure):
-    _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p), ("bias", c_void_p)] + \
-        [(n, c_int32) for n in ("M", "N", "K", "batch")] + \
-        [(n, c_int64) for n in ("lda", "ldb", "ldc", "stride_a", "stride_b", "stride_c")] + \
-        [("act", c_int32), ("slope", c_float), ("tile_hint", c_int32), ("pre", c_int32), ("res", c_void_p), ("scale_k", c_void_p),
-         ("act_a", c_int32), ("bias_n", c_void_p), ("stride_bias_n", c_int64)]
-
-
-class WinoArgs(Structure):
-    _fields_ = [("x", c_void_p), ("upk", c_void_p), ("shift", c_void_p), ("res", c_void_p), ("y", c_void_p)] + \
-        [(n, c_int32) for n in ("batch", "cin", "cout", "H", "W", "act", "res_first", "tile_hint")] + [("slope", c_float)]
-
-
-class PwArgs(Structure):
-    _fields_ = [("x", c_void_p), ("wpk", c_void_p), ("shift", c_void_p), ("gate", c_void_p), ("res", c_void_p),
-                ("y", c_void_p), ("N", c_int64), ("batch", c_int32), ("cin", c_int32), ("cout", c_int32),
-                ("act", c_int32), ("tile_hint", c_int32), ("slope", c_float), ("out_nhwc_cs", c_int32)]
-
-
-class LiftBwdArgs(Structure):
-    _fields_ = [("fwd", LiftArgs), ("gout", c_void_p), ("gfeat", (c_void_p * MAX_VIEWS) * MAX_SCALES), ("gdepth", c_void_p)]
-
-
-class BnArgs(Structure):
-    _fields_ = [(n, c_void_p) for n in ("x", "gy", "y", "res", "out", "out2", "a", "b", "mean", "invstd", "k1", "k2", "k3",
-                                        "partial")] + \
-        [("rows", c_int64), ("S", c_int64), ("batch", c_int32), ("C", c_int32), ("cw", c_int32), ("dtype", c_int32),
-         ("layout", c_int32)] + \
-        [(n, c_int32) for n in ("x_cs", "x_coff", "gy_cs", "gy_coff", "y_cs", "y_coff", "res_cs", "res_coff", "out_cs",
-                                "out_coff", "out2_cs", "out2_coff", "act", "res_first")] + \
-        [("slope", c_float), ("nblk", c_int32)]
-
-
-class FrustumArgs(Structure):
-    _fields_ = [("cam_E", c_void_p), ("cam_k", c_void_p), ("target", c_void_p), ("masks", c_void_p), ("dists", c_void_p),
-                ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
-        [(n, c_int32) for n in ("batch", "n_views", "X", "Y", "Z", "img_w", "img_h", "frustum_size", "n_classes")]
-
-
-class ConfusionRegion(Structure):
-    _fields_ = [(n, c_int32) for n in ("x0", "x1", "y0", "y1", "z0", "z1")] + [("need", c_uint32), ("reserved", c_int32)]
-
-
-class ConfusionRegionsArgs(Structure):
-    _fields_ = [("logits", c_void_p), ("labels", c_void_p), ("target", c_void_p), ("masks", c_void_p * 3), ("fov", c_void_p),
-                ("cam_E", c_void_p), ("cam_k", c_void_p), ("hist", c_void_p),
-                ("s_b", c_int64), ("s_c", c_int64), ("s_v", c_int64), ("frame_stride", c_int64),
-                ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
-        [(n, c_int32) for n in ("batch", "C", "X", "Y", "Z", "R", "n_views", "view_mask", "img_w", "img_h")] + \
-        [("regions", ConfusionRegion * 8)]
-
-
-class Vox2PixArgs(Structure):
-    _fields_ = [("cam_E", c_void_p), ("cam_k", c_void_p), ("ida", c_void_p), ("pix", c_void_p), ("fov", c_void_p),
-                ("pix_z", c_void_p), ("vox_origin", c_double * 3), ("voxel_size", c_double)] + \
-        [(n, c_int32) for n in ("batch", "n_views", "X", "Y", "Z", "img_w", "img_h")]
-
-
-OPTIM_CHUNK = 8192   # OCCD_OPTIM_CHUNK: elements per chunk descriptor
-
-
-class OptimChunk(Structure):
-    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("step", c_void_p),
-                ("offset", c_int64), ("count", c_int32), ("reserved0", c_int32), ("acc", c_void_p)]
-
-
-class ClipAdamWArgs(Structure):
-    _fields_ = [("chunks", c_void_p), ("partials", c_void_p), ("norm_out", c_void_p), ("lr_dev", c_void_p),
-                ("n_chunks", c_int64), ("n_elems", c_int64)] + \
-        [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
-
-
-class AccumAdamWArgs(Structure):
-    _fields_ = [("chunks", c_void_p), ("partials", c_void_p), ("norm_out", c_void_p), ("lr_dev", c_void_p),
-                ("flags_dev", c_void_p), ("n_chunks", c_int64), ("n_elems", c_int64)] + \
-        [(n, c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "scale")] + \
-        [("first", c_int32), ("last", c_int32)]
-
-
-class ProfRow(Structure):
-    _fields_ = [("tag", c_char * 64), ("launches", c_int64), ("ms", c_double), ("flops", c_double),
-                ("bytes", c_double)]
-
-
-EXPORTS = {
-    "occd_abi_version": (c_int32, []),
-    "occd_strerror": (c_char_p, [c_int32]),
-    "occd_conv3d_fwd": (c_int32, [POINTER(Conv3dArgs), c_void_p]),
-    "occd_conv3d_fwd_phases": (c_int32, [POINTER(Conv3dArgs), c_int32, c_void_p]),
-    "occd_conv3d_bf16_fwd_phases": (c_int32, [POINTER(Conv3dArgs), c_int32, c_int32, c_void_p]),
-    "occd_packed_weight_floats": (c_int64, [c_int32, c_int32, c_int32]),
-    "occd_pack_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                    c_int32, c_void_p]),
-    "occd_flosp_sample_fwd": (c_int32, [POINTER(FlospArgs), c_void_p]),
-    "occd_rows_gemm_fwd": (c_int32, [POINTER(RowsGemmArgs), c_void_p]),
-    "occd_gemm_f32x3": (c_int32, [POINTER(GemmArgs), c_void_p]),
-    "occd_gemm_f32x3_nt": (c_int32, [POINTER(GemmArgs), c_void_p]),
-    "occd_gemm_f32x3_nt_splits": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
-    "occd_gemm_x3_packed_elems": (c_int64, [c_int32, c_int32]),
-    "occd_gemm_x3_pack": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int64, c_void_p]),
-    "occd_rows_gemm_packed_floats": (c_int64, [c_int32, c_int32]),
-    "occd_rows_gemm_pack": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
-    "occd_bottleneck3d_weight_floats": (c_int64, [c_int32, c_int32]),
-    "occd_bottleneck3d_fwd": (c_int32, [POINTER(BneckArgs), c_void_p]),
-    "occd_lift_proj_fwd": (c_int32, [POINTER(LiftProjArgs), c_void_p]),
-    "occd_lift_fwd": (c_int32, [POINTER(LiftArgs), c_void_p]),
-    "occd_lift_bwd": (c_int32, [POINTER(LiftBwdArgs), c_void_p]),
-    "occd_nchw_to_nhwc": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p]),
-    "occd_nhwc_to_nchw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p]),
-    "occd_softmax_channels": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                        c_int32, c_void_p]),
-    "occd_affine_act_nchw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
-                                       c_int32, c_float, c_int32, c_void_p]),
-    "occd_dwconv2d_nchw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 11 + [c_void_p]),
-    "occd_upsample_bilinear_cat_nchw": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p]),
-    "occd_swish_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "occd_upconv_gather_skip_nchw": (c_int32, [c_void_p] * 5 + [c_int32] * 7 + [c_int64, c_int64, ctypes.c_float, c_void_p]),
-    "occd_upconv_gather_nchw": (c_int32, [c_void_p, c_void_p] + [c_int32] * 6 + [c_int64, c_int64, c_void_p]),
-    "occd_wino_input_transform_nchw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                                 c_void_p]),
-    "occd_wino_output_transform_nchw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                                  c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_void_p]),
-    "occd_wino_packed_floats": (c_int64, [c_int32, c_int32]),
-    "occd_wino_pack_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
-    "occd_wino_conv3x3_fwd": (c_int32, [POINTER(WinoArgs), c_void_p]),
-    "occd_wino_packed_f16x2_bytes": (c_int64, [c_int32, c_int32]),
-    "occd_wino_pack_weights_f16x2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
-    "occd_wino_conv3x3_f16x2_fwd": (c_int32, [POINTER(WinoArgs), c_void_p]),
-    "occd_wino_conv3x3_f16x2_fwd_ex": (c_int32, [POINTER(WinoArgs), c_int32, c_void_p]),
-    "occd_softmax_nchw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
-    "occd_dwconv2d_bwd_data_nchw": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p]),
-    "occd_dwconv2d_bwd_weight_workspace_floats": (c_int64, [c_int32] * 5),
-    "occd_dwconv2d_bwd_weight_nchw": (c_int32, [c_void_p] * 4 + [c_int32] * 10 + [c_void_p]),
-    "occd_dwconv2d_pool_blocks": (c_int32, [c_int32, c_int32]),
-    "occd_dwconv2d_pool_nchw": (c_int32, [c_void_p] * 6 + [c_int32] * 11 + [c_int64, c_void_p]),
-    "occd_se_gate": (c_int32, [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]),
-    "occd_pw_packed_floats": (c_int64, [c_int32, c_int32]),
-    "occd_pw_pack_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
-    "occd_pw_conv_fwd": (c_int32, [POINTER(PwArgs), c_void_p]),
-    "occd_project_voxels": (c_int32, [c_void_p, c_void_p, c_void_p, c_double] + [c_int32] * 5
-                            + [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "occd_argmax_channels": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
-    "occd_cascade_tail_fwd": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 8 + [c_void_p]),
-    "occd_conv3d_wgrad_workspace_floats": (c_int64, [POINTER(WgradArgs)]),
-    "occd_conv3d_wgrad": (c_int32, [POINTER(WgradArgs), c_void_p]),
-    "occd_packed_weight_bf16_elems": (c_int64, [c_int32, c_int32, c_int32]),
-    "occd_pack_weights_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                         c_int32, c_void_p]),
-    "occd_conv3d_bf16_fwd": (c_int32, [POINTER(Conv3dArgs), c_int32, c_void_p]),
-    "occd_upsample_bilinear_cat_nhwc": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p]),
-    "occd_upsample_bilinear_cat_nhwc_rows": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 8 + [c_void_p]),
-    "occd_upsample_bilinear_nhwc_bwd": (c_int32, [c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p]),
-    "occd_pack_weights_gather": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64,
-                                           c_void_p, c_void_p]),
-    "occd_pack_weights_bf16_gather": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64,
-                                                c_void_p, c_void_p]),
-    "occd_pack_weights_bf16x3_gather": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64,
-                                                c_void_p, c_void_p]),
-    "occd_pack_weights_bf16x3": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                           c_int32, c_void_p]),
-    "occd_packed_weight_f16x2_bytes": (c_int64, [c_int32, c_int32, c_int32]),
-    "occd_pack_weights_f16x2": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                          c_int32, c_void_p]),
-    "occd_conv3d_wgrad_bf16_workspace_floats": (c_int64, [POINTER(WgradArgs), c_int32]),
-    "occd_conv3d_wgrad_bf16": (c_int32, [POINTER(WgradArgs), c_int32, c_void_p]),
-    "occd_bn_blocks": (c_int32, [POINTER(BnArgs)]),
-    "occd_bn_stats": (c_int32, [POINTER(BnArgs), c_void_p]),
-    "occd_bn_stats_combine": (c_int32, [POINTER(BnArgs), c_void_p, c_void_p]),
-    "occd_bn_finish": (c_int32, [c_void_p, c_int32, c_float, c_float] + [c_void_p] * 9 + [c_void_p]),
-    "occd_bn_apply": (c_int32, [POINTER(BnArgs), c_void_p]),
-    "occd_bn_bwd_reduce": (c_int32, [POINTER(BnArgs), c_void_p]),
-    "occd_bn_bwd_combine": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
-    "occd_bn_bwd_finish": (c_int32, [c_void_p, c_void_p, c_int32] + [c_void_p] * 9 + [c_void_p]),
-    "occd_bn_bwd_apply": (c_int32, [POINTER(BnArgs), c_void_p]),
-    "occd_bn_stats_finish": (c_int32, [POINTER(BnArgs), c_void_p, c_float, c_float] + [c_void_p] * 9 + [c_void_p]),
-    "occd_bn_bwd_combine_finish": (c_int32, [c_void_p, c_int32, c_int32] + [c_void_p] * 9 + [c_void_p]),
-    "occd_bn_small_ok": (c_int32, [POINTER(BnArgs)]),
-    "occd_bn_fwd_small": (c_int32, [POINTER(BnArgs), c_void_p, c_float, c_float] + [c_void_p] * 9 + [c_void_p]),
-    "occd_bn_bwd_small": (c_int32, [POINTER(BnArgs), c_void_p, c_void_p, c_void_p]),
-    "occd_bn_xchg_mailbox_bytes": (c_int64, [c_int32, c_int32]),
-    "occd_bn_fwd_small_xchg": (c_int32, [POINTER(BnArgs), c_void_p, c_float, c_float] + [c_void_p] * 9 +
-                               [POINTER(c_void_p), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "occd_bn_bwd_small_xchg": (c_int32, [POINTER(BnArgs), c_void_p, c_void_p, c_void_p, POINTER(c_void_p), c_int32, c_int32,
-                                         c_int32, c_int32, c_void_p, c_void_p]),
-    "occd_ssc_stats_len": (c_int64, [c_int32, c_int32]),
-    "occd_ssc_loss_stats_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
-                                          c_int32, c_int32, c_void_p]),
-    "occd_ssc_loss_stats_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
-                                          c_int64, c_int32, c_int32, c_void_p]),
-    "occd_ssc_confusion": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p]),
-    "occd_ssc_loss_stats_fwd_strided": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
-                                                  c_int32, c_int32, c_int64, c_int64, c_int64, c_void_p]),
-    "occd_ssc_loss_stats_bwd_strided": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
-                                                  c_int64, c_int32, c_int32] + [c_int64] * 6 + [c_int32, c_void_p]),
-    "occd_ssc_confusion_strided": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64,
-                                             c_int64, c_int64, c_void_p]),
-    "occd_relation_bce_stats": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32] + [c_int64] * 6 + [c_void_p]),
-    "occd_relation_bce_grad": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32] + [c_int64] * 6 +
-                               [c_void_p]),
-    "occd_depth_bce_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64] + [c_int32] * 6 + [c_int64, c_float, c_float,
-                                                                                               c_void_p]),
-    "occd_depth_bce_grad": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int32] * 6 +
-                            [c_int64, c_float, c_float, c_void_p]),
-    "occd_flosp_sample_bwd": (c_int32, [POINTER(FlospBwdArgs), c_void_p]),
-    "occd_stem_conv3x3_nchw": (c_int32, [c_void_p] * 5 + [c_int32] * 10 + [c_void_p]),
-    "occd_ipc_mailbox_bytes": (c_int64, [c_int32, c_int64]),
-    "occd_ipc_mailbox_create": (c_int32, [c_int64, POINTER(c_void_p), c_void_p]),
-    "occd_ipc_mailbox_open": (c_int32, [c_void_p, POINTER(c_void_p)]),
-    "occd_ipc_mailbox_close": (c_int32, [c_void_p]),
-    "occd_ipc_mailbox_free": (c_int32, [c_void_p]),
-    "occd_ipc_allreduce": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_void_p), c_int32, c_int32, c_int64,
-                                     c_int32, c_void_p, c_void_p]),
-    "occd_plane_reduce": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "occd_se_bwd": (c_int32, [c_void_p] * 13 + [c_int32, c_int32, c_int32, c_int64, c_void_p]),
-    "occd_depthnet_gate": (c_int32, [c_void_p, c_void_p, c_int64, c_float] + [c_void_p] * 9 + [c_int32, c_int32, c_void_p]),
-    "occd_prof_enable": (c_int32, [c_int32]),
-    "occd_gemm_f32x3_splitk_plan": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
-                                              POINTER(c_int32), POINTER(c_int64)]),
-    "occd_gemm_f32x3_splitk": (c_int32, [POINTER(GemmArgs), c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
-    "occd_se_gate_set_fused": (c_int32, [c_int32]),
-    "occd_graph_replace_memsets": (c_int32, [c_void_p]),
-    "occd_frustum_targets": (c_int32, [POINTER(FrustumArgs), c_void_p]),
-    "occd_vox2pix": (c_int32, [POINTER(Vox2PixArgs), c_void_p]),
-    "occd_ssc_confusion_regions": (c_int32, [POINTER(ConfusionRegionsArgs), c_void_p]),
-    "occd_downsample_label": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
-    "occd_cp_mega_matrix": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
-    "occd_kitti_labels": (c_int32, [c_void_p] * 4 + [c_int32] + [c_void_p] * 3 + [c_int32, c_int64, c_void_p]),
-    "occd_grad_sumsq": (c_int32, [POINTER(ClipAdamWArgs), c_void_p]),
-    "occd_clip_adamw": (c_int32, [POINTER(ClipAdamWArgs), c_void_p]),
-    "occd_accum_clip_adamw": (c_int32, [POINTER(AccumAdamWArgs), c_void_p]),
-    "occd_prof_set_tag": (c_int32, [c_char_p]),
-    "occd_prof_report": (c_int32, [POINTER(ProfRow), c_int32]),
-}
 
 _lib = None
 _PROFILING = False
@@ -643,7 +360,8 @@ def conv3d_bf16(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 
     return out
 
 
-GEMM_ACT = {None: 0, "none": 0, "swish": 1, "leaky": 2}
+GEMM_ACT = {None: abi.CONSTANTS["OCCD_GEMM_ACT_NONE"], "none": abi.CONSTANTS["OCCD_GEMM_ACT_NONE"],
+            "swish": abi.CONSTANTS["OCCD_GEMM_ACT_SWISH"], "leaky": abi.CONSTANTS["OCCD_GEMM_ACT_LEAKY"]}
 
 
 class GemmPacked:
@@ -2264,7 +1982,6 @@ def ssc_confusion(hist, target, logits=None, labels=None):
     return hist
 
 
-MAX_REGIONS = 8
 NEED_FOV = 1                    # `need` bits of a region: the camera FOV, then mask slot i -> NEED_MASK0 << i
 NEED_MASK0 = 2
 

@@ -1,5 +1,6 @@
 """CPU: libocc_hip.so builds, loads, and exports exactly what include/occdepth_amd.h declares; the
-ctypes structures in occdepth_amd/hip.py have the C layout (checked against gcc's sizeof/offsetof)."""
+ctypes structures occdepth_amd/abi.py derives from the header have the C layout (checked against gcc's
+sizeof/offsetof); the parser accepts the header's subset of C and raises on everything else."""
 import ctypes
 import os
 import re
@@ -44,12 +45,9 @@ def test_argument_validation_without_gpu(hip_lib):
 
 
 def test_ctypes_structs_match_c_layout(tmp_path):
-    from occdepth_amd import hip
-    structs = {"occd_conv3d_args": hip.Conv3dArgs, "occd_flosp_args": hip.FlospArgs, "occd_lift_args": hip.LiftArgs,
-               "occd_prof_row": hip.ProfRow, "occd_conv3d_wgrad_args": hip.WgradArgs, "occd_wino_args": hip.WinoArgs,
-               "occd_pw_args": hip.PwArgs, "occd_lift_bwd_args": hip.LiftBwdArgs, "occd_bn_args": hip.BnArgs,
-               "occd_lift_proj_args": hip.LiftProjArgs, "occd_bneck_args": hip.BneckArgs,
-               "occd_rows_gemm_args": hip.RowsGemmArgs, "occd_gemm_args": hip.GemmArgs}
+    from occdepth_amd import abi
+    structs = abi.STRUCTS                   # every structure the header declares
+    assert sorted(structs) == sorted(re.findall(r"^typedef struct (\w+)", open(HEADER).read(), flags=re.M)) and len(structs) >= 21
     rename = {"inp": "in"}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, st in structs.items():
@@ -187,3 +185,155 @@ def test_gemm_entry_point_validates_kernel_hints(hip_lib):
     assert hip_lib.occd_gemm_f32x3(ctypes.byref(q), None) == -1
     q.act_a, q.K = 0, 60                                 # K % 8
     assert hip_lib.occd_gemm_f32x3(ctypes.byref(q), None) == -1
+
+
+# ----------------------------------------------------------------------------- the header parser, on small strings
+SMALL = """
+/* a comment with a ; and a { in it */
+#ifndef SMALL_H
+#define SMALL_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define OCCD_MAX_VIEWS 4
+#define OCCD_MAX_SCALES 3
+#define OCCD_EINVAL (-1)   /* parenthesised */
+#define OCCD_HEX 0x10
+typedef struct occd_inner {
+    float* out;
+    double origin[3];
+    char tag[8];
+} occd_inner;
+typedef struct occd_outer {
+    const float* in;                                   /* `in` is a Python keyword */
+    const float* feat[OCCD_MAX_SCALES][OCCD_MAX_VIEWS];
+    int32_t feat_h[OCCD_MAX_SCALES], feat_w[OCCD_MAX_SCALES];
+    float scale_const;
+    const uint8_t* const_ptr, *second;
+    int64_t rows;
+    uint32_t need;
+    occd_inner inner;
+    occd_inner two[2];
+    const occd_inner* table;
+} occd_outer;
+int occd_version(void);
+const char* occd_text(int code);
+int64_t occd_run(const occd_outer* a, int32_t n, double x, void** created, void* const* boxes, const void* h,
+                 int32_t* status, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* SMALL_H */
+"""
+
+
+def small():
+    from occdepth_amd import abi
+    return abi.parse(SMALL)
+
+
+def test_parser_constants():
+    consts, _, _ = small()
+    assert consts == {"OCCD_MAX_VIEWS": 4, "OCCD_MAX_SCALES": 3, "OCCD_EINVAL": -1, "OCCD_HEX": 16}
+
+
+def test_parser_scalar_pointer_and_array_fields():
+    from ctypes import c_char, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
+    _, structs, _ = small()
+    assert list(structs) == ["occd_inner", "occd_outer"]
+    assert structs["occd_inner"]._fields_ == [("out", c_void_p), ("origin", c_double * 3), ("tag", c_char * 8)]
+    f = dict(structs["occd_outer"]._fields_)
+    assert [n for n, _ in structs["occd_outer"]._fields_] == [
+        "inp", "feat", "feat_h", "feat_w", "scale_const", "const_ptr", "second", "rows", "need", "inner", "two", "table"]
+    assert f["inp"] is c_void_p and f["rows"] is c_int64 and f["need"] is c_uint32
+    assert f["scale_const"] is c_float                 # a name that contains `const` keeps it
+    assert f["const_ptr"] is c_void_p and f["second"] is c_void_p
+    assert f["feat_h"] is c_int32 * 3 and f["feat_w"] is c_int32 * 3      # two declarators, one base type
+    assert f["table"] is c_void_p                      # pointer fields hold raw addresses, whatever they point to
+
+
+def test_parser_2d_array_of_pointers_takes_integers():
+    from ctypes import c_void_p
+    _, structs, _ = small()
+    assert dict(structs["occd_outer"]._fields_)["feat"] is (c_void_p * 4) * 3
+    a = structs["occd_outer"]()
+    a.feat[2][3] = 0x1000
+    a.inp = 0x2000
+    assert a.feat[2][3] == 0x1000 and a.feat[0][0] is None and a.inp == 0x2000
+    with pytest.raises(IndexError):
+        a.feat[3][0] = 1
+
+
+def test_parser_nested_struct():
+    _, structs, _ = small()
+    inner, outer = structs["occd_inner"], structs["occd_outer"]
+    f = dict(outer._fields_)
+    assert f["inner"] is inner and f["two"] is inner * 2
+    assert outer.two.offset - outer.inner.offset == ctypes.sizeof(inner) == 8 + 24 + 8
+
+
+def test_parser_prototypes():
+    from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_void_p
+    _, structs, exports = small()
+    assert list(exports) == ["occd_version", "occd_text", "occd_run"]
+    assert exports["occd_version"] == (c_int32, [])                       # (void)
+    assert exports["occd_text"] == (c_char_p, [c_int32])                  # const char* return
+    assert exports["occd_run"] == (c_int64, [POINTER(structs["occd_outer"]), c_int32, c_double, POINTER(c_void_p),
+                                             POINTER(c_void_p), c_void_p, c_void_p, c_void_p])
+
+
+@pytest.mark.parametrize("name,text", [
+    ("unknown type", "typedef struct occd_t { size_t n; } occd_t;"),
+    ("unknown parameter type", "int occd_f(unsigned n);"),
+    ("function-pointer field", "typedef struct occd_t { int (*cb)(int); } occd_t;"),
+    ("bitfield", "typedef struct occd_t { int32_t a : 3; } occd_t;"),
+    ("extent that is no integer", "#define OCCD_N (2 * 3)\ntypedef struct occd_t { int32_t a[OCCD_N]; } occd_t;"),
+    ("extent that is not defined", "typedef struct occd_t { int32_t a[OCCD_N]; } occd_t;"),
+    ("leftover text", "int occd_f(void);\nstray words\nint occd_g(void);"),
+    ("unterminated declaration", "int occd_f(void);\nint occd_g(void)"),
+    ("function body", "int occd_f(void) { return 0; }"),
+    ("empty parameter list", "int occd_f();"),
+    ("anonymous struct", "typedef struct { int32_t a; } occd_t;"),
+    ("nested definition", "typedef struct occd_t { struct { int32_t a; } s; } occd_t;"),
+    ("field without a name", "typedef struct occd_t { int32_t; } occd_t;"),
+    ("void field", "typedef struct occd_t { void a; } occd_t;"),
+    ("array parameter", "int occd_f(int32_t a[3]);"),
+    ("function-like macro", "#define OCCD_F(x) x"),
+    ("conditional", "#if 1\nint occd_f(void);\n#endif"),
+    ("line comment", "int occd_f(void); // no"),
+    ("function declared twice", "int occd_f(void);\nint occd_f(void);"),
+])
+def test_parser_rejects(name, text):
+    from occdepth_amd import abi
+    with pytest.raises(abi.HeaderError):
+        abi.parse(text)
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    """Without the header there is no binding: importing abi raises and names the path (run on a copy of the module,
+    so the loaded binding is left alone)."""
+    import importlib.util
+    from occdepth_amd import abi
+    pkg = tmp_path / "pkg"
+    pkg.mkdir()
+    (pkg / "abi.py").write_text(open(abi.__file__).read())
+    spec = importlib.util.spec_from_file_location("abi_without_header", str(pkg / "abi.py"))
+    with pytest.raises(RuntimeError, match="occdepth_amd.h is missing"):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+
+
+def test_derived_prototypes_spot_pinned():
+    """A handful of prototypes of the real header against literals: a parser regression shows as a readable diff."""
+    from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
+    from occdepth_amd import abi, hip
+    assert hip.EXPORTS is abi.EXPORTS and hip.ABI_VERSION == abi.ABI_VERSION == abi.CONSTANTS["OCCD_ABI_VERSION"]
+    assert abi.EXPORTS["occd_abi_version"] == (c_int32, [])
+    assert abi.EXPORTS["occd_conv3d_fwd"] == (c_int32, [POINTER(hip.Conv3dArgs), c_void_p])
+    assert abi.EXPORTS["occd_bn_fwd_small_xchg"] == (
+        c_int32, [POINTER(hip.BnArgs), c_void_p, c_float, c_float] + [c_void_p] * 9 +
+        [POINTER(c_void_p), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p])
+    assert abi.EXPORTS["occd_gemm_f32x3_splitk"] == (
+        c_int32, [POINTER(hip.GemmArgs), c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p])
+    assert hip.Conv3dArgs._fields_[0] == ("inp", c_void_p) and hip.Conv3dArgs is abi.STRUCTS["occd_conv3d_args"]
+    assert dict(hip.LiftArgs._fields_)["feat"] is (c_void_p * hip.MAX_VIEWS) * hip.MAX_SCALES

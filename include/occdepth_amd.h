@@ -665,6 +665,60 @@ int occd_argmax_channels(const float* x, int64_t rows, int32_t cs, int32_t coff,
                          const uint16_t* lut, uint16_t* out, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Headless voxel renderer (csrc/render.hip): ray-cast label volumes to images, one launch for batch x n_views x H x W
+ * pixels, one thread per pixel -- the GPU counterpart of the reference's mayavi / open3d viewers
+ * (scripts/visualization/kitti_vis_pred.py, NYU_vis_pred.py), which need a display.  Added without an ABI bump: entries
+ * and structures only, every older caller stays valid.  No atomics, no allocation, no host sync (capture-safe).
+ *
+ * Ray of pixel (u, v) of a view, in GRID units (one voxel = 1; the volume is the box [0,X] x [0,Y] x [0,Z]):
+ *   origin = o0 + (u + 1/2) ou + (v + 1/2) ov,   dir = d0 + (u + 1/2) du + (v + 1/2) dv          (float32, no fma)
+ * -- a pinhole camera (constant origin; scale dir so that t is camera depth), an orthographic view (constant dir) or a
+ * mirrored one (negated du) alike; the kernel knows nothing about calibration.
+ * Traversal: slab test against the box (a zero direction component is `parallel`: inside or outside by the origin; a
+ * non-finite ray misses); t_enter = max(largest near-slab t, 0); entry face = the axis of that slab (lowest axis on
+ * ties), 3 when t_enter = 0; first voxel = clamp(floor(origin + dir t_enter), 0, dims - 1); then Amanatides-Woo steps
+ * with tmax_a = ((index_a + (dir_a > 0)) - origin_a) * (1 / dir_a) recomputed from the boundary at every step, the lowest
+ * axis winning ties; the stepped axis becomes the face and t that tmax; the walk ends at the first visible voxel, when
+ * the index leaves the grid, when no boundary is left to cross, or after X + Y + Z + 3 steps (never reached: every step
+ * moves one index one way).  Every index is in range before its load.
+ * Visible: class mode (target == NULL) 0 < label < 255.  Error mode: target == 255 is transparent; else visible when the
+ * prediction (0 < label < 255) or the target (!= 0) is occupied.
+ * Colour (integers): c = palette[row] * shade[face] >> 8, shade = {160, 208, 256, 256}; c = c / 3 * 2 when fov != NULL and
+ * fov[voxel] == 0; row = min(label, n_palette - 1) in class mode; in error mode the last three palette rows are {occupied
+ * with the wrong class, false positive, false negative} and a correct voxel takes row min(label, n_palette - 4).  With a
+ * background image: hit -> (alpha c + (256 - alpha) bg) >> 8, miss -> bg; without: miss -> bg_colour.  Pixels of the
+ * (H, W) canvas outside a view's own view_w x view_h rectangle (0 = the whole canvas) are misses.
+ * OCCD_EINVAL without a launch: NULL labels / views / palette / rgb, non-positive sizes, X Y Z > 2^31 - 1, label_bytes or
+ * (with a target) target_bytes other than 1 or 2, n_views > OCCD_RENDER_MAX_VIEWS, alpha outside 0..256, n_palette < 1 (4
+ * in error mode), a view rectangle larger than the canvas.
+ * ------------------------------------------------------------------------ */
+#define OCCD_RENDER_MAX_VIEWS 8
+typedef struct OccdRenderView {
+    float o0[3], ou[3], ov[3];
+    float d0[3], du[3], dv[3];
+} OccdRenderView;
+
+typedef struct OccdRenderArgs {
+    const void* labels;            /* (B, X, Y, Z) uint8 / uint16 prediction                                  */
+    const void* target;            /* (B, X, Y, Z) uint8 / uint16, or NULL: class mode                        */
+    const uint8_t* fov;            /* (B, X, Y, Z) bytes, 0 = outside the camera's FOV (dimmed), or NULL      */
+    const OccdRenderView* views;   /* (B, n_views) device                                                     */
+    const uint8_t* palette;        /* (n_palette, 3) device                                                   */
+    const uint8_t* background;     /* (B, n_views, H, W, 3), or NULL                                          */
+    uint8_t* rgb;                  /* (B, n_views, H, W, 3)                                                   */
+    int32_t* hit;                  /* (B, n_views, H, W) voxel index (x Y + y) Z + z or -1, or NULL           */
+    uint8_t* face;                 /* (B, n_views, H, W) 0 / 1 / 2 = x / y / z, 3 = started inside or miss, or NULL */
+    float* depth;                  /* (B, n_views, H, W) t at the hit, +inf on a miss, or NULL                */
+    int32_t batch, n_views, H, W;
+    int32_t X, Y, Z;
+    int32_t label_bytes, target_bytes;
+    int32_t n_palette, alpha;
+    int32_t view_w[OCCD_RENDER_MAX_VIEWS], view_h[OCCD_RENDER_MAX_VIEWS];
+    uint8_t bg_colour[4];
+} OccdRenderArgs;
+int occd_render_voxels(const OccdRenderArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * K8: weight gradient of a 3-D convolution (training step):
  *   dw[co][ci][kx][ky][kz] = sum_{b,xo,yo,zo} gy[b,xo,yo,zo][co] * x[b, xo*sx - px + kx*dx, ...][ci]
  * -- what autograd computes for nn.Conv3d.weight in the reference's training step

@@ -48,6 +48,9 @@ Vox2PixArgs = abi.STRUCTS["occd_vox2pix_args"]
 OptimChunk = abi.STRUCTS["occd_optim_chunk"]
 ClipAdamWArgs = abi.STRUCTS["occd_clip_adamw_args"]
 AccumAdamWArgs = abi.STRUCTS["occd_accum_adamw_args"]
+RenderView = abi.STRUCTS["OccdRenderView"]
+RenderArgs = abi.STRUCTS["OccdRenderArgs"]
+RENDER_MAX_VIEWS = abi.CONSTANTS["OCCD_RENDER_MAX_VIEWS"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -1830,12 +1833,13 @@ def vox2pix(cam_E, cam_k, ida, vox_origin, voxel_size, dims, img_wh, with_z=Fals
     return (pix, fov, z) if with_z else (pix, fov)
 
 
-def argmax_labels(logits, lut=None):
-    """(B, C, X, Y, Z) float32 GPU logits -> (B, X, Y, Z) int32 class volume (argmax over C, first maximum wins),
-    optionally mapped through `lut` (e.g. SemanticKITTI learning_map_inv).  Channels-last views returned by the
-    eval path (rows of a possibly wider buffer) are consumed in place."""
-    if logits.dtype != torch.float32 or not logits.is_cuda:
-        raise RuntimeError("argmax_labels needs float32 GPU logits")
+def argmax_labels_u16(logits, lut=None):
+    """(B, C, X, Y, Z) float32 GPU logits -> the (B, X, Y, Z) volume occd_argmax_channels writes: uint16 values in an int16
+    tensor (arg-max over C, first maximum wins, optionally mapped through `lut`), which `render_voxels` reads in place.
+    Channels-last views returned by the eval path (rows of a possibly wider buffer) are consumed in place.  Without a
+    `lut`: one launch, one allocation, capture-safe."""
+    if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 5:
+        raise RuntimeError("argmax_labels needs float32 GPU logits of shape (B, C, X, Y, Z)")
     cl = logits.permute(0, 2, 3, 4, 1)
     B, X, Y, Z, C = cl.shape
     cs = cl.stride(3)
@@ -1845,13 +1849,79 @@ def argmax_labels(logits, lut=None):
         cl = cl.contiguous()
         cs = C
     rows = B * X * Y * Z
-    out = torch.empty(rows, dtype=torch.int16, device=logits.device)
+    out = torch.empty((B, X, Y, Z), dtype=torch.int16, device=logits.device)
     lut_t = None
     if lut is not None:
         lut_t = torch.as_tensor(lut, dtype=torch.int32).to(torch.int16).to(logits.device).contiguous()
     _check(load().occd_argmax_channels(cl.data_ptr(), rows, cs, 0, C, lut_t.data_ptr() if lut_t is not None else None,
                                        out.data_ptr(), _stream()), "occd_argmax_channels")
-    return (out.to(torch.int32) & 0xFFFF).view(B, X, Y, Z)
+    return out
+
+
+def argmax_labels(logits, lut=None):
+    """(B, C, X, Y, Z) float32 GPU logits -> (B, X, Y, Z) int32 class volume (argmax over C, first maximum wins),
+    optionally mapped through `lut` (e.g. SemanticKITTI learning_map_inv).  Channels-last views returned by the
+    eval path (rows of a possibly wider buffer) are consumed in place."""
+    return argmax_labels_u16(logits, lut).to(torch.int32) & 0xFFFF
+
+
+_LABEL_BYTES = {torch.uint8: 1, torch.int16: 2, getattr(torch, "uint16", torch.int16): 2}
+
+
+def render_voxels(labels, views, size, palette, target=None, fov=None, background=None, alpha=256,
+                  bg_colour=(255, 255, 255), view_sizes=None, aux=False):
+    """Ray-cast label volumes to images in one launch (occd_render_voxels; the contract is in include/occdepth_amd.h).
+    labels (B, X, Y, Z) uint8 / int16 / uint16; views (B, V, 18) float32 ray generators; size = (H, W) of the canvas and
+    view_sizes an optional list of V (h, w) rectangles inside it; palette (P, 3) uint8; target like labels (error mode);
+    fov (B, X, Y, Z) bool / uint8; background (B, V, H, W, 3) uint8 blended with `alpha` (0..256).  All on the GPU and
+    contiguous.  -> rgb (B, V, H, W, 3) uint8, and with aux also hit int32, face uint8, depth float32 (B, V, H, W)."""
+    if labels.dim() != 4 or labels.dtype not in _LABEL_BYTES:
+        raise RuntimeError("labels must be a (B, X, Y, Z) uint8 / int16 / uint16 volume, got %s %s"
+                           % (tuple(labels.shape), labels.dtype))
+    B, X, Y, Z = (int(d) for d in labels.shape)
+    if views.dtype != torch.float32 or views.dim() != 3 or views.shape[0] != B or views.shape[2] != 18:
+        raise RuntimeError("views must be float32 (B, V, 18), got %s %s" % (tuple(views.shape), views.dtype))
+    V = int(views.shape[1])
+    H, W = int(size[0]), int(size[1])
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3:
+        raise RuntimeError("palette must be uint8 (P, 3)")
+    dev = labels.device
+    a = RenderArgs()
+    a.labels, a.views, a.palette = _ptr(labels, "labels"), _ptr(views, "views"), _ptr(palette, "palette")
+    a.label_bytes = _LABEL_BYTES[labels.dtype]
+    if target is not None:
+        if target.dtype not in _LABEL_BYTES or target.shape != labels.shape:
+            raise RuntimeError("target must be a uint8 / int16 / uint16 volume with the shape of labels")
+        a.target, a.target_bytes = _ptr(target, "target"), _LABEL_BYTES[target.dtype]
+    if fov is not None:
+        a.fov = _ptr(_byte_mask(fov, B, X * Y * Z, "fov"), "fov")
+    if background is not None:
+        if background.dtype != torch.uint8 or tuple(background.shape) != (B, V, H, W, 3):
+            raise RuntimeError("background must be uint8 (B, V, H, W, 3) = %s" % ((B, V, H, W, 3),))
+        a.background = _ptr(background, "background")
+    for t, name in ((views, "views"), (palette, "palette"), (target, "target"), (fov, "fov"), (background, "background")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, labels on {dev}")
+    if view_sizes is not None:
+        if len(view_sizes) != V:
+            raise RuntimeError("view_sizes needs one (h, w) per view")
+        for i, (h, w) in enumerate(view_sizes):
+            a.view_h[i], a.view_w[i] = int(h), int(w)
+    rgb = torch.empty((B, V, H, W, 3), dtype=torch.uint8, device=dev)
+    a.rgb = rgb.data_ptr()
+    hit = face = depth = None
+    if aux:
+        hit = torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+        face = torch.empty((B, V, H, W), dtype=torch.uint8, device=dev)
+        depth = torch.empty((B, V, H, W), dtype=torch.float32, device=dev)
+        a.hit, a.face, a.depth = hit.data_ptr(), face.data_ptr(), depth.data_ptr()
+    a.batch, a.n_views, a.H, a.W = B, V, H, W
+    a.X, a.Y, a.Z = X, Y, Z
+    a.n_palette, a.alpha = int(palette.shape[0]), int(alpha)
+    for i in range(3):
+        a.bg_colour[i] = int(bg_colour[i])
+    _check(load().occd_render_voxels(ctypes.byref(a), _stream()), "occd_render_voxels")
+    return (rgb, hit, face, depth) if aux else rgb
 
 
 # ----------------------------------------------------------------------------- training-step statistics (N1 / N4)

@@ -143,6 +143,13 @@ class OccDepth(_Base):
         self.report_metrics = {}
         if env("OCCDEPTH_EVAL_REPORT", ""):
             self.enable_eval_report(env("OCCDEPTH_EVAL_REPORT"))
+        # Qualitative frames (render.py: predictions ray-cast to PNG on the GPU), OFF by default: `enable_render()` -- or
+        # OCCDEPTH_RENDER_DIR=<dir> [OCCDEPTH_RENDER_EVERY=n] [OCCDEPTH_RENDER_MODE=class|error] in the environment of an
+        # unmodified scripts/eval.py.  Off: nothing is allocated or launched.
+        self.render = None
+        if env("OCCDEPTH_RENDER_DIR", ""):
+            self.enable_render(env("OCCDEPTH_RENDER_DIR"), every=int(env("OCCDEPTH_RENDER_EVERY", "1")),
+                               mode=env("OCCDEPTH_RENDER_MODE", "class"))
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -597,6 +604,103 @@ class OccDepth(_Base):
             print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
         metric.reset()
 
+    # ---------------------------------------------------------------- qualitative frames (render.py)
+    RENDER_VOXEL_METRES = {"kitti": 0.2, "NYU": 0.08}       # full-resolution voxel of each dataset
+
+    def enable_render(self, out_dir, every=1, views=("camera", "bev"), mode="class", overlay=False, max_frames=None):
+        """Draw the prediction of every `every`-th test / validation batch on the GPU and write
+        <out_dir>/<sequence>/<frame_id>_<view>.png (NYU: <out_dir>/<name>_<view>.png).  views: "camera" (the left camera's
+        own view; overlay=True blends it over the input frame), "bev" (from above), "oblique" (third person).  mode
+        "error" colours the prediction against the step's target.  Voxels outside the batch's `fov_mask_1` are dimmed.
+        max_frames caps the frames written.  The pixels are the only device -> host transfer."""
+        from .. import render
+        views = tuple(views)
+        bad = [v for v in views if v not in render.VIEW_NAMES]
+        if bad or not views:
+            raise ValueError("unknown render view(s) %s (have %s)" % (bad, render.VIEW_NAMES))
+        if mode not in render.MODES:
+            raise ValueError("unknown render mode %r (have %s)" % (mode, render.MODES))
+        if int(every) < 1:
+            raise ValueError("every must be >= 1, got %r" % (every,))
+        self.render = {"out_dir": str(out_dir), "every": int(every), "views": views, "mode": mode, "overlay": bool(overlay),
+                       "max_frames": None if max_frames is None else int(max_frames), "seen": 0, "written": 0,
+                       "logged": False, "paths": []}
+        return self
+
+    def _render_views(self, batch, dims, img_hw, dev, names=None):
+        """The ray generators of the enabled views (or of `names`) for this batch -> ([(18,) or (B, 18) tensors], [(h, w)])."""
+        from .. import render
+        vs = self.RENDER_VOXEL_METRES.get(self.dataset, 0.2) * float(self.full_scene_size[0]) / float(dims[0])
+
+        def camera():
+            origin = self._kitti_origin(batch) if self.dataset == "kitti" else None
+            k, E, origin = render.batch_camera(batch, self.dataset, origin, dev)
+            return render.camera_view(k, E, origin, vs), img_hw
+
+        return render.standard_views(self.render["views"] if names is None else names, dims, dev, camera)
+
+    def _render_names(self, batch, i, index):
+        if "name" in batch:
+            return "", str(batch["name"][i])
+        seq = str(batch["sequence"][i]) if "sequence" in batch else "frames"
+        return seq, str(batch["frame_id"][i]) if "frame_id" in batch else "%06d" % index
+
+    def _render_logger(self):
+        try:
+            exp = getattr(self.logger, "experiment", None)
+        except (AttributeError, RuntimeError):
+            return None
+        return exp if hasattr(exp, "add_image") else None
+
+    def _render_step(self, step_type, batch, ssc_pred, target):
+        from .. import hip, render
+        st = self.render
+        st["seen"] += 1
+        if (st["seen"] - 1) % st["every"] or (st["max_frames"] is not None and st["written"] >= st["max_frames"]):
+            return
+        labels = hip.argmax_labels_u16(ssc_pred.detach())
+        B = labels.shape[0]
+        dims = tuple(int(d) for d in labels.shape[1:])
+        dev = labels.device
+        img = batch["img"]
+        views, sizes = self._render_views(batch, dims, img.shape[-2:], dev)
+        fov = self._report_fov(batch, target) if batch.get("fov_mask_1") is not None else None
+        kw = {"fov": fov if torch.is_tensor(fov) else None, "mode": st["mode"], "n_classes": self.n_classes,
+              "target": target if st["mode"] == "error" else None,
+              "palette": self.dataset if self.dataset in ("kitti", "NYU") else None}
+        images = [None] * len(views)
+        rest = list(range(len(views)))
+        if st["overlay"] and "camera" in st["views"]:
+            c = st["views"].index("camera")
+            mean = torch.tensor([0.485, 0.456, 0.406], device=dev).view(1, 3, 1, 1)
+            std = torch.tensor([0.229, 0.224, 0.225], device=dev).view(1, 3, 1, 1)
+            frame = ((img[:, 0].to(dev).float() * std + mean).clamp(0, 1) * 255).to(torch.uint8)
+            images[c] = render.render_labels(labels, [views[c]], sizes[c], background=frame.permute(0, 2, 3, 1)[:, None].contiguous(),
+                                             **kw)[:, 0]
+            rest.remove(c)
+        if rest:
+            for i, t in zip(rest, render.render_labels(labels, [views[i] for i in rest], [sizes[i] for i in rest], **kw)):
+                images[i] = t
+        # the only transfer: a few hundred KB per view into pinned memory, queued behind the step's kernels
+        host = [torch.empty(t.shape, dtype=torch.uint8, pin_memory=True).copy_(t, non_blocking=True) for t in images]
+        done = torch.cuda.Event()
+        done.record()
+        done.synchronize()
+        for i in range(B):
+            if st["max_frames"] is not None and st["written"] >= st["max_frames"]:
+                break
+            seq, frame_id = self._render_names(batch, i, st["written"])
+            d = os.path.join(st["out_dir"], seq)
+            os.makedirs(d, exist_ok=True)
+            for name, h in zip(st["views"], host):
+                st["paths"].append(render.write_png(os.path.join(d, "%s_%s.png" % (frame_id, name)), h[i].numpy()))
+            st["written"] += 1
+        exp = self._render_logger() if step_type == "val" and not st["logged"] else None
+        if exp is not None:
+            st["logged"] = True
+            for name, h in zip(st["views"], host):
+                exp.add_image("val_render/" + name, h[0].numpy(), getattr(self, "global_step", 0), dataformats="HWC")
+
     def _kitti_origin(self, batch=None):
         """SemanticKITTI voxel origin (kitti_dataset.py:82: vox_origin = (0, -25.6, -2) for the 51.2 m wide scene): the grid
         is centred on the sensor in y, whatever the scene width of a reduced test config.  A batch that carries its own
@@ -844,6 +948,8 @@ class OccDepth(_Base):
         if self.eval_report is not None and step_type in ("test", "val"):
             self._report_count(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
+        if self.render is not None and step_type in ("test", "val"):
+            self._render_step(step_type, batch, ssc_pred, target)     # last: its copy waits for the step's kernels
         return loss
 
     @staticmethod
@@ -1176,6 +1282,8 @@ class OccDepth(_Base):
                 self.log("val_region/{}/mIoU".format(name), stats["iou_ssc_mean"], sync_dist=True)
                 self.log("val_region/{}/IoU".format(name), stats["iou"], sync_dist=True)
             rep.reset()
+        if self.render is not None:
+            self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
     def test_step(self, batch, batch_idx):
         self.step(batch, "test", self.test_metrics)

@@ -719,6 +719,65 @@ typedef struct OccdRenderArgs {
 int occd_render_voxels(const OccdRenderArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Stereo depth targets from a rectified image pair (csrc/stereo.hip): census transform, semi-global matching over the
+ * four axis-aligned paths, winner-take-all with three validity checks, sub-pixel fit, depth = f B / disparity -- the
+ * `gt_depth` map of use_stereo_depth_gt, which the reference reads from 16-bit PNGs an external stereo network wrote
+ * (kitti_dataset.py:40-44, :338-348).  Added without an ABI bump: entries and one structure only, every older caller
+ * stays valid.  No atomics, no allocation, no host sync, no dependency between workgroups of a launch (capture-safe);
+ * every index is in range before its load.  Diagonal paths, median / speckle filtering and an adaptive P2 are not built.
+ *
+ * Per frame b: gray images L = gray[b][0], R = gray[b][1] (H, W) uint8, D = max_disp disparities, and a direction s:
+ * s = -1 when ida != NULL and ida[b][0][0][0] < 0 (a frame the loader mirrored: left pixel x matches right pixel x + d),
+ * else s = +1 (it matches x - d).  One launch may hold frames of both kinds.
+ * Gray (occd_stereo_census with img != NULL; float32, no fma): u_c = clamp(rint((img_c std[c] + mean[c]) 255), 0, 255),
+ *   g = (77 u_R + 150 u_G + 29 u_B + 128) >> 8, written to `gray`.  With img == NULL `gray` is the input.
+ * Census: window 9 wide x 7 tall, coordinates clamped to the image; the 62 neighbours row-major from the top-left,
+ *   skipping the centre; bit k of the 64-bit word is set when neighbour k < centre.
+ * Cost: C(y, x, d) = popcount(cl[y, x] ^ cr[y, x - s d]) when 0 <= x - s d < W, else 62 (never stored).
+ * Paths, four (left to right, right to left, downwards, upwards): the first pixel of a path has L = C; after it
+ *   L(p, d) = C(p, d) + min(L(q, d), L(q, d - 1) + P1, L(q, d + 1) + P1, m(q) + P2) - m(q),  m(q) = min_k L(q, k),
+ *   q the previous pixel of the path, the d - 1 / d + 1 terms absent at the ends of the range.  L <= 62 + P2 <= 255.
+ *   S = the sum of the four paths (uint16, <= 4 (62 + P2)).
+ * Winner: d0 = argmin_d S (lowest d on ties), best = S[d0].
+ * Flags (bit 0, 1, 2), all three required: unique 100 best <= U S2 with S2 = min S[d] over |d - d0| > 1;
+ *   consistent xr = x - s d0 inside the image and |dR(y, xr) - d0| <= 1, where dR(y, x') = argmin_d S(y, x' + s d, d)
+ *   over the d that stay inside the image (lowest d on ties); inner 1 <= d0 <= D - 2.
+ * Sub-pixel (float32): a = S[d0 - 1], b = S[d0 + 1], den = 2 (a + b - 2 best), sub = den > 0 ? (float)(a - b) /
+ *   (float)den : 0; disp = (float)d0 + sub where flags == 7, else 0.
+ * Depth (occd_stereo_depth): fB = (float)(cam_k[b][0][0][0] * sqrt((tx tx + ty ty) + tz tz)) in float64 on the device,
+ *   t = cam_E[b][0][:3, 3] - cam_E[b][1][:3, 3] (view 0 is taken to be the left camera of the rectified pair);
+ *   depth = disp > 0 ? fB / disp : 0.
+ * Workspace: occd_stereo_workspace_bytes(batch, H, W, max_disp) bytes, 256-byte aligned, owned by the caller (four byte
+ *   volumes (B, 4, H, W, D), one per path direction, and the dR map); its content is scratch.
+ * OCCD_EINVAL without a launch: a NULL structure or a NULL pointer the entry needs (census: gray, census; sgm: census,
+ *   workspace, S, d0, flags, disp; depth: disp, depth, cam_k, cam_E), non-positive batch / H / W (or batch > 32767,
+ *   H > 65535, H W > 2^29), max_disp no multiple of 64 or outside 64..256, P1 < 0, P1 > P2, P2 > 193, uniqueness outside
+ *   1..100, ida with ida_views < 1, calib_views < 2 (depth).  occd_stereo_workspace_bytes returns OCCD_EINVAL likewise.
+ * ------------------------------------------------------------------------ */
+typedef struct OccdStereoArgs {
+    const float* img;              /* (B, 2, 3, H, W) normalised float32, or NULL: `gray` is the input          */
+    uint8_t* gray;                 /* (B, 2, H, W)                                                              */
+    void* census;                  /* (B, 2, H, W) 64-bit words                                                 */
+    const float* ida;              /* (B, ida_views, 4, 4) float32, or NULL: no frame is mirrored               */
+    void* workspace;               /* occd_stereo_workspace_bytes(...) bytes                                    */
+    uint16_t* S;                   /* (B, H, W, D) summed path costs                                            */
+    int32_t* d0;                   /* (B, H, W) winner                                                          */
+    uint8_t* flags;                /* (B, H, W) 1 unique | 2 consistent | 4 inner                               */
+    float* disp;                   /* (B, H, W) sub-pixel disparity, 0 = invalid                                */
+    const double* cam_k;           /* (B, calib_views, 3, 3) float64                                            */
+    const double* cam_E;           /* (B, calib_views, 4, 4) float64, world -> camera                           */
+    float* depth;                  /* (B, H, W) metres, 0 = invalid                                             */
+    int32_t batch, H, W, max_disp;
+    int32_t p1, p2, uniqueness;
+    int32_t ida_views, calib_views;
+    float mean[3], std[3];
+} OccdStereoArgs;
+int64_t occd_stereo_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t max_disp);
+int occd_stereo_census(const OccdStereoArgs* a, void* stream);
+int occd_stereo_sgm(const OccdStereoArgs* a, void* stream);
+int occd_stereo_depth(const OccdStereoArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * K8: weight gradient of a 3-D convolution (training step):
  *   dw[co][ci][kx][ky][kz] = sum_{b,xo,yo,zo} gy[b,xo,yo,zo][co] * x[b, xo*sx - px + kx*dx, ...][ci]
  * -- what autograd computes for nn.Conv3d.weight in the reference's training step

@@ -50,6 +50,7 @@ ClipAdamWArgs = abi.STRUCTS["occd_clip_adamw_args"]
 AccumAdamWArgs = abi.STRUCTS["occd_accum_adamw_args"]
 RenderView = abi.STRUCTS["OccdRenderView"]
 RenderArgs = abi.STRUCTS["OccdRenderArgs"]
+StereoArgs = abi.STRUCTS["OccdStereoArgs"]
 RENDER_MAX_VIEWS = abi.CONSTANTS["OCCD_RENDER_MAX_VIEWS"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
@@ -1922,6 +1923,96 @@ def render_voxels(labels, views, size, palette, target=None, fov=None, backgroun
         a.bg_colour[i] = int(bg_colour[i])
     _check(load().occd_render_voxels(ctypes.byref(a), _stream()), "occd_render_voxels")
     return (rgb, hit, face, depth) if aux else rgb
+
+
+# ----------------------------------------------------------------------------- stereo depth targets (csrc/stereo.hip)
+def _stereo_geometry(t, name, shape):
+    """(B, H, W) of a GPU tensor shaped (B, 2, ..., H, W) with `shape` naming its dimensions."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (the stereo matcher has no CPU path)")
+    if t.dim() != len(shape) or t.shape[1] != 2 or min(t.shape) < 1:
+        raise RuntimeError(f"{name} must be a non-empty ({', '.join(shape)}) tensor, got {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[-2]), int(t.shape[-1])
+
+
+def stereo_census(gray=None, img=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """occd_stereo_census: gray (B, 2, H, W) uint8 -- or img (B, 2, 3, H, W) normalised float32, converted on the way --
+    -> (gray, census); census is (B, 2, H, W) int64 holding the 64-bit words."""
+    if (gray is None) == (img is None):
+        raise RuntimeError("stereo_census takes either a uint8 gray pair or a normalised float32 image pair")
+    a = StereoArgs()
+    if img is not None:
+        B, H, W = _stereo_geometry(img, "img", ("B", "2", "3", "H", "W"))
+        if img.dtype != torch.float32 or img.shape[2] != 3:
+            raise RuntimeError("img must be float32 (B, 2, 3, H, W), got %s %s" % (tuple(img.shape), img.dtype))
+        a.img = _ptr(img, "img")
+        gray = torch.empty((B, 2, H, W), dtype=torch.uint8, device=img.device)
+        for c in range(3):
+            a.mean[c], a.std[c] = float(mean[c]), float(std[c])
+    else:
+        B, H, W = _stereo_geometry(gray, "gray", ("B", "2", "H", "W"))
+        if gray.dtype != torch.uint8:
+            raise RuntimeError("gray must be uint8 (B, 2, H, W), got %s" % gray.dtype)
+    census = torch.empty((B, 2, H, W), dtype=torch.int64, device=gray.device)
+    a.gray, a.census = _ptr(gray, "gray"), census.data_ptr()
+    a.batch, a.H, a.W = B, H, W
+    _check(load().occd_stereo_census(ctypes.byref(a), _stream()), "occd_stereo_census")
+    return gray, census
+
+
+def stereo_sgm(census, max_disp=192, ida=None, p1=10, p2=120, uniqueness=95):
+    """occd_stereo_sgm on census words (B, 2, H, W) int64: -> S (B, H, W, D) int16 (uint16 values <= 1020), d0 (B, H, W)
+    int32, flags (B, H, W) uint8 (1 unique | 2 consistent | 4 inner), disp (B, H, W) float32 (0 = invalid).  ida
+    (B, V, 4, 4) float32 or None: frame b is mirrored when ida[b, 0, 0, 0] < 0 (read on the device).  The workspace is a
+    tensor of this call (nothing module-level that a captured graph could outlive)."""
+    B, H, W = _stereo_geometry(census, "census", ("B", "2", "H", "W"))
+    if census.dtype != torch.int64:
+        raise RuntimeError("census must be int64 (B, 2, H, W), got %s" % census.dtype)
+    D = int(max_disp)
+    need = load().occd_stereo_workspace_bytes(B, H, W, D)
+    if need < 0:
+        raise ValueError("stereo_sgm: max_disp must be a multiple of 64 in 64..256 (got %d) and the images at most "
+                         "65535 rows and 2^29 pixels (got %d x %d, batch %d)" % (D, H, W, B))
+    if not (0 <= int(p1) <= int(p2) <= 193):
+        raise ValueError("stereo_sgm: needs 0 <= p1 <= p2 <= 193 (a path value must fit a byte), got p1=%s p2=%s" % (p1, p2))
+    if not (1 <= int(uniqueness) <= 100):
+        raise ValueError("stereo_sgm: uniqueness must be in 1..100, got %s" % (uniqueness,))
+    dev = census.device
+    a = StereoArgs()
+    a.census = _ptr(census, "census")
+    if ida is not None:
+        if ida.dtype != torch.float32 or ida.dim() != 4 or ida.shape[0] != B or tuple(ida.shape[2:]) != (4, 4):
+            raise RuntimeError("ida must be float32 (B, V, 4, 4), got %s %s" % (tuple(ida.shape), ida.dtype))
+        if ida.device != dev:
+            raise RuntimeError(f"ida is on {ida.device}, census on {dev}")
+        a.ida, a.ida_views = _ptr(ida, "ida"), int(ida.shape[1])
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    S = torch.empty((B, H, W, D), dtype=torch.int16, device=dev)
+    d0 = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    flags = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    disp = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    a.workspace, a.S, a.d0, a.flags, a.disp = work.data_ptr(), S.data_ptr(), d0.data_ptr(), flags.data_ptr(), disp.data_ptr()
+    a.batch, a.H, a.W, a.max_disp = B, H, W, D
+    a.p1, a.p2, a.uniqueness = int(p1), int(p2), int(uniqueness)
+    _check(load().occd_stereo_sgm(ctypes.byref(a), _stream()), "occd_stereo_sgm")
+    return S, d0, flags, disp
+
+
+def stereo_depth(disp, cam_k, cam_E):
+    """occd_stereo_depth: disp (B, H, W) float32, cam_k (B, V, 3, 3) and cam_E (B, V, 4, 4) float64 device tensors, V >= 2,
+    view 0 the left camera -> depth (B, H, W) float32 = fB / disp, 0 where disp is 0; fB is computed on the device."""
+    if not torch.is_tensor(disp) or not disp.is_cuda or disp.dtype != torch.float32 or disp.dim() != 3:
+        raise RuntimeError("disp must be a float32 (B, H, W) GPU tensor (the stereo matcher has no CPU path)")
+    B, H, W = (int(d) for d in disp.shape)
+    _check_calibration(B, int(cam_E.shape[1]) if cam_E.dim() == 4 else -1, cam_E, cam_k)
+    if cam_E.shape[1] < 2:
+        raise RuntimeError("stereo_depth needs the calibration of both cameras, got %d view(s)" % cam_E.shape[1])
+    depth = torch.empty_like(disp)
+    a = StereoArgs()
+    a.disp, a.depth, a.cam_k, a.cam_E = _ptr(disp, "disp"), depth.data_ptr(), cam_k.data_ptr(), cam_E.data_ptr()
+    a.batch, a.H, a.W, a.calib_views = B, H, W, int(cam_E.shape[1])
+    _check(load().occd_stereo_depth(ctypes.byref(a), _stream()), "occd_stereo_depth")
+    return depth
 
 
 # ----------------------------------------------------------------------------- training-step statistics (N1 / N4)

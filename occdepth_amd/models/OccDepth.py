@@ -112,6 +112,16 @@ class OccDepth(_Base):
                                  "training targets (OCCDEPTH_GPU_TARGETS=auto or 1), not OCCDEPTH_GPU_TARGETS=0")
             from ..targets import defer_dataset_projection
             self._projection_hook = defer_dataset_projection()
+        # OCCDEPTH_GPU_STEREO=1: the stereo depth target (`gt_depth` of use_stereo_depth_gt) is matched on the GPU from the
+        # batch's own image pair (`enable_stereo_depth`, stereo.py) whenever the batch brings none, and the loader's
+        # `load_depth` is rebound to a stub (targets.defer_dataset_stereo_depth), so no depth PNG is read.  OFF by default:
+        # nothing is allocated or launched.  OCCDEPTH_GPU_STEREO_DISP: the number of disparities (192).
+        self.gpu_stereo = None
+        self._stereo_hook = None
+        if env("OCCDEPTH_GPU_STEREO", "0") == "1":
+            self.enable_stereo_depth(max_disp=int(env("OCCDEPTH_GPU_STEREO_DISP", "192")))
+            from ..targets import defer_dataset_stereo_depth
+            self._stereo_hook = defer_dataset_stereo_depth()
         if infer_mode:
             self.context_prior = False
         assert not (config.use_stereo_depth_gt and config.use_lidar_depth_gt), "only with one depth data supported."
@@ -753,6 +763,71 @@ class OccDepth(_Base):
         k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64).contiguous()
         return hip.vox2pix(E, k, self._flip_mats(batch, E), self._kitti_origin(batch), 0.2 * ps, dims, (int(W), int(H)))
 
+    # ---------------------------------------------------------------- stereo depth target on the GPU
+    def enable_stereo_depth(self, max_disp=192, p1=10, p2=120, uniqueness=95, mean=None, std=None):
+        """Build the depth target of `use_stereo_depth_gt` in the step, from the batch's rectified image pair and its
+        calibration (stereo.stereo_depth: census, four-path SGM, uniqueness / left-right / inner checks, sub-pixel fit,
+        depth = f B / disparity), for every batch that brings no `gt_depth` (key missing or zero elements: what a loader
+        hooked by targets.defer_dataset_stereo_depth delivers).  A batch that brings `gt_depth` is used as it is; the batch
+        is never modified; "test" steps build nothing.  Works eagerly and inside the captured training step (no host
+        read, the workspace is allocated per call).  max_disp: a multiple of 64 in 64..256; mean / std: the loader's
+        normalisation (ImageNet's by default).  The same switch from the environment: OCCDEPTH_GPU_STEREO=1.
+
+        What is matched: `img` (B, 2, 3, H, W), view 0 taken to be the LEFT camera of a rectified pair, turned back into
+        8-bit gray.  The loader jitters colour per view independently (kitti_dataset.py:374): census depends only on the
+        local order of gray values, so brightness and contrast changes are harmless; matching quality under saturation or
+        hue jitter is not claimed.  A batch key `img_gray_u8` (B, 2, H, W) uint8 -- the un-jittered pair -- is matched
+        instead of `img` when present.  Frames the loader mirrored (ida_mats[b, 0, 0, 0] < 0) are matched towards x + d."""
+        from .. import stereo
+        max_disp = int(max_disp)
+        if max_disp % 64 or not 64 <= max_disp <= 256:
+            raise ValueError("enable_stereo_depth: max_disp must be a multiple of 64 in 64..256, got %d" % max_disp)
+        if not 0 <= int(p1) <= int(p2) <= 193 or not 1 <= int(uniqueness) <= 100:
+            raise ValueError("enable_stereo_depth: needs 0 <= p1 <= p2 <= 193 and uniqueness in 1..100, got p1=%s p2=%s "
+                             "uniqueness=%s" % (p1, p2, uniqueness))
+        self.gpu_stereo = dict(max_disp=max_disp, p1=int(p1), p2=int(p2), uniqueness=int(uniqueness),
+                               mean=tuple(mean) if mean is not None else stereo.IMAGENET_MEAN,
+                               std=tuple(std) if std is not None else stereo.IMAGENET_STD)
+        self._fast_train = None                      # a captured step was captured without the matcher
+        return self
+
+    def _build_stereo_depth(self, batch, step_type):
+        return self.gpu_stereo is not None and self.use_stereo_depth_gt and self.trans_2d_to_3d == "flosp_depth" \
+            and step_type != "test" and self._tables_absent(batch, "gt_depth")
+
+    def stereo_depth_on_gpu(self, batch):
+        """The left camera's depth map of the batch's stereo pair -> (B, 1, H, W) float32 metres, 0 = no measurement
+        (`enable_stereo_depth` describes the matcher and its assumptions).  Device calibration, no host read."""
+        from .. import stereo
+        if self.gpu_stereo is None:
+            raise RuntimeError("stereo_depth_on_gpu: call enable_stereo_depth() first (or set OCCDEPTH_GPU_STEREO=1)")
+        if self.dataset != "kitti":
+            raise NotImplementedError("the stereo depth target is matched on the GPU for SemanticKITTI's rectified pair "
+                                      "only; a %s batch must bring `gt_depth`" % self.dataset)
+        missing = [k for k in ("cam_k", "T_velo_2_cam") if k not in batch]
+        if missing:
+            raise KeyError("stereo depth on the GPU needs the pair's calibration in the batch; missing: %s"
+                           % ", ".join(missing))
+        pair = batch["img_gray_u8"] if "img_gray_u8" in batch else batch["img"]
+        if pair.dim() < 4 or pair.shape[1] != 2:
+            raise ValueError("stereo depth on the GPU needs both views of the pair: `%s` has %s view(s) (shape %s)"
+                             % ("img_gray_u8" if "img_gray_u8" in batch else "img",
+                                pair.shape[1] if pair.dim() > 1 else 0, tuple(pair.shape)))
+        if not pair.is_cuda:
+            raise RuntimeError("the stereo depth target is matched on the GPU only (csrc/stereo.hip); a CPU batch must "
+                               "bring `gt_depth`")
+        dev = pair.device
+        ext = batch.get("T_velo_2_cam_f64", batch["T_velo_2_cam"])
+        E = torch.stack([e.to(dev) for e in ext]).to(torch.float64).contiguous()
+        k = torch.stack([c.to(dev) for c in batch["cam_k"]]).to(torch.float64).contiguous()
+        if E.dim() != 4 or E.shape[1] < 2 or k.shape[:2] != E.shape[:2]:
+            raise ValueError("stereo depth on the GPU needs the calibration of both cameras: cam_k %s, T_velo_2_cam %s"
+                             % (tuple(k.shape), tuple(E.shape)))
+        ida = batch.get("ida_mats")
+        if ida is not None:
+            ida = (torch.stack([t.to(dev) for t in ida]) if isinstance(ida, (list, tuple)) else ida.to(dev)).to(torch.float32)
+        return stereo.stereo_depth(pair, k, E, ida=ida, **self.gpu_stereo)
+
     # ---------------------------------------------------------------- whole-forward hipGraph
     @staticmethod
     def _batch_signature(batch):
@@ -910,14 +985,18 @@ class OccDepth(_Base):
                 loss = loss + loss_occluded
                 self._log(step_type + "/loss_occluded", loss_occluded)
 
-        if self.with_depth_gt and self.trans_2d_to_3d == "flosp_depth" and "gt_depth" in batch:
+        gt_depth = batch["gt_depth"] if "gt_depth" in batch else None
+        if self.gpu_stereo is not None and self._tables_absent(batch, "gt_depth"):
+            # matched from the batch's image pair (the batch is not changed); a hooked loader's zero-size map is no target
+            gt_depth = self.stereo_depth_on_gpu(batch) if self._build_stereo_depth(batch, step_type) else None
+        if self.with_depth_gt and self.trans_2d_to_3d == "flosp_depth" and gt_depth is not None:
             if self.use_stereo_depth_gt:
                 depth_pred = out_dict["depth_pred"][:, 0].unsqueeze(1)        # only the left camera has ground truth
             elif self.use_lidar_depth_gt or self.use_depth_gt:
                 depth_pred = out_dict["depth_pred"]
             else:
                 raise NotImplementedError("Only stereo depth gt supported.")
-            loss_depth = self.depth_loss_fn.get_depth_loss(batch["gt_depth"].to(dev), depth_pred) * self.depth_loss_w
+            loss_depth = self.depth_loss_fn.get_depth_loss(gt_depth.to(dev), depth_pred) * self.depth_loss_w
             loss = loss + loss_depth
             self._log(step_type + "/loss_depth", loss_depth)
 

@@ -302,3 +302,24 @@ def defer_dataset_projection(module=None):
         except Exception:
             return DatasetTargetsHook(None, {})
     return _rebind(module, (("vox2pix", _no_vox2pix), ("compute_local_frustums", _no_frustums)))
+
+
+def _no_depth(*args, **kwargs):
+    """Stands in for load_depth (kitti_dataset.py:40-44): a zero-size float32 map, which survives the dataset's crop and
+    np.fliplr (kitti_dataset.py:338-348) and the collate's torch.stack; OccDepth treats a zero-element `gt_depth` as
+    absent and matches the batch's image pair on the GPU."""
+    return np.zeros((0, 0), dtype=np.float32)
+
+
+def defer_dataset_stereo_depth(module=None):
+    """Rebind `load_depth` inside the reference's SemanticKITTI dataset module (when importable; or `module`) to a stub,
+    so its workers stop reading the per-frame stereo depth PNGs -- files of a side dataset the user may not have;
+    `OccDepth.step` then builds the depth target from the batch's image pair (stereo.stereo_depth, OCCDEPTH_GPU_STEREO).
+    Returns a DatasetTargetsHook (undo, context manager; inactive when the module cannot be imported).  The same process
+    / fork caveats as `defer_dataset_targets` apply; OCCDEPTH_GPU_STEREO=1 installs it when the model is constructed."""
+    if module is None:
+        try:
+            module = importlib.import_module(KITTI_DATASET_MODULE)
+        except Exception:
+            return DatasetTargetsHook(None, {})
+    return _rebind(module, (("load_depth", _no_depth),))

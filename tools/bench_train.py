@@ -1,8 +1,10 @@
 """Training-step baseline for SURVEY 8(f) row N1 (dev tool; needs the GPU):  forward (ATen / MIOpen autograd graph)
 + the fused loss statistics kernels + backward + AdamW on one synthetic config-2 stereo frame.
 
-    python tools/bench_train.py [steps=3] [config=kitti_a100|kitti_2080ti] [bf16]
-Prints ms per phase.  This is the number later rounds' hand-written backward kernels have to beat."""
+    python tools/bench_train.py [steps=3] [config=kitti_a100|kitti_2080ti] [bf16|fp32] [stereo]
+Prints ms per phase.  This is the number later rounds' hand-written backward kernels have to beat.
+`stereo`: the batch brings no `gt_depth`; the step matches it from the image pair (OccDepth.enable_stereo_depth) -- run
+both forms in one session to see what the matcher adds to the step."""
 import os
 import sys
 import time
@@ -15,7 +17,7 @@ from occdepth_amd.loss.sscMetrics import SSCMetrics
 from occdepth_amd.models.OccDepth import OccDepth
 
 
-def main(steps=3, cfg_name="kitti_a100", amp=None):
+def main(steps=3, cfg_name="kitti_a100", amp=None, stereo=False):
     torch.manual_seed(0)
     dev = torch.device("cuda")
     cfg = getattr(configs, cfg_name).clone()
@@ -36,6 +38,9 @@ def main(steps=3, cfg_name="kitti_a100", amp=None):
     masks = torch.stack([fid == f for f in range(nf)], 0)
     batch.update(target=target, frustums_masks=[masks], frustums_class_dists=[torch.rand(nf, C, device=dev)],
                  gt_depth=torch.rand(1, 1, 370, 1220, device=dev) * 50.0)
+    if stereo:
+        del batch["gt_depth"]
+        model.enable_stereo_depth()
     opt = model.configure_optimizers()[0][0]               # AdamW (fused on the GPU) + the reference's MultiStepLR
     metric = SSCMetrics(C)
     times = []
@@ -79,4 +84,4 @@ def main(steps=3, cfg_name="kitti_a100", amp=None):
 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 3, sys.argv[2] if len(sys.argv) > 2 else "kitti_a100",
-         sys.argv[3] if len(sys.argv) > 3 else None)
+         sys.argv[3] if len(sys.argv) > 3 and sys.argv[3] != "fp32" else None, stereo="stereo" in sys.argv[4:])

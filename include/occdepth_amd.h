@@ -895,6 +895,8 @@ int occd_bn_bwd_small_xchg(const occd_bn_args* a, const double* packed_fwd, floa
  * occdepth/models/unet2d.py:24-46, as X = 1 volumes of channels-last images).
  * `dtype` selects the storage type of the activation tensors (in, out, res1, res2 / x, gy): 0 = fp32 (converted to
  * bf16 while staging: "bf16 MFMA, fp32 storage"), 1 = bf16 (pointers are cast; *_cs / *_coff count elements).
+ * occd_conv3d_bf16_fwd[_phases] also take 2 (float32, 3-way bf16 split), 3 (float32, two-term fp16 split, head geometry only,
+ * not _phases) and 4 (float32, two-term fp16 split, generic); see below.
  * bias, dw and the workspace stay fp32.  `wpk` is the image of occd_pack_weights_bf16():
  *   wpk[tap][k16][nt][lane][j] (bf16),  value = W[cout = nt*32 + (lane & 31)][cin = k16*16 + (lane >> 5)*8 + j][tap].
  * act_in: NONE or RELU.  K8b stages voxel rows row-major in LDS and reads both MFMA operands with the gfx950
@@ -932,7 +934,10 @@ int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk,
  * OCCD_EINVAL.  Finite activations with |x| >= 32760 overflow the fp16 operand and make the outputs they reach non-finite.
  * Its weight image (occd_packed_weight_f16x2_bytes() bytes, 16-byte aligned) comes from occd_pack_weights_f16x2: three fp16
  * images hi | hs | lo of w' = 2^k[co] w (layout of occd_pack_weights_bf16) and 32 * ceil(cout / 32) float epilogue factors.
- * Weights must be finite.                                                                                              */
+ * Weights must be finite.
+ * dtype 4 of occd_conv3d_bf16_fwd and occd_conv3d_bf16_fwd_phases = the same numerics and weight image on the generic kernel
+ * (K2bh: any geometry dtype 2 takes; act_in NONE or RELU only): only the hi and lo images are streamed, hs = hi 2^-11 is formed
+ * in registers, the epilogue reads the factors of each phase's own image.  Same overflow contract as dtype 3.               */
 int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps);
 int occd_pack_weights_f16x2(const float* w, const float* scale, void* wpk,
                             int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,

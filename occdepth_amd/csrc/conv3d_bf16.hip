@@ -29,6 +29,7 @@ namespace {
 // what differs between the sub-pixel phases of one transposed convolution (see K2's PhaseP, csrc/conv3d_igemm.hip)
 struct PhaseBP {
     const u32x4* wpk;
+    const float* fac;       // SPLIT = 2: the per-cout epilogue factors of this phase's image (its trailer)
     int KX, KY, KZ, oox, ooy, ooz, YIN, ZIN;
     FastDiv div_zin;
 };
@@ -64,19 +65,27 @@ __device__ __forceinline__ f32x4 unpack_lo(u32x2 v) {       // 4 bf16 -> 4 float
 
 constexpr int kRSB = 80;   // LDS row stride in bytes: 32 bf16 channels + 16 B pad
 constexpr int kRSB3 = 208; // SPLIT = 3: three bf16 planes (hi, mid, lo) of the 32 channels + 16 B pad (13 slots: odd)
+constexpr int kRSB2 = 144; // SPLIT = 2: two fp16 planes (hi, lo') of the 32 channels + 16 B pad (9 slots: odd)
 
 // (activations act3d_x4, pack_bf16x8 and the three-term split split3_bf16x8: device.h)
 
 // SPLIT = 1: plain bf16 operands.  SPLIT = 3 (opt-in experiment): float32 activations and weights as
 // three bf16 terms each, six MFMAs per K step instead of one -- float32-level accuracy at 6/16 of the fp32-MFMA time.
+// SPLIT = 2 (K2bh): K2s3h's numerics (csrc/conv3d_c32p.hip, design A) on this skeleton -- float32 activations staged once as
+// x' = 2^kF2XExp x = hi + 2^-11 lo' (split2_f16x8), weights from the image of occd_pack_weights_f16x2 (this kernel's fragment
+// order; hi | hs | lo | per-cout factors), three v_mfma_f32_32x32x16_f16 per K step: lo_w hi_x + hs_w lo'_x + hi_w hi_x, smallest
+// first.  Only hi and lo stream from L2 (4 bytes per weight element instead of the 6 of SPLIT = 3, which is what bounds the
+// small-volume launches); hs = hi 2^-11 is formed in registers (four v_pk_mul_f16 per fragment, fp16 denormals on: exact
+// wherever the stored hs is).  The epilogue multiplies by the per-cout factor before the bias -- after the K groups are summed.
 // KS > 1: in-workgroup split-K as in K2 (conv3d_igemm.hip): the KS wave groups take interleaved 32-channel chunks, each with
 // its own LDS slab, and their accumulators are summed through LDS before the epilogue -- the 3x3x3 convolutions of the 1/8
 // level (4096 voxels, K = 27 x 256): 128 output tiles for 256 CUs.
 template <int MT, int NT, int WM, int WN, bool IN_BF16, bool OUT_BF16, int SPLIT = 1, int KS = 1>
 __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const ConvBP p) {
     constexpr int NTH = WM * WN * 64;   // threads of one K group
-    constexpr int RSB = SPLIT == 3 ? kRSB3 : kRSB;
-    static_assert(SPLIT == 1 || (SPLIT == 3 && !IN_BF16 && !OUT_BF16), "the 3-way split takes and returns float32");
+    constexpr int RSB = SPLIT == 3 ? kRSB3 : SPLIT == 2 ? kRSB2 : kRSB;
+    constexpr int WIMG = SPLIT == 2 ? 2 : 1;   // streamed weight image sp lies WIMG * sp images into the buffer (SPLIT = 2: hi, lo)
+    static_assert(SPLIT == 1 || ((SPLIT == 2 || SPLIT == 3) && !IN_BF16 && !OUT_BF16), "the splits take and return float32");
     extern __shared__ __attribute__((aligned(16))) unsigned char slab_all[];
 
     const int lane = threadIdx.x & 63;
@@ -142,16 +151,26 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = \
         __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b_cur[nt][WS]),                         \
                                                 __builtin_bit_cast(bf16x8, a_cur[mt][XS]), acc[mt][nt], 0, 0, 0)
-    // smallest terms first: (mid, mid), (hi, lo), (lo, hi), (hi, mid), (mid, hi), (hi, hi)
+#define OCCD_MFMA1H(W, XS)                                                                                          \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = \
+        __builtin_amdgcn_mfma_f32_32x32x16_f16(W, __builtin_bit_cast(f16x8, a_cur[mt][XS]), acc[mt][nt], 0, 0, 0)
+    // smallest terms first: (mid, mid), (hi, lo), (lo, hi), (hi, mid), (mid, hi), (hi, hi); SPLIT = 2: (lo, hi), (hs, lo'), (hi, hi)
 #define OCCD_MFMA_BLOCK()                                                  \
-    if (SPLIT == 3) {                                                      \
+    if (SPLIT == 2) {                                                      \
+        f16x8 w_hs[NT];                                                    \
+        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                  \
+            w_hs[nt] = __builtin_bit_cast(f16x8, b_cur[nt][0]) * (_Float16)(1.f / 2048.f); \
+        OCCD_MFMA1H(__builtin_bit_cast(f16x8, b_cur[nt][SPLIT == 2 ? 1 : 0]), 0); \
+        OCCD_MFMA1H(w_hs[nt], SPLIT == 2 ? 1 : 0);                         \
+        OCCD_MFMA1H(__builtin_bit_cast(f16x8, b_cur[nt][0]), 0);           \
+    } else if (SPLIT == 3) {                                               \
         OCCD_MFMA1(SPLIT == 3 ? 1 : 0, SPLIT == 3 ? 1 : 0);                \
         OCCD_MFMA1(0, SPLIT == 3 ? 2 : 0);                                 \
         OCCD_MFMA1(SPLIT == 3 ? 2 : 0, 0);                                 \
         OCCD_MFMA1(0, SPLIT == 3 ? 1 : 0);                                 \
         OCCD_MFMA1(SPLIT == 3 ? 1 : 0, 0);                                 \
     }                                                                      \
-    OCCD_MFMA1(0, 0)
+    if (SPLIT != 2) { OCCD_MFMA1(0, 0); }
 
     for (int kx = 0; kx < ph.KX; ++kx) {
         const int xi = xo * p.SX - p.PX + kx * p.DX;
@@ -170,7 +189,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int sp = 0; sp < SPLIT; ++sp) b_cur[nt][sp] = wp[wofs[nt] + sp * w_img];
+                for (int sp = 0; sp < SPLIT; ++sp) b_cur[nt][sp] = wp[wofs[nt] + sp * WIMG * w_img];
 
             __syncthreads();   // previous slab fully consumed
             const int F = rows << sh;
@@ -211,6 +230,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
                             lo = act3d_x4(lo, OCCD_ACT_SIGMOID); hi = act3d_x4(hi, OCCD_ACT_SIGMOID);
                         }
                         if (SPLIT == 3) split3_bf16x8(lo, hi, w[0], w[SPLIT == 3 ? 1 : 0], w[SPLIT == 3 ? 2 : 0]);
+                        else if (SPLIT == 2) split2_f16x8(lo, hi, w[0], w[SPLIT == 2 ? 1 : 0]);
                         else w[0] = pack_bf16x8(lo, hi);
                     }
 #pragma unroll
@@ -252,7 +272,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                    for (int sp = 0; sp < SPLIT; ++sp) b_nxt[nt][sp] = wp[wofs[nt] + sp * w_img];
+                    for (int sp = 0; sp < SPLIT; ++sp) b_nxt[nt][sp] = wp[wofs[nt] + sp * WIMG * w_img];
                 OCCD_MFMA_BLOCK();
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
@@ -267,6 +287,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
         }
     }
 #undef OCCD_MFMA1
+#undef OCCD_MFMA1H
 #undef OCCD_MFMA_BLOCK
 
     if (KS > 1) {
@@ -314,6 +335,7 @@ __global__ void __launch_bounds__(WM* WN * KS * 64) conv3d_bf16_kernel(const Con
                 if (ok && c < p.cout_store) {
                     f32x4 v = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2],
                                acc[mt][nt][4 * g + 3]};
+                    if (SPLIT == 2) v *= *(const f32x4*)(ph.fac + c);     // 2^-(k[cout] + kF2XExp): exact
                     if (p.bias != nullptr) v += *(const f32x4*)(p.bias + c);
                     if (p.act_out == OCCD_ACT_RELU_PRE) v = act3d_x4(v, OCCD_ACT_RELU);
                     if (OUT_BF16) {
@@ -424,14 +446,15 @@ __global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, const flo
 
 struct VariantB {
     int MT, NT, WM, WN, KS;
-    void (*kern[3])(const ConvBP);   // [0] fp32 in / fp32 out, [1] bf16 in / bf16 out, [2] fp32 with the 3-way split (or null)
+    // [0] fp32 in / fp32 out, [1] bf16 in / bf16 out, [2] fp32 with the 3-way bf16 split, [3] fp32 with the 2-term fp16 split (or null)
+    void (*kern[4])(const ConvBP);
 };
 
 #define OCCD_VARIANT_B(MT, NT, WM, WN) \
-    VariantB { MT, NT, WM, WN, 1, { conv3d_bf16_kernel<MT, NT, WM, WN, false, false>, conv3d_bf16_kernel<MT, NT, WM, WN, true, true>, nullptr } }
+    VariantB { MT, NT, WM, WN, 1, { conv3d_bf16_kernel<MT, NT, WM, WN, false, false>, conv3d_bf16_kernel<MT, NT, WM, WN, true, true>, nullptr, nullptr } }
 #define OCCD_VARIANT_B3(MT, NT, WM, WN) \
     VariantB { MT, NT, WM, WN, 1, { conv3d_bf16_kernel<MT, NT, WM, WN, false, false>, conv3d_bf16_kernel<MT, NT, WM, WN, true, true>, \
-                                    conv3d_bf16_kernel<MT, NT, WM, WN, false, false, 3> } }
+                                    conv3d_bf16_kernel<MT, NT, WM, WN, false, false, 3>, conv3d_bf16_kernel<MT, NT, WM, WN, false, false, 2> } }
 
 const VariantB kVariantsB[] = {
     OCCD_VARIANT_B(4, 1, 4, 1),    // 0: M512 x N32
@@ -442,8 +465,9 @@ const VariantB kVariantsB[] = {
     OCCD_VARIANT_B(4, 2, 2, 2),    // 5: M256 x N128
     OCCD_VARIANT_B3(2, 2, 2, 2),   // 6: M128 x N128
     OCCD_VARIANT_B3(1, 2, 2, 2),   // 7: M64  x N128
-    // 8: M32 x N128 with the 3-way split and 4-way in-workgroup split-K (16 waves): small volumes with a long K
-    VariantB { 1, 1, 1, 4, 4, { nullptr, nullptr, conv3d_bf16_kernel<1, 1, 1, 4, false, false, 3, 4> } },
+    // 8: M32 x N128 with either split and 4-way in-workgroup split-K (16 waves): small volumes with a long K
+    VariantB { 1, 1, 1, 4, 4, { nullptr, nullptr, conv3d_bf16_kernel<1, 1, 1, 4, false, false, 3, 4>,
+                                conv3d_bf16_kernel<1, 1, 1, 4, false, false, 2, 4> } },
 };
 constexpr int kNumVariantsB = sizeof(kVariantsB) / sizeof(kVariantsB[0]);
 constexpr size_t kMaxLdsB = 160 * 1024;
@@ -591,10 +615,12 @@ static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32
 // accuracy on the bf16 matrix pipe, an opt-in experiment beside the exact-fp32 kernels.
 // dtype 3 = float32 tensors with the two-term fp16 split (wpk from occd_pack_weights_f16x2): the head convolutions on
 // K2s3h (conv3d_c32p.hip) only; any other geometry is rejected (OCCD_EINVAL), there is no generic form.
+// dtype 4 = float32 tensors with the two-term fp16 split on this kernel (K2bh; wpk from occd_pack_weights_f16x2): any
+// geometry K2b takes, act_in NONE or RELU.
 namespace {
 
 int validate_b(const occd_conv3d_args* a, int32_t dtype) {
-    if (!a || !a->in || !a->wpk || !a->out || dtype < 0 || dtype > 3) return OCCD_EINVAL;
+    if (!a || !a->in || !a->wpk || !a->out || dtype < 0 || dtype > 4) return OCCD_EINVAL;
     const int ksel = dtype;                           // kernel table column
     if (dtype >= 2) dtype = 0;                        // storage: float32
     if (a->batch <= 0 || a->X <= 0 || a->Y <= 0 || a->Z <= 0 || a->cin <= 0 || a->cout <= 0) return OCCD_EINVAL;
@@ -632,8 +658,8 @@ int validate_b(const occd_conv3d_args* a, int32_t dtype) {
 
 // n phases (n = 1: a plain launch) that differ only in wpk, kx / ky / kz and o_off_*: ONE launch
 int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream) {
-    const int ksel = dtype;                           // kernel table column
-    if (dtype == 2) dtype = 0;                        // storage: float32
+    const int ksel = dtype == 4 ? 3 : dtype;          // kernel table column
+    if (dtype >= 2) dtype = 0;                        // storage: float32
     const int esz = dtype == 1 ? 2 : 4;
     const int cin8 = (a->cin + 7) & ~7;
     const int cin16 = (a->cin + 15) & ~15;
@@ -656,7 +682,7 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
     } else {
         order[no++] = 5; order[no++] = 6; order[no++] = 7;
     }
-    const int rsb = ksel == 2 ? kRSB3 : kRSB;
+    const int rsb = ksel == 2 ? kRSB3 : ksel == 3 ? kRSB2 : kRSB;
     int pick = -1;
     TilingB til{};
     for (int i = 0; i < no; ++i) {
@@ -668,7 +694,7 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
         if (t.nwg * t.ngroups * copies >= 512) break;   // else keep refining to the finest fit
     }
     if (pick < 0) return OCCD_ENOMEM;
-    if (ksel == 2 && a->tile_hint == 0 && til.nwg * til.ngroups * copies <= 320 && cin16 >= 128 && NTtot % 4 == 0) {
+    if (ksel >= 2 && a->tile_hint == 0 && til.nwg * til.ngroups * copies <= 320 && cin16 >= 128 && NTtot % 4 == 0) {
         // too few output tiles to fill the chip: multiply the waves by splitting K inside the workgroup (K2's rule)
         TilingB t{};
         if (plan_b(&big, kVariantsB[8], NTtot, &t, rsb) && t.nwg * t.ngroups * copies <= 1024) {
@@ -709,6 +735,10 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
         const occd_conv3d_args* ai = a + ord[i];
         PhaseBP& ph = p.ph[i];
         ph.wpk = (const u32x4*)ai->wpk;
+        // the trailer of the fp16 image: after its three images of taps * K16 * NT * 512 halves each
+        ph.fac = ksel == 3 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(ai->wpk) +
+                                                            3 * (size_t)ai->kx * ai->ky * ai->kz * (cin16 / 16) * NTtot * 512)
+                           : nullptr;
         ph.KX = ai->kx; ph.KY = ai->ky; ph.KZ = ai->kz;
         ph.oox = ai->o_off_x; ph.ooy = ai->o_off_y; ph.ooz = ai->o_off_z;
         ph.YIN = (til.TY - 1) * ai->sy + (ai->ky - 1) * ai->dy + 1;      // (the shared tile, this phase's extent)
@@ -724,7 +754,8 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
 
     void (*kern)(const ConvBP) = v.kern[ksel];
     if (til.lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
-    occd::ProfScope prof(n > 1 ? "conv3d_bf16x3_phases" : ksel == 2 ? "conv3d_bf16x3" : dtype == 1 ? "conv3d_bf16s" : "conv3d_bf16",
+    occd::ProfScope prof(n > 1 ? (ksel == 3 ? "conv3d_bf16x3_phases_f16x2" : "conv3d_bf16x3_phases") :
+                         ksel == 3 ? "conv3d_bf16x3_f16x2" : ksel == 2 ? "conv3d_bf16x3" : dtype == 1 ? "conv3d_bf16s" : "conv3d_bf16",
                          stream, flops, bytes);
     hipLaunchKernelGGL(kern, p.ph_fast ? dim3((unsigned)(til.nwg * n), (unsigned)a->batch, (unsigned)til.ngroups)
                                        : dim3((unsigned)til.nwg, (unsigned)copies, (unsigned)til.ngroups),

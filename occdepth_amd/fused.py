@@ -188,12 +188,40 @@ def set_head_split(v):
     HEAD_SPLIT = _parse_head_split(v)
 
 
+# Which split K2b's float32-accurate launches take while the split is on (OCCDEPTH_BF16X3 != 0) -- the long-K 3x3x3
+# convolutions of small volumes and the merged phase launches of the transposed convolutions:
+#   OCCDEPTH_K2B_SPLIT=f16x2   (default) K2bh, K2s3h's numerics on the generic kernel (csrc/conv3d_bf16.hip, SPLIT = 2): three
+#                              v_mfma_f32_32x32x16_f16 per K step and 4 streamed bytes per weight element instead of six MFMAs
+#                              and 6 bytes; error against float64 within 2x of the exact-fp32 K2 (tests/test_k2b_f16x2.py);
+#                              finite activations |x| >= 32760 overflow to non-finite outputs;
+#                              plans whose weights are not all finite keep bf16x3
+#   OCCDEPTH_K2B_SPLIT=bf16x3  the three-term bf16 split as before (the bit-for-bit previous path)
+# The head launches (OCCDEPTH_HEAD_SPLIT), the OCCDEPTH_BF16X3=1 experiment, the opt-in 1x1x1 / sigmoid route and training
+# are unchanged by this switch.
+def _parse_k2b_split(v):
+    v = (v or "f16x2").strip().lower()
+    if v not in ("f16x2", "bf16x3"):
+        raise ValueError(f"OCCDEPTH_K2B_SPLIT={v!r}: expected f16x2 or bf16x3")
+    return v
+
+
+K2B_SPLIT = _parse_k2b_split(os.environ.get("OCCDEPTH_K2B_SPLIT", "f16x2"))
+
+
+def set_k2b_split(v):
+    """'f16x2' / 'bf16x3'; plans re-pack their weights on the next call."""
+    global K2B_SPLIT
+    K2B_SPLIT = _parse_k2b_split(v)
+
+
 class _DualW:
     """Both weight images of a plan while the split is on: the hi | mid | lo one for the launches the split kernels take,
-    the exact-fp32 one for the rest; f16x2: K2s3h's image for the head launches (None: they take K2s3)."""
+    the exact-fp32 one for the rest; f16x2: the fp16 two-term image for the head launches (K2s3h) or, k2bh, for K2b's
+    small-volume / merged-phase launches (None: they take the bf16x3 image)."""
 
     def __init__(self, f32, x3, f16x2=None):
         self.f32, self.x3, self.f16x2 = f32, x3, f16x2
+        self.k2bh = False        # f16x2 is K2bh's operand (small volumes, merged phases), not the head's
 
 
 BF16X3_DILATED = os.environ.get("OCCDEPTH_BF16X3_DILATED", "0") == "1"
@@ -236,9 +264,13 @@ def _f16x2_ok(w, scale):
 
 def _pack_w(w, scale=None, layout=0):
     if BF16X3 == "all" or (BF16X3 == "head" and (_head_weight(w, layout) or _smallvol_weight(w, layout))):
-        f16 = (hip.pack_weights_f16x2(w, scale, layout)
-               if HEAD_SPLIT == "f16x2" and _head_weight(w, layout) and _f16x2_ok(w, scale) else None)
-        return _DualW(hip.pack_weights(w, scale, layout), hip.pack_weights_bf16(w, scale, layout, split3=True), f16)
+        head = HEAD_SPLIT == "f16x2" and _head_weight(w, layout)
+        k2bh = (not head and K2B_SPLIT == "f16x2" and layout == 0 and _smallvol_weight(w, 0)
+                and tuple(w.shape[2:]) == (3, 3, 3))
+        f16 = hip.pack_weights_f16x2(w, scale, layout) if (head or k2bh) and _f16x2_ok(w, scale) else None
+        dual = _DualW(hip.pack_weights(w, scale, layout), hip.pack_weights_bf16(w, scale, layout, split3=True), f16)
+        dual.k2bh = k2bh and f16 is not None
+        return dual
     return hip.pack_weights(w, scale, layout)
 
 
@@ -257,10 +289,12 @@ def _smallvol_eligible(x, wpk, cout, kernel, out, **kw):
 def _conv3d(x, wpk, bias, cout, kernel, out, **kw):
     if isinstance(wpk, _DualW):
         if hip.c32x3_eligible(x, cout, kernel, out, **kw):        # K2s3h / K2s3 (all three dilations)
-            if wpk.f16x2 is not None:
+            if wpk.f16x2 is not None and not wpk.k2bh:
                 return hip.conv3d_f16x2(x, wpk.f16x2, bias, cout, kernel, out, **kw)
             return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
         if _smallvol_eligible(x, wpk, cout, kernel, out, **kw):   # K2b split form, in-workgroup split-K
+            if wpk.k2bh and tuple(kernel) == (3, 3, 3) and kw.get("act_in", ACT_NONE) in (ACT_NONE, ACT_RELU):
+                return hip.conv3d_bf16(x, wpk.f16x2, bias, cout, kernel, out, f16x2=True, **kw)
             return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
         aligned = x.cs % 8 == 0 and x.coff % 8 == 0          # K2b stages 8 channels per 16-byte LDS chunk
         dil = tuple(kw.get("dilation", (1, 1, 1)))
@@ -286,7 +320,7 @@ class ConvPlan:
         return self.conv.out_channels
 
     def _prepare(self):
-        key = (_stamp(self.conv, self.bn), BF16X3, HEAD_SPLIT)
+        key = (_stamp(self.conv, self.bn), BF16X3, HEAD_SPLIT, K2B_SPLIT)
         if key == self._key:
             return
         w = self.conv.weight.detach().float()
@@ -345,7 +379,7 @@ class DerivedConvPlan:
         self.cout = self.kernel = None
 
     def _prepare(self):
-        key = (_stamp(*self.modules), BF16X3, HEAD_SPLIT)
+        key = (_stamp(*self.modules), BF16X3, HEAD_SPLIT, K2B_SPLIT)
         if key == self._key:
             return
         w, b = self.derive()
@@ -398,14 +432,17 @@ class ConvTransposePlan:
         return self.convt.out_channels
 
     def _prepare(self):
-        key = (_stamp(self.convt, self.bn), BF16X3, PHASES_X3)
+        key = (_stamp(self.convt, self.bn), BF16X3, PHASES_X3, K2B_SPLIT)
         if key == self._key:
             return
         x3 = bool(BF16X3) and PHASES_X3 and PHASES_ONE_LAUNCH
 
         def pack(w, scale):      # both images of a phase's tap subset when the merged launch may take the split kernel
             if x3:
-                return _DualW(hip.pack_weights(w, scale), hip.pack_weights_bf16(w, scale, split3=True))
+                f16 = hip.pack_weights_f16x2(w, scale) if K2B_SPLIT == "f16x2" and _f16x2_ok(w, scale) else None
+                dual = _DualW(hip.pack_weights(w, scale), hip.pack_weights_bf16(w, scale, split3=True), f16)
+                dual.k2bh = f16 is not None
+                return dual
             return _pack_w(w, scale)
         wt = self.convt.weight.detach().float()  # (Cin, Cout, 3, 3, 3)
         dev = wt.device
@@ -442,6 +479,10 @@ class ConvTransposePlan:
 
         if PHASES_ONE_LAUNCH and len(self._phases) > 1 and BF16X3 and PHASES_X3 and x.buf.dtype == torch.float32 and \
                 x.cs % 8 == 0 and x.coff % 8 == 0 and all(isinstance(ph[3], _DualW) for ph in self._phases):
+            if all(ph[3].k2bh for ph in self._phases):
+                # one K2bh launch for the 8 phases, two-term fp16 split
+                return hip.conv3d_phases(x, [(wpk.f16x2, kern, off) for off, kern, _, wpk in self._phases], self._bias, self.cout,
+                                         out, res1=res1, act_out=act_out, out_pos=x.dims, o_stride=(self.up,) * 3, f16x2=True)
             # one K2b launch for the 8 phases, 3-way bf16 split
             return hip.conv3d_phases(x, [(wpk.x3, kern, off) for off, kern, _, wpk in self._phases], self._bias, self.cout, out,
                                      res1=res1, act_out=act_out, out_pos=x.dims, o_stride=(self.up,) * 3, split3=True)

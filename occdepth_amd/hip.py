@@ -251,13 +251,22 @@ def conv3d(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 1, 1)
     return out
 
 
-def conv3d_phases(x, phases, bias, cout, out, res1=None, act_out=ACT_NONE, out_pos=None, o_stride=(1, 1, 1), split3=False):
+def conv3d_phases(x, phases, bias, cout, out, res1=None, act_out=ACT_NONE, out_pos=None, o_stride=(1, 1, 1), split3=False,
+                  f16x2=False):
     """The sub-pixel phases of one transposed convolution as ONE launch: K2 (occd_conv3d_fwd_phases) or, split3, K2b with the
-    3-way bf16 split (occd_conv3d_bf16_fwd_phases).
-    phases: 1 / 2 / 4 / 8 tuples (wpk, kernel, o_off) -- the packed weights of the phase's tap subset (pack_weights, or
-    pack_weights_bf16(split3=True)), its extent and where its voxels land in `out`; padding 0, stride / dilation 1, everything
-    else shared."""
+    3-way bf16 split (occd_conv3d_bf16_fwd_phases), or, f16x2, K2bh: K2b with the two-term fp16 split.
+    phases: 1 / 2 / 4 / 8 tuples (wpk, kernel, o_off) -- the packed weights of the phase's tap subset (pack_weights,
+    pack_weights_bf16(split3=True) or pack_weights_f16x2), its extent and where its voxels land in `out`; padding 0, stride /
+    dilation 1, everything else shared."""
     n = len(phases)
+    if f16x2:
+        if split3:
+            raise RuntimeError("conv3d_phases: split3 and f16x2 are two forms of one launch, pick one")
+        if any(wpk.dtype != torch.uint8 for wpk, _, _ in phases):
+            raise RuntimeError("conv3d_phases(f16x2=True) needs the images of pack_weights_f16x2")
+        if x.buf.dtype != torch.float32:
+            raise RuntimeError("the fp16 split takes float32 tensors")
+        split3 = True                      # (below: raw image pointers, the bf16-pipe entry point)
     arr = (Conv3dArgs * n)()
     for i, (wpk, kernel, o_off) in enumerate(phases):
         a = _conv3d_args(x, _ptr(wpk, "wpk") if split3 else _f32(wpk, "wpk"), bias, cout, kernel, out, (1, 1, 1), (1, 1, 1),
@@ -266,7 +275,7 @@ def conv3d_phases(x, phases, bias, cout, out, res1=None, act_out=ACT_NONE, out_p
     if _PROFILING:
         set_tag("%d>%d k333 s222 transposed: %d phases @%dx%dx%d" % ((x.C, cout, n) + tuple(x.dims)))
     if split3:
-        _check(load().occd_conv3d_bf16_fwd_phases(arr, n, 2, _stream()), "occd_conv3d_bf16_fwd_phases")
+        _check(load().occd_conv3d_bf16_fwd_phases(arr, n, 4 if f16x2 else 2, _stream()), "occd_conv3d_bf16_fwd_phases")
     else:
         _check(load().occd_conv3d_fwd_phases(arr, n, _stream()), "occd_conv3d_fwd_phases")
     return out
@@ -311,7 +320,8 @@ def pack_weights_bf16(w, scale=None, layout=0, split3=False):
 
 
 def pack_weights_f16x2(w, scale=None, layout=0):
-    """fp32 master weights -> the image of K2s3h, the two-term fp16 split of the head convolutions (conv3d_f16x2): three fp16
+    """fp32 master weights -> the image of K2s3h and K2bh, the two-term fp16 split (conv3d_f16x2 for the head convolutions,
+    conv3d_bf16 / conv3d_phases(..., f16x2=True) for any other geometry): three fp16
     images hi | hs | lo of the per-channel power-of-two scaled weights plus the epilogue factors (a uint8 tensor of
     occd_packed_weight_f16x2_bytes bytes).  The weights must be finite."""
     if layout == 2:
@@ -348,10 +358,23 @@ def conv3d_f16x2(x, wpk, bias, cout, kernel, out, **kw):
 
 def conv3d_bf16(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 1, 1), padding=(0, 0, 0),
                 res1=None, res2=None, act_in=ACT_NONE, act_out=ACT_NONE, out_pos=None, o_stride=(1, 1, 1),
-                o_off=(0, 0, 0), cin=None, tile_hint=0, split3=False):
+                o_off=(0, 0, 0), cin=None, tile_hint=0, split3=False, f16x2=False):
     """K2b: `conv3d` on the bf16 matrix pipe (fp32 accumulate).  x / out / res1 / res2 are all float32 Vox tensors
     (converted to bf16 while staging) or all bfloat16 ones; wpk = pack_weights_bf16(w).
-    split3 (float32 tensors, wpk = pack_weights_bf16(w, split3=True)): the 3-way split experiment, float32-level accuracy."""
+    split3 (float32 tensors, wpk = pack_weights_bf16(w, split3=True)): the 3-way split experiment, float32-level accuracy.
+    f16x2 (float32 tensors, wpk = pack_weights_f16x2(w), act_in none / relu): K2bh, the same kernel on the f16 matrix pipe with
+    the two-term fp16 split -- K2s3h's numerics at any geometry; finite |x| >= 32760 overflow to non-finite outputs."""
+    if f16x2:
+        if split3:
+            raise RuntimeError("conv3d_bf16: split3 and f16x2 are two forms of one launch, pick one")
+        if wpk.dtype != torch.uint8:
+            raise RuntimeError("conv3d_bf16(f16x2=True) needs the image of pack_weights_f16x2")
+        if x.buf.dtype != torch.float32:
+            raise RuntimeError("the fp16 split takes float32 tensors")
+        a = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, stride, dilation, padding, res1, res2, act_in, act_out,
+                         out_pos, o_stride, o_off, cin, tile_hint, _act_ptr(x.buf.dtype))
+        _check(load().occd_conv3d_bf16_fwd(ctypes.byref(a), 4, _stream()), "occd_conv3d_bf16_fwd (f16x2)")
+        return out
     if wpk.dtype != torch.bfloat16:
         raise RuntimeError("conv3d_bf16 needs the bf16 weight image of pack_weights_bf16")
     if split3 and x.buf.dtype != torch.float32:

@@ -895,8 +895,9 @@ int occd_bn_bwd_small_xchg(const occd_bn_args* a, const double* packed_fwd, floa
  * occdepth/models/unet2d.py:24-46, as X = 1 volumes of channels-last images).
  * `dtype` selects the storage type of the activation tensors (in, out, res1, res2 / x, gy): 0 = fp32 (converted to
  * bf16 while staging: "bf16 MFMA, fp32 storage"), 1 = bf16 (pointers are cast; *_cs / *_coff count elements).
- * occd_conv3d_bf16_fwd[_phases] also take 2 (float32, 3-way bf16 split), 3 (float32, two-term fp16 split, head geometry only,
- * not _phases) and 4 (float32, two-term fp16 split, generic); see below.
+ * occd_conv3d_bf16_fwd[_phases] take the OCCD_CONV_* modes below: those two and OCCD_CONV_BF16X3 (float32, 3-way bf16
+ * split), OCCD_CONV_F16X2_HEAD (float32, two-term fp16 split, head geometry only, not _phases) and OCCD_CONV_F16X2 (float32,
+ * two-term fp16 split, generic); see the packers of their weight images further down.
  * bias, dw and the workspace stay fp32.  `wpk` is the image of occd_pack_weights_bf16():
  *   wpk[tap][k16][nt][lane][j] (bf16),  value = W[cout = nt*32 + (lane & 31)][cin = k16*16 + (lane >> 5)*8 + j][tap].
  * act_in: NONE or RELU.  K8b stages voxel rows row-major in LDS and reads both MFMA operands with the gfx950
@@ -906,8 +907,13 @@ int64_t occd_packed_weight_bf16_elems(int32_t cout, int32_t cin, int32_t taps);
 int occd_pack_weights_bf16(const float* w, const float* scale, void* wpk,
                            int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,
                            int32_t layout, void* stream);
+#define OCCD_CONV_F32 0        /* float32 tensors, converted to bf16 while staging */
+#define OCCD_CONV_BF16 1       /* bfloat16 tensors */
+#define OCCD_CONV_BF16X3 2     /* float32 tensors, 3-way bf16 split (image of occd_pack_weights_bf16x3) */
+#define OCCD_CONV_F16X2_HEAD 3 /* float32 tensors, two-term fp16 split on K2s3h: the head geometry only */
+#define OCCD_CONV_F16X2 4      /* float32 tensors, two-term fp16 split on the generic kernel (K2bh) */
 int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, void* stream);
-/* the bf16-pipe twin of occd_conv3d_fwd_phases (same contract; dtype as above; with dtype 2 also act_in = SIGMOID) */
+/* the bf16-pipe twin of occd_conv3d_fwd_phases (same contract; dtype as above; with OCCD_CONV_BF16X3 also act_in = SIGMOID) */
 int occd_conv3d_bf16_fwd_phases(const occd_conv3d_args* a, int32_t n, int32_t dtype, void* stream);
 /* Pack a VIEW of a dense float32 weight tensor: element (co, ci, tap) of the packed operator is
  * w[co * s_co + ci * s_ci + tap_ofs[tap]] (tap_ofs: HOST array of ntaps <= 27 element offsets).  One launch instead of the
@@ -918,26 +924,26 @@ int occd_pack_weights_gather(const float* w, const float* scale, float* wpk, int
 int occd_pack_weights_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
                                   int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, void* stream);
 /* the same view as three images hi | mid | lo (3 x occd_packed_weight_bf16_elems elements): data-gradient operators of the 3-way
- * split (occd_conv3d_bf16_fwd dtype 2) */
+ * split (occd_conv3d_bf16_fwd, OCCD_CONV_BF16X3) */
 int occd_pack_weights_bf16x3_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
                                   int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, void* stream);
-/* Opt-in experiment: dtype 2 of occd_conv3d_bf16_fwd = float32 tensors, both operands split into three
+/* Opt-in experiment: OCCD_CONV_BF16X3 of occd_conv3d_bf16_fwd = float32 tensors, both operands split into three
  * bf16 terms (x = hi + mid + lo), six bf16 MFMAs per K step (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid), fp32
  * accumulate: float32-level accuracy at 6/16 of the fp32-MFMA time.  Its weight image (3 x
  * occd_packed_weight_bf16_elems() elements: hi | mid | lo) comes from occd_pack_weights_bf16x3.                     */
 int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk,
                              int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,
                              int32_t layout, void* stream);
-/* dtype 3 of occd_conv3d_bf16_fwd = float32 tensors, the two-term fp16 split (x = hi + 2^-11 lo', three fp16 MFMAs per K
+/* OCCD_CONV_F16X2_HEAD of occd_conv3d_bf16_fwd = float32 tensors, the two-term fp16 split (x = hi + 2^-11 lo', three fp16 MFMAs per K
  * step: lo_w * hi_x, hs_w * lo'_x, hi_w * hi_x), fp32 accumulate; the full-resolution head convolutions only (K2s3h: 3x3x3,
  * dilation = padding 1 / 2 / 3, <= 32 -> <= 32 channels on rows of >= 32 channels, Z a multiple of 32), anything else is
  * OCCD_EINVAL.  Finite activations with |x| >= 32760 overflow the fp16 operand and make the outputs they reach non-finite.
  * Its weight image (occd_packed_weight_f16x2_bytes() bytes, 16-byte aligned) comes from occd_pack_weights_f16x2: three fp16
  * images hi | hs | lo of w' = 2^k[co] w (layout of occd_pack_weights_bf16) and 32 * ceil(cout / 32) float epilogue factors.
  * Weights must be finite.
- * dtype 4 of occd_conv3d_bf16_fwd and occd_conv3d_bf16_fwd_phases = the same numerics and weight image on the generic kernel
- * (K2bh: any geometry dtype 2 takes; act_in NONE or RELU only): only the hi and lo images are streamed, hs = hi 2^-11 is formed
- * in registers, the epilogue reads the factors of each phase's own image.  Same overflow contract as dtype 3.               */
+ * OCCD_CONV_F16X2 of occd_conv3d_bf16_fwd and occd_conv3d_bf16_fwd_phases = the same numerics and weight image on the generic kernel
+ * (K2bh: any geometry OCCD_CONV_BF16X3 takes; act_in NONE or RELU only): only the hi and lo images are streamed, hs = hi 2^-11 is formed
+ * in registers, the epilogue reads the factors of each phase's own image.  Same overflow contract as OCCD_CONV_F16X2_HEAD.               */
 int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps);
 int occd_pack_weights_f16x2(const float* w, const float* scale, void* wpk,
                             int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,

@@ -609,28 +609,48 @@ static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32
     return occd::check_launch();
 }
 
-// `a->in`, `a->out`, `a->res1`, `a->res2` point at fp32 (dtype 0) or bf16 (dtype 1) channels-last rows -- all four
-// the same type --, `a->wpk` at the image of occd_pack_weights_bf16, `a->bias` at fp32.  *_cs / *_coff count ELEMENTS.
-// dtype 2 = float32 tensors with the 3-way bf16 split of both operands (wpk from occd_pack_weights_bf16x3): float32-level
+// `a->in`, `a->out`, `a->res1`, `a->res2` point at fp32 or bf16 channels-last rows -- all four the same type --, `a->wpk`
+// at the image of occd_pack_weights_bf16, `a->bias` at fp32.  *_cs / *_coff count ELEMENTS.  The `dtype` argument of the
+// two entry points is a mode, OCCD_CONV_* of the header, one row of kModesB each:
+// F32 / BF16 = bf16 operands from float32 / bfloat16 tensors.
+// BF16X3 = float32 tensors with the 3-way bf16 split of both operands (wpk from occd_pack_weights_bf16x3): float32-level
 // accuracy on the bf16 matrix pipe, an opt-in experiment beside the exact-fp32 kernels.
-// dtype 3 = float32 tensors with the two-term fp16 split (wpk from occd_pack_weights_f16x2): the head convolutions on
+// F16X2_HEAD = float32 tensors with the two-term fp16 split (wpk from occd_pack_weights_f16x2): the head convolutions on
 // K2s3h (conv3d_c32p.hip) only; any other geometry is rejected (OCCD_EINVAL), there is no generic form.
-// dtype 4 = float32 tensors with the two-term fp16 split on this kernel (K2bh; wpk from occd_pack_weights_f16x2): any
+// F16X2 = float32 tensors with the two-term fp16 split on this kernel (K2bh; wpk from occd_pack_weights_f16x2): any
 // geometry K2b takes, act_in NONE or RELU.
 namespace {
 
-int validate_b(const occd_conv3d_args* a, int32_t dtype) {
-    if (!a || !a->in || !a->wpk || !a->out || dtype < 0 || dtype > 4) return OCCD_EINVAL;
-    const int ksel = dtype;                           // kernel table column
-    if (dtype >= 2) dtype = 0;                        // storage: float32
+struct ModeB {
+    int storage;              // activation tensors: 0 = float32, 1 = bfloat16
+    int ksel;                 // column of kVariantsB[].kern (-1: no kernel here)
+    int rsb;                  // LDS row stride of that kernel's staging
+    bool sigmoid_in;          // act_in = SIGMOID allowed
+    const char* name;         // profile row of a plain launch ...
+    const char* name_phases;  // ... and of a merged phase launch
+};
+constexpr ModeB kModesB[] = {
+    {0, 0, kRSB, false, "conv3d_bf16", "conv3d_bf16x3_phases"},                     // OCCD_CONV_F32
+    {1, 1, kRSB, false, "conv3d_bf16s", "conv3d_bf16x3_phases"},                    // OCCD_CONV_BF16
+    {0, 2, kRSB3, true, "conv3d_bf16x3", "conv3d_bf16x3_phases"},                   // OCCD_CONV_BF16X3
+    {0, -1, 0, false, nullptr, nullptr},                                            // OCCD_CONV_F16X2_HEAD
+    {0, 3, kRSB2, false, "conv3d_bf16x3_f16x2", "conv3d_bf16x3_phases_f16x2"},      // OCCD_CONV_F16X2
+};
+constexpr int kNumModesB = sizeof(kModesB) / sizeof(kModesB[0]);
+static_assert(OCCD_CONV_F32 == 0 && OCCD_CONV_BF16 == 1 && OCCD_CONV_BF16X3 == 2 && OCCD_CONV_F16X2_HEAD == 3 &&
+              OCCD_CONV_F16X2 == 4 && kNumModesB == 5, "kModesB is indexed by OCCD_CONV_*");
+
+int validate_b(const occd_conv3d_args* a, int32_t mode) {
+    if (!a || !a->in || !a->wpk || !a->out || mode < 0 || mode >= kNumModesB) return OCCD_EINVAL;
+    const ModeB& m = kModesB[mode];
     if (a->batch <= 0 || a->X <= 0 || a->Y <= 0 || a->Z <= 0 || a->cin <= 0 || a->cout <= 0) return OCCD_EINVAL;
     if (a->kx <= 0 || a->ky <= 0 || a->kz <= 0 || a->sx <= 0 || a->sy <= 0 || a->sz <= 0) return OCCD_EINVAL;
     if (a->Xo <= 0 || a->Yo <= 0 || a->Zo <= 0) return OCCD_EINVAL;
     const int cin8 = (a->cin + 7) & ~7;
     const int cin16 = (a->cin + 15) & ~15;
     const int NTtot = (a->cout + 31) / 32;
-    const int al = dtype == 1 ? 7 : 3;               // 16-byte staging loads: 8 bf16 / 4 (+4) floats
-    const int esz = dtype == 1 ? 2 : 4;
+    const int al = m.storage == 1 ? 7 : 3;           // 16-byte staging loads: 8 bf16 / 4 (+4) floats
+    const int esz = m.storage == 1 ? 2 : 4;
     if ((a->in_cs & al) || (a->in_coff & al) || a->in_coff + cin8 > a->in_cs) return OCCD_EINVAL;
     if ((reinterpret_cast<uintptr_t>(a->in) & 15) || (reinterpret_cast<uintptr_t>(a->wpk) & 15)) return OCCD_EINVAL;
     if (a->cout_store < a->cout || a->cout_store > NTtot * 32 || a->out_coff + a->cout_store > a->out_cs)
@@ -650,17 +670,18 @@ int validate_b(const occd_conv3d_args* a, int32_t dtype) {
         (a->Zo - 1) * a->o_stride_z + a->o_off_z >= a->OZ)
         return OCCD_EINVAL;
     // (input sigmoid: the CRP products sigmoid(P_logits) @ mega, CRP3D.py:80 -- float32 operands with the split only)
-    if (a->act_in != OCCD_ACT_NONE && a->act_in != OCCD_ACT_RELU && !(a->act_in == OCCD_ACT_SIGMOID && ksel == 2)) return OCCD_EINVAL;
+    if (a->act_in != OCCD_ACT_NONE && a->act_in != OCCD_ACT_RELU && !(a->act_in == OCCD_ACT_SIGMOID && m.sigmoid_in)) return OCCD_EINVAL;
     if (a->act_out != OCCD_ACT_NONE && a->act_out != OCCD_ACT_RELU && a->act_out != OCCD_ACT_RELU_PRE)
         return OCCD_EINVAL;
     return OCCD_OK;
 }
 
 // n phases (n = 1: a plain launch) that differ only in wpk, kx / ky / kz and o_off_*: ONE launch
-int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream) {
-    const int ksel = dtype == 4 ? 3 : dtype;          // kernel table column
-    if (dtype >= 2) dtype = 0;                        // storage: float32
-    const int esz = dtype == 1 ? 2 : 4;
+int launch_b(const occd_conv3d_args* a, int n, int32_t mode, hipStream_t stream) {
+    const ModeB& m = kModesB[mode];
+    const int ksel = m.ksel;
+    if (ksel < 0) return OCCD_EINVAL;
+    const int esz = m.storage == 1 ? 2 : 4;
     const int cin8 = (a->cin + 7) & ~7;
     const int cin16 = (a->cin + 15) & ~15;
     const int NTtot = (a->cout + 31) / 32;
@@ -682,7 +703,7 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
     } else {
         order[no++] = 5; order[no++] = 6; order[no++] = 7;
     }
-    const int rsb = ksel == 2 ? kRSB3 : ksel == 3 ? kRSB2 : kRSB;
+    const int rsb = m.rsb;
     int pick = -1;
     TilingB til{};
     for (int i = 0; i < no; ++i) {
@@ -754,9 +775,7 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
 
     void (*kern)(const ConvBP) = v.kern[ksel];
     if (til.lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
-    occd::ProfScope prof(n > 1 ? (ksel == 3 ? "conv3d_bf16x3_phases_f16x2" : "conv3d_bf16x3_phases") :
-                         ksel == 3 ? "conv3d_bf16x3_f16x2" : ksel == 2 ? "conv3d_bf16x3" : dtype == 1 ? "conv3d_bf16s" : "conv3d_bf16",
-                         stream, flops, bytes);
+    occd::ProfScope prof(n > 1 ? m.name_phases : m.name, stream, flops, bytes);
     hipLaunchKernelGGL(kern, p.ph_fast ? dim3((unsigned)(til.nwg * n), (unsigned)a->batch, (unsigned)til.ngroups)
                                        : dim3((unsigned)til.nwg, (unsigned)copies, (unsigned)til.ngroups),
                        dim3(v.WM * v.WN * v.KS * 64), til.lds, stream, p);
@@ -768,11 +787,11 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t dtype, hipStream_t stream
 extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, void* stream) {
     const int bad = validate_b(a, dtype);
     if (bad != OCCD_OK) return bad;
-    if (dtype == 3) {   // K2s3h: the head launches only
+    if (dtype == OCCD_CONV_F16X2_HEAD) {   // K2s3h: the head launches only
         const int r = occd::try_conv3d_c32_slide_x3(a, (hipStream_t)stream, true);
         return r < 0 ? r : r == 0 ? OCCD_EINVAL : OCCD_OK;
     }
-    if (dtype == 2) {   // the full-resolution head launches: sliding-window form of the split (K2s3, conv3d_c32p.hip)
+    if (dtype == OCCD_CONV_BF16X3) {   // the full-resolution head launches: sliding-window form of the split (K2s3, conv3d_c32p.hip)
         const int r = occd::try_conv3d_c32_slide_x3(a, (hipStream_t)stream);
         if (r != 0) return r < 0 ? r : OCCD_OK;
     }
@@ -782,7 +801,7 @@ extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, vo
 // The n in {1, 2, 4, 8} sub-pixel phases of ONE transposed convolution on K2b as one launch (the bf16-pipe twin of
 // occd_conv3d_fwd_phases, same contract: a[0..n) differ ONLY in wpk, kx / ky / kz and o_off_*).
 extern "C" int occd_conv3d_bf16_fwd_phases(const occd_conv3d_args* a, int32_t n, int32_t dtype, void* stream) {
-    if (!a || (n != 1 && n != 2 && n != 4 && n != 8) || dtype == 3) return OCCD_EINVAL;
+    if (!a || (n != 1 && n != 2 && n != 4 && n != 8) || dtype == OCCD_CONV_F16X2_HEAD) return OCCD_EINVAL;
     for (int i = 0; i < n; ++i) {
         const int bad = validate_b(a + i, dtype);
         if (bad != OCCD_OK) return bad;

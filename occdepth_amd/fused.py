@@ -1,10 +1,11 @@
 """Eval-mode execution plans: nn.Conv3d / ConvTranspose3d / AvgPool3d+Conv3d (+ BatchNorm3d)
 folded into one packed-weight launch of the HIP implicit-GEMM kernel (K2).
 
-A plan owns no parameters: it references the live nn modules, folds BatchNorm running
-statistics into (weight scale, bias) and packs on first use; the packed image is rebuilt
+A plan owns no parameters: it references the live nn modules and folds BatchNorm running
+statistics into (weight scale, bias) on first use; the folded weights (a PackedW) are rebuilt
 whenever a source tensor is replaced or modified in place (load_state_dict, optimizer step),
-detected through (data_ptr, _version).
+detected through (data_ptr, _version).  Which kernel a launch takes is decided per launch by
+route(); a weight image is packed at the first launch that routes to it.
 """
 import os
 
@@ -75,28 +76,95 @@ def bn_affine_cached(bn):
     return cached[1], cached[2]
 
 
-# Which kernel the fused Winograd 3x3 convolutions of the eval forward take (the decoder levels of unet2d.py, DepthNet's 3x3 +
-# BatchNorm + ReLU of flosp_depth.py):
-#   OCCDEPTH_WINO_SPLIT=f16x2  (default) K10h, K10 on the f16 matrix pipe with the two-term fp16 split, wherever
-#                              hip.wino_f16x2_wins says it is faster (per launch geometry); error against float64 within 2x of
-#                              K10's (tests/test_wino_f16x2.py); finite activations |x| >= 8190 overflow to non-finite outputs
-#                              (INTEGRATION.md section 6); weights that are not all finite keep K10
-#   OCCDEPTH_WINO_SPLIT=fp32   K10 everywhere (the bit-for-bit previous path)
-# Training (hip.conv2d_3x3_autograd) is K10 in either mode.
-def _parse_wino_split(v):
-    v = (v or "f16x2").strip().lower()
-    if v not in ("f16x2", "fp32"):
-        raise ValueError(f"OCCDEPTH_WINO_SPLIT={v!r}: expected f16x2 or fp32")
-    return v
+def _same(*values):
+    return {v: v for v in values}
 
 
-WINO_SPLIT = _parse_wino_split(os.environ.get("OCCDEPTH_WINO_SPLIT", "f16x2"))
+# The switches that take a value out of a set, declared once: name -> (environment variable, value when it is unset, value
+# when it is empty, {accepted spelling: value}, the "expected ..." text of the error).
+_SWITCHES = {
+    # Which kernel the fused Winograd 3x3 convolutions of the eval forward take (the decoder levels of unet2d.py, DepthNet's 3x3 +
+    # BatchNorm + ReLU of flosp_depth.py):
+    #   OCCDEPTH_WINO_SPLIT=f16x2  (default) K10h, K10 on the f16 matrix pipe with the two-term fp16 split, wherever
+    #                              hip.wino_f16x2_wins says it is faster (per launch geometry); error against float64 within 2x of
+    #                              K10's (tests/test_wino_f16x2.py); finite activations |x| >= 8190 overflow to non-finite outputs
+    #                              (INTEGRATION.md section 6); weights that are not all finite keep K10
+    #   OCCDEPTH_WINO_SPLIT=fp32   K10 everywhere (the bit-for-bit previous path)
+    # Training (hip.conv2d_3x3_autograd) is K10 in either mode.
+    "WINO_SPLIT": ("OCCDEPTH_WINO_SPLIT", "f16x2", "f16x2", _same("f16x2", "fp32"), "f16x2 or fp32"),
+    # The 3-way bf16 split (x = hi + mid + lo, six bf16 MFMAs per K step, float32-level accuracy on the bf16 matrix pipe):
+    #   OCCDEPTH_BF16X3=head  (default since round 4) the full-resolution head convolutions (<= 32 -> <= 32 channels, 3x3x3,
+    #                         dilation 1 / 2 / 3, Z = 32) on K2s3, the sliding-window form of the split (csrc/conv3d_c32p.hip;
+    #                         since ABI 15 by default on its fp16 two-term twin K2s3h instead, see OCCDEPTH_HEAD_SPLIT below):
+    #                         0.51 ms per launch against 0.90 ms for the exact-fp32 K2s, error against float64 no larger than
+    #                         K2s' own (tests/test_bf16_conv.py::test_conv3d_slide_x3_head_kernel, profiles/r04_head_x3_ab.txt);
+    #                         also (see below) the long-K 3x3x3 convolutions of small volumes and the merged phase launches of the
+    #                         transposed convolutions on K2b's split form; everything else exact fp32
+    #   OCCDEPTH_BF16X3=0     exact-fp32 MFMA everywhere (v_mfma_f32_32x32x2_f32): the bit-for-bit round-3 path
+    #   OCCDEPTH_BF16X3=1     additionally every other large dilation-1 K2 launch on the generic K2b skeleton with the split
+    #                         (csrc/conv3d_bf16.hip; the round-3 experiment)
+    "BF16X3": ("OCCDEPTH_BF16X3", "head", "0", {"0": False, "": False, "off": False, "false": False, "1": "all", "all": "all",
+                                                "on": "all", "true": "all", "head": "head"}, "0, head or 1"),
+    # Which split the full-resolution head launches (K2s3's geometry) take while the split is on (OCCDEPTH_BF16X3 != 0):
+    #   OCCDEPTH_HEAD_SPLIT=f16x2   (default) K2s3h, the two-term fp16 split: x = hi + 2^-11 lo', three v_mfma_f32_32x32x16_f16
+    #                               per K step instead of six bf16 ones; error against float64 within 2x of the exact-fp32 K2s
+    #                               (tests/test_head_f16x2.py); finite activations |x| >= 32760 overflow to non-finite outputs
+    #                               (INTEGRATION.md section 6); plans whose weights are not all finite keep bf16x3
+    #   OCCDEPTH_HEAD_SPLIT=bf16x3  K2s3 as before (the bit-for-bit previous path)
+    # Everything else -- the K2b split launches, the 2-D GEMMs, training (autograd3d.py) -- is unchanged by this switch.
+    "HEAD_SPLIT": ("OCCDEPTH_HEAD_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
+    # Which split K2b's float32-accurate launches take while the split is on (OCCDEPTH_BF16X3 != 0) -- the long-K 3x3x3
+    # convolutions of small volumes and the merged phase launches of the transposed convolutions:
+    #   OCCDEPTH_K2B_SPLIT=f16x2   (default) K2bh, K2s3h's numerics on the generic kernel (csrc/conv3d_bf16.hip, SPLIT = 2): three
+    #                              v_mfma_f32_32x32x16_f16 per K step and 4 streamed bytes per weight element instead of six MFMAs
+    #                              and 6 bytes; error against float64 within 2x of the exact-fp32 K2 (tests/test_k2b_f16x2.py);
+    #                              finite activations |x| >= 32760 overflow to non-finite outputs;
+    #                              plans whose weights are not all finite keep bf16x3
+    #   OCCDEPTH_K2B_SPLIT=bf16x3  the three-term bf16 split as before (the bit-for-bit previous path)
+    # The head launches (OCCDEPTH_HEAD_SPLIT), the OCCDEPTH_BF16X3=1 experiment, the opt-in 1x1x1 / sigmoid route and training
+    # are unchanged by this switch.
+    "K2B_SPLIT": ("OCCDEPTH_K2B_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
+}
+
+
+def _parse(name, v):
+    env, _, empty, spellings, expected = _SWITCHES[name]
+    v = (v or empty).strip().lower()
+    if v not in spellings:
+        raise ValueError(f"{env}={v!r}: expected {expected}")
+    return spellings[v]
+
+
+def _from_env(name):
+    return _parse(name, os.environ.get(*_SWITCHES[name][:2]))
+
+
+WINO_SPLIT, BF16X3 = _from_env("WINO_SPLIT"), _from_env("BF16X3")
+HEAD_SPLIT, K2B_SPLIT = _from_env("HEAD_SPLIT"), _from_env("K2B_SPLIT")
 
 
 def set_wino_split(v):
     """'f16x2' / 'fp32'; the cached operands are re-packed on the next call."""
     global WINO_SPLIT
-    WINO_SPLIT = _parse_wino_split(v)
+    WINO_SPLIT = _parse("WINO_SPLIT", v)
+
+
+def set_bf16x3(on):
+    """False / 'head' / 'all' (True = 'all'); takes effect at the next launch."""
+    global BF16X3
+    BF16X3 = "all" if on is True else _parse("BF16X3", str(on)) if on else False
+
+
+def set_head_split(v):
+    """'f16x2' / 'bf16x3'; takes effect at the next launch."""
+    global HEAD_SPLIT
+    HEAD_SPLIT = _parse("HEAD_SPLIT", v)
+
+
+def set_k2b_split(v):
+    """'f16x2' / 'bf16x3'; takes effect at the next launch."""
+    global K2B_SPLIT
+    K2B_SPLIT = _parse("K2B_SPLIT", v)
 
 
 def wino_pack(w, scale=None):
@@ -134,102 +202,7 @@ def _pad_bias(bias, cout):
     return out
 
 
-# The 3-way bf16 split (x = hi + mid + lo, six bf16 MFMAs per K step, float32-level accuracy on the bf16 matrix pipe):
-#   OCCDEPTH_BF16X3=head  (default since round 4) the full-resolution head convolutions (<= 32 -> <= 32 channels, 3x3x3,
-#                         dilation 1 / 2 / 3, Z = 32) on K2s3, the sliding-window form of the split (csrc/conv3d_c32p.hip;
-#                         since ABI 15 by default on its fp16 two-term twin K2s3h instead, see OCCDEPTH_HEAD_SPLIT below):
-#                         0.51 ms per launch against 0.90 ms for the exact-fp32 K2s, error against float64 no larger than
-#                         K2s' own (tests/test_bf16_conv.py::test_conv3d_slide_x3_head_kernel, profiles/r04_head_x3_ab.txt);
-#                         also (see below) the long-K 3x3x3 convolutions of small volumes and the merged phase launches of the
-#                         transposed convolutions on K2b's split form; everything else exact fp32
-#   OCCDEPTH_BF16X3=0     exact-fp32 MFMA everywhere (v_mfma_f32_32x32x2_f32): the bit-for-bit round-3 path
-#   OCCDEPTH_BF16X3=1     additionally every other large dilation-1 K2 launch on the generic K2b skeleton with the split
-#                         (csrc/conv3d_bf16.hip; the round-3 experiment)
-def _parse_bf16x3(v):
-    v = (v or "0").strip().lower()
-    if v in ("0", "", "off", "false"):
-        return False
-    if v in ("1", "all", "on", "true"):
-        return "all"
-    if v == "head":
-        return "head"
-    raise ValueError(f"OCCDEPTH_BF16X3={v!r}: expected 0, head or 1")
-
-
-BF16X3 = _parse_bf16x3(os.environ.get("OCCDEPTH_BF16X3", "head"))
-
-
-def set_bf16x3(on):
-    """False / 'head' / 'all' (True = 'all'); plans re-pack their weights on the next call."""
-    global BF16X3
-    BF16X3 = "all" if on is True else _parse_bf16x3(str(on)) if on else False
-
-
-# Which split the full-resolution head launches (K2s3's geometry) take while the split is on (OCCDEPTH_BF16X3 != 0):
-#   OCCDEPTH_HEAD_SPLIT=f16x2   (default) K2s3h, the two-term fp16 split: x = hi + 2^-11 lo', three v_mfma_f32_32x32x16_f16
-#                               per K step instead of six bf16 ones; error against float64 within 2x of the exact-fp32 K2s
-#                               (tests/test_head_f16x2.py); finite activations |x| >= 32760 overflow to non-finite outputs
-#                               (INTEGRATION.md section 6); plans whose weights are not all finite keep bf16x3
-#   OCCDEPTH_HEAD_SPLIT=bf16x3  K2s3 as before (the bit-for-bit previous path)
-# Everything else -- the K2b split launches, the 2-D GEMMs, training (autograd3d.py) -- is unchanged by this switch.
-def _parse_head_split(v):
-    v = (v or "f16x2").strip().lower()
-    if v not in ("f16x2", "bf16x3"):
-        raise ValueError(f"OCCDEPTH_HEAD_SPLIT={v!r}: expected f16x2 or bf16x3")
-    return v
-
-
-HEAD_SPLIT = _parse_head_split(os.environ.get("OCCDEPTH_HEAD_SPLIT", "f16x2"))
-
-
-def set_head_split(v):
-    """'f16x2' / 'bf16x3'; plans re-pack their weights on the next call."""
-    global HEAD_SPLIT
-    HEAD_SPLIT = _parse_head_split(v)
-
-
-# Which split K2b's float32-accurate launches take while the split is on (OCCDEPTH_BF16X3 != 0) -- the long-K 3x3x3
-# convolutions of small volumes and the merged phase launches of the transposed convolutions:
-#   OCCDEPTH_K2B_SPLIT=f16x2   (default) K2bh, K2s3h's numerics on the generic kernel (csrc/conv3d_bf16.hip, SPLIT = 2): three
-#                              v_mfma_f32_32x32x16_f16 per K step and 4 streamed bytes per weight element instead of six MFMAs
-#                              and 6 bytes; error against float64 within 2x of the exact-fp32 K2 (tests/test_k2b_f16x2.py);
-#                              finite activations |x| >= 32760 overflow to non-finite outputs (INTEGRATION.md section 6);
-#                              plans whose weights are not all finite keep bf16x3
-#   OCCDEPTH_K2B_SPLIT=bf16x3  the three-term bf16 split as before (the bit-for-bit previous path)
-# The head launches (OCCDEPTH_HEAD_SPLIT), the OCCDEPTH_BF16X3=1 experiment, the opt-in 1x1x1 / sigmoid route and training
-# are unchanged by this switch.
-def _parse_k2b_split(v):
-    v = (v or "f16x2").strip().lower()
-    if v not in ("f16x2", "bf16x3"):
-        raise ValueError(f"OCCDEPTH_K2B_SPLIT={v!r}: expected f16x2 or bf16x3")
-    return v
-
-
-K2B_SPLIT = _parse_k2b_split(os.environ.get("OCCDEPTH_K2B_SPLIT", "f16x2"))
-
-
-def set_k2b_split(v):
-    """'f16x2' / 'bf16x3'; plans re-pack their weights on the next call."""
-    global K2B_SPLIT
-    K2B_SPLIT = _parse_k2b_split(v)
-
-
-class _DualW:
-    """Both weight images of a plan while the split is on: the hi | mid | lo one for the launches the split kernels take,
-    the exact-fp32 one for the rest; f16x2: the fp16 two-term image for the head launches (K2s3h) or, k2bh, for K2b's
-    small-volume / merged-phase launches (None: they take the bf16x3 image)."""
-
-    def __init__(self, f32, x3, f16x2=None):
-        self.f32, self.x3, self.f16x2 = f32, x3, f16x2
-        self.k2bh = False        # f16x2 is K2bh's operand (small volumes, merged phases), not the head's
-
-
 BF16X3_DILATED = os.environ.get("OCCDEPTH_BF16X3_DILATED", "0") == "1"
-
-
-def _head_weight(w, layout):
-    return layout == 0 and w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and w.shape[0] <= 32 and 24 < w.shape[1] <= 32
-
 
 # Also part of the default ("head") mode since late round 4: the 3x3x3 convolutions with a long K on a SMALL volume (the
 # ASPP branches and `mega_context` of the CRP at the 1/8 level: 256 -> 256 / 512 on 32x32x4 = 4096 voxels, K = 27 x 256).
@@ -243,41 +216,65 @@ SMALLVOL_MAX_VOXELS = 8192
 #  78: two MFMA steps per staged chunk.  OCCDEPTH_BF16X3_SMALLVOL_K1=1 routes them there for A/B.)
 SMALLVOL_KERNELS = ((3, 3, 3), (1, 1, 1)) if os.environ.get("OCCDEPTH_BF16X3_SMALLVOL_K1", "0") == "1" else ((3, 3, 3),)
 
+# the 8 sub-pixel phases of a stride-2 transposed convolution as one launch (occd_conv3d_fwd_phases); 0 = eight launches
+PHASES_ONE_LAUNCH = os.environ.get("OCCDEPTH_PHASES_ONE_LAUNCH", "1") == "1"
+# ... and that one launch on K2b with the split (occd_conv3d_bf16_fwd_phases; K2bh or bf16x3 by OCCDEPTH_K2B_SPLIT) instead of
+# the exact-fp32 K2, while the split is on at all (OCCDEPTH_BF16X3 != 0): float32-level accuracy, 6/16 of the fp32
+# instruction's MFMA time.  0 = K2.
+PHASES_X3 = os.environ.get("OCCDEPTH_PHASES_X3", "1") == "1"
 
-def _smallvol_weight(w, layout):
-    if not BF16X3_SMALLVOL:
-        return False
-    if layout == 2:          # a dynamic (K, N) row-GEMM operand: the CRP products sigmoid(P_logits) @ mega
-        return (1, 1, 1) in SMALLVOL_KERNELS and w.dim() == 2 and w.shape[0] >= 128 and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0
-    return (layout == 0 and w.dim() == 5 and tuple(w.shape[2:]) in SMALLVOL_KERNELS and w.shape[1] >= 128
-            and w.shape[1] % 16 == 0 and w.shape[0] % 128 == 0)
-
-
-def _f16x2_ok(w, scale):
-    """K2s3h's weight image needs finite weights (its per-channel power-of-two scale) on the GPU; otherwise the plan keeps
-    bf16x3 (CPU tensors: the emulated path of the host-logic tests, which has no K2s3h twin)."""
-    if not w.is_cuda:
-        return False
-    ws = w if scale is None else w * scale.view(-1, *([1] * (w.dim() - 1)))
-    return bool(torch.isfinite(ws).all())
-
-
-def _pack_w(w, scale=None, layout=0):
-    if BF16X3 == "all" or (BF16X3 == "head" and (_head_weight(w, layout) or _smallvol_weight(w, layout))):
-        head = HEAD_SPLIT == "f16x2" and _head_weight(w, layout)
-        k2bh = (not head and K2B_SPLIT == "f16x2" and layout == 0 and _smallvol_weight(w, 0)
-                and tuple(w.shape[2:]) == (3, 3, 3))
-        f16 = hip.pack_weights_f16x2(w, scale, layout) if (head or k2bh) and _f16x2_ok(w, scale) else None
-        dual = _DualW(hip.pack_weights(w, scale, layout), hip.pack_weights_bf16(w, scale, layout, split3=True), f16)
-        dual.k2bh = k2bh and f16 is not None
-        return dual
-    return hip.pack_weights(w, scale, layout)
+# The kernels an eval-path 3-D convolution can take: route -> (weight image it consumes, hip entry point, its flags).
+# route() / route_phases() pick one per LAUNCH; DESIGN.md ("3-D convolution routes") has the table with the switches.
+K2, K2S3H, K2S3, K2BH, K2B3 = "K2", "K2s3h", "K2s3", "K2bh", "K2b3"
+ROUTES = {
+    K2: ("f32", "conv3d", {}),                                 # exact fp32
+    K2S3H: ("f16x2", "conv3d_f16x2", {}),                      # head, two-term fp16 split
+    K2S3: ("x3", "conv3d_bf16", {"split3": True}),             # head, bf16x3 (the entry point picks the sliding-window form)
+    K2BH: ("f16x2", "conv3d_bf16", {"f16x2": True}),           # generic kernel, two-term fp16 split
+    K2B3: ("x3", "conv3d_bf16", {"split3": True}),             # generic kernel, bf16x3
+}
+_PACKERS = {"f32": lambda w, s, l: hip.pack_weights(w, s, l), "x3": lambda w, s, l: hip.pack_weights_bf16(w, s, l, split3=True),
+            "f16x2": lambda w, s, l: hip.pack_weights_f16x2(w, s, l)}
 
 
-def _smallvol_eligible(x, wpk, cout, kernel, out, **kw):
-    if not BF16X3_SMALLVOL or tuple(kernel) not in SMALLVOL_KERNELS or kw.get("cin") not in (None, x.C) or x.C < 128 or cout % 128:
-        return False
-    if x.cs % 8 or x.coff % 8 or x.buf.dtype != torch.float32:
+class PackedW:
+    """The weights of one launch (`w`, per-cout `scale`, `layout` as hip.pack_weights) and their packed images by kind
+    ("f32" / "x3" / "f16x2"), each packed at the first launch that routes to it.  Warm-up before a graph capture runs the
+    same shapes and therefore packs everything the capture needs: the rule that already holds for a plan's `_prepare`.
+    The fp16 image needs finite weights on the GPU (its per-channel power-of-two scale; CPU tensors: the emulated path of
+    the host-logic tests, which has no fp16 twin); that test -- one host sync -- runs once, at the first launch that asks."""
+
+    def __init__(self, w, scale=None, layout=0):
+        self.w, self.scale, self.layout = w, scale, layout
+        self.cout, self.cin = (w.shape[1], w.shape[0]) if layout == 2 else (w.shape[0], w.shape[1])
+        self.kernel = (1, 1, 1) if layout == 2 else tuple(w.shape[2:])
+        self._images = {}
+        self._f16x2_ok = None
+
+    def image(self, kind):
+        img = self._images.get(kind)
+        if img is None:
+            img = self._images[kind] = _PACKERS[kind](self.w, self.scale, self.layout)
+        return img
+
+    # (plan._wpk.x3: the operand of an explicit hip.conv3d_bf16 / conv3d_phases call, as the tests of the split routes make)
+    f32, x3 = property(lambda self: self.image("f32")), property(lambda self: self.image("x3"))
+
+    def f16x2_ok(self):
+        if self._f16x2_ok is None:
+            w, scale = self.w, self.scale
+            self._f16x2_ok = w.is_cuda and bool(torch.isfinite(
+                w if scale is None else w * scale.view(-1, *([1] * (w.dim() - 1)))).all())
+        return self._f16x2_ok
+
+
+def _aligned(x):
+    return x.cs % 8 == 0 and x.coff % 8 == 0        # K2b stages 8 channels per 16-byte LDS chunk
+
+
+def _small_volume(x, cout, kernel, **kw):
+    """The launch side of the small-volume route: a long K on at most SMALLVOL_MAX_VOXELS output voxels."""
+    if kw.get("cin") not in (None, x.C) or x.C < 128 or cout % 128 or not _aligned(x) or x.buf.dtype != torch.float32:
         return False
     pos = kw.get("out_pos")
     if pos is None:
@@ -286,24 +283,46 @@ def _smallvol_eligible(x, wpk, cout, kernel, out, **kw):
     return x.batch * pos[0] * pos[1] * pos[2] <= SMALLVOL_MAX_VOXELS and kw.get("tile_hint", 0) == 0
 
 
-def _conv3d(x, wpk, bias, cout, kernel, out, **kw):
-    if isinstance(wpk, _DualW):
-        if hip.c32x3_eligible(x, cout, kernel, out, **kw):        # K2s3h / K2s3 (all three dilations)
-            if wpk.f16x2 is not None and not wpk.k2bh:
-                return hip.conv3d_f16x2(x, wpk.f16x2, bias, cout, kernel, out, **kw)
-            return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
-        if _smallvol_eligible(x, wpk, cout, kernel, out, **kw):   # K2b split form, in-workgroup split-K
-            if wpk.k2bh and tuple(kernel) == (3, 3, 3) and kw.get("act_in", ACT_NONE) in (ACT_NONE, ACT_RELU):
-                return hip.conv3d_bf16(x, wpk.f16x2, bias, cout, kernel, out, f16x2=True, **kw)
-            return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
-        aligned = x.cs % 8 == 0 and x.coff % 8 == 0          # K2b stages 8 channels per 16-byte LDS chunk
-        dil = tuple(kw.get("dilation", (1, 1, 1)))
-        big = kernel[0] * kernel[1] * kernel[2] >= 8
-        if BF16X3 == "all" and aligned and big and (dil == (1, 1, 1) or BF16X3_DILATED) and kw.get("cin") is None and \
-                kw.get("act_in", ACT_NONE) in (ACT_NONE, ACT_RELU):
-            return hip.conv3d_bf16(x, wpk.x3, bias, cout, kernel, out, split3=True, **kw)
-        wpk = wpk.f32
-    return hip.conv3d(x, wpk, bias, cout, kernel, out, **kw)
+def route(wsrc, x, cout, kernel, out, **kw):
+    """The kernel of ONE launch (a key of ROUTES) -- the only reader of BF16X3, HEAD_SPLIT, K2B_SPLIT, BF16X3_SMALLVOL,
+    SMALLVOL_KERNELS and BF16X3_DILATED, so a switch takes effect at the next launch.  Each split route wants its weights
+    (shape tests on `wsrc`) AND its launch geometry; a route's fp16 form additionally wsrc.f16x2_ok(), else its bf16x3 one."""
+    if not BF16X3:
+        return K2
+    kernel = tuple(kernel)
+    head_w = wsrc.layout == 0 and wsrc.kernel == (3, 3, 3) and wsrc.cout <= 32 and 24 < wsrc.cin <= 32
+    small_w = (BF16X3_SMALLVOL and wsrc.kernel in SMALLVOL_KERNELS and wsrc.cin >= 128 and wsrc.cin % 16 == 0
+               and wsrc.cout % 128 == 0)           # (layout 2, the row operand of gemm_rows, is 1x1x1: opted in with it)
+    if BF16X3 != "all" and not (head_w or small_w):
+        return K2
+    act_in = kw.get("act_in", ACT_NONE)
+    if hip.c32x3_eligible(x, cout, kernel, out, **kw):         # the full-resolution head convolutions, all three dilations
+        return K2S3H if HEAD_SPLIT == "f16x2" and head_w and wsrc.f16x2_ok() else K2S3
+    if BF16X3_SMALLVOL and kernel in SMALLVOL_KERNELS and _small_volume(x, cout, kernel, **kw):   # in-workgroup split-K
+        if (K2B_SPLIT == "f16x2" and small_w and wsrc.layout == 0 and kernel == (3, 3, 3) and act_in in (ACT_NONE, ACT_RELU)
+                and wsrc.f16x2_ok()):
+            return K2BH
+        return K2B3
+    big = kernel[0] * kernel[1] * kernel[2] >= 8
+    if BF16X3 == "all" and _aligned(x) and big and (tuple(kw.get("dilation", (1, 1, 1))) == (1, 1, 1) or BF16X3_DILATED) and \
+            kw.get("cin") is None and act_in in (ACT_NONE, ACT_RELU):
+        return K2B3                                            # the round-3 experiment: every other large launch
+    return K2
+
+
+def route_phases(phases, x):
+    """The kernel of the merged launch of a transposed convolution's sub-pixel phases (`phases`: their PackedW): K2BH, K2B3
+    or K2 (exact fp32), or None: one launch per phase, each through route()."""
+    if not PHASES_ONE_LAUNCH or len(phases) < 2:
+        return None
+    if BF16X3 and PHASES_X3 and x.buf.dtype == torch.float32 and _aligned(x):
+        return K2BH if K2B_SPLIT == "f16x2" and all(w.f16x2_ok() for w in phases) else K2B3
+    return K2 if BF16X3 != "all" else None
+
+
+def _conv3d(x, wsrc, bias, cout, kernel, out, **kw):
+    image, entry, flags = ROUTES[route(wsrc, x, cout, kernel, out, **kw)]
+    return getattr(hip, entry)(x, wsrc.image(image), bias, cout, kernel, out, **flags, **kw)
 
 
 class ConvPlan:
@@ -320,7 +339,7 @@ class ConvPlan:
         return self.conv.out_channels
 
     def _prepare(self):
-        key = (_stamp(self.conv, self.bn), BF16X3, HEAD_SPLIT, K2B_SPLIT)
+        key = _stamp(self.conv, self.bn)
         if key == self._key:
             return
         w = self.conv.weight.detach().float()
@@ -334,7 +353,7 @@ class ConvPlan:
             # mean over the pooling window then 1x1x1 conv == conv with k = stride = window, w / |window|
             kx, ky, kz = self.pool
             w = (w / float(kx * ky * kz)).expand(-1, -1, kx, ky, kz).contiguous()
-        self._wpk = _pack_w(w, scale)
+        self._wpk = PackedW(w, scale)
         self._bias = _pad_bias(shift, cout)
         self._wrows = None
         if self.pool is None and tuple(w.shape[2:]) == (1, 1, 1) and _triple(self.conv.stride) == (1, 1, 1):
@@ -379,13 +398,13 @@ class DerivedConvPlan:
         self.cout = self.kernel = None
 
     def _prepare(self):
-        key = (_stamp(*self.modules), BF16X3, HEAD_SPLIT, K2B_SPLIT)
+        key = _stamp(*self.modules)
         if key == self._key:
             return
         w, b = self.derive()
         w = w.detach().float().contiguous()
         self.cout, self.kernel = w.shape[0], tuple(w.shape[2:])
-        self._wpk = _pack_w(w)
+        self._wpk = PackedW(w)
         self._bias = _pad_bias(b.detach().float(), self.cout) if b is not None else None
         self._key = key
 
@@ -398,13 +417,6 @@ class DerivedConvPlan:
         return _conv3d(x, self._wpk, self._bias, self.cout, self.kernel, out, stride=self.stride,
                           dilation=self.dilation, padding=self.padding, res1=res1, res2=res2, act_in=act_in,
                           act_out=act_out)
-
-
-# the 8 sub-pixel phases of a stride-2 transposed convolution as one launch (occd_conv3d_fwd_phases); 0 = eight launches
-PHASES_ONE_LAUNCH = os.environ.get("OCCDEPTH_PHASES_ONE_LAUNCH", "1") == "1"
-# ... and that one launch on K2b with the 3-way bf16 split (occd_conv3d_bf16_fwd_phases) instead of the exact-fp32 K2, while the
-# split is on at all (OCCDEPTH_BF16X3 != 0): float32-level accuracy, 6/16 of the fp32 instruction's MFMA time.  0 = K2.
-PHASES_X3 = os.environ.get("OCCDEPTH_PHASES_X3", "1") == "1"
 
 
 class ConvTransposePlan:
@@ -432,18 +444,9 @@ class ConvTransposePlan:
         return self.convt.out_channels
 
     def _prepare(self):
-        key = (_stamp(self.convt, self.bn), BF16X3, PHASES_X3, K2B_SPLIT)
+        key = _stamp(self.convt, self.bn)
         if key == self._key:
             return
-        x3 = bool(BF16X3) and PHASES_X3 and PHASES_ONE_LAUNCH
-
-        def pack(w, scale):      # both images of a phase's tap subset when the merged launch may take the split kernel
-            if x3:
-                f16 = hip.pack_weights_f16x2(w, scale) if K2B_SPLIT == "f16x2" and _f16x2_ok(w, scale) else None
-                dual = _DualW(hip.pack_weights(w, scale), hip.pack_weights_bf16(w, scale, split3=True), f16)
-                dual.k2bh = f16 is not None
-                return dual
-            return _pack_w(w, scale)
         wt = self.convt.weight.detach().float()  # (Cin, Cout, 3, 3, 3)
         dev = wt.device
         scale, shift = _bn_affine(self.bn, self.cout, dev)
@@ -453,7 +456,7 @@ class ConvTransposePlan:
         w = wt.permute(1, 0, 2, 3, 4)  # (Cout, Cin, k, k, k), k indexes the scatter offset o = s*i - 1 + k
         phases = []
         if self.up == 1:
-            phases.append(((0, 0, 0), (3, 3, 3), (1, 1, 1), _pack_w(w.flip(2, 3, 4).contiguous(), scale)))
+            phases.append(((0, 0, 0), (3, 3, 3), (1, 1, 1), PackedW(w.flip(2, 3, 4).contiguous(), scale)))
         else:
             # even outputs (o = 2j) see only k=1 at i=j; odd outputs (o = 2j+1) see k=2 at i=j and k=0 at i=j+1
             taps = ([1], [2, 0])
@@ -461,7 +464,7 @@ class ConvTransposePlan:
                 for py in (0, 1):
                     for pz in (0, 1):
                         sub = w[:, :, taps[px]][:, :, :, taps[py]][:, :, :, :, taps[pz]].contiguous()
-                        phases.append(((px, py, pz), tuple(sub.shape[2:]), (0, 0, 0), pack(sub, scale)))
+                        phases.append(((px, py, pz), tuple(sub.shape[2:]), (0, 0, 0), PackedW(sub, scale)))
         self._phases = phases
         self._bias = _pad_bias(shift, self.cout)
         self._key = key
@@ -477,20 +480,12 @@ class ConvTransposePlan:
             return lambda: _conv3d(x, wpk, self._bias, self.cout, kern, out, padding=pad, res1=res1, act_out=act_out,
                                    out_pos=x.dims, o_stride=(self.up,) * 3, o_off=off)
 
-        if PHASES_ONE_LAUNCH and len(self._phases) > 1 and BF16X3 and PHASES_X3 and x.buf.dtype == torch.float32 and \
-                x.cs % 8 == 0 and x.coff % 8 == 0 and all(isinstance(ph[3], _DualW) for ph in self._phases):
-            if all(ph[3].k2bh for ph in self._phases):
-                # one K2bh launch for the 8 phases, two-term fp16 split
-                return hip.conv3d_phases(x, [(wpk.f16x2, kern, off) for off, kern, _, wpk in self._phases], self._bias, self.cout,
-                                         out, res1=res1, act_out=act_out, out_pos=x.dims, o_stride=(self.up,) * 3, f16x2=True)
-            # one K2b launch for the 8 phases, 3-way bf16 split
-            return hip.conv3d_phases(x, [(wpk.x3, kern, off) for off, kern, _, wpk in self._phases], self._bias, self.cout, out,
-                                     res1=res1, act_out=act_out, out_pos=x.dims, o_stride=(self.up,) * 3, split3=True)
-        if PHASES_ONE_LAUNCH and len(self._phases) > 1 and BF16X3 != "all":
-            # one K2 launch for the 8 phases (phase = low bits of blockIdx.y, heaviest tap subset first); exact-fp32 images
-            return hip.conv3d_phases(x, [(wpk.f32 if isinstance(wpk, _DualW) else wpk, kern, off) for off, kern, _, wpk in self._phases],
-                                     self._bias, self.cout, out, res1=res1, act_out=act_out, out_pos=x.dims,
-                                     o_stride=(self.up,) * 3)
+        merged = route_phases([ph[3] for ph in self._phases], x)
+        if merged is not None:
+            # one launch for the 8 phases (phase = low bits of blockIdx.y, heaviest tap subset first)
+            image, _, flags = ROUTES[merged]
+            return hip.conv3d_phases(x, [(wpk.image(image), kern, off) for off, kern, _, wpk in self._phases], self._bias, self.cout,
+                                     out, res1=res1, act_out=act_out, out_pos=x.dims, o_stride=(self.up,) * 3, **flags)
         thunks = [phase(*ph) for ph in self._phases]
         if x.buf.is_cuda and len(thunks) > 1:
             run_parallel(thunks)                     # the phases write disjoint voxels of `out`
@@ -514,11 +509,14 @@ def _rows_gemm_wins(x, K):
 
 
 def pack_rows(b_rows):
-    """(K, N) row-major device matrix -> the B operand of `gemm_rows`: the matrix itself for K15, else K2's packed image
-    (occd_pack_weights layout 2)."""
+    """(K, N) row-major device matrix -> the B operand of `gemm_rows`: the matrix itself for K15, else its PackedW
+    (occd_pack_weights layout 2) with the exact-fp32 image packed now, on this stream -- the launches that share the operand
+    may run on forked streams (run_parallel).  The opt-in split route packs its own image at its first launch."""
     if ROWS_GEMM and b_rows.is_cuda and b_rows.dtype == torch.float32 and b_rows.shape[0] % 16 == 0 and b_rows.shape[1] % 8 == 0:
         return hip.RowsGemmWeights(b_rows), tuple(b_rows.shape)
-    return _pack_w(b_rows, layout=2), tuple(b_rows.shape)
+    wsrc = PackedW(b_rows, layout=2)
+    wsrc.image("f32")
+    return wsrc, tuple(b_rows.shape)
 
 
 def gemm_rows(a, b_rows, out, act_in=ACT_NONE):

@@ -258,27 +258,25 @@ def conv3d_phases(x, phases, bias, cout, out, res1=None, act_out=ACT_NONE, out_p
     phases: 1 / 2 / 4 / 8 tuples (wpk, kernel, o_off) -- the packed weights of the phase's tap subset (pack_weights,
     pack_weights_bf16(split3=True) or pack_weights_f16x2), its extent and where its voxels land in `out`; padding 0, stride /
     dilation 1, everything else shared."""
+    mode = _split_mode("conv3d_phases", split3, f16x2)
+    if mode is not None:
+        error = ("conv3d_phases(f16x2=True) needs the images of pack_weights_f16x2" if f16x2 else
+                 "conv3d_phases(split3=True) needs the images of pack_weights_bf16(split3=True)")
+        return _conv3d_bf16_pipe(mode, error, x, phases, bias, cout, out, merged=True, res1=res1, act_out=act_out, out_pos=out_pos,
+                                 o_stride=o_stride)
     n = len(phases)
-    if f16x2:
-        if split3:
-            raise RuntimeError("conv3d_phases: split3 and f16x2 are two forms of one launch, pick one")
-        if any(wpk.dtype != torch.uint8 for wpk, _, _ in phases):
-            raise RuntimeError("conv3d_phases(f16x2=True) needs the images of pack_weights_f16x2")
-        if x.buf.dtype != torch.float32:
-            raise RuntimeError("the fp16 split takes float32 tensors")
-        split3 = True                      # (below: raw image pointers, the bf16-pipe entry point)
     arr = (Conv3dArgs * n)()
     for i, (wpk, kernel, o_off) in enumerate(phases):
-        a = _conv3d_args(x, _ptr(wpk, "wpk") if split3 else _f32(wpk, "wpk"), bias, cout, kernel, out, (1, 1, 1), (1, 1, 1),
-                         (0, 0, 0), res1, None, ACT_NONE, act_out, out_pos, o_stride, o_off, None, 0, _f32)
-        ctypes.memmove(ctypes.byref(arr, i * ctypes.sizeof(Conv3dArgs)), ctypes.byref(a), ctypes.sizeof(Conv3dArgs))
+        arr[i] = _conv3d_args(x, _f32(wpk, "wpk"), bias, cout, kernel, out, (1, 1, 1), (1, 1, 1), (0, 0, 0), res1, None, ACT_NONE,
+                              act_out, out_pos, o_stride, o_off, None, 0, _f32)
+    _tag_phases(x, cout, n)
+    _check(load().occd_conv3d_fwd_phases(arr, n, _stream()), "occd_conv3d_fwd_phases")
+    return out
+
+
+def _tag_phases(x, cout, n):
     if _PROFILING:
         set_tag("%d>%d k333 s222 transposed: %d phases @%dx%dx%d" % ((x.C, cout, n) + tuple(x.dims)))
-    if split3:
-        _check(load().occd_conv3d_bf16_fwd_phases(arr, n, 4 if f16x2 else 2, _stream()), "occd_conv3d_bf16_fwd_phases")
-    else:
-        _check(load().occd_conv3d_fwd_phases(arr, n, _stream()), "occd_conv3d_fwd_phases")
-    return out
 
 
 # ----------------------------------------------------------------------------- K2b / K8b (bf16 MFMA)
@@ -290,12 +288,56 @@ def _act_ptr(dtype):
     return ptr
 
 
+# the `dtype` argument of occd_conv3d_bf16_fwd[_phases] (include/occdepth_amd.h)
+CONV_F32, CONV_BF16, CONV_BF16X3, CONV_F16X2_HEAD, CONV_F16X2 = (
+    abi.CONSTANTS["OCCD_CONV_" + n] for n in ("F32", "BF16", "BF16X3", "F16X2_HEAD", "F16X2"))
+# mode -> (dtype of its weight image, the error when the activation tensors are not float32 / None: they pick the mode)
+_CONV_MODES = {
+    CONV_F32: (torch.bfloat16, None), CONV_BF16: (torch.bfloat16, None),
+    CONV_BF16X3: (torch.bfloat16, "the 3-way split takes float32 tensors"),
+    CONV_F16X2_HEAD: (torch.uint8, "the fp16 split takes float32 tensors"),
+    CONV_F16X2: (torch.uint8, "the fp16 split takes float32 tensors"),
+}
+
+
 def _storage_code(dtype):
     if dtype == torch.float32:
-        return 0
+        return CONV_F32
     if dtype == torch.bfloat16:
-        return 1
+        return CONV_BF16
     raise RuntimeError(f"the bf16-MFMA kernels take float32 or bfloat16 activations, got {dtype}")
+
+
+def _split_mode(who, split3, f16x2):
+    """The mode of the public flags: CONV_F16X2 / CONV_BF16X3, or None when neither is set."""
+    if split3 and f16x2:
+        raise RuntimeError(f"{who}: split3 and f16x2 are two forms of one launch, pick one")
+    return CONV_F16X2 if f16x2 else CONV_BF16X3 if split3 else None
+
+
+def _conv3d_bf16_pipe(mode, image_error, x, phases, bias, cout, out, merged=False, stride=(1, 1, 1), dilation=(1, 1, 1),
+                      padding=(0, 0, 0), res1=None, res2=None, act_in=ACT_NONE, act_out=ACT_NONE, out_pos=None, o_stride=(1, 1, 1),
+                      cin=None, tile_hint=0):
+    """The one launcher of the bf16-pipe entry points in `mode` (a CONV_* constant): occd_conv3d_bf16_fwd on the single
+    (wpk, kernel, o_off) of `phases`, or, merged, occd_conv3d_bf16_fwd_phases on all of them."""
+    image_dtype, f32_only = _CONV_MODES[mode]
+    if any(wpk.dtype != image_dtype for wpk, _, _ in phases):
+        raise RuntimeError(image_error)
+    if f32_only and x.buf.dtype != torch.float32:
+        raise RuntimeError(f32_only)
+    ptr = _act_ptr(x.buf.dtype)
+    n = len(phases)
+    arr = (Conv3dArgs * n)()
+    for i, (wpk, kernel, o_off) in enumerate(phases):
+        arr[i] = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, stride, dilation, padding, res1, res2, act_in, act_out,
+                              out_pos, o_stride, o_off, cin, tile_hint, ptr)
+    if merged:
+        _tag_phases(x, cout, n)
+        _check(load().occd_conv3d_bf16_fwd_phases(arr, n, mode, _stream()), "occd_conv3d_bf16_fwd_phases")
+    else:
+        _check(load().occd_conv3d_bf16_fwd(arr, mode, _stream()),
+               "occd_conv3d_bf16_fwd" + (" (f16x2)" if image_dtype == torch.uint8 else ""))
+    return out
 
 
 def pack_weights_bf16(w, scale=None, layout=0, split3=False):
@@ -341,19 +383,11 @@ def pack_weights_f16x2(w, scale=None, layout=0):
     return out
 
 
-def conv3d_f16x2(x, wpk, bias, cout, kernel, out, **kw):
+def conv3d_f16x2(x, wpk, bias, cout, kernel, out, o_off=(0, 0, 0), **kw):
     """K2s3h: `conv3d` of a full-resolution head convolution (`c32x3_eligible`) with the two-term fp16 split of both
     operands (float32 tensors, wpk = pack_weights_f16x2(w)).  Other geometries are an error: there is no generic form."""
-    if wpk.dtype != torch.uint8:
-        raise RuntimeError("conv3d_f16x2 needs the image of pack_weights_f16x2")
-    if x.buf.dtype != torch.float32:
-        raise RuntimeError("the fp16 split takes float32 tensors")
-    a = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, kw.get("stride", (1, 1, 1)), kw.get("dilation", (1, 1, 1)),
-                     kw.get("padding", (0, 0, 0)), kw.get("res1"), kw.get("res2"), kw.get("act_in", ACT_NONE),
-                     kw.get("act_out", ACT_NONE), kw.get("out_pos"), kw.get("o_stride", (1, 1, 1)), kw.get("o_off", (0, 0, 0)),
-                     kw.get("cin"), kw.get("tile_hint", 0), _act_ptr(x.buf.dtype))
-    _check(load().occd_conv3d_bf16_fwd(ctypes.byref(a), 3, _stream()), "occd_conv3d_bf16_fwd (f16x2)")
-    return out
+    return _conv3d_bf16_pipe(CONV_F16X2_HEAD, "conv3d_f16x2 needs the image of pack_weights_f16x2", x, [(wpk, kernel, o_off)],
+                             bias, cout, out, **kw)
 
 
 def conv3d_bf16(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 1, 1), padding=(0, 0, 0),
@@ -364,27 +398,14 @@ def conv3d_bf16(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 
     split3 (float32 tensors, wpk = pack_weights_bf16(w, split3=True)): the 3-way split experiment, float32-level accuracy.
     f16x2 (float32 tensors, wpk = pack_weights_f16x2(w), act_in none / relu): K2bh, the same kernel on the f16 matrix pipe with
     the two-term fp16 split -- K2s3h's numerics at any geometry; finite |x| >= 32760 overflow to non-finite outputs."""
-    if f16x2:
-        if split3:
-            raise RuntimeError("conv3d_bf16: split3 and f16x2 are two forms of one launch, pick one")
-        if wpk.dtype != torch.uint8:
-            raise RuntimeError("conv3d_bf16(f16x2=True) needs the image of pack_weights_f16x2")
-        if x.buf.dtype != torch.float32:
-            raise RuntimeError("the fp16 split takes float32 tensors")
-        a = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, stride, dilation, padding, res1, res2, act_in, act_out,
-                         out_pos, o_stride, o_off, cin, tile_hint, _act_ptr(x.buf.dtype))
-        _check(load().occd_conv3d_bf16_fwd(ctypes.byref(a), 4, _stream()), "occd_conv3d_bf16_fwd (f16x2)")
-        return out
-    if wpk.dtype != torch.bfloat16:
-        raise RuntimeError("conv3d_bf16 needs the bf16 weight image of pack_weights_bf16")
-    if split3 and x.buf.dtype != torch.float32:
-        raise RuntimeError("the 3-way split takes float32 tensors")
-    ptr = _act_ptr(x.buf.dtype)
-    a = _conv3d_args(x, _ptr(wpk, "wpk"), bias, cout, kernel, out, stride, dilation, padding, res1, res2, act_in, act_out,
-                     out_pos, o_stride, o_off, cin, tile_hint, ptr)
-    _check(load().occd_conv3d_bf16_fwd(ctypes.byref(a), 2 if split3 else _storage_code(x.buf.dtype), _stream()),
-           "occd_conv3d_bf16_fwd")
-    return out
+    mode = _split_mode("conv3d_bf16", split3, f16x2)
+    error = ("conv3d_bf16(f16x2=True) needs the image of pack_weights_f16x2" if f16x2 else
+             "conv3d_bf16 needs the bf16 weight image of pack_weights_bf16")
+    if mode is None:
+        mode = _storage_code(x.buf.dtype)
+    return _conv3d_bf16_pipe(mode, error, x, [(wpk, kernel, o_off)], bias, cout, out, stride=stride,
+                             dilation=dilation, padding=padding, res1=res1, res2=res2, act_in=act_in, act_out=act_out,
+                             out_pos=out_pos, o_stride=o_stride, cin=cin, tile_hint=tile_hint)
 
 
 GEMM_ACT = {None: abi.CONSTANTS["OCCD_GEMM_ACT_NONE"], "none": abi.CONSTANTS["OCCD_GEMM_ACT_NONE"],

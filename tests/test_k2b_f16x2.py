@@ -144,7 +144,7 @@ def test_k2bh_merged_phases(hip, case):
             convs = [t for t in prof.rows if t.startswith("conv3d")]
             assert convs and all(t.startswith("conv3d_bf16x3_phases") and "f16x2" not in t for t in convs), convs
             out = hip.Vox.empty(B, tuple(2 * n for n in dims), cout, DEV)
-            hip.conv3d_phases(vx, [(wpk.x3, kern, off) for off, kern, _, wpk in plan._phases], plan._bias, cout, out, res1=vr,
+            hip.conv3d_phases(vx, [(wpk.image("x3"), kern, off) for off, kern, _, wpk in plan._phases], plan._bias, cout, out, res1=vr,
                               act_out=hip.ACT_RELU, out_pos=vx.dims, o_stride=(2, 2, 2), split3=True)
             assert torch.equal(one_3, out.ncdhw())
             fused.PHASES_X3 = False
@@ -305,7 +305,7 @@ def test_k2bh_routing(hip, geom):
             assert tags and all(t.startswith("conv3d_bf16x3") and "f16x2" not in t for t in tags), tags
             k, s, dl, p = plan.geometry()
             out = hip.Vox.empty(1, plan.out_dims(vx.dims), cout, DEV)
-            hip.conv3d_bf16(vx, plan._wpk.x3, plan._bias, cout, k, out, stride=s, dilation=dl, padding=p, act_out=hip.ACT_RELU,
+            hip.conv3d_bf16(vx, plan._wpk.image("x3"), plan._bias, cout, k, out, stride=s, dilation=dl, padding=p, act_out=hip.ACT_RELU,
                             split3=True)
             assert torch.equal(got_3.buf, out.buf)
             y = F.conv3d(x.double(), conv.weight.double(), None, stride=conv.stride, padding=conv.padding, dilation=conv.dilation)

@@ -3,7 +3,8 @@
 //   out[vox][co] = act_out( sum_{tap,ci} bf16(act_in(in[vox*stride - pad + tap*dil][ci])) * bf16(W[co][ci][tap])
 //                           + bias[co] + res1[vox][co] + res2[vox][co] )          (fp32 accumulate)
 //
-// Same GEMM view, tiling, output scatter and epilogue as K2 (conv3d_igemm.hip); what changes is the instruction --
+// Same GEMM view, tiling, output scatter and epilogue as K2 (conv3d_igemm.hip), same validation, parameter fill and launch
+// (conv3d_tile.h); what changes is the instruction --
 // v_mfma_f32_32x32x16_bf16: 16 K values per instruction at 32 cycles, 16x the fp32 MFMA rate -- and with it the
 // bottleneck: operand delivery.  A wave therefore owns up to 4 x 2 tiles of 32 voxels x 32 couts (each B fragment
 // loaded from L2 feeds MT MFMAs, each A fragment read from LDS feeds NT), the staged slab holds bf16 (half the LDS
@@ -15,14 +16,10 @@
 //
 // Reference semantics replaced (training step, N1): occdepth/models/DDR.py:111-139, modules.py:40-46,158-175,278-296,
 // CRP3D.py:54-97, unet2d.py:24-46 -- forward and, on dL/dy with flipped weights, the data gradient.
-#include "device.h"
-
-#include <algorithm>
-#include <cstddef>
-#include <cstdlib>
-#include <cstring>
+#include "conv3d_tile.h"
 
 using occd::FastDiv;
+using occd::Tiling;
 
 namespace {
 
@@ -33,7 +30,6 @@ struct PhaseBP {
     int KX, KY, KZ, oox, ooy, ooz, YIN, ZIN;
     FastDiv div_zin;
 };
-constexpr int kMaxPhasesB = 8;
 
 struct ConvBP {
     const void* in;
@@ -51,7 +47,7 @@ struct ConvBP {
     int nph_log2;           // blockIdx.y = (batch index << nph_log2) | phase, or (ph_fast) linear id = (tile << nph_log2) | phase
     int ph_fast;
     FastDiv div_tz, div_ztiles, div_ytiles;
-    PhaseBP ph[kMaxPhasesB];
+    PhaseBP ph[occd::kMaxPhases];
 };
 
 __device__ __forceinline__ f32x4 unpack_lo(u32x2 v) {       // 4 bf16 -> 4 floats
@@ -378,10 +374,7 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, const floa
     const int ci = k16 * 16 + (lane >> 5) * 8 + j;
     float v = 0.f;
     if (co < cout && ci < cin) {
-        if (layout == 0) v = w[((size_t)co * cin + ci) * taps + tap];
-        else if (layout == 1) v = w[((size_t)ci * cout + co) * taps + tap];
-        else if (layout == 2) v = w[(size_t)ci * cout + co];
-        else v = w[(size_t)co * tm.s_co + (size_t)ci * tm.s_ci + tm.ofs[tap]];     // (see pack_weights_kernel, layout 3)
+        v = conv3d_weight_src(w, layout, co, ci, tap, cout, cin, taps, &tm);
         if (scale != nullptr) v *= scale[co];
     }
     const __bf16 hi = (__bf16)v;
@@ -405,8 +398,7 @@ __global__ void f16x2_scale_kernel(const float* __restrict__ w, const float* __r
     if (co < cout) {
         for (int ci = 0; ci < cin; ++ci)
             for (int tap = 0; tap < taps; ++tap) {
-                float v = layout == 0 ? w[((size_t)co * cin + ci) * taps + tap] : layout == 1 ? w[((size_t)ci * cout + co) * taps + tap]
-                                                                                             : w[(size_t)ci * cout + co];
+                float v = conv3d_weight_src(w, layout, co, ci, tap, cout, cin, taps, nullptr);
                 if (scale != nullptr) v *= scale[co];
                 m = fmaxf(m, fabsf(v));
             }
@@ -432,9 +424,7 @@ __global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, const flo
     const int ci = k16 * 16 + (lane >> 5) * 8 + j;
     float v = 0.f;
     if (co < cout && ci < cin) {
-        if (layout == 0) v = w[((size_t)co * cin + ci) * taps + tap];
-        else if (layout == 1) v = w[((size_t)ci * cout + co) * taps + tap];
-        else v = w[(size_t)ci * cout + co];
+        v = conv3d_weight_src(w, layout, co, ci, tap, cout, cin, taps, nullptr);
         if (scale != nullptr) v *= scale[co];
         v *= 0.5f / fac[co];                                      // 2^k[co]: exact
     }
@@ -470,18 +460,10 @@ const VariantB kVariantsB[] = {
                                 conv3d_bf16_kernel<1, 1, 1, 4, false, false, 2, 4> } },
 };
 constexpr int kNumVariantsB = sizeof(kVariantsB) / sizeof(kVariantsB[0]);
-constexpr size_t kMaxLdsB = 160 * 1024;
-
-struct TilingB {
-    int TY, TZ, YIN, ZIN, ytiles, ztiles, ngroups;
-    size_t lds;
-    long nwg;
-    double cost;
-};
 
 // Tile of mwg output positions as TY x TZ: the candidate that stages the fewest input rows per launch (halo + ragged
 // edges) among those that fit LDS.  2-D images (Zo = W >> mwg) get a TY > 1 tile instead of a one-row strip.
-bool plan_b(const occd_conv3d_args* a, const VariantB& v, int NTtot, TilingB* best, int rsb) {
+bool plan_b(const occd_conv3d_args* a, const VariantB& v, int NTtot, Tiling* best, int rsb) {
     const int mwg = v.MT * v.WM * 32;
     bool found = false;
     int cands[16];
@@ -490,7 +472,7 @@ bool plan_b(const occd_conv3d_args* a, const VariantB& v, int NTtot, TilingB* be
     for (int tz = 8; tz <= mwg; tz *= 2)
         if (tz < a->Zo) cands[nc++] = tz;
     for (int i = 0; i < nc; ++i) {
-        TilingB t;
+        Tiling t;
         t.TZ = cands[i];
         t.TY = mwg / t.TZ;
         if (t.TY < 1) continue;
@@ -505,7 +487,7 @@ bool plan_b(const occd_conv3d_args* a, const VariantB& v, int NTtot, TilingB* be
         const int nwg_n = v.NT * v.WN;
         t.ngroups = (NTtot + nwg_n - 1) / nwg_n;
         t.nwg = (long)a->Xo * t.ytiles * t.ztiles;
-        if (t.lds > kMaxLdsB || (long)t.YIN * t.ZIN >= 65536 || t.nwg >= (1L << 24)) continue;
+        if (t.lds > occd::kMaxConvLds || (long)t.YIN * t.ZIN >= 65536 || t.nwg >= (1L << 24)) continue;
         // staged rows per launch + idle M slots of a tile smaller than mwg (they still cost MFMA time)
         t.cost = (double)t.nwg * ((double)t.YIN * t.ZIN + 2.0 * (mwg - (double)t.TY * t.TZ));
         if (t.lds > 80 * 1024) t.cost *= 1.15;                   // one workgroup per CU instead of two
@@ -522,37 +504,60 @@ extern "C" int64_t occd_packed_weight_bf16_elems(int32_t cout, int32_t cin, int3
     return (int64_t)taps * K16 * NT * 512;
 }
 
-static int pack_bf16(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t kx, int32_t ky,
-                     int32_t kz, int32_t layout, int nsplit, void* stream);
-
-extern "C" int occd_pack_weights_bf16(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
-                                      int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
-    return pack_bf16(w, scale, wpk, cout, cin, kx, ky, kz, layout, 1, stream);
-}
-
-// three images (hi | mid | lo), 3 * occd_packed_weight_bf16_elems() elements: the weight operand of the 3-way split
-extern "C" int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
-                                        int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
-    return pack_bf16(w, scale, wpk, cout, cin, kx, ky, kz, layout, 3, stream);
-}
-
-static int pack_bf16(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t kx, int32_t ky,
-                     int32_t kz, int32_t layout, int nsplit, void* stream) {
-    if (!w || !wpk || layout < 0 || layout > 2) return OCCD_EINVAL;
-    const int taps = kx * ky * kz;
+// tap_ofs == nullptr: layout 0 / 1 / 2 of a dense tensor; else layout 3, the gathered view (s_co, s_ci, tap_ofs[taps]).
+// nsplit = 3: the hi | mid | lo images of the 3-way split, 3 * occd_packed_weight_bf16_elems() elements.
+static int pack_bf16(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t taps, int32_t layout,
+                     int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, int nsplit, void* stream) {
     const int64_t total = occd_packed_weight_bf16_elems(cout, cin, taps);
-    if (total <= 0 || (layout == 2 && taps != 1)) return OCCD_EINVAL;
+    if (total <= 0) return OCCD_EINVAL;
+    occd::TapMap tm{};
+    tm.s_co = s_co; tm.s_ci = s_ci;
+    for (int i = 0; tap_ofs != nullptr && i < taps; ++i) tm.ofs[i] = tap_ofs[i];
     const int K16 = (cin + 15) / 16, NT = (cout + 31) / 32;
     const int th = 256;
     const long blocks = (total + th - 1) / th;
     occd::ProfScope prof("pack_weights_bf16", (hipStream_t)stream, 0.0, (double)total * 6);
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)blocks), dim3(th), 0, (hipStream_t)stream, w, scale,
-                       (uint16_t*)wpk, cout, cin, taps, K16, NT, layout, (long)total, nsplit, occd::TapMap{});
+                       (uint16_t*)wpk, cout, cin, taps, K16, NT, layout, (long)total, nsplit, tm);
     return occd::check_launch();
 }
 
+static int pack_bf16_dense(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t kx, int32_t ky,
+                           int32_t kz, int32_t layout, int nsplit, void* stream) {
+    if (!w || !wpk || layout < 0 || layout > 2 || (layout == 2 && kx * ky * kz != 1)) return OCCD_EINVAL;
+    return pack_bf16(w, scale, wpk, cout, cin, kx * ky * kz, layout, 0, 0, nullptr, nsplit, stream);
+}
+
 static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t ntaps,
-                            int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, int nsplit, void* stream);
+                            int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, int nsplit, void* stream) {
+    if (!w || !wpk || !tap_ofs || ntaps <= 0 || ntaps > occd::kMaxTaps) return OCCD_EINVAL;
+    return pack_bf16(w, scale, wpk, cout, cin, ntaps, 3, s_co, s_ci, tap_ofs, nsplit, stream);
+}
+
+extern "C" int occd_pack_weights_bf16(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
+                                      int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
+    return pack_bf16_dense(w, scale, wpk, cout, cin, kx, ky, kz, layout, 1, stream);
+}
+
+// three images (hi | mid | lo): the weight operand of the 3-way split
+extern "C" int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
+                                        int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
+    return pack_bf16_dense(w, scale, wpk, cout, cin, kx, ky, kz, layout, 3, stream);
+}
+
+extern "C" int occd_pack_weights_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
+                                             int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs,
+                                             void* stream) {
+    return pack_bf16_gather(w, scale, wpk, cout, cin, ntaps, s_co, s_ci, tap_ofs, 1, stream);
+}
+
+// the hi | mid | lo images of the gathered operator: the 3-way split of the data-gradient operators (float32-accurate dgrad
+// of the head convolutions on K2s3 in the fp32 training mode)
+extern "C" int occd_pack_weights_bf16x3_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
+                                               int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs,
+                                               void* stream) {
+    return pack_bf16_gather(w, scale, wpk, cout, cin, ntaps, s_co, s_ci, tap_ofs, 3, stream);
+}
 
 extern "C" int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps) {
     const int64_t n = occd_packed_weight_bf16_elems(cout, cin, taps);
@@ -578,37 +583,6 @@ extern "C" int occd_pack_weights_f16x2(const float* w, const float* scale, void*
     return occd::check_launch();
 }
 
-extern "C" int occd_pack_weights_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
-                                             int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs,
-                                             void* stream) {
-    return pack_bf16_gather(w, scale, wpk, cout, cin, ntaps, s_co, s_ci, tap_ofs, 1, stream);
-}
-
-// the hi | mid | lo images of the gathered operator (3 * occd_packed_weight_bf16_elems() elements): the 3-way split of the
-// data-gradient operators (float32-accurate dgrad of the head convolutions on K2s3 in the fp32 training mode)
-extern "C" int occd_pack_weights_bf16x3_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin,
-                                               int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs,
-                                               void* stream) {
-    return pack_bf16_gather(w, scale, wpk, cout, cin, ntaps, s_co, s_ci, tap_ofs, 3, stream);
-}
-
-static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32_t cout, int32_t cin, int32_t ntaps,
-                            int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, int nsplit, void* stream) {
-    if (!w || !wpk || !tap_ofs || ntaps <= 0 || ntaps > occd::kMaxTaps) return OCCD_EINVAL;
-    const int64_t total = occd_packed_weight_bf16_elems(cout, cin, ntaps);
-    if (total <= 0) return OCCD_EINVAL;
-    occd::TapMap tm{};
-    tm.s_co = s_co; tm.s_ci = s_ci;
-    for (int i = 0; i < ntaps; ++i) tm.ofs[i] = tap_ofs[i];
-    const int K16 = (cin + 15) / 16, NT = (cout + 31) / 32;
-    const int th = 256;
-    const long blocks = (total + th - 1) / th;
-    occd::ProfScope prof("pack_weights_bf16", (hipStream_t)stream, 0.0, (double)total * 6);
-    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)blocks), dim3(th), 0, (hipStream_t)stream, w, scale,
-                       (uint16_t*)wpk, cout, cin, ntaps, K16, NT, 3, (long)total, nsplit, tm);
-    return occd::check_launch();
-}
-
 // `a->in`, `a->out`, `a->res1`, `a->res2` point at fp32 or bf16 channels-last rows -- all four the same type --, `a->wpk`
 // at the image of occd_pack_weights_bf16, `a->bias` at fp32.  *_cs / *_coff count ELEMENTS.  The `dtype` argument of the
 // two entry points is a mode, OCCD_CONV_* of the header, one row of kModesB each:
@@ -621,76 +595,37 @@ static int pack_bf16_gather(const float* w, const float* scale, void* wpk, int32
 // geometry K2b takes, act_in NONE or RELU.
 namespace {
 
+constexpr unsigned kActRelu = 1u << OCCD_ACT_NONE | 1u << OCCD_ACT_RELU;
+// (input sigmoid: the CRP products sigmoid(P_logits) @ mega, CRP3D.py:80 -- float32 operands with the 3-way split only)
+constexpr occd::ConvStorage kF32 = {4, 4, kActRelu}, kF32Sigmoid = {4, 4, kActRelu | 1u << OCCD_ACT_SIGMOID};
+constexpr occd::ConvStorage kBf16 = {2, 8, kActRelu};     // 16-byte staging loads: 8 bf16 / 4 (+4) floats
+
 struct ModeB {
-    int storage;              // activation tensors: 0 = float32, 1 = bfloat16
+    occd::ConvStorage st;     // the activation tensors
     int ksel;                 // column of kVariantsB[].kern (-1: no kernel here)
     int rsb;                  // LDS row stride of that kernel's staging
-    bool sigmoid_in;          // act_in = SIGMOID allowed
     const char* name;         // profile row of a plain launch ...
     const char* name_phases;  // ... and of a merged phase launch
 };
 constexpr ModeB kModesB[] = {
-    {0, 0, kRSB, false, "conv3d_bf16", "conv3d_bf16x3_phases"},                     // OCCD_CONV_F32
-    {1, 1, kRSB, false, "conv3d_bf16s", "conv3d_bf16x3_phases"},                    // OCCD_CONV_BF16
-    {0, 2, kRSB3, true, "conv3d_bf16x3", "conv3d_bf16x3_phases"},                   // OCCD_CONV_BF16X3
-    {0, -1, 0, false, nullptr, nullptr},                                            // OCCD_CONV_F16X2_HEAD
-    {0, 3, kRSB2, false, "conv3d_bf16x3_f16x2", "conv3d_bf16x3_phases_f16x2"},      // OCCD_CONV_F16X2
+    {kF32, 0, kRSB, "conv3d_bf16", "conv3d_bf16x3_phases"},                       // OCCD_CONV_F32
+    {kBf16, 1, kRSB, "conv3d_bf16s", "conv3d_bf16x3_phases"},                     // OCCD_CONV_BF16
+    {kF32Sigmoid, 2, kRSB3, "conv3d_bf16x3", "conv3d_bf16x3_phases"},             // OCCD_CONV_BF16X3
+    {kF32, -1, 0, nullptr, nullptr},                                              // OCCD_CONV_F16X2_HEAD
+    {kF32, 3, kRSB2, "conv3d_bf16x3_f16x2", "conv3d_bf16x3_phases_f16x2"},        // OCCD_CONV_F16X2
 };
 constexpr int kNumModesB = sizeof(kModesB) / sizeof(kModesB[0]);
 static_assert(OCCD_CONV_F32 == 0 && OCCD_CONV_BF16 == 1 && OCCD_CONV_BF16X3 == 2 && OCCD_CONV_F16X2_HEAD == 3 &&
               OCCD_CONV_F16X2 == 4 && kNumModesB == 5, "kModesB is indexed by OCCD_CONV_*");
-
-int validate_b(const occd_conv3d_args* a, int32_t mode) {
-    if (!a || !a->in || !a->wpk || !a->out || mode < 0 || mode >= kNumModesB) return OCCD_EINVAL;
-    const ModeB& m = kModesB[mode];
-    if (a->batch <= 0 || a->X <= 0 || a->Y <= 0 || a->Z <= 0 || a->cin <= 0 || a->cout <= 0) return OCCD_EINVAL;
-    if (a->kx <= 0 || a->ky <= 0 || a->kz <= 0 || a->sx <= 0 || a->sy <= 0 || a->sz <= 0) return OCCD_EINVAL;
-    if (a->Xo <= 0 || a->Yo <= 0 || a->Zo <= 0) return OCCD_EINVAL;
-    const int cin8 = (a->cin + 7) & ~7;
-    const int cin16 = (a->cin + 15) & ~15;
-    const int NTtot = (a->cout + 31) / 32;
-    const int al = m.storage == 1 ? 7 : 3;           // 16-byte staging loads: 8 bf16 / 4 (+4) floats
-    const int esz = m.storage == 1 ? 2 : 4;
-    if ((a->in_cs & al) || (a->in_coff & al) || a->in_coff + cin8 > a->in_cs) return OCCD_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(a->in) & 15) || (reinterpret_cast<uintptr_t>(a->wpk) & 15)) return OCCD_EINVAL;
-    if (a->cout_store < a->cout || a->cout_store > NTtot * 32 || a->out_coff + a->cout_store > a->out_cs)
-        return OCCD_EINVAL;
-    // 4-channel epilogue groups: 16 B (fp32) / 8 B (bf16) accesses
-    if ((a->cout_store & 3) || (a->out_cs & 3) || (a->out_coff & 3) ||
-        (reinterpret_cast<uintptr_t>(a->out) & (4 * esz - 1)))
-        return OCCD_EINVAL;
-    if (a->res1 && ((a->res1_cs & 3) || (a->res1_coff & 3) || (reinterpret_cast<uintptr_t>(a->res1) & (4 * esz - 1)) ||
-                    a->res1_coff + a->cout_store > a->res1_cs))
-        return OCCD_EINVAL;
-    if (a->res2 && ((a->res2_cs & 3) || (a->res2_coff & 3) || (reinterpret_cast<uintptr_t>(a->res2) & (4 * esz - 1)) ||
-                    a->res2_coff + a->cout_store > a->res2_cs))
-        return OCCD_EINVAL;
-    if (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 15)) return OCCD_EINVAL;
-    if ((a->Xo - 1) * a->o_stride_x + a->o_off_x >= a->OX || (a->Yo - 1) * a->o_stride_y + a->o_off_y >= a->OY ||
-        (a->Zo - 1) * a->o_stride_z + a->o_off_z >= a->OZ)
-        return OCCD_EINVAL;
-    // (input sigmoid: the CRP products sigmoid(P_logits) @ mega, CRP3D.py:80 -- float32 operands with the split only)
-    if (a->act_in != OCCD_ACT_NONE && a->act_in != OCCD_ACT_RELU && !(a->act_in == OCCD_ACT_SIGMOID && m.sigmoid_in)) return OCCD_EINVAL;
-    if (a->act_out != OCCD_ACT_NONE && a->act_out != OCCD_ACT_RELU && a->act_out != OCCD_ACT_RELU_PRE)
-        return OCCD_EINVAL;
-    return OCCD_OK;
-}
 
 // n phases (n = 1: a plain launch) that differ only in wpk, kx / ky / kz and o_off_*: ONE launch
 int launch_b(const occd_conv3d_args* a, int n, int32_t mode, hipStream_t stream) {
     const ModeB& m = kModesB[mode];
     const int ksel = m.ksel;
     if (ksel < 0) return OCCD_EINVAL;
-    const int esz = m.storage == 1 ? 2 : 4;
-    const int cin8 = (a->cin + 7) & ~7;
     const int cin16 = (a->cin + 15) & ~15;
     const int NTtot = (a->cout + 31) / 32;
-    // tiling for the phase with the largest slab (the largest ky / kz over the phases)
-    occd_conv3d_args big = a[0];
-    for (int i = 1; i < n; ++i) {
-        big.ky = a[i].ky > big.ky ? a[i].ky : big.ky;
-        big.kz = a[i].kz > big.kz ? a[i].kz : big.kz;
-    }
+    const occd_conv3d_args big = occd::conv3d_widest_phase(a, n);
     const long copies = (long)a->batch * n;
     int order[kNumVariantsB];
     int no = 0;
@@ -703,13 +638,12 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t mode, hipStream_t stream)
     } else {
         order[no++] = 5; order[no++] = 6; order[no++] = 7;
     }
-    const int rsb = m.rsb;
     int pick = -1;
-    TilingB til{};
+    Tiling til{};
     for (int i = 0; i < no; ++i) {
-        TilingB t{};
+        Tiling t{};
         if (kVariantsB[order[i]].kern[ksel] == nullptr) continue;
-        if (!plan_b(&big, kVariantsB[order[i]], NTtot, &t, rsb)) continue;
+        if (!plan_b(&big, kVariantsB[order[i]], NTtot, &t, m.rsb)) continue;
         pick = order[i];
         til = t;
         if (t.nwg * t.ngroups * copies >= 512) break;   // else keep refining to the finest fit
@@ -717,8 +651,8 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t mode, hipStream_t stream)
     if (pick < 0) return OCCD_ENOMEM;
     if (ksel >= 2 && a->tile_hint == 0 && til.nwg * til.ngroups * copies <= 320 && cin16 >= 128 && NTtot % 4 == 0) {
         // too few output tiles to fill the chip: multiply the waves by splitting K inside the workgroup (K2's rule)
-        TilingB t{};
-        if (plan_b(&big, kVariantsB[8], NTtot, &t, rsb) && t.nwg * t.ngroups * copies <= 1024) {
+        Tiling t{};
+        if (plan_b(&big, kVariantsB[8], NTtot, &t, m.rsb) && t.nwg * t.ngroups * copies <= 1024) {
             pick = 8;
             til = t;
         }
@@ -726,66 +660,23 @@ int launch_b(const occd_conv3d_args* a, int n, int32_t mode, hipStream_t stream)
     const VariantB& v = kVariantsB[pick];
 
     ConvBP p{};
-    p.in = a->in; p.bias = a->bias; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.X = a->X; p.Y = a->Y; p.Z = a->Z; p.cin8 = cin8; p.cin16 = cin16; p.in_cs = a->in_cs; p.in_coff = a->in_coff;
-    p.K16tot = cin16 / 16; p.NTtot = NTtot;
-    p.out_cs = a->out_cs; p.out_coff = a->out_coff;
-    p.res1_cs = a->res1_cs; p.res1_coff = a->res1_coff; p.res2_cs = a->res2_cs; p.res2_coff = a->res2_coff;
-    p.SX = a->sx; p.SY = a->sy; p.SZ = a->sz;
-    p.DX = a->dx; p.DY = a->dy; p.DZ = a->dz; p.PX = a->px; p.PY = a->py; p.PZ = a->pz;
-    p.Xo = a->Xo; p.Yo = a->Yo; p.Zo = a->Zo; p.OX = a->OX; p.OY = a->OY; p.OZ = a->OZ;
-    p.osx = a->o_stride_x; p.osy = a->o_stride_y; p.osz = a->o_stride_z;
-    p.act_in = a->act_in; p.act_out = a->act_out; p.cout_store = a->cout_store;
-    p.TY = til.TY; p.TZ = til.TZ;
-    p.ytiles = til.ytiles; p.ztiles = til.ztiles; p.nwg = (int)til.nwg;
-    p.div_tz = occd::make_fastdiv(til.TZ);
-    p.div_ztiles = occd::make_fastdiv(til.ztiles); p.div_ytiles = occd::make_fastdiv(til.ytiles);
-    p.nph_log2 = n == 1 ? 0 : n == 2 ? 1 : n == 4 ? 2 : 3;
-    // phase-major dispatch is the default (see occd_conv3d_fwd_phases: the tile-major order, OCCD_PHASE_FAST=1, measured slower)
-    static const bool phase_fast = occd::env_flag("OCCD_PHASE_FAST", false);
-    p.ph_fast = n > 1 && phase_fast ? 1 : 0;
-    if (p.ph_fast) p.nwg = (int)(til.nwg * n);
-    if (til.nwg * n >= (1L << 24)) return OCCD_EINVAL;
-    // heaviest tap subset first in dispatch order: the single-tap phases fill the tail
-    int ord[kMaxPhasesB];
-    for (int i = 0; i < n; ++i) ord[i] = i;
-    std::stable_sort(ord, ord + n, [&](int l, int r) { return a[l].kx * a[l].ky * a[l].kz > a[r].kx * a[r].ky * a[r].kz; });
-    double flops = 0.0, bytes = 0.0;
-    const double pos = (double)a->batch * a->Xo * a->Yo * a->Zo;
-    for (int i = 0; i < n; ++i) {
-        const occd_conv3d_args* ai = a + ord[i];
-        PhaseBP& ph = p.ph[i];
-        ph.wpk = (const u32x4*)ai->wpk;
+    p.cin16 = cin16;
+    p.K16tot = cin16 / 16;
+    const occd::ConvLaunch L = {n > 1 ? m.name_phases : m.name, v.WM * v.WN * v.KS * 64, (size_t)m.rsb * v.KS, m.st, 2.0, false};
+    return occd::conv3d_launch(a, n, til, v.kern[ksel], p, L, [&](PhaseBP& ph, const occd_conv3d_args& ai) {
+        ph.wpk = (const u32x4*)ai.wpk;
         // the trailer of the fp16 image: after its three images of taps * K16 * NT * 512 halves each
-        ph.fac = ksel == 3 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(ai->wpk) +
-                                                            3 * (size_t)ai->kx * ai->ky * ai->kz * (cin16 / 16) * NTtot * 512)
+        ph.fac = ksel == 3 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(ai.wpk) +
+                                                            3 * (size_t)ai.kx * ai.ky * ai.kz * (cin16 / 16) * NTtot * 512)
                            : nullptr;
-        ph.KX = ai->kx; ph.KY = ai->ky; ph.KZ = ai->kz;
-        ph.oox = ai->o_off_x; ph.ooy = ai->o_off_y; ph.ooz = ai->o_off_z;
-        ph.YIN = (til.TY - 1) * ai->sy + (ai->ky - 1) * ai->dy + 1;      // (the shared tile, this phase's extent)
-        ph.ZIN = (til.TZ - 1) * ai->sz + (ai->kz - 1) * ai->dz + 1;
-        ph.div_zin = occd::make_fastdiv(ph.ZIN);
-        if ((size_t)ph.YIN * ph.ZIN * rsb * v.KS > til.lds) return OCCD_EINVAL;
-        const double taps = (double)ai->kx * ai->ky * ai->kz;
-        flops += 2.0 * pos * taps * ai->cin * ai->cout;
-        bytes += (double)esz * ((i == 0 ? (double)a->batch * a->X * a->Y * a->Z * a->cin : 0.0) +
-                                pos * a->cout * (1 + (a->res1 != nullptr) + (a->res2 != nullptr))) + 2.0 * taps * a->cin * a->cout;
-    }
-    if (copies > 65535) return OCCD_EINVAL;
-
-    void (*kern)(const ConvBP) = v.kern[ksel];
-    if (til.lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
-    occd::ProfScope prof(n > 1 ? m.name_phases : m.name, stream, flops, bytes);
-    hipLaunchKernelGGL(kern, p.ph_fast ? dim3((unsigned)(til.nwg * n), (unsigned)a->batch, (unsigned)til.ngroups)
-                                       : dim3((unsigned)til.nwg, (unsigned)copies, (unsigned)til.ngroups),
-                       dim3(v.WM * v.WN * v.KS * 64), til.lds, stream, p);
-    return occd::check_launch();
+    }, stream);
 }
 
 }  // namespace
 
 extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, void* stream) {
-    const int bad = validate_b(a, dtype);
+    if (dtype < 0 || dtype >= kNumModesB) return OCCD_EINVAL;
+    const int bad = occd::conv3d_validate(a, kModesB[dtype].st);
     if (bad != OCCD_OK) return bad;
     if (dtype == OCCD_CONV_F16X2_HEAD) {   // K2s3h: the head launches only
         const int r = occd::try_conv3d_c32_slide_x3(a, (hipStream_t)stream, true);
@@ -801,14 +692,8 @@ extern "C" int occd_conv3d_bf16_fwd(const occd_conv3d_args* a, int32_t dtype, vo
 // The n in {1, 2, 4, 8} sub-pixel phases of ONE transposed convolution on K2b as one launch (the bf16-pipe twin of
 // occd_conv3d_fwd_phases, same contract: a[0..n) differ ONLY in wpk, kx / ky / kz and o_off_*).
 extern "C" int occd_conv3d_bf16_fwd_phases(const occd_conv3d_args* a, int32_t n, int32_t dtype, void* stream) {
-    if (!a || (n != 1 && n != 2 && n != 4 && n != 8) || dtype == OCCD_CONV_F16X2_HEAD) return OCCD_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const int bad = validate_b(a + i, dtype);
-        if (bad != OCCD_OK) return bad;
-        occd_conv3d_args t = a[i];
-        t.wpk = a[0].wpk; t.kx = a[0].kx; t.ky = a[0].ky; t.kz = a[0].kz;
-        t.o_off_x = a[0].o_off_x; t.o_off_y = a[0].o_off_y; t.o_off_z = a[0].o_off_z;
-        if (memcmp(&t, &a[0], offsetof(occd_conv3d_args, tile_hint) + sizeof(int32_t)) != 0) return OCCD_EINVAL;
-    }
+    if (dtype < 0 || dtype >= kNumModesB || dtype == OCCD_CONV_F16X2_HEAD) return OCCD_EINVAL;
+    const int bad = occd::conv3d_validate_phases(a, n, kModesB[dtype].st);
+    if (bad != OCCD_OK) return bad;
     return launch_b(a, n, dtype, (hipStream_t)stream);
 }

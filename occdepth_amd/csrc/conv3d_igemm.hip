@@ -19,14 +19,10 @@
 //
 // Reference semantics replaced: occdepth/models/DDR.py:111-139,
 // occdepth/models/modules.py:40-46,158-175,278-296, occdepth/models/CRP3D.py:54-97.
-#include "device.h"
-
-#include <algorithm>
-#include <cstddef>
-#include <cstdlib>
-#include <cstring>
+#include "conv3d_tile.h"
 
 using occd::FastDiv;
+using occd::Tiling;
 
 namespace {
 
@@ -38,7 +34,6 @@ struct PhaseP {
     int KX, KY, KZ, oox, ooy, ooz, YIN, ZIN;
     FastDiv div_zin;
 };
-constexpr int kMaxPhases = 8;
 
 struct ConvP {
     const float* in;
@@ -56,7 +51,7 @@ struct ConvP {
     int nph_log2;           // blockIdx.y = (batch index << nph_log2) | phase, or (ph_fast) linear id = (tile << nph_log2) | phase
     int ph_fast;
     FastDiv div_tz, div_ztiles, div_ytiles;
-    PhaseP ph[kMaxPhases];
+    PhaseP ph[occd::kMaxPhases];
 };
 
 // KS > 1: in-workgroup split-K.  The KS wave groups take interleaved cin chunks (each with its own LDS slab),
@@ -282,9 +277,7 @@ __global__ void __launch_bounds__(WM* WN* KS * 64) conv3d_igemm_kernel(const Con
     }
 }
 
-// ---------------------------------------------------------------- weight packing
-// layout 3 (occd_pack_weights_gather): element (co, ci, tap) of the packed operator is w[co * s_co + ci * s_ci + ofs[tap]] --
-// any transposed / flipped / tap-subset view of a dense weight tensor without materialising it (the data-gradient phases)
+// ---------------------------------------------------------------- weight packing (layouts: conv3d_weight_src, conv3d_tile.h)
 __global__ void pack_weights_kernel(const float* __restrict__ w, const float* __restrict__ scale,
                                     float* __restrict__ wpk, int cout, int cin, int taps, int KT, int NT,
                                     int layout, long total, const occd::TapMap tm) {
@@ -300,10 +293,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, const float* __
     const int ci = kt * 8 + (lane >> 5) * 4 + q;
     float v = 0.f;
     if (co < cout && ci < cin) {
-        if (layout == 0) v = w[((size_t)co * cin + ci) * taps + tap];
-        else if (layout == 1) v = w[((size_t)ci * cout + co) * taps + tap];
-        else if (layout == 2) v = w[(size_t)ci * cout + co];
-        else v = w[(size_t)co * tm.s_co + (size_t)ci * tm.s_ci + tm.ofs[tap]];
+        v = conv3d_weight_src(w, layout, co, ci, tap, cout, cin, taps, &tm);
         if (scale != nullptr) v *= scale[co];
     }
     wpk[i] = v;
@@ -331,13 +321,6 @@ const Variant kVariants[] = {
     OCCD_VARIANT_KS(1, 1, 2, 2, 32, 2),  // 8: M64 x N64, 2-way split-K (8 waves)
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-constexpr size_t kMaxLds = 160 * 1024;
-
-struct Tiling {
-    int TY, TZ, YIN, ZIN, ytiles, ztiles, ngroups;
-    size_t lds;
-    long nwg;
-};
 
 bool plan(const occd_conv3d_args* a, const Variant& v, int NTtot, Tiling* t) {
     const int mwg = v.MT * v.WM * 32;
@@ -359,7 +342,7 @@ bool plan(const occd_conv3d_args* a, const Variant& v, int NTtot, Tiling* t) {
     const int nwg_n = v.NT * v.WN;
     t->ngroups = (NTtot + nwg_n - 1) / nwg_n;
     t->nwg = (long)a->Xo * t->ytiles * t->ztiles;
-    return t->lds <= kMaxLds && t->YIN * t->ZIN < 65536 && t->nwg < (1L << 24);
+    return t->lds <= occd::kMaxConvLds &&t->YIN * t->ZIN < 65536 && t->nwg < (1L << 24);
 }
 
 }  // namespace
@@ -370,69 +353,38 @@ extern "C" int64_t occd_packed_weight_floats(int32_t cout, int32_t cin, int32_t 
     return (int64_t)taps * KT * NT * 256;
 }
 
-extern "C" int occd_pack_weights(const float* w, const float* scale, float* wpk, int32_t cout, int32_t cin,
-                                 int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
-    if (!w || !wpk || layout < 0 || layout > 2) return OCCD_EINVAL;
-    const int taps = kx * ky * kz;
+// tap_ofs == nullptr: layout 0 / 1 / 2 of a dense tensor; else layout 3, the gathered view (s_co, s_ci, tap_ofs[taps])
+static int pack_f32(const float* w, const float* scale, float* wpk, int32_t cout, int32_t cin, int32_t taps, int32_t layout,
+                    int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, void* stream) {
     const int64_t total = occd_packed_weight_floats(cout, cin, taps);
-    if (total <= 0 || (layout == 2 && taps != 1)) return OCCD_EINVAL;
+    if (total <= 0) return OCCD_EINVAL;
+    occd::TapMap tm{};
+    tm.s_co = s_co; tm.s_ci = s_ci;
+    for (int i = 0; tap_ofs != nullptr && i < taps; ++i) tm.ofs[i] = tap_ofs[i];
     const int KT = (cin + 7) / 8, NT = (cout + 31) / 32;
     const int th = 256;
     const long blocks = (total + th - 1) / th;
     occd::ProfScope prof("pack_weights", (hipStream_t)stream, 0.0, (double)total * 8);
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)blocks), dim3(th), 0, (hipStream_t)stream, w, scale,
-                       wpk, cout, cin, taps, KT, NT, layout, (long)total, occd::TapMap{});
+                       wpk, cout, cin, taps, KT, NT, layout, (long)total, tm);
     return occd::check_launch();
+}
+
+extern "C" int occd_pack_weights(const float* w, const float* scale, float* wpk, int32_t cout, int32_t cin,
+                                 int32_t kx, int32_t ky, int32_t kz, int32_t layout, void* stream) {
+    if (!w || !wpk || layout < 0 || layout > 2 || (layout == 2 && kx * ky * kz != 1)) return OCCD_EINVAL;
+    return pack_f32(w, scale, wpk, cout, cin, kx * ky * kz, layout, 0, 0, nullptr, stream);
 }
 
 extern "C" int occd_pack_weights_gather(const float* w, const float* scale, float* wpk, int32_t cout, int32_t cin,
                                         int32_t ntaps, int64_t s_co, int64_t s_ci, const int32_t* tap_ofs, void* stream) {
     if (!w || !wpk || !tap_ofs || ntaps <= 0 || ntaps > occd::kMaxTaps) return OCCD_EINVAL;
-    const int64_t total = occd_packed_weight_floats(cout, cin, ntaps);
-    if (total <= 0) return OCCD_EINVAL;
-    occd::TapMap tm{};
-    tm.s_co = s_co; tm.s_ci = s_ci;
-    for (int i = 0; i < ntaps; ++i) tm.ofs[i] = tap_ofs[i];
-    const int KT = (cin + 7) / 8, NT = (cout + 31) / 32;
-    const int th = 256;
-    const long blocks = (total + th - 1) / th;
-    occd::ProfScope prof("pack_weights", (hipStream_t)stream, 0.0, (double)total * 8);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)blocks), dim3(th), 0, (hipStream_t)stream, w, scale,
-                       wpk, cout, cin, ntaps, KT, NT, 3, (long)total, tm);
-    return occd::check_launch();
+    return pack_f32(w, scale, wpk, cout, cin, ntaps, 3, s_co, s_ci, tap_ofs, stream);
 }
 
 namespace {
 
-int validate(const occd_conv3d_args* a) {
-    if (!a || !a->in || !a->wpk || !a->out) return OCCD_EINVAL;
-    if (a->batch <= 0 || a->X <= 0 || a->Y <= 0 || a->Z <= 0 || a->cin <= 0 || a->cout <= 0) return OCCD_EINVAL;
-    if (a->kx <= 0 || a->ky <= 0 || a->kz <= 0 || a->sx <= 0 || a->sy <= 0 || a->sz <= 0) return OCCD_EINVAL;
-    if (a->Xo <= 0 || a->Yo <= 0 || a->Zo <= 0) return OCCD_EINVAL;
-    const int cin8 = (a->cin + 7) & ~7;
-    const int NTtot = (a->cout + 31) / 32;
-    // every staged float4 must be 16-byte aligned and inside the row
-    if ((a->in_cs & 3) || (a->in_coff & 3) || a->in_coff + cin8 > a->in_cs) return OCCD_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(a->in) & 15) || (reinterpret_cast<uintptr_t>(a->wpk) & 15)) return OCCD_EINVAL;
-    if (a->cout_store < a->cout || a->cout_store > NTtot * 32 || a->out_coff + a->cout_store > a->out_cs)
-        return OCCD_EINVAL;
-    // float4 epilogue: rows, slices and the stored width are multiples of 4 floats, buffers 16-byte aligned
-    if ((a->cout_store & 3) || (a->out_cs & 3) || (a->out_coff & 3) || (reinterpret_cast<uintptr_t>(a->out) & 15))
-        return OCCD_EINVAL;
-    if (a->res1 && ((a->res1_cs & 3) || (a->res1_coff & 3) || (reinterpret_cast<uintptr_t>(a->res1) & 15)))
-        return OCCD_EINVAL;
-    if (a->res2 && ((a->res2_cs & 3) || (a->res2_coff & 3) || (reinterpret_cast<uintptr_t>(a->res2) & 15)))
-        return OCCD_EINVAL;
-    if (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 15)) return OCCD_EINVAL;
-    if (a->res1 && a->res1_coff + a->cout_store > a->res1_cs) return OCCD_EINVAL;
-    if (a->res2 && a->res2_coff + a->cout_store > a->res2_cs) return OCCD_EINVAL;
-    if ((a->Xo - 1) * a->o_stride_x + a->o_off_x >= a->OX || (a->Yo - 1) * a->o_stride_y + a->o_off_y >= a->OY ||
-        (a->Zo - 1) * a->o_stride_z + a->o_off_z >= a->OZ)
-        return OCCD_EINVAL;
-    if (a->act_out != OCCD_ACT_NONE && a->act_out != OCCD_ACT_RELU && a->act_out != OCCD_ACT_RELU_PRE)
-        return OCCD_EINVAL;
-    return OCCD_OK;
-}
+constexpr occd::ConvStorage kStorageF32 = {4, 4, occd::kAnyActIn};
 
 // ---- variant choice: widest N tile the layer fills, then the largest M tile that fits LDS and still yields >= 2
 // workgroups per CU.  `copies` = launches' worth of workgroups that share the grid (batch x phases).
@@ -475,85 +427,36 @@ int choose(const occd_conv3d_args* a, long copies, Tiling* til) {
     return pick;
 }
 
-void fill_shared(const occd_conv3d_args* a, const Tiling& til, ConvP* p) {
-    const int cin8 = (a->cin + 7) & ~7;
-    p->in = a->in; p->bias = a->bias; p->res1 = a->res1; p->res2 = a->res2; p->out = a->out;
-    p->X = a->X; p->Y = a->Y; p->Z = a->Z; p->cin8 = cin8; p->in_cs = a->in_cs; p->in_coff = a->in_coff;
-    p->KTtot = cin8 / 8; p->NTtot = (a->cout + 31) / 32;
-    p->out_cs = a->out_cs; p->out_coff = a->out_coff;
-    p->res1_cs = a->res1_cs; p->res1_coff = a->res1_coff; p->res2_cs = a->res2_cs; p->res2_coff = a->res2_coff;
-    p->SX = a->sx; p->SY = a->sy; p->SZ = a->sz;
-    p->DX = a->dx; p->DY = a->dy; p->DZ = a->dz; p->PX = a->px; p->PY = a->py; p->PZ = a->pz;
-    p->Xo = a->Xo; p->Yo = a->Yo; p->Zo = a->Zo; p->OX = a->OX; p->OY = a->OY; p->OZ = a->OZ;
-    p->osx = a->o_stride_x; p->osy = a->o_stride_y; p->osz = a->o_stride_z;
-    p->act_in = a->act_in; p->act_out = a->act_out; p->cout_store = a->cout_store;
-    p->TY = til.TY; p->TZ = til.TZ;
-    p->ytiles = til.ytiles; p->ztiles = til.ztiles; p->nwg = (int)til.nwg;
-    p->div_tz = occd::make_fastdiv(til.TZ);
-    p->div_ztiles = occd::make_fastdiv(til.ztiles); p->div_ytiles = occd::make_fastdiv(til.ytiles);
-}
-
-void fill_phase(const occd_conv3d_args* a, const Tiling& til, PhaseP* ph) {
-    ph->wpk = a->wpk;
-    ph->KX = a->kx; ph->KY = a->ky; ph->KZ = a->kz;
-    ph->oox = a->o_off_x; ph->ooy = a->o_off_y; ph->ooz = a->o_off_z;
-    ph->YIN = til.YIN; ph->ZIN = til.ZIN;
-    ph->div_zin = occd::make_fastdiv(til.ZIN);
-}
-
-void cost(const occd_conv3d_args* a, double* flops, double* bytes, bool first) {
-    const double taps = (double)a->kx * a->ky * a->kz;
-    const double pos = (double)a->batch * a->Xo * a->Yo * a->Zo;
-    *flops += 2.0 * pos * taps * a->cin * a->cout;
-    *bytes += 4.0 * ((first ? (double)a->batch * a->X * a->Y * a->Z * a->cin : 0.0) +
-                     pos * a->cout * (1 + (a->res1 != nullptr) + (a->res2 != nullptr)) + taps * a->cin * a->cout);
+// n phases (n = 1: a plain convolution) as ONE launch
+int launch(const occd_conv3d_args* a, int n, const char* name, bool any_batch, hipStream_t stream) {
+    const occd_conv3d_args big = occd::conv3d_widest_phase(a, n);
+    Tiling til{};
+    const int pick = choose(&big, (long)a->batch * n, &til);
+    if (pick < 0) return OCCD_ENOMEM;
+    const Variant& v = kVariants[pick];
+    ConvP p{};
+    p.KTtot = ((a->cin + 7) & ~7) / 8;
+    const occd::ConvLaunch L = {name, v.WM * v.WN * v.KS * 64, (v.CK + 4) * sizeof(float) * v.KS, kStorageF32, 4.0, any_batch};
+    return occd::conv3d_launch(a, n, til, v.kern, p, L, [](PhaseP& ph, const occd_conv3d_args& ai) { ph.wpk = ai.wpk; }, stream);
 }
 
 }  // namespace
 
 extern "C" int occd_conv3d_fwd(const occd_conv3d_args* a, void* stream) {
-    const int bad = validate(a);
+    const int bad = occd::conv3d_validate(a, kStorageF32);
     if (bad != OCCD_OK) return bad;
-    {
-        const int taken = occd::try_conv3d_c32_persist(a, (hipStream_t)stream);
-        if (taken != 0) return taken > 0 ? OCCD_OK : taken;
-    }
-    Tiling til{};
-    const int pick = choose(a, a->batch, &til);
-    if (pick < 0) return OCCD_ENOMEM;
-    const Variant& v = kVariants[pick];
-    ConvP p{};
-    fill_shared(a, til, &p);
-    fill_phase(a, til, &p.ph[0]);
-    p.nph_log2 = 0;
-    p.ph_fast = 0;
-    if (til.lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(v.kern)) != OCCD_OK) return OCCD_ELAUNCH;
-    double flops = 0.0, bytes = 0.0;
-    cost(a, &flops, &bytes, true);
-    occd::ProfScope prof("conv3d_igemm", (hipStream_t)stream, flops, bytes);
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)til.nwg, (unsigned)a->batch, (unsigned)til.ngroups),
-                       dim3(v.WM * v.WN * v.KS * 64), til.lds, (hipStream_t)stream, p);
-    return occd::check_launch();
+    const int taken = occd::try_conv3d_c32_persist(a, (hipStream_t)stream);
+    if (taken != 0) return taken > 0 ? OCCD_OK : taken;
+    return launch(a, 1, "conv3d_igemm", true, (hipStream_t)stream);
 }
 
 // The sub-pixel phases of ONE transposed convolution (ConvTranspose3d(k3, s2, p1, op1) = 8 phase convolutions over tap
-// subsets that scatter to interleaved voxels, occdepth/models/modules.py:278-296) as ONE launch: the phase is the low bits
-// of blockIdx.y, every phase walks the same output tiling of the (shared) input volume, and the heaviest phase comes first in
-// dispatch order so that the single-tap ones fill the tail.  a[0..n): n in {1, 2, 4, 8} descriptors that may differ ONLY
-// in wpk, kx / ky / kz and o_off_*; anything else must match a[0].  Replaces n launches of occd_conv3d_fwd (24 per frame
-// at config 2, the smallest 16 us long).
+// subsets that scatter to interleaved voxels, occdepth/models/modules.py:278-296) as ONE launch (conv3d_launch,
+// conv3d_tile.h).  a[0..n): n in {1, 2, 4, 8} descriptors that may differ ONLY in wpk, kx / ky / kz and o_off_*; anything
+// else must match a[0].  Replaces n launches of occd_conv3d_fwd (24 per frame at config 2, the smallest 16 us long).
 extern "C" int occd_conv3d_fwd_phases(const occd_conv3d_args* a, int32_t n, void* stream) {
-    if (!a || (n != 1 && n != 2 && n != 4 && n != 8)) return OCCD_EINVAL;
-    int heavy = 0;
-    for (int i = 0; i < n; ++i) {
-        const int bad = validate(a + i);
-        if (bad != OCCD_OK) return bad;
-        occd_conv3d_args t = a[i];
-        t.wpk = a[0].wpk; t.kx = a[0].kx; t.ky = a[0].ky; t.kz = a[0].kz;
-        t.o_off_x = a[0].o_off_x; t.o_off_y = a[0].o_off_y; t.o_off_z = a[0].o_off_z;
-        if (memcmp(&t, &a[0], offsetof(occd_conv3d_args, tile_hint) + sizeof(int32_t)) != 0) return OCCD_EINVAL;
-        if (a[i].kx * a[i].ky * a[i].kz > a[heavy].kx * a[heavy].ky * a[heavy].kz) heavy = i;
-    }
+    const int bad = occd::conv3d_validate_phases(a, n, kStorageF32);
+    if (bad != OCCD_OK) return bad;
     if (a[0].cin <= 32 && n > 1) {             // (the <= 32-channel sliding-window kernels are single-phase: issue them one by one)
         for (int i = 0; i < n; ++i) {
             const int rc = occd_conv3d_fwd(a + i, stream);
@@ -561,43 +464,5 @@ extern "C" int occd_conv3d_fwd_phases(const occd_conv3d_args* a, int32_t n, void
         }
         return OCCD_OK;
     }
-    // one variant / output tiling for all phases: the one the heaviest phase would take with n x batch copies in the grid
-    occd_conv3d_args big = a[heavy];
-    for (int i = 0; i < n; ++i) {               // (slab extents: the largest ky / kz over the phases)
-        big.ky = a[i].ky > big.ky ? a[i].ky : big.ky;
-        big.kz = a[i].kz > big.kz ? a[i].kz : big.kz;
-    }
-    Tiling til{};
-    const int pick = choose(&big, (long)a[0].batch * n, &til);
-    if (pick < 0) return OCCD_ENOMEM;
-    const Variant& v = kVariants[pick];
-    const int NTtot = (a[0].cout + 31) / 32;
-    ConvP p{};
-    fill_shared(&a[0], til, &p);
-    int order[kMaxPhases];
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order, order + n, [&](int l, int r) {
-        return a[l].kx * a[l].ky * a[l].kz > a[r].kx * a[r].ky * a[r].kz;
-    });
-    double flops = 0.0, bytes = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const occd_conv3d_args* ai = a + order[i];
-        Tiling ti{};
-        if (!plan(ai, v, NTtot, &ti) || ti.TY != til.TY || ti.TZ != til.TZ || ti.lds > til.lds) return OCCD_EINVAL;
-        fill_phase(ai, ti, &p.ph[i]);
-        cost(ai, &flops, &bytes, i == 0);
-    }
-    p.nph_log2 = n == 1 ? 0 : n == 2 ? 1 : n == 4 ? 2 : 3;
-    // phase-major dispatch (all tiles of the heaviest phase first) is the default; the phases of a tile next to each other on
-    // one XCD (OCCD_PHASE_FAST=1) measured SLOWER: 64 -> 32 at 128x128x16 0.47 against 0.35 ms on K2, 0.36 against 0.34 on K2b
-    static const bool phase_fast = occd::env_flag("OCCD_PHASE_FAST", false);
-    p.ph_fast = phase_fast ? 1 : 0;
-    if (p.ph_fast) p.nwg = (int)(til.nwg * n);
-    if ((long)a[0].batch * n > 65535 || til.nwg * n >= (1L << 24)) return OCCD_EINVAL;
-    if (til.lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(v.kern)) != OCCD_OK) return OCCD_ELAUNCH;
-    occd::ProfScope prof("conv3d_igemm_phases", (hipStream_t)stream, flops, bytes);
-    hipLaunchKernelGGL(v.kern, p.ph_fast ? dim3((unsigned)(til.nwg * n), (unsigned)a[0].batch, (unsigned)til.ngroups)
-                                         : dim3((unsigned)til.nwg, (unsigned)(a[0].batch * n), (unsigned)til.ngroups),
-                       dim3(v.WM * v.WN * v.KS * 64), til.lds, (hipStream_t)stream, p);
-    return occd::check_launch();
+    return launch(a, n, "conv3d_igemm_phases", false, (hipStream_t)stream);
 }

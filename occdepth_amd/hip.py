@@ -162,14 +162,17 @@ def packed_weight_floats(cout, cin, taps):
     return n
 
 
-def pack_weights(w, scale=None, layout=0):
-    """w: (Cout, Cin, kx, ky, kz) [layout 0] / (K, N) row-major GEMM B operand [layout 2]."""
+def _weight_geometry(w, layout):
+    """(cout, cin, kernel) of a weight tensor: (Cout, Cin, kx, ky, kz), or [layout 2] a (K, N) row-major GEMM B operand."""
     if layout == 2:
         cin, cout = w.shape
-        k = (1, 1, 1)
-    else:
-        cout, cin = w.shape[0], w.shape[1]
-        k = tuple(w.shape[2:])
+        return cout, cin, (1, 1, 1)
+    return w.shape[0], w.shape[1], tuple(w.shape[2:])
+
+
+def pack_weights(w, scale=None, layout=0):
+    """w: (Cout, Cin, kx, ky, kz) [layout 0] / (K, N) row-major GEMM B operand [layout 2]."""
+    cout, cin, k = _weight_geometry(w, layout)
     w = w.contiguous()
     out = torch.empty(packed_weight_floats(cout, cin, k[0] * k[1] * k[2]), device=w.device, dtype=torch.float32)
     sc = scale.contiguous() if scale is not None else None
@@ -343,12 +346,7 @@ def _conv3d_bf16_pipe(mode, image_error, x, phases, bias, cout, out, merged=Fals
 def pack_weights_bf16(w, scale=None, layout=0, split3=False):
     """fp32 master weights -> the bf16 fragment image of K2b (shapes / layouts as `pack_weights`); split3: the three images
     hi | mid | lo of the 3-way split experiment (conv3d_bf16(..., split3=True))."""
-    if layout == 2:
-        cin, cout = w.shape
-        k = (1, 1, 1)
-    else:
-        cout, cin = w.shape[0], w.shape[1]
-        k = tuple(w.shape[2:])
+    cout, cin, k = _weight_geometry(w, layout)
     w = w.detach().float().contiguous()
     n = load().occd_packed_weight_bf16_elems(cout, cin, k[0] * k[1] * k[2])
     if n <= 0:
@@ -366,12 +364,7 @@ def pack_weights_f16x2(w, scale=None, layout=0):
     conv3d_bf16 / conv3d_phases(..., f16x2=True) for any other geometry): three fp16
     images hi | hs | lo of the per-channel power-of-two scaled weights plus the epilogue factors (a uint8 tensor of
     occd_packed_weight_f16x2_bytes bytes).  The weights must be finite."""
-    if layout == 2:
-        cin, cout = w.shape
-        k = (1, 1, 1)
-    else:
-        cout, cin = w.shape[0], w.shape[1]
-        k = tuple(w.shape[2:])
+    cout, cin, k = _weight_geometry(w, layout)
     w = w.detach().float().contiguous()
     n = load().occd_packed_weight_f16x2_bytes(cout, cin, k[0] * k[1] * k[2])
     if n <= 0:

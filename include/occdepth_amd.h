@@ -71,7 +71,9 @@ extern "C" {
  * 21: occd_wino_packed_f16x2_bytes, occd_wino_pack_weights_f16x2, occd_wino_conv3x3_f16x2_fwd (K10h, the fused Winograd
  *     3x3 convolution on the two-term fp16 split)
  * 22: occd_confusion_region, occd_confusion_regions_args, occd_ssc_confusion_regions (SSC confusion counts by region --
- *     index box x camera FOV x byte masks, shared or per frame -- in one pass) */
+ *     index box x camera FOV x byte masks, shared or per frame -- in one pass); added since without a change of any
+ *     struct or prototype: occd_gemm_f16x2_packed_elems, occd_gemm_f16x2_pack and occd_gemm_args.pre = OCCD_GEMM_PRE_F16X2
+ *     (the two-term fp16 split of the 2-D GEMMs that read pre-split weights: K16p, K21, K16 on the A image) */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -286,6 +288,7 @@ int occd_rows_gemm_pack(const float* w, float* wpk, int32_t K, int32_t N, int32_
 #define OCCD_GEMM_ACT_NONE 0
 #define OCCD_GEMM_ACT_SWISH 1
 #define OCCD_GEMM_ACT_LEAKY 2
+#define OCCD_GEMM_PRE_F16X2 4 /* occd_gemm_args.pre: A = the image of occd_gemm_f16x2_pack (two-term fp16 split, below) */
 typedef struct occd_gemm_args {
     const float* A;
     const float* B;
@@ -297,7 +300,8 @@ typedef struct occd_gemm_args {
     int32_t act;
     float slope;
     int32_t tile_hint;
-    int32_t pre;                           /* 0: A, B float32; 1: A = occd_gemm_x3_pack(role 0) image; 2: B = role-1 image */
+    int32_t pre;                           /* 0: A, B float32; 1: A = occd_gemm_x3_pack(role 0) image; 2: B = role-1 image;
+                                              3: float32 operands rounded to one bf16 term; OCCD_GEMM_PRE_F16X2: see below   */
     const float* res;                      /* optional (ABI 9): C += res[b][m][n] after bias / activation, laid out like C
                                               (ldc, stride_c): the skip connection of an MBConv project convolution      */
     const float* scale_k;                  /* optional (ABI 9): (batch, K) floats, B[b][k][:] is multiplied by scale_k[b][k]
@@ -341,6 +345,21 @@ int32_t occd_gemm_f32x3_nt_splits(int32_t M, int32_t N, int32_t K, int32_t batch
 int64_t occd_gemm_x3_packed_elems(int32_t rows, int32_t K);
 int occd_gemm_x3_pack(const float* w, void* out, int32_t rows, int32_t K, int64_t ld, int32_t role, int32_t batch,
                       int64_t in_stride, void* stream);
+/* The two-term fp16 split ("f16x2") of the GEMMs that read pre-split weights -- K16p, K21 and K16 on the A image -- with the
+ * numerics of the head convolutions (OCCD_CONV_F16X2_HEAD): an A operand (rows x K, k contiguous, ld >= K) is packed once as
+ * w'[m][k] = 2^k[m] w[m][k] (k[m]: the row's max |w'| in [2^13, 2^14); an all-zero row: k = 0), hi = fp16(w'),
+ * lo = fp16(w' - hi), in the fragment order of the role-0 image above with two terms, [row tile 32][k16][hi, lo][lane][8],
+ * followed by one float per row of the padded row tiles, fac[m] = 2^-(k[m] + 1).  occd_gemm_f16x2_packed_elems: 16-bit
+ * elements per batch item, factors included (a multiple of 64); `out` 16-byte aligned.  occd_gemm_f16x2_pack returns
+ * OCCD_EINVAL when a weight is not finite (it reads the factors back: a set-up call, not for a captured stream); the caller
+ * keeps the three-term image.  A launch with pre = OCCD_GEMM_PRE_F16X2 (occd_gemm_f32x3 with tile_hint 0 .. 5 or 8, or
+ * occd_gemm_f32x3_splitk; stride_a in 16-bit elements; no act_a, no bias_n) stages B as 2 x (after scale_k, in float32),
+ * split hi + 2^-11 lo' in fp16, issues three v_mfma_f32_32x32x16_f16 per 16-k step -- (lo_a, hi_b), (2^-11 hi_a, lo'_b),
+ * (hi_a, hi_b) -- and stores act(fac[m] * acc + bias[m]) (+ res).  Finite |B| >= 32760 overflow to non-finite outputs in
+ * the columns they reach; routes and plans are those of pre = 1.                                */
+int64_t occd_gemm_f16x2_packed_elems(int32_t rows, int32_t K);
+int occd_gemm_f16x2_pack(const float* w, void* out, int32_t rows, int32_t K, int64_t ld, int32_t batch, int64_t in_stride,
+                         void* stream);
 
 /* The eval lift without its tables (SURVEY 8(f) N2 fused into K1b): the kernel projects every voxel
  * centroid itself (the arithmetic of occd_project_voxels: occdepth/data/utils/helpers.py:94-169, integer-exact), samples the

@@ -11,6 +11,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;   // what ds_read_b64_tr_b16 takes (see tr_frag_bf16x8)
@@ -82,6 +83,20 @@ __device__ __forceinline__ void split2_f16x8(f32x4 a, f32x4 b, u32x4& hi, u32x4&
     }
     hi = __builtin_bit_cast(u32x4, h);
     lo = __builtin_bit_cast(u32x4, l);
+}
+
+// (the same split of four values: the B panels of the 2-D GEMMs are staged in 4-column chunks)
+__device__ __forceinline__ void split2_f16x4(f32x4 a, u32x2& hi, u32x2& lo) {
+    const float s = (float)(1 << kF2XExp);
+    float x[4] = {a.x * s, a.y * s, a.z * s, a.w * s};
+    f16x4 h, l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        h[j] = (_Float16)x[j];
+        l[j] = (_Float16)((x[j] - (float)h[j]) * 2048.f);
+    }
+    hi = __builtin_bit_cast(u32x2, h);
+    lo = __builtin_bit_cast(u32x2, l);
 }
 
 // 8 floats -> 8 bf16 (round-to-nearest-even), 16 bytes

@@ -21,6 +21,7 @@
 // (through the tap-GEMM / Winograd-domain forms of this repo's unet2d.py) and the geffnet MBConv expand convolutions.
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 #include "device.h"
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // rows of odd length: dword-aligned 16-byte loads
@@ -44,6 +45,8 @@ struct GemmP {
     int mtiles, ntiles, n_fast;         // n_fast: the N-tile index runs fastest in the block order (A tile reused), else M
     int mr_tiles;                       // K16p: 32-row tiles per row range (mtiles = the number of ranges)
     unsigned nwg;
+    const float* fac = nullptr;         // f16x2 image (pre = 4): 2^-(k[m] + kF2XExp) per row of the FIRST batch item's image
+    long s_fac = 0;                     // floats between the batch items' factors (0 = shared image)
 };
 
 constexpr int kARow = 208;              // bytes per A row in LDS: 3 x 64 B (32 k of one term) + 16 B pad
@@ -55,7 +58,10 @@ constexpr int kARow = 208;              // bytes per A row in LDS: 3 x 64 B (32 
 // no split arithmetic, no ds_write for that operand); 2 = B is (role 1 image: [column tile 32][k16][term][lane][8]).
 // TERMS: 3 = the split (float32-level accuracy); 1 = plain bf16 operands, ONE MFMA per 16-k step (the bf16 training mode,
 // BASELINE configs[3]: "bf16 MFMA, fp32 storage and accumulate" like K2b): same staging and layout, only the hi plane is
-// written and read.
+// written and read; 2 = the two-term fp16 split (PRE = 1 only: A is the image of occd_gemm_f16x2_pack, [row tile 32][k16][hi, lo]
+// [lane][8 fp16] of w' = 2^k[m] w; B is staged as 2^kF2XExp x = hi + 2^-11 lo' in TWO fp16 planes; three
+// v_mfma_f32_32x32x16_f16 per 16-k step -- (lo_a, hi_b), (hs_a, lo'_b), (hi_a, hi_b) with hs = 2^-11 hi formed in registers -- and
+// the epilogue multiplies by fac[m] = 2^-(k[m] + kF2XExp) ahead of the bias: the numerics of K2s3h / K2bh, conv3d_c32p.hip).
 // KS > 1: in-workgroup split-K (the long-K / few-pixel project convolutions: 96 ... 230 output tiles for 256 CUs and K = 960 ...
 // 3840).  The KS wave groups of a workgroup own the same output tile, take interleaved 32-k steps (each group with its own LDS
 // stage), and their accumulators meet in LDS once, after the loop; group 0 runs the epilogue.  16 waves per CU instead of 4:
@@ -63,6 +69,8 @@ constexpr int kARow = 208;              // bytes per A row in LDS: 3 x 64 B (32 
 template <int MT, int NT, int WM, int WN, int PRE, int TERMS = 3, int KS = 1>
 __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p) {
     static_assert(KS == 1 || PRE == 0, "split-K stages both operands");
+    static_assert(TERMS != 2 || PRE == 1, "the fp16 split reads A from its pre-scaled image");
+    constexpr int NPL = TERMS == 2 ? 2 : 3;         // term planes of the B tile in LDS / terms per record of the A image
     constexpr int NTH = WM * WN * 64, TM = WM * MT * 32, TN = WN * NT * 32;
     constexpr int SB = TN * 2 + 64;                 // bytes per B row (one k, one term): = 64 mod 128
     constexpr int BTERM = 32 * SB;                  // bytes per term of the B tile
@@ -76,7 +84,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
     // barriers are).  So 1 everywhere; the loop keeps the general form.
     constexpr int PF = 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char glds[];
-    constexpr int STAGE = (PRE == 1 ? 0 : TM * kARow) + (PRE == 2 ? 0 : 3 * BTERM);   // LDS bytes of one K group
+    constexpr int STAGE = (PRE == 1 ? 0 : TM * kARow) + (PRE == 2 ? 0 : NPL * BTERM);   // LDS bytes of one K group
     const int kg = KS == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x / NTH);   // K group of this wave
     unsigned char* const lA = glds + kg * STAGE;
     unsigned char* const lB = lA + (PRE == 1 ? 0 : TM * kARow);
@@ -184,6 +192,12 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
                 v.w = sh == 0 ? w.w : 0.f;
             }
             u32x2 hi, mid, lo;
+            if (TERMS == 2) {
+                split2_f16x4(v, hi, lo);
+                *(u32x2*)(lB + b_dst[i]) = hi;
+                *(u32x2*)(lB + BTERM + b_dst[i]) = lo;
+                continue;
+            }
             split3_bf16x4(v, hi, mid, lo);
             *(u32x2*)(lB + b_dst[i]) = hi;
             if (TERMS == 3) {
@@ -213,6 +227,9 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
 #define OCCD_GX3(WT, XT)                                                                                              \
     _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[mt][nt] =  \
         __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[mt][WT]), bf[nt][XT], acc[mt][nt], 0, 0, 0)
+#define OCCD_GX3H(W, XT)                                                                                              \
+    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[mt][nt] =  \
+        __builtin_amdgcn_mfma_f32_32x32x16_f16(W, __builtin_bit_cast(f16x8, bf[nt][XT]), acc[mt][nt], 0, 0, 0)
 
     // pre-split operand: fragment records of this wave's tiles, one K16 sub-step ahead of the MFMAs
     const int K16tot = (p.K + 15) >> 4;
@@ -221,7 +238,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
         const u32x4* base = reinterpret_cast<const u32x4*>(p.A) + (size_t)bz * p.sA + lane;       // sA: u32x4 per batch item
         const int last = (p.M + 31) / 32 - 1;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) pk[mt] = base + (size_t)min(m0 / 32 + wm * MT + mt, last) * K16tot * 192;
+        for (int mt = 0; mt < MT; ++mt) pk[mt] = base + (size_t)min(m0 / 32 + wm * MT + mt, last) * K16tot * (64 * NPL);
     } else if (PRE == 2) {
         const u32x4* base = reinterpret_cast<const u32x4*>(p.B) + (size_t)bz * p.sB + lane;
         const int last = (p.N + 31) / 32 - 1;
@@ -233,13 +250,13 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
     // into it -- a full step (two barriers, 48 MFMAs per wave on the 256 x 128 tile) ahead.  (Round 4 requested ONE sub-step ahead
     // into a single set; its ISA waits for the fragments a few instructions after requesting them: vmcnt(0) in front of every
     // sub-step's MFMAs -- an L2 round trip per 16 k, which is why the pre-split form never beat splitting on the fly.)
-    u32x4 pn[2][NPK][3];
+    u32x4 pn[2][NPK][NPL];
     auto fetch_pk = [&](int slot, int k16) {
         const int kc = min(k16, K16tot - 1);      // (a step past K multiplies the other operand's zeros)
 #pragma unroll
         for (int i = 0; i < NPK; ++i)
 #pragma unroll
-            for (int t = 0; t < 3; ++t) pn[slot][i][t] = pk[i][(kc * 3 + t) * 64];
+            for (int t = 0; t < NPL; ++t) pn[slot][i][t] = pk[i][(kc * NPL + t) * 64];
     };
 
     const int ksteps = (p.K + 31) >> 5;
@@ -274,7 +291,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int t = 0; t < 3; ++t) af[mt][t] = pn[ks][mt][t];
+                    for (int t = 0; t < NPL; ++t) af[mt][t] = pn[ks][mt][t];
             } else {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
@@ -293,6 +310,15 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
                     for (int t = 0; t < TERMS; ++t) bf[nt][t] = tr_frag_bf16x8(lB + t * BTERM + b_lane[nt] + ks * 16 * SB, 4 * SB);
             }
             if (PRE != 0) fetch_pk(ks, s * 2 + ks + 2);
+            if (TERMS == 2) {                     // smallest terms first: (lo_a, hi_b), (hs_a, lo'_b), (hi_a, hi_b)
+                f16x8 ahs[MT];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) ahs[mt] = __builtin_bit_cast(f16x8, af[mt][0]) * (_Float16)(1.f / 2048.f);
+                OCCD_GX3H(__builtin_bit_cast(f16x8, af[mt][TERMS == 2 ? 1 : 0]), 0);
+                OCCD_GX3H(ahs[mt], TERMS == 2 ? 1 : 0);
+                OCCD_GX3H(__builtin_bit_cast(f16x8, af[mt][0]), 0);
+                continue;
+            }
             if (TERMS == 3) {
                 OCCD_GX3(1, 1);
                 OCCD_GX3(0, TERMS == 3 ? 2 : 0);
@@ -308,6 +334,7 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
     if ((p.K & 31) == 0 && n0 + TN <= p.N) kloop(std::true_type{});
     else kloop(std::false_type{});
 #undef OCCD_GX3
+#undef OCCD_GX3H
 
     if (KS > 1) {
         // sum the K groups' accumulators through LDS (the stages are dead after the barrier), group 0 stores
@@ -335,6 +362,25 @@ __global__ void __launch_bounds__(WM* WN * 64 * KS) gemm_x3_kernel(const GemmP p
                         acc[mt][nt][r] += red[((((g - 1) * WM * WN + wave) * MT + mt) * NT + nt) * 1024 + r * 64 + lane];
     }
 
+    // f16x2: acc *= fac[m] = 2^-(k[m] + kF2XExp) (exact), ahead of everything the epilogue adds.  A pass of its own, fenced: the 16
+    // factors of a row tile (registers r <-> rows (r & 3) + 8 (r >> 2) + 4 h: four 16-byte loads, the factors are padded to whole row
+    // tiles) are dead before the epilogue's bias loads and row addresses go live.
+    if (TERMS == 2) {
+        const float* const Fb = p.fac + (size_t)bz * p.s_fac;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int mb = m0 + (wm * MT + mt) * 32 + 4 * h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 f4 = *(const f32x4*)(Fb + min(mb + 8 * g, ((p.M + 31) & ~31) - 4));      // (rows >= M: never stored)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[mt][nt][4 * g + i] *= f4[i];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // bias along N (ABI 13: one value per COLUMN -- a lane is a column, so one load per tile column; rows-times-weights
     // products whose rows are voxels / pixels: the CRP's relation-logit convolutions), added ahead of the activation
     if (p.bias_n != nullptr) {                                  // (uniform branch)
@@ -636,7 +682,11 @@ __global__ void __launch_bounds__(512, 2) gemm_x3_ws_kernel(const GemmP p) {
 // LDS bytes per k of a panel of NT x 32 columns: [hi | mid | lo] x (64 NT) B, + 64 B for NT = 2: 192 / 448, both = 64 mod 128
 // (conflict-free transposing reads).  NT = 1 (32 columns): twice the panels for the few-pixel stages (468 / 1848 pixels), K up
 // to 848, at twice the weight-fragment traffic per MFMA -- which a launch that small does not notice.
-constexpr int panel_row_bytes(int nt) { return 3 * 64 * nt + (nt == 1 ? 0 : 64); }
+// SPLIT = 2 (the f16x2 image, pre = 4; numerics above gemm_x3_kernel): [hi | lo'] x (64 NT) B + 64 B for EITHER width -- 192 / 320,
+// again 64 mod 128.  The 32-column row keeps its 192 bytes (same K limit, 848); the 64-column row shrinks from 448 to 320.
+constexpr int panel_row_bytes(int nt, int split = 3) {
+    return split == 2 ? 2 * 64 * nt + 64 : 3 * 64 * nt + (nt == 1 ? 0 : 64);
+}
 // Development probe (tools/panel_timeline.cpp builds this file with -DOCCD_PANEL_TIMELINE; never in libocc_hip.so): the shader
 // clock of every wave of ONE workgroup at the phase boundaries of the kernel below.
 #ifdef OCCD_PANEL_TIMELINE
@@ -651,9 +701,10 @@ __device__ int g_panel_probe_wg = 0;
 #define OCCD_TL(idx) do { } while (0)
 #endif
 constexpr int kPanelPass = 6;                         // float4 loads in flight per thread while the panel is staged
-template <int MT, int NT, int PD>
+template <int MT, int NT, int PD, int SPLIT = 3>
 __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
-    constexpr int TN = 32 * NT, SB = panel_row_bytes(NT), TB = 64 * NT, C4 = TN / 4;   // TB: bytes of one term's columns in a row
+    constexpr int TN = 32 * NT, SB = panel_row_bytes(NT, SPLIT), TB = 64 * NT, C4 = TN / 4;   // TB: bytes of one term's columns in a row
+    constexpr int NPL = SPLIT;                            // terms per weight record / term planes of a panel row
     extern __shared__ __attribute__((aligned(16))) unsigned char glds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -673,16 +724,16 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
     // first PD steps are requested before the panel is staged
     const u32x4* const Abase = reinterpret_cast<const u32x4*>(p.A) + (size_t)bz * p.sA + lane;
     const u32x4* pk[MT];
-    u32x4 an[PD][MT][3];
+    u32x4 an[PD][MT][NPL];
     auto fetch_a = [&](int d, int k16) {
 #pragma unroll
         for (int j = 0; j < MT; ++j)
 #pragma unroll
-            for (int t = 0; t < 3; ++t) an[d][j][t] = pk[j][(k16 * 3 + t) * 64];
+            for (int t = 0; t < NPL; ++t) an[d][j][t] = pk[j][(k16 * NPL + t) * 64];
     };
     auto first_a = [&](int tb) {
 #pragma unroll
-        for (int j = 0; j < MT; ++j) pk[j] = Abase + (size_t)min(tb + j, tiles_all - 1) * K16tot * 192;
+        for (int j = 0; j < MT; ++j) pk[j] = Abase + (size_t)min(tb + j, tiles_all - 1) * K16tot * (64 * NPL);
 #pragma unroll
         for (int d = 0; d < PD; ++d)
             fetch_a(d, min(d, K16tot - 1));
@@ -722,21 +773,28 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
                     w.w = sh == 0 ? u.w : 0.f;
                 }
                 u32x2 hi, mid, lo;
-                split3_bf16x4(w, hi, mid, lo);
                 unsigned char* dst = glds + k * SB + c4 * 8;
-                *(u32x2*)dst = hi;
-                *(u32x2*)(dst + TB) = mid;
-                *(u32x2*)(dst + 2 * TB) = lo;
+                if (SPLIT == 2) {
+                    split2_f16x4(w, hi, lo);
+                    *(u32x2*)dst = hi;
+                    *(u32x2*)(dst + TB) = lo;
+                } else {
+                    split3_bf16x4(w, hi, mid, lo);
+                    *(u32x2*)dst = hi;
+                    *(u32x2*)(dst + TB) = mid;
+                    *(u32x2*)(dst + 2 * TB) = lo;
+                }
             }
         }
     }
-    OCCD_TL(3);                                            // panel split and written (this wave's share)
+    OCCD_TL(3);                                           // panel split and written (this wave's share)
     __syncthreads();
     OCCD_TL(4);                                            // panel complete
     int b_lane[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) b_lane[nt] = (8 * h + (i16 >> 2)) * SB + (nt * 32 + 16 * g1 + 4 * (i16 & 3)) * 2;
     float* const Cb = p.C + (size_t)bz * p.sC;
+    const float* const Fb = SPLIT == 2 ? p.fac + (size_t)bz * p.s_fac : nullptr;
 
     for (int tb = t0 + wave * MT; tb < t1; tb += 8 * MT) {
         f32x16 acc[MT][NT];
@@ -746,17 +804,20 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][nt][r] = 0.f;
-        bf16x8 bn[NT][3];
+        bf16x8 bn[NT][NPL];
         auto fetch_b = [&](int k16) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
+                for (int t = 0; t < NPL; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
         };
         fetch_b(0);
 #define OCCD_GP(WT, XT)                                                                                              \
     _Pragma("unroll") for (int j = 0; j < MT; ++j) _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[j][nt] =    \
         __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[j][WT]), bf[nt][XT], acc[j][nt], 0, 0, 0)
+#define OCCD_GPH(W, XT)                                                                                              \
+    _Pragma("unroll") for (int j = 0; j < MT; ++j) _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[j][nt] =    \
+        __builtin_amdgcn_mfma_f32_32x32x16_f16(W, __builtin_bit_cast(f16x8, bf[nt][XT]), acc[j][nt], 0, 0, 0)
         // One 16-k step on fragment set d (a compile-time index).  Requests are UNCONDITIONAL and come from clamped addresses (the
         // last steps re-read the last fragments): behind a branch the compiler cannot count the loads in flight and waits for
         // vmcnt(0) at the join -- every step then pays a full L2 round trip however deep the prefetch (tools/panel_timeline.cpp:
@@ -765,7 +826,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
             u32x4 af[MT][3];
             bf16x8 bf[NT][3];
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
+            for (int t = 0; t < NPL; ++t) {
 #pragma unroll
                 for (int j = 0; j < MT; ++j) af[j][t] = an[d][j][t];
 #pragma unroll
@@ -774,12 +835,21 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
             if (tb == t0 + wave * MT) OCCD_TL(8 + k16);      // step k16 of the first row tile: operands in registers
             if (more_a) fetch_a(d, min(k16 + PD, K16tot - 1));
             fetch_b(min(k16 + 1, K16tot - 1));
-            OCCD_GP(1, 1);
-            OCCD_GP(0, 2);
-            OCCD_GP(2, 0);
-            OCCD_GP(0, 1);
-            OCCD_GP(1, 0);
-            OCCD_GP(0, 0);
+            if constexpr (SPLIT == 2) {                      // smallest terms first: (lo_a, hi_b), (hs_a, lo'_b), (hi_a, hi_b)
+                f16x8 ahs[MT];
+#pragma unroll
+                for (int j = 0; j < MT; ++j) ahs[j] = __builtin_bit_cast(f16x8, af[j][0]) * (_Float16)(1.f / 2048.f);
+                OCCD_GPH(__builtin_bit_cast(f16x8, af[j][1]), 0);
+                OCCD_GPH(ahs[j], 1);
+                OCCD_GPH(__builtin_bit_cast(f16x8, af[j][0]), 0);
+            } else {
+                OCCD_GP(1, 1);
+                OCCD_GP(0, 2);
+                OCCD_GP(2, 0);
+                OCCD_GP(0, 1);
+                OCCD_GP(1, 0);
+                OCCD_GP(0, 0);
+            }
         };
         // main loop: whole groups of PD steps, NO branch inside the body (exact vmcnt counts); then the < PD remaining steps,
         // whose fragments are already on their way
@@ -792,10 +862,28 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_kernel(const GemmP p) {
         for (int d = 0; d < PD - 1; ++d)
             if (k0 + d < K16tot) step(k0 + d, d, false);
 #undef OCCD_GP
+#undef OCCD_GPH
         // the next row tile's first fragments go out BEFORE this tile's stores (loads return in order among loads; queued behind
         // the stores they would wait for them to drain)
         if (tb + 8 * MT < t1) first_a(tb + 8 * MT);
         if (tb == t0 + wave * MT) OCCD_TL(5);              // K loop of the first row tile issued
+        // f16x2: acc *= fac[m] = 2^-(k[m] + kF2XExp) (exact) in a fenced pass of its own, as in K16 (row tiles < t1 only: their
+        // factors exist, four 16-byte loads per tile)
+        if (SPLIT == 2) {
+#pragma unroll
+            for (int j = 0; j < MT; ++j) {
+                const int mb = min(tb + j, tiles_all - 1) * 32 + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 f4 = *(const f32x4*)(Fb + mb + 8 * g);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[j][nt][4 * g + i] *= f4[i];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // epilogue of this tile set: lane -> column, registers -> rows (as K16)
         auto store_all = [&](auto has_bias, auto act_sel) {
             constexpr bool BIAS = decltype(has_bias)::value;
@@ -856,10 +944,13 @@ struct GemmSKP {
     long ld_ws, z_stride, b_stride;     // floats: row pitch (multiple of 32), between K chunks, between batch items
 };
 
-template <int NT, int PD>
+// SPLIT = 2: the f16x2 image (pre = 4).  The partial tiles stay in the scaled domain; `splitk_reduce_kernel` multiplies the SUM
+// by fac[m] -- once per output, where a factor at the partial store would cost nz multiplications (both are exact).
+template <int NT, int PD, int SPLIT = 3>
 __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP q) {
     const GemmP& p = q.g;
-    constexpr int TN = 32 * NT, SB = panel_row_bytes(NT), TB = 64 * NT, C4 = TN / 4;
+    constexpr int TN = 32 * NT, SB = panel_row_bytes(NT, SPLIT), TB = 64 * NT, C4 = TN / 4;
+    constexpr int NPL = SPLIT;
     extern __shared__ __attribute__((aligned(16))) unsigned char glds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -878,15 +969,15 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
     const int tiles_all = (p.M + 31) >> 5;
     const int t0 = mr_i * p.mr_tiles, t1 = min(t0 + p.mr_tiles, tiles_all);
 
-    const u32x4* const Abase = reinterpret_cast<const u32x4*>(p.A) + (size_t)bz * p.sA + (size_t)ks0 * 192 + lane;
+    const u32x4* const Abase = reinterpret_cast<const u32x4*>(p.A) + (size_t)bz * p.sA + (size_t)ks0 * (64 * NPL) + lane;
     const u32x4* pk;
-    u32x4 an[PD][3];
+    u32x4 an[PD][NPL];
     auto fetch_a = [&](int d, int k16) {
 #pragma unroll
-        for (int t = 0; t < 3; ++t) an[d][t] = pk[(k16 * 3 + t) * 64];
+        for (int t = 0; t < NPL; ++t) an[d][t] = pk[(k16 * NPL + t) * 64];
     };
     auto first_a = [&](int tb) {
-        pk = Abase + (size_t)min(tb, tiles_all - 1) * K16tot * 192;
+        pk = Abase + (size_t)min(tb, tiles_all - 1) * K16tot * (64 * NPL);
 #pragma unroll
         for (int d = 0; d < PD; ++d) fetch_a(d, min(d, nst - 1));
     };
@@ -925,11 +1016,17 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
                     w.w = sh == 0 ? u.w : 0.f;
                 }
                 u32x2 hi, mid, lo;
-                split3_bf16x4(w, hi, mid, lo);
                 unsigned char* dst = glds + k * SB + c4 * 8;
-                *(u32x2*)dst = hi;
-                *(u32x2*)(dst + TB) = mid;
-                *(u32x2*)(dst + 2 * TB) = lo;
+                if (SPLIT == 2) {
+                    split2_f16x4(w, hi, lo);
+                    *(u32x2*)dst = hi;
+                    *(u32x2*)(dst + TB) = lo;
+                } else {
+                    split3_bf16x4(w, hi, mid, lo);
+                    *(u32x2*)dst = hi;
+                    *(u32x2*)(dst + TB) = mid;
+                    *(u32x2*)(dst + 2 * TB) = lo;
+                }
             }
         }
     }
@@ -945,35 +1042,45 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-        bf16x8 bn[NT][3];
+        bf16x8 bn[NT][NPL];
         auto fetch_b = [&](int k16) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
+                for (int t = 0; t < NPL; ++t) bn[nt][t] = tr_frag_bf16x8(glds + t * TB + b_lane[nt] + k16 * 16 * SB, 4 * SB);
         };
         fetch_b(0);
 #define OCCD_GP(WT, XT)                                                                                              \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[nt] =                                                      \
         __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[WT]), bf[nt][XT], acc[nt], 0, 0, 0)
+#define OCCD_GPH(W, XT)                                                                                              \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) acc[nt] =                                                      \
+        __builtin_amdgcn_mfma_f32_32x32x16_f16(W, __builtin_bit_cast(f16x8, bf[nt][XT]), acc[nt], 0, 0, 0)
         // (requests unconditional from clamped steps, branch-free groups of PD steps: see K16p)
         auto step = [&](int k16, int d, bool more_a) {
             u32x4 af[3];
             bf16x8 bf[NT][3];
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
+            for (int t = 0; t < NPL; ++t) {
                 af[t] = an[d][t];
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) bf[nt][t] = bn[nt][t];
             }
             if (more_a) fetch_a(d, min(k16 + PD, nst - 1));
             fetch_b(min(k16 + 1, nst - 1));
-            OCCD_GP(1, 1);
-            OCCD_GP(0, 2);
-            OCCD_GP(2, 0);
-            OCCD_GP(0, 1);
-            OCCD_GP(1, 0);
-            OCCD_GP(0, 0);
+            if constexpr (SPLIT == 2) {                      // (lo_a, hi_b), (hs_a, lo'_b), (hi_a, hi_b)
+                const f16x8 ahs = __builtin_bit_cast(f16x8, af[0]) * (_Float16)(1.f / 2048.f);
+                OCCD_GPH(__builtin_bit_cast(f16x8, af[1]), 0);
+                OCCD_GPH(ahs, 1);
+                OCCD_GPH(__builtin_bit_cast(f16x8, af[0]), 0);
+            } else {
+                OCCD_GP(1, 1);
+                OCCD_GP(0, 2);
+                OCCD_GP(2, 0);
+                OCCD_GP(0, 1);
+                OCCD_GP(1, 0);
+                OCCD_GP(0, 0);
+            }
         };
         int k0 = 0;
         for (; k0 + PD <= nst; k0 += PD) {
@@ -984,6 +1091,7 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
         for (int d = 0; d < PD - 1; ++d)
             if (k0 + d < nst) step(k0 + d, d, false);
 #undef OCCD_GP
+#undef OCCD_GPH
         if (tb + 8 < t1) first_a(tb + 8);
         // partial tile: lane -> column, registers -> rows; the workspace rows are 128-byte aligned (ld_ws % 32 == 0)
         const int mb = tb * 32 + 4 * h;
@@ -1000,11 +1108,13 @@ __global__ void __launch_bounds__(512) gemm_x3_panel_splitk_kernel(const GemmSKP
     }
 }
 
-// out[b][m][n] = act(sum_z ws[b][z][m][n] + bias[m]) + res[b][m][n]; z in index order.  One thread = 4 consecutive n.
+// out[b][m][n] = act(fac[m] * sum_z ws[b][z][m][n] + bias[m]) + res[b][m][n]; z in index order; fac: the row factors of an f16x2
+// weight image, or NULL (bf16x3: no factor).  One thread = 4 consecutive n.
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out,
                                                             const float* __restrict__ bias, const float* __restrict__ res,
                                                             int M, int N, int nz, long ld_ws, long z_stride, long b_stride,
-                                                            long ldc, long sC, int act, float slope, int vec_ok) {
+                                                            long ldc, long sC, int act, float slope, int vec_ok,
+                                                            const float* __restrict__ fac) {
     const int n4 = (N + 3) >> 2;
     const long item = (long)blockIdx.x * 256 + threadIdx.x;
     if (item >= (long)M * n4) return;
@@ -1013,6 +1123,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
     const float* src = ws + (size_t)b * b_stride + (size_t)m * ld_ws + n;
     f32x4 s = *(const f32x4*)src;                               // (the pad columns of the workspace rows exist: ld_ws >= N rounded to 32)
     for (int z = 1; z < nz; ++z) s += *(const f32x4*)(src + (size_t)z * z_stride);
+    if (fac != nullptr) s *= fac[m];                            // 2^-(k[m] + kF2XExp): exact
     if (bias != nullptr) s += bias[m];
     float v[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
@@ -1182,11 +1293,12 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_x3_nt_kernel(const GemmP p) 
 
 struct VariantG {
     int MT, NT, WM, WN;
-    void (*kern[4])(const GemmP);     // [pre 0 / 1 / 2] with the split; [3] = float32 operands rounded to ONE bf16 term
+    void (*kern[5])(const GemmP);     // [pre 0 / 1 / 2] with the split; [3] = float32 operands rounded to ONE bf16 term;
+                                      // [4] = A from the f16x2 image, the two-term fp16 split
 };
 #define OCCD_VARIANT_G(MT, NT, WM, WN) \
     VariantG{MT, NT, WM, WN, {gemm_x3_kernel<MT, NT, WM, WN, 0>, gemm_x3_kernel<MT, NT, WM, WN, 1>, gemm_x3_kernel<MT, NT, WM, WN, 2>, \
-                              gemm_x3_kernel<MT, NT, WM, WN, 0, 1>}}
+                              gemm_x3_kernel<MT, NT, WM, WN, 0, 1>, gemm_x3_kernel<MT, NT, WM, WN, 1, 2>}}
 const VariantG kVariantsG[] = {
     OCCD_VARIANT_G(2, 2, 4, 2),   // 0: 256 x 128, 512 threads
     OCCD_VARIANT_G(2, 2, 2, 2),   // 1: 128 x 128, 256 threads
@@ -1221,7 +1333,98 @@ __global__ void gemm_x3_pack_kernel(const float* __restrict__ w, uint16_t* __res
     dst[1024] = __builtin_bit_cast(uint16_t, lo);
 }
 
+// The f16x2 image of an A operand: the fragment order above with two fp16 terms, [row tile 32][k16][hi, lo][lane][8], of
+// w'[m][k] = 2^k[m] w[m][k] -- k[m] puts the row's max |w'| into [2^13, 2^14); an all-zero row keeps k = 0 -- followed by one
+// float per row of the padded row tiles, fac[m] = 2^-(k[m] + kF2XExp): the scheme of occd_pack_weights_f16x2
+// (csrc/conv3d_bf16.hip) and wino_pack_f16x2_kernel, per ROW of a GEMM.  One 64-thread block per row finds the scale; a row with
+// a non-finite weight is marked with a NaN factor, which the entry point reads back.
+__global__ void __launch_bounds__(64) gemm_f16x2_scale_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int rows,
+                                                              int K, long ld, long in_stride, long out_stride, long img) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const float* src = w + (size_t)blockIdx.y * in_stride + (size_t)r * ld;
+    float m = 0.f;
+    int bad = 0;
+    if (r < rows) {
+        for (int k = lane; k < K; k += 64) {
+            const float v = fabsf(src[k]);
+            if (!(v <= 3.0e38f)) bad = 1;                  // Inf or NaN (fmaxf would drop it)
+            m = fmaxf(m, v);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m = fmaxf(m, __shfl_xor(m, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    if (lane != 0) return;
+    int e = 0;
+    const bool ok = m > 0.f && !bad;
+    if (ok) frexpf(m, &e);                                 // m in [2^(e-1), 2^e)
+    const int k = ok ? min(max(14 - e, -100), 100) : 0;
+    float* fac = reinterpret_cast<float*>(out + (size_t)blockIdx.y * out_stride + img);
+    fac[r] = bad ? __builtin_nanf("") : ldexpf(1.f, -(k + kF2XExp));
+}
+
+__global__ void gemm_f16x2_pack_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int rows, int K, long ld,
+                                       long in_stride, long out_stride, long img) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= img / 2) return;
+    const int j = i & 7, lane = (i >> 3) & 63;
+    const long t = i >> 9;
+    const int K16 = (K + 15) >> 4;
+    const int k16 = t % K16;
+    const int rt = t / K16;
+    const int r = rt * 32 + (lane & 31), k = k16 * 16 + (lane >> 5) * 8 + j;
+    uint16_t* const dst0 = out + (size_t)blockIdx.y * out_stride;
+    const float* fac = reinterpret_cast<const float*>(dst0 + img);
+    float v = 0.f;
+    if (r < rows && k < K) v = w[(size_t)blockIdx.y * in_stride + (size_t)r * ld + k] * (ldexpf(1.f, -kF2XExp) / fac[r]);   // 2^k[m]: exact
+    const _Float16 hi = (_Float16)v;
+    const _Float16 lo = (_Float16)(v - (float)hi);
+    uint16_t* dst = dst0 + ((size_t)(rt * K16 + k16) * 2) * 512 + lane * 8 + j;
+    dst[0] = __builtin_bit_cast(uint16_t, hi);
+    dst[512] = __builtin_bit_cast(uint16_t, lo);
+}
+
+// 16-bit elements of the f16x2 image in front of its factors
+inline int64_t f16x2_image_elems(int32_t rows, int32_t K) { return (int64_t)((rows + 31) / 32) * ((K + 15) / 16) * 2 * 512; }
+
 }  // namespace
+
+extern "C" int64_t occd_gemm_f16x2_packed_elems(int32_t rows, int32_t K) {
+    if (rows <= 0 || K <= 0) return OCCD_EINVAL;
+    return f16x2_image_elems(rows, K) + (int64_t)((rows + 31) / 32) * 32 * 2;
+}
+
+extern "C" int occd_gemm_f16x2_pack(const float* w, void* out, int32_t rows, int32_t K, int64_t ld, int32_t batch,
+                                    int64_t in_stride, void* stream) {
+    if (!w || !out || rows <= 0 || K <= 0 || batch <= 0 || batch > 65535 || ld < K) return OCCD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(out) & 15) return OCCD_EINVAL;
+    const int64_t per = occd_gemm_f16x2_packed_elems(rows, K), img = f16x2_image_elems(rows, K);
+    const int rows_pad = (rows + 31) / 32 * 32;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        occd::ProfScope prof("gemm_f16x2_pack", st, 0.0, (double)per * 2 * batch);
+        hipLaunchKernelGGL(gemm_f16x2_scale_kernel, dim3((unsigned)rows_pad, (unsigned)batch), dim3(64), 0, st, w, (uint16_t*)out,
+                           rows, K, (long)ld, (long)in_stride, (long)per, (long)img);
+        hipLaunchKernelGGL(gemm_f16x2_pack_kernel, dim3((unsigned)((img / 2 + 255) / 256), (unsigned)batch), dim3(256), 0, st, w,
+                           (uint16_t*)out, rows, K, (long)ld, (long)in_stride, (long)per, (long)img);
+        const int rc = occd::check_launch();
+        if (rc != OCCD_OK) return rc;
+    }
+    // a non-finite weight has no power-of-two scale: read the factors back (packing is a set-up step, never part of a captured
+    // forward) and refuse; the caller keeps the bf16x3 image of occd_gemm_x3_pack
+    std::vector<float> host((size_t)rows_pad);
+    for (int b = 0; b < batch; ++b) {
+        const float* fac = reinterpret_cast<const float*>(static_cast<const uint16_t*>(out) + (size_t)b * per + img);
+        if (hipMemcpyAsync(host.data(), fac, host.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return OCCD_ELAUNCH;
+        for (float f : host)
+            if (f != f) return OCCD_EINVAL;
+    }
+    return OCCD_OK;
+}
 
 extern "C" int64_t occd_gemm_x3_packed_elems(int32_t rows, int32_t K) {
     if (rows <= 0 || K <= 0) return OCCD_EINVAL;
@@ -1243,16 +1446,21 @@ extern "C" int occd_gemm_x3_pack(const float* w, void* out, int32_t rows, int32_
 // a->tile_hint: 0 = pick (see below), 1 .. 5 = force a tile variant, 6 = force K16w, 7 = force the 64 x 64 split-K form,
 // 8 = force K16p (pre = 1, K <= 848, no res / scale_k).
 // a->pre: 0 = A and B float32; 1 = a->A is the role-0 image of occd_gemm_x3_pack (lda ignored, stride_a = bf16 elements
-// between batch items, 0 = shared); 2 = a->B is the role-1 image (ldb ignored, stride_b likewise).
+// between batch items, 0 = shared); 2 = a->B is the role-1 image (ldb ignored, stride_b likewise); OCCD_GEMM_PRE_F16X2 (4) = a->A
+// is the image of occd_gemm_f16x2_pack (stride_a = 16-bit elements, factors included): the two-term fp16 split on the tile
+// variants and K16p (hints 0 .. 5 and 8; no act_a / bias_n).
 extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     if (!a || !a->A || !a->B || !a->C) return OCCD_EINVAL;
     if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0 || a->batch > 65535) return OCCD_EINVAL;
-    if (a->pre < 0 || a->pre > 3) return OCCD_EINVAL;      // 3: float32 operands, plain bf16 arithmetic (one term)
+    if (a->pre < 0 || a->pre > OCCD_GEMM_PRE_F16X2) return OCCD_EINVAL;      // 3: float32 operands, plain bf16 arithmetic (one term)
+    const bool f16x2 = a->pre == OCCD_GEMM_PRE_F16X2, img_a = a->pre == 1 || f16x2;
+    if (f16x2 && (a->act_a != 0 || a->bias_n != nullptr || a->tile_hint == kNumVariantsG + 1 || a->tile_hint == kNumVariantsG + 2))
+        return OCCD_EINVAL;
     if ((a->K & 7) || a->ldc < a->N || a->N < 4) return OCCD_EINVAL;
-    if (a->pre != 1 && ((a->lda & 3) || a->lda < a->K || (reinterpret_cast<uintptr_t>(a->A) & 15) || (a->stride_a & 3)))
+    if (!img_a && ((a->lda & 3) || a->lda < a->K || (reinterpret_cast<uintptr_t>(a->A) & 15) || (a->stride_a & 3)))
         return OCCD_EINVAL;
     if (a->pre != 2 && (a->ldb < a->N || (reinterpret_cast<uintptr_t>(a->B) & 3))) return OCCD_EINVAL;
-    if (a->pre == 1 && ((reinterpret_cast<uintptr_t>(a->A) & 15) || (a->stride_a & 7))) return OCCD_EINVAL;
+    if (img_a && ((reinterpret_cast<uintptr_t>(a->A) & 15) || (a->stride_a & 7))) return OCCD_EINVAL;
     if (a->pre == 2 && ((reinterpret_cast<uintptr_t>(a->B) & 15) || (a->stride_b & 7))) return OCCD_EINVAL;
     if (reinterpret_cast<uintptr_t>(a->C) & 3) return OCCD_EINVAL;
     if (a->act < 0 || a->act > 2 || a->tile_hint < 0 || a->tile_hint > kNumVariantsG + 3) return OCCD_EINVAL;
@@ -1266,7 +1474,7 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
         // PRE = 1 kernel for A/B)
         static const bool panel_off = !occd::env_flag("OCCD_GEMM_PANEL", true);
         const int KP = ((a->K + 15) / 16) * 16;
-        const bool plain = a->pre == 1 && a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr;
+        const bool plain = img_a && a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr;
         const bool fits1 = plain && (size_t)KP * panel_row_bytes(1) <= 160 * 1024;      // K <= 848
         const bool fits2 = plain && (size_t)KP * panel_row_bytes(2) <= 160 * 1024;      // K <= 352
         if (a->tile_hint == kNumVariantsG + 3 && !fits1) return OCCD_EINVAL;
@@ -1281,6 +1489,10 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
             p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.sA = a->stride_a / 8; p.sB = a->stride_b; p.sC = a->stride_c;
             p.act = a->act; p.slope = a->slope; p.act_a = 0; p.n_fast = 1;
             const int tiles = (a->M + 31) / 32, r8 = (tiles + 7) / 8;
+            if (f16x2) {
+                p.fac = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a->A) + f16x2_image_elems(a->M, a->K));
+                p.s_fac = a->stride_a / 2;
+            }
             // panel width: 64 columns while two workgroups fit a CU's LDS with them (K <= 176), else 32 (measured, kernel trace,
             // profiles/r05_gemm_panel.txt: tap 1/2 (K = 320) 332 against 362 us, 224 -> 1344 on 1848 pixels 22 against 27 us; the
             // 64-column form ahead by 3 ... 10 % on K = 48 ... 160): a second resident workgroup stages its panel under the
@@ -1312,8 +1524,12 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
             // -- tools/panel_timeline.cpp shows a 16-k step at ~700 cycles (32 columns) / ~950 (64) whatever the depth: the two
             // waves of a SIMD keep the matrix pipe 55 - 70 % busy INSIDE the loop; the launch-level 22 - 35 % is prologue (kernel
             // arguments + panel staging: 7k cycles of a 29k-cycle workgroup at 384 -> 2304 on 468 pixels), epilogue and dispatch.
+            // f16x2: the same widths and depths (the routing limits above are those of the three-term rows, so that a launch takes
+            // the same route under either split; the 64-column row of 320 B would leave two workgroups per CU up to K = 256 --
+            // not measured, K <= 176 kept)
             void (*kern)(const GemmP) = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2> : gemm_x3_panel_kernel<1, 1, 1>;
-            const size_t plds = (size_t)KP * panel_row_bytes(nt);
+            if (f16x2) kern = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1, 2> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2, 2> : gemm_x3_panel_kernel<1, 1, 1, 2>;
+            const size_t plds = (size_t)KP * panel_row_bytes(nt, f16x2 ? 2 : 3);
             if (plds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
             const double flops = 2.0 * a->M * a->N * a->K * a->batch;
             const double bytes = 4.0 * ((double)a->M * a->K * (a->stride_a != 0 ? a->batch : 1) + ((double)a->K + a->M) * a->N * a->batch);
@@ -1362,7 +1578,7 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     // the longest K (tap GEMM of the 1/16 level, K = 2560: 0.438 against 0.462 ms); K16w keeps that launch
     if ((a->res != nullptr || a->scale_k != nullptr) && (a->tile_hint == kNumVariantsG + 1 || a->pre == 2)) return OCCD_EINVAL;
     if (a->res != nullptr && (reinterpret_cast<uintptr_t>(a->res) & 3)) return OCCD_EINVAL;
-    if (a->act_a != 0 && (a->act_a != 1 || a->pre == 1 || a->pre == 3 || a->tile_hint == kNumVariantsG + 1)) return OCCD_EINVAL;
+    if (a->act_a != 0 && (a->act_a != 1 || img_a || a->pre == 3 || a->tile_hint == kNumVariantsG + 1)) return OCCD_EINVAL;
     const bool ws = a->pre == 0 && a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr &&
                     (a->tile_hint == kNumVariantsG + 1 || (a->tile_hint == 0 && pick == 0 && !ws_off && a->K >= 2048));
     if (a->tile_hint == kNumVariantsG + 1 && a->pre != 0) return OCCD_EINVAL;
@@ -1378,7 +1594,11 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.res = a->res; p.kscale = a->scale_k;
     p.M = a->M; p.N = a->N; p.K = a->K;
     p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.sA = a->stride_a; p.sB = a->stride_b; p.sC = a->stride_c;
-    if (a->pre == 1) p.sA = a->stride_a / 8;        // bf16 elements -> u32x4 records
+    if (img_a) p.sA = a->stride_a / 8;              // 16-bit elements -> u32x4 records
+    if (f16x2) {
+        p.fac = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a->A) + f16x2_image_elems(a->M, a->K));
+        p.s_fac = a->stride_a / 2;
+    }
     if (a->pre == 2) p.sB = a->stride_b / 8;
     p.act = a->act; p.slope = a->slope; p.act_a = a->act_a;
     p.bias_n = a->bias_n; p.s_bias_n = a->stride_bias_n;
@@ -1391,7 +1611,7 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     p.nwg = (unsigned)nwg;
     constexpr int kKS = 4;
     const size_t lds = ws ? (size_t)2 * kWsStage
-                          : ((a->pre == 1 ? 0 : (size_t)TM * kARow) + (a->pre == 2 ? 0 : (size_t)3 * 32 * (TN * 2 + 64))) * (ksplit ? kKS : 1);
+                          : ((img_a ? 0 : (size_t)TM * kARow) + (a->pre == 2 ? 0 : (size_t)(f16x2 ? 2 : 3) * 32 * (TN * 2 + 64))) * (ksplit ? kKS : 1);
     void (*kern)(const GemmP) = ws ? gemm_x3_ws_kernel<0> : ksplit ? gemm_x3_kernel<1, 1, 2, 2, 0, 3, kKS> : v.kern[a->pre];
 #ifdef OCCD_GEMM_DEV_VARIANTS
     if (ws && getenv("OCCD_GEMM_DBG") != nullptr)
@@ -1402,13 +1622,14 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     if (lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
     const double flops = 2.0 * a->M * a->N * a->K * a->batch;
     const double bytes = 4.0 * ((double)a->M * a->K * (a->stride_a != 0 ? a->batch : 1) + ((double)a->K + a->M) * a->N * a->batch);
-    occd::ProfScope prof(ws ? "gemm_f32x3_ws" : a->pre == 0 ? "gemm_f32x3" : a->pre == 1 ? "gemm_f32x3_preA" : a->pre == 2 ? "gemm_f32x3_preB" : "gemm_bf16", (hipStream_t)stream, flops, bytes);
+    occd::ProfScope prof(ws ? "gemm_f32x3_ws" : a->pre == 0 ? "gemm_f32x3" : img_a ? "gemm_f32x3_preA" : a->pre == 2 ? "gemm_f32x3_preB" : "gemm_bf16", (hipStream_t)stream, flops, bytes);
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg, (unsigned)a->batch), dim3(ws ? 512 : v.WM * v.WN * 64 * (ksplit ? kKS : 1)), lds,
                        (hipStream_t)stream, p);
     return occd::check_launch();
 }
 
-// K21 (see gemm_x3_panel_splitk_kernel): a->pre must be 1 (A = the role-0 image of occd_gemm_x3_pack), B float32 with n
+// K21 (see gemm_x3_panel_splitk_kernel): a->pre must be 1 (A = the role-0 image of occd_gemm_x3_pack) or OCCD_GEMM_PRE_F16X2
+// (the image of occd_gemm_f16x2_pack), B float32 with n
 // contiguous, optional bias / act / res / scale_k as occd_gemm_f32x3.  `nz` K chunks of `k16_per_z` 16-k steps each
 // (occd_gemm_f32x3_splitk_plan proposes them; k16_per_z * 192 B <= 160 KB of LDS, two workgroups per CU up to 26 steps),
 // `row_ranges` >= 1 row ranges per panel, workspace: >= batch * nz * M * round_up(N, 32) floats.
@@ -1441,7 +1662,8 @@ extern "C" int occd_gemm_f32x3_splitk(const occd_gemm_args* a, int32_t k16_per_z
                                       float* workspace, int64_t workspace_floats, void* stream) {
     if (!a || !a->A || !a->B || !a->C || !workspace) return OCCD_EINVAL;
     if (a->M <= 0 || a->N < 4 || a->K <= 0 || (a->K & 7) || a->batch <= 0 || a->batch > 65535) return OCCD_EINVAL;
-    if (a->pre != 1 || a->act_a != 0 || a->act < 0 || a->act > 2 || a->ldc < a->N || a->ldb < a->N || a->bias_n != nullptr) return OCCD_EINVAL;
+    const bool f16x2 = a->pre == OCCD_GEMM_PRE_F16X2;
+    if ((a->pre != 1 && !f16x2) || a->act_a != 0 || a->act < 0 || a->act > 2 || a->ldc < a->N || a->ldb < a->N || a->bias_n != nullptr) return OCCD_EINVAL;
     if ((reinterpret_cast<uintptr_t>(a->A) & 15) || (a->stride_a & 7) || (reinterpret_cast<uintptr_t>(a->B) & 3) ||
         (reinterpret_cast<uintptr_t>(a->C) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 127))
         return OCCD_EINVAL;
@@ -1471,6 +1693,10 @@ extern "C" int occd_gemm_f32x3_splitk(const occd_gemm_args* a, int32_t k16_per_z
     q.z_stride = (long)a->M * ld_ws;
     q.b_stride = (long)nz * q.z_stride;
     void (*kern)(const GemmSKP) = k16_per_z >= 16 ? gemm_x3_panel_splitk_kernel<1, 2> : gemm_x3_panel_splitk_kernel<1, 1>;
+    if (f16x2) kern = k16_per_z >= 16 ? gemm_x3_panel_splitk_kernel<1, 2, 2> : gemm_x3_panel_splitk_kernel<1, 1, 2>;
+    // (the 32-column row of the f16x2 panel is 192 B as well: the same LDS bound, the same plan)
+    const float* const fac = f16x2 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a->A) + f16x2_image_elems(a->M, a->K))
+                                   : nullptr;
     if (lds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
     hipStream_t st = (hipStream_t)stream;
     const double flops = 2.0 * a->M * a->N * a->K * a->batch;
@@ -1482,7 +1708,7 @@ extern "C" int occd_gemm_f32x3_splitk(const occd_gemm_args* a, int32_t k16_per_z
     const long items = (long)a->M * ((a->N + 3) / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)a->batch), dim3(256), 0, st,
                        (const float*)workspace, a->C, a->bias, a->res, a->M, a->N, nz, ld_ws, q.z_stride, q.b_stride,
-                       (long)a->ldc, (long)a->stride_c, a->act, a->slope, vec_ok);
+                       (long)a->ldc, (long)a->stride_c, a->act, a->slope, vec_ok, fac);
     return occd::check_launch();
 }
 

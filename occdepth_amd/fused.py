@@ -124,6 +124,17 @@ _SWITCHES = {
     # The head launches (OCCDEPTH_HEAD_SPLIT), the OCCDEPTH_BF16X3=1 experiment, the opt-in 1x1x1 / sigmoid route and training
     # are unchanged by this switch.
     "K2B_SPLIT": ("OCCDEPTH_K2B_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
+    # Which weight image the 2-D network's operand builders (efficientnet.gemm_operands / splitk_operands, the tap-GEMM and the
+    # merged conv_head o conv2 operands of unet2d.py) make for the GEMMs that read pre-split weights -- K16p, K21 and K16's
+    # pre-split form (csrc/gemm_x3.hip):
+    #   OCCDEPTH_GEMM_SPLIT=f16x2   (default) the image of occd_gemm_f16x2_pack: three v_mfma_f32_32x32x16_f16 per K step and 4
+    #                               streamed bytes per weight element instead of six bf16 MFMAs and 6 bytes; error against float64
+    #                               within the bounds of tests/test_gemm_f16x2.py; finite activations |x| >= 32760 overflow to
+    #                               non-finite outputs; matrices with a non-finite weight keep bf16x3
+    #   OCCDEPTH_GEMM_SPLIT=bf16x3  the three-term bf16 image as before (the bit-for-bit previous path)
+    # Explicit hip.GemmPacked(w, role) / hip.matmul_operand(w, role) callers, the on-the-fly K16 launches (Winograd-domain products,
+    # project convolutions with gate and residual), role-"b" images and training are unchanged by this switch.
+    "GEMM_SPLIT": ("OCCDEPTH_GEMM_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
 }
 
 
@@ -141,6 +152,7 @@ def _from_env(name):
 
 WINO_SPLIT, BF16X3 = _from_env("WINO_SPLIT"), _from_env("BF16X3")
 HEAD_SPLIT, K2B_SPLIT = _from_env("HEAD_SPLIT"), _from_env("K2B_SPLIT")
+GEMM_SPLIT = _from_env("GEMM_SPLIT")
 
 
 def set_wino_split(v):
@@ -165,6 +177,12 @@ def set_k2b_split(v):
     """'f16x2' / 'bf16x3'; takes effect at the next launch."""
     global K2B_SPLIT
     K2B_SPLIT = _parse("K2B_SPLIT", v)
+
+
+def set_gemm_split(v):
+    """'f16x2' / 'bf16x3'; the operand builders re-pack on the next call (hip.set_gemm_split is the same switch)."""
+    global GEMM_SPLIT
+    GEMM_SPLIT = _parse("GEMM_SPLIT", v)
 
 
 def wino_pack(w, scale=None):

@@ -405,20 +405,41 @@ GEMM_ACT = {None: abi.CONSTANTS["OCCD_GEMM_ACT_NONE"], "none": abi.CONSTANTS["OC
             "swish": abi.CONSTANTS["OCCD_GEMM_ACT_SWISH"], "leaky": abi.CONSTANTS["OCCD_GEMM_ACT_LEAKY"]}
 
 
+GEMM_PRE_F16X2 = abi.CONSTANTS["OCCD_GEMM_PRE_F16X2"]
+
+
 class GemmPacked:
     """A static GEMM operand (weights) split once into its three bf16 terms in MFMA fragment order (occd_gemm_x3_pack):
-    role "a" = the left operand (M, K) / (batch, M, K), role "b" = the right operand (K, N) / (batch, K, N)."""
+    role "a" = the left operand (M, K) / (batch, M, K), role "b" = the right operand (K, N) / (batch, K, N).
+    split="f16x2" (role "a" only): the image of occd_gemm_f16x2_pack instead -- rows scaled by powers of two, two fp16 terms,
+    the row factors behind them -- which K16p, K21 and K16's pre-split form multiply with three fp16 MFMAs per K step (the
+    numerics of the head convolutions; finite |b| >= 32760 overflow).  Raises ValueError when a weight is not finite: such a
+    matrix has no f16x2 image."""
 
-    def __init__(self, w, role):
+    def __init__(self, w, role, split="bf16x3"):
         if role not in ("a", "b") or w.dim() not in (2, 3) or w.dtype != torch.float32 or not w.is_cuda:
             raise RuntimeError("GemmPacked: a 2-D / 3-D float32 GPU tensor and role 'a' or 'b'")
+        if split not in ("bf16x3", "f16x2") or (split == "f16x2" and role != "a"):
+            raise RuntimeError("GemmPacked: split is 'bf16x3', or 'f16x2' with role 'a'")
         w = w.detach().contiguous()
-        self.role, self.batch = role, (w.shape[0] if w.dim() == 3 else None)
+        self.role, self.batch, self.split = role, (w.shape[0] if w.dim() == 3 else None), split
         if role == "a":
             self.rows, self.K = w.shape[-2], w.shape[-1]
         else:
             self.K, self.rows = w.shape[-2], w.shape[-1]
         self.shape = tuple(w.shape)
+        if split == "f16x2":
+            self.per = load().occd_gemm_f16x2_packed_elems(self.rows, self.K)
+            if self.per <= 0:
+                raise RuntimeError("occd_gemm_f16x2_packed_elems: bad shape")
+            nb = self.batch or 1
+            self.buf = torch.empty(nb * self.per, device=w.device, dtype=torch.float16)
+            rc = load().occd_gemm_f16x2_pack(w.data_ptr(), self.buf.data_ptr(), self.rows, self.K, w.shape[-1], nb,
+                                             w.shape[-2] * w.shape[-1], _stream())
+            if rc == abi.CONSTANTS["OCCD_EINVAL"]:
+                raise ValueError("occd_gemm_f16x2_pack: a weight is not finite")
+            _check(rc, "occd_gemm_f16x2_pack")
+            return
         self.per = load().occd_gemm_x3_packed_elems(self.rows, self.K)
         if self.per <= 0:
             raise RuntimeError("occd_gemm_x3_packed_elems: bad shape")
@@ -502,9 +523,12 @@ def gemm_x3(a, b, bias=None, act=None, slope=0.01, out=None, tile_hint=0, plain_
     q.stride_b = (b.per if nb_b else 0) if pb else (b.stride(0) if b.dim() == 3 else 0)
     q.stride_c = out.stride(0) if out.dim() == 3 else 0
     q.act, q.slope, q.tile_hint = GEMM_ACT[act], slope, tile_hint
-    q.pre = 1 if pa else 2 if pb else (3 if plain_bf16 else 0)
+    f16x2 = pa and a.split == "f16x2"
+    q.pre = (GEMM_PRE_F16X2 if f16x2 else 1) if pa else 2 if pb else (3 if plain_bf16 else 0)
     if plain_bf16 and (pa or pb):
         raise RuntimeError("gemm_x3: plain_bf16 takes float32 tensor operands")
+    if f16x2 and bias_n is not None:
+        raise RuntimeError("gemm_x3: an f16x2 image takes no column bias")
     if res is not None:
         if res.dtype != torch.float32 or res.shape != out.shape or res.stride() != out.stride():
             raise RuntimeError("gemm_x3: res must be laid out like out")
@@ -523,7 +547,7 @@ def gemm_x3(a, b, bias=None, act=None, slope=0.01, out=None, tile_hint=0, plain_
             raise RuntimeError("gemm_x3: bias_n must be (N,) or (batch, N) contiguous floats")
         q.bias_n, q.stride_bias_n = bias_n.data_ptr(), (N if bias_n.dim() == 2 else 0)
     if _PROFILING:
-        set_tag("%dx%dx%d b%d" % (M, N, K, batch))
+        set_tag("%dx%dx%d b%d%s" % (M, N, K, batch, " f16x2" if f16x2 else ""))
     _check(load().occd_gemm_f32x3(ctypes.byref(q), _stream()), "occd_gemm_f32x3")
     return out[0] if squeeze and out.dim() == 3 else out
 
@@ -572,7 +596,7 @@ def gemm_x3_splitk(a, b, bias=None, act=None, slope=0.01, out=None, res=None, k_
     q.M, q.N, q.K, q.batch = M, N, K, batch
     q.lda, q.ldb, q.ldc = K, b.stride(-2), out.stride(-2)
     q.stride_a, q.stride_b, q.stride_c = 0, (b.stride(0) if b.dim() == 3 else 0), out.stride(0)
-    q.act, q.slope, q.tile_hint, q.pre = GEMM_ACT[act], slope, 0, 1
+    q.act, q.slope, q.tile_hint, q.pre = GEMM_ACT[act], slope, 0, (GEMM_PRE_F16X2 if a.split == "f16x2" else 1)
     if res is not None:
         if res.dtype != torch.float32 or res.shape != out.shape or res.stride() != out.stride():
             raise RuntimeError("gemm_x3_splitk: res must be laid out like out")
@@ -582,7 +606,7 @@ def gemm_x3_splitk(a, b, bias=None, act=None, slope=0.01, out=None, res=None, k_
             raise RuntimeError("gemm_x3_splitk: k_scale must be (batch, K) contiguous floats")
         q.scale_k = k_scale.data_ptr()
     if _PROFILING:
-        set_tag("%dx%dx%d b%d z%d" % (M, N, K, batch, nz))
+        set_tag("%dx%dx%d b%d z%d%s" % (M, N, K, batch, nz, " f16x2" if a.split == "f16x2" else ""))
     _check(load().occd_gemm_f32x3_splitk(ctypes.byref(q), per, nz, rr, ws.data_ptr(), ws.numel(), _stream()),
            "occd_gemm_f32x3_splitk")
     return out[0] if squeeze else out
@@ -719,11 +743,48 @@ def _presplit_launch(pa, b):
     return pa.K >= 512 and -(-pa.rows // 256) * -(-n // 128) * batch >= 320
 
 
-def matmul_operand(w, role):
-    """A static operand (weights) in the form hip.matmul wants it: (the float32 tensor, its GemmPacked image or None)."""
+def gemm_split():
+    """'f16x2' / 'bf16x3': which image the model's operand builders make for the GEMMs that read pre-split weights (K16p, K21,
+    K16's pre-split form) -- OCCDEPTH_GEMM_SPLIT, or the last `set_gemm_split` (the switch is declared in fused.py)."""
+    from . import fused
+    return fused.GEMM_SPLIT
+
+
+def set_gemm_split(v):
+    """'f16x2' / 'bf16x3'; the builders' caches carry the switch in their keys: the next launch packs the other image."""
+    from . import fused
+    fused.set_gemm_split(v)
+
+
+# K21 on the f16x2 image, per launch geometry (tools/bench_gemm_split.py, profiles/gemm_f16x2_ab.txt): 1.19 - 1.27x wherever a
+# workgroup has >= 210 (row tile, 16-k step) pairs to multiply, 1.05x at 150 (160 x 1848 x 960: 5 tiles x 30 steps) and 1.00x at
+# 126 (384 x 468 x 1344: 6 x 21) -- a launch that small is its panel staging, the second launch and dispatch, whichever split
+# multiplies.  Below this many pairs per workgroup a K21 launch keeps the bf16x3 image.
+SPLITK_F16X2_MIN_TILE_STEPS = 140
+
+
+def splitk_f16x2_wins(M, N, K, batch):
+    """The host rule of K21: does the f16x2 image beat bf16x3 on this launch under the library's plan?"""
+    per, _, rr, _ = gemm_x3_splitk_plan(M, N, K, batch)
+    return -(-(-(-M // 32)) // rr) * per >= SPLITK_F16X2_MIN_TILE_STEPS
+
+
+def gemm_packed_a(w, split):
+    """The role-"a" image of `w` under `split`; a matrix the f16x2 pack refuses (a non-finite weight) keeps bf16x3."""
+    if split == "f16x2":
+        try:
+            return GemmPacked(w, "a", split="f16x2")
+        except ValueError:
+            pass
+    return GemmPacked(w, "a")
+
+
+def matmul_operand(w, role, split=None):
+    """A static operand (weights) in the form hip.matmul wants it: (the float32 tensor, its GemmPacked image or None).
+    split: None = the three-term bf16 image; the model's builders pass `gemm_split()` (role "a" only)."""
     w = w.detach().float().contiguous()
     if GEMM_X3 and w.is_cuda and (GEMM_X3_PACK or _panel_operand(w, role)):
-        return w, GemmPacked(w, role)
+        return w, (gemm_packed_a(w, split) if split is not None and role == "a" else GemmPacked(w, role))
     return w, None
 
 

@@ -74,7 +74,7 @@ def pw_operands(owner, conv, bn=None):
 def gemm_operands(owner, conv, bn):
     """(W * BatchNorm scale as a (Cout, Cin) matrix, shift) of a 1x1 convolution + BatchNorm for K16 (hip.matmul), cached on
     `owner` until a source tensor changes."""
-    key = _stamp(conv, bn)
+    key = (_stamp(conv, bn), hip.gemm_split())
     cache = owner.__dict__.setdefault("_gemm_cache", {})
     hit = cache.get(id(conv))
     if hit is None or hit[0] != key:
@@ -82,7 +82,7 @@ def gemm_operands(owner, conv, bn):
         w = conv.weight.detach().float().flatten(1) * scale.view(-1, 1)
         if conv.bias is not None:
             shift = conv.bias.detach().float() * scale + shift
-        hit = (key, hip.matmul_operand(w, "a"), shift.contiguous())
+        hit = (key, hip.matmul_operand(w, "a", split=key[1]), shift.contiguous())
         cache[id(conv)] = hit
     return hit[1], hit[2]
 
@@ -119,9 +119,14 @@ PW_PROJECT_SPLITK_MIN_K = int(os.environ.get("OCCDEPTH_PW_PROJECT_SPLITK_MIN_K",
 PW_PROJECT_SPLITK_MAX_PIXELS = int(os.environ.get("OCCDEPTH_PW_PROJECT_SPLITK_MAX_PIXELS", "8000"))
 
 
-def splitk_operands(owner, conv, bn):
-    """(GemmPacked image of W * BatchNorm scale, shift) for K21, cached on `owner` until a source tensor changes."""
-    key = _stamp(conv, bn)
+def splitk_operands(owner, conv, bn, pixels=None, batch=1):
+    """(GemmPacked image of W * BatchNorm scale, shift) for K21, cached on `owner` until a source tensor, the switch or the
+    verdict of the host rule changes.  The image is f16x2 when hip.gemm_split() says so and hip.splitk_f16x2_wins does for a
+    launch on batch x pixels columns (pixels None: no launch geometry, the switch alone); else bf16x3."""
+    split = hip.gemm_split()
+    if split == "f16x2" and pixels is not None and not hip.splitk_f16x2_wins(conv.out_channels, pixels, conv.in_channels, batch):
+        split = "bf16x3"
+    key = (_stamp(conv, bn), split)
     cache = owner.__dict__.setdefault("_splitk_cache", {})
     hit = cache.get(id(conv))
     if hit is None or hit[0] != key:
@@ -129,7 +134,7 @@ def splitk_operands(owner, conv, bn):
         w = (conv.weight.detach().float().flatten(1) * scale.view(-1, 1)).contiguous()
         if conv.bias is not None:
             shift = conv.bias.detach().float() * scale + shift
-        hit = (key, hip.GemmPacked(w, "a"), shift.contiguous())
+        hit = (key, hip.gemm_packed_a(w, key[1]), shift.contiguous())
         cache[id(conv)] = hit
     return hit[1], hit[2]
 
@@ -142,7 +147,7 @@ def project_conv(owner, conv, bn, y, gate, res):
     if (PW_PROJECT_SPLITK and hip.GEMM_X3 and y.is_cuda and C % 8 == 0 and C >= PW_PROJECT_SPLITK_MIN_K and H * W >= 4
             and B * H * W <= PW_PROJECT_SPLITK_MAX_PIXELS and y.is_contiguous() and gate.is_contiguous()
             and tuple(gate.shape) == (B, C) and (res is None or res.is_contiguous())):
-        pa, shift = splitk_operands(owner, conv, bn)
+        pa, shift = splitk_operands(owner, conv, bn, H * W, B)
         out = hip.gemm_x3_splitk(pa, y.view(B, C, H * W), bias=shift, k_scale=gate,
                                  res=res.view(B, cout, H * W) if res is not None else None)
         return out.view(B, cout, H, W)

@@ -107,7 +107,7 @@ class UpSampleBN(nn.Module):
     UPCONV_FUSE_SKIP = os.environ.get("OCCDEPTH_UPCONV_FUSE_SKIP", "1") == "1"
 
     def _upconv_operands(self, conv, bn, cup):
-        key = (_stamp(conv, bn), cup, _fused.WINO_SPLIT)
+        key = (_stamp(conv, bn), cup, _fused.WINO_SPLIT, hip.gemm_split())
         hit = self.__dict__.get("_upconv_cache")
         if hit is None or hit[0] != key:
             scale, shift = bn_affine_cached(bn)
@@ -118,7 +118,7 @@ class UpSampleBN(nn.Module):
             # rows t * Cout + co (t = ky * 3 + kx) of the tap GEMM, BatchNorm scale folded in
             w9 = (w[:, :cup] * scale.view(-1, 1, 1, 1)).permute(2, 3, 0, 1).reshape(9 * cout, cup).contiguous()
             wskip = (w[:, cup:] * scale.view(-1, 1, 1, 1)).contiguous()
-            hit = (key, hip.pw_pack_weights(w9), hip.matmul_operand(w9, "a"),
+            hit = (key, hip.pw_pack_weights(w9), hip.matmul_operand(w9, "a", split=key[3]),
                    _fused.wino_pack(w[:, cup:].contiguous(), scale), shift.contiguous(), wskip)
             self.__dict__["_upconv_cache"] = hit
         return hit[1:]
@@ -233,13 +233,13 @@ class DecoderBN(nn.Module):
         """conv2(conv_head(f)) as ONE convolution: both are 1x1 and nothing sits between them (the reference taps
         features[11] = conv_head's raw output, unet2d.py:146,183), so W = W_conv2 . W_head (formed once in float64) and the
         2560 -> 2560 GEMM on the 1/32 map disappears: 640 -> 2560 with conv2's bias and conv2's padding=1 frame."""
-        key = _stamp(self.conv2, conv_head)
+        key = (_stamp(self.conv2, conv_head), hip.gemm_split())
         hit = self.__dict__.get("_merged_head")
         if hit is None or hit[0] != key:
             w2 = self.conv2.weight.detach().double().flatten(1)
             wh = conv_head.weight.detach().double().flatten(1)
             w = (w2 @ wh).float().reshape(w2.shape[0], wh.shape[1], 1, 1).contiguous()
-            hit = (key, w, hip.matmul_operand(w.view(w.shape[0], -1), "a") if w.is_cuda else None)
+            hit = (key, w, hip.matmul_operand(w.view(w.shape[0], -1), "a", split=key[1]) if w.is_cuda else None)
             self.__dict__["_merged_head"] = hit
         pad = self.conv2.padding
         if (hip.GEMM_X3 and _fused.on_gpu(f) and self.conv2.stride == (1, 1) and self.conv2.bias is not None

@@ -606,6 +606,12 @@ int occd_dwconv2d_pool_nchw(const float* x, const float* w, const float* scale, 
                             float* pool_part, int32_t batch, int32_t C, int32_t H, int32_t W, int32_t k,
                             int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo,
                             int32_t act, int64_t x_plane_stride, void* stream);
+/* How occd_dwconv2d_nchw / occd_dwconv2d_pool_nchw stage the input rows of a workgroup in LDS: 1 (the default) in 16-byte
+ * chunks with every load of the tile in flight at once, planes of at most 128 items two to a workgroup; 0 element by element
+ * (the form before; also what W < 4 runs); 2 chunks with one plane per workgroup everywhere (measurement only).  y and
+ * pool_part are bit-identical in all three.  OCCD_DW_STAGE=0 in the environment (read once) selects 0 as well; returns the
+ * previous setting; a value outside 0..2 selects 1.  (Added without a change of any struct or prototype: no ABI bump.)  */
+int32_t occd_dwconv2d_set_stage(int32_t form);
 /* Squeeze-excite in TRAINING (autograd of geffnet's SqueezeExcite in training_step):
  *   forward : sums = occd_plane_reduce(x, NULL)  ->  occd_se_gate(sums, ..., nblk = 1, S)  ->  occd_affine_act_nchw (x * gate)
  *   backward: gg = occd_plane_reduce(gout, x)    ->  occd_se_bwd                           ->  occd_affine_act_nchw

@@ -11,8 +11,10 @@
 //                        (F.interpolate + torch.cat of unet2d.py:38-46 in one pass)
 //
 // Reference semantics: occdepth/models/unet2d.py:24-46 and the geffnet EfficientNet blocks (third party).
+#include <atomic>
 #include <cstdlib>
 #include "device.h"
+#include "dwconv_stage.h"
 
 namespace {
 
@@ -125,16 +127,37 @@ __global__ void __launch_bounds__(256) dwconv2d_direct_kernel(const float* __res
 // with fully coalesced loads (lane = consecutive float; zero padding written into the tile, so the compute phase has no
 // bounds checks), then every thread reads its window rows as aligned 16-byte LDS vectors (column j of the tile is image
 // column j - pad_l, so the window of output quad q starts at j = 4 q STRIDE).
-template <int K, int STRIDE>
+//
+// CHUNK (the default form, W >= 4): the staging unit is the 16-byte chunk (row r, tile columns 4m .. 4m+3; csrc/dwconv_stage.h)
+// -- one dword-aligned 16-byte load and one ds_write_b128 per chunk, occd::kDwPass chunks of a thread in flight at once.  The
+// element-wise loop below compiles to two 4-byte loads, `s_waitcnt vmcnt(1)`, `vmcnt(0)`, one ds_write2st64_b32 per trip:
+// ceil(tile / 512) DEPENDENT round trips in front of the barrier (2 at 12x39 k5, 6 at 185x610, 13 at its stride-2 launch), and a
+// workgroup is a chain of latencies; in chunks a tile is 1 pass (2 at 185x610 stride 2).  The four outputs of a thread leave as
+// one dword-aligned 16-byte store.  The tile's contents, the arithmetic and the order of the pooling sum are those of the
+// element-wise form: y and the partials are bit-identical (tests/test_dwconv_staged.py).
+//
+// PAIR (planes of one block of <= 128 items: the 12 x 39 maps of the last two stages have 120 for 256 threads): two planes to a
+// workgroup, threads [0, 128) the first, [128, 256) the second, a tile each.  Half as many workgroups, each with both planes'
+// loads in flight together; a plane's partial keeps its index and its sum -- its two waves, then the (0 + 0) of the two waves
+// of dead lanes the unpaired block adds.  Measured per geometry in profiles/dwconv_stage_ab.txt: at 12 x 39 the chunked form with
+// one plane per workgroup is SLOWER than the element-wise one (13.9 against 11.8 us), paired it is faster (10.2 us).
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // rows of odd width: dword-aligned 16-byte accesses
+template <int K, int STRIDE, bool CHUNK, bool PAIR = false>
 __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        float* __restrict__ y, int C, int H, int W, int Ho, int Wo,
                                                        int pad_t, int pad_l, int act, float* __restrict__ pool_part,
-                                                       int wp, occd::FastDiv wpd, long xps) {
+                                                       int wp, occd::FastDiv wpd, long xps, int planes) {
+    static_assert(CHUNK || !PAIR, "paired planes are a variant of the chunked form");
     constexpr int NX = 4, SPAN = (NX - 1) * STRIDE + K, SPAN4 = (SPAN + 3) / 4;
-    extern __shared__ __attribute__((aligned(16))) float tile[];          // [rows][wp]
+    constexpr int NT = PAIR ? occd::kDwPairItems : 256;                   // threads of a plane's block
+    extern __shared__ __attribute__((aligned(16))) float tile_all[];      // [rows][wp] (PAIR: one per half)
     __shared__ float wsum[4];
-    const int plane = blockIdx.y;
+    const int half = PAIR ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / NT) : 0;   // (wave-uniform: c and the weights stay scalar)
+    const int tid = PAIR ? (int)threadIdx.x % NT : (int)threadIdx.x;
+    const int plane_raw = PAIR ? (int)blockIdx.y * 2 + half : (int)blockIdx.y;
+    const bool pvalid = !PAIR || plane_raw < planes;                      // (an odd plane count: the last second half idles)
+    const int plane = pvalid ? plane_raw : planes - 1;
     const int c = plane % C;
     const int wq = (Wo + NX - 1) / NX;
     const int nitems = Ho * wq;
@@ -144,7 +167,40 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
     const int iy_first = oy_first * STRIDE - pad_t;
     const int nrows = (oy_last - oy_first) * STRIDE + K;
     const float* xp = x + (size_t)plane * xps;            // xps: floats between input planes (>= H * W: rows of a padded GEMM result)
+    float* const tile = tile_all + (PAIR ? half * nrows * wp : 0);
+    float wr[K * K];
+    if constexpr (CHUNK) {                                 // (requested in front of the tile: one scalar round trip less after it)
+#pragma unroll
+        for (int i = 0; i < K * K; ++i) wr[i] = w[(size_t)c * K * K + i];
+    }
     // ---- stage: unconditional clamped loads, padding as a bit mask on the loaded value
+    if constexpr (CHUNK) {
+        // (wpd divides by wp / 4 here.)  All loads of a pass go out before the first is used, none behind a branch: the compiler
+        // counts them (vmcnt(occd::kDwPass - 1) ... vmcnt(0) in front of the LDS writes); a thread past the last chunk re-reads the last
+        const occd::DwRows tr = occd::dw_tile_rows((int)blockIdx.x, Ho, Wo, K, STRIDE, pad_t);
+        const int wp4 = wp >> 2, nchunks = tr.nrows * wp4;
+        for (int base = tid; base < nchunks; base += NT * occd::kDwPass) {
+            f32x4 v[occd::kDwPass];
+#pragma unroll
+            for (int i = 0; i < occd::kDwPass; ++i)
+                v[i] = *(const f32x4u*)(xp + occd::dw_chunk(min(base + i * NT, nchunks - 1), wp4, wpd.magic, tr.iy_first, pad_l, H, W).off);
+#pragma unroll
+            for (int i = 0; i < occd::kDwPass; ++i) {
+                const int f = base + i * NT;
+                if (f >= nchunks) continue;
+                const occd::DwChunk ch = occd::dw_chunk(f, wp4, wpd.magic, tr.iy_first, pad_l, H, W);
+                f32x4 u = v[i];
+                if (ch.sh != 0) {                            // a chunk across (or beyond) the left / right edge of the image
+                    const uint32_t l[4] = {__float_as_uint(u.x), __float_as_uint(u.y), __float_as_uint(u.z), __float_as_uint(u.w)};
+                    uint32_t o[4];
+                    occd::dw_shift(l, ch.sh, o);
+                    u = f32x4{__uint_as_float(o[0]), __uint_as_float(o[1]), __uint_as_float(o[2]), __uint_as_float(o[3])};
+                }
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                *(f32x4*)(tile + 4 * f) = ch.row_ok ? u : z;
+            }
+        }
+    } else {
     const int total = nrows * wp;
     for (int e = threadIdx.x; e < total; e += 256) {
         const int r = (int)occd_fastdiv((uint32_t)e, wpd), j = e - r * wp;      // (one mul-hi instead of ~25 instructions)
@@ -153,14 +209,16 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
         const float v = xp[(size_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)];
         tile[e] = __uint_as_float(__float_as_uint(v) & ok);
     }
-    float wr[K * K];
+    }
+    if constexpr (!CHUNK) {
 #pragma unroll
-    for (int i = 0; i < K * K; ++i) wr[i] = w[(size_t)c * K * K + i];
+        for (int i = 0; i < K * K; ++i) wr[i] = w[(size_t)c * K * K + i];
+    }
     __syncthreads();
     // ---- compute
-    const int item_raw = item0 + threadIdx.x;
-    const bool live = item_raw < nitems;
-    const int item = live ? item_raw : item0;               // (dead lanes of the last block still join the reduction)
+    const int item_raw = item0 + tid;
+    const bool live = item_raw < nitems && pvalid;
+    const int item = item_raw < nitems ? item_raw : item0;  // (dead lanes of the last block still join the reduction)
     const int oy = item / wq, q = item - oy * wq, ox0 = q * NX;
     const float* trow = tile + (size_t)((oy - oy_first) * STRIDE) * wp + q * NX * STRIDE;
     float acc[NX] = {0.f, 0.f, 0.f, 0.f};
@@ -180,6 +238,15 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
     const float s = scale ? scale[c] : 1.f, t = shift ? shift[c] : 0.f;
     float* yp = y + ((size_t)plane * Ho + oy) * Wo + ox0;
     float part = 0.f;
+    if (CHUNK && live && ox0 + NX - 1 < Wo) {
+        float v[NX];
+#pragma unroll
+        for (int o = 0; o < NX; ++o) {
+            v[o] = act2d_fast(acc[o] * s + t, act, 0.f);
+            part += v[o];
+        }
+        *(f32x4u*)yp = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
 #pragma unroll
     for (int o = 0; o < NX; ++o)
         if (live && ox0 + o < Wo) {
@@ -187,6 +254,7 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
             yp[o] = v;
             part += v;
         }
+    }
     if (pool_part != nullptr) {
         // squeeze-excite pooling: this workgroup's share of sum_{y,x} y[b][c] in a FIXED order (wave tree, then 4
         // partials), one float per (plane, workgroup); occd_se_gate sums the partials in index order: deterministic
@@ -194,7 +262,12 @@ __global__ void __launch_bounds__(256) dwconv2d_kernel(const float* __restrict__
         for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
         __syncthreads();
+        if constexpr (PAIR) {
+            // a plane's block of <= 128 items: in the unpaired form its waves 2 and 3 hold dead lanes only and add (0 + 0)
+            if (tid == 0 && pvalid) pool_part[(size_t)plane] = (wsum[2 * half] + wsum[2 * half + 1]) + (0.f + 0.f);
+        } else {
         if (threadIdx.x == 0) pool_part[(size_t)plane * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        }
     }
 }
 
@@ -880,6 +953,12 @@ extern "C" int occd_affine_act_nchw(const float* x, const float* res, float* y, 
     return occd::check_launch();
 }
 
+// Staging form of dwconv2d_kernel: 1 (default) = 16-byte chunks under the host rule below, 0 = the element-wise form it replaced
+// (kept: the A/B partner and the W < 4 path; bit-identical), 2 = chunks with one plane per workgroup everywhere (the A/B partner
+// of the paired launches).  OCCD_DW_STAGE=0 in the environment (read once) or occd_dwconv2d_set_stage(0) select the old form.
+static std::atomic<int> g_dw_stage{occd::env_flag("OCCD_DW_STAGE", true) ? 1 : 0};
+extern "C" int32_t occd_dwconv2d_set_stage(int32_t form) { return g_dw_stage.exchange(form < 0 || form > 2 ? 1 : form); }
+
 static int dwconv_launch(const float* x, const float* w, const float* scale, const float* shift, float* y,
                          int32_t batch, int32_t C, int32_t H, int32_t W, int32_t k, int32_t stride, int32_t pad_top,
                          int32_t pad_left, int32_t Ho, int32_t Wo, int32_t act, float* pool_part, int64_t x_plane_stride,
@@ -897,19 +976,34 @@ static int dwconv_launch(const float* x, const float* w, const float* scale, con
     hipStream_t st = (hipStream_t)stream;
     // LDS tile of the staged kernel: rows of one workgroup's 256 items x padded width (see dwconv2d_kernel)
     const int wq = (Wo + 3) / 4;
-    const int span4 = ((3 * stride + k) + 3) / 4;
-    const int wp = 4 * (wq - 1) * stride + 4 * span4;
+    const int wp = occd::dw_tile_wp(Wo, k, stride);
     int dmax = (255 + wq - 1) / wq;
     if (dmax > Ho - 1) dmax = Ho - 1;
     const size_t lds = (size_t)(dmax * stride + k) * wp * sizeof(float);
     if (lds <= 48 * 1024) {
+        // chunked staging needs a 16-byte load inside every row (and plane offsets that fit an int, as the item count does)
+        const int stage = g_dw_stage.load();
+        const bool chunk = stage != 0 && W >= 4 && (int64_t)H * W <= INT32_MAX;
+        // Host rule (profiles/dwconv_stage_ab.txt, every depthwise geometry of the config-2 frame): chunks are ahead of the
+        // element-wise form beyond the spread on all of them (1.02 - 1.55x) provided that planes of one block of <= 128 items
+        // (12 x 39 outputs: 120) go two to a workgroup; with one plane per workgroup those launches LOSE 10 - 18 %.
+        const bool pair = chunk && stage == 1 && items <= occd::kDwPairItems && 2 * lds <= 48 * 1024;
+        const int planes = batch * C;
+        const occd::FastDiv wp4d{occd::dw_div_magic((uint32_t)(wp / 4)), (uint32_t)(wp / 4)};
 #define OCCD_DW(KK, SS)                                                                                             \
-    hipLaunchKernelGGL((dwconv2d_kernel<KK, SS>), grid, dim3(256), lds, st, x, w, scale, shift, y, C, H, W, Ho, Wo, \
-                       pad_top, pad_left, act, pool_part, wp, occd::make_fastdiv((uint32_t)wp), xps)
-        if (k == 3 && stride == 1) OCCD_DW(3, 1);
-        else if (k == 3) OCCD_DW(3, 2);
-        else if (stride == 1) OCCD_DW(5, 1);
-        else OCCD_DW(5, 2);
+    if (pair)                                                                                                       \
+        hipLaunchKernelGGL((dwconv2d_kernel<KK, SS, true, true>), dim3(1, (unsigned)((planes + 1) / 2)), dim3(256), 2 * lds, st, x, w, \
+                           scale, shift, y, C, H, W, Ho, Wo, pad_top, pad_left, act, pool_part, wp, wp4d, xps, planes);  \
+    else if (chunk)                                                                                                 \
+        hipLaunchKernelGGL((dwconv2d_kernel<KK, SS, true>), grid, dim3(256), lds, st, x, w, scale, shift, y, C, H, W, Ho, Wo, \
+                           pad_top, pad_left, act, pool_part, wp, wp4d, xps, planes);                               \
+    else                                                                                                            \
+        hipLaunchKernelGGL((dwconv2d_kernel<KK, SS, false>), grid, dim3(256), lds, st, x, w, scale, shift, y, C, H, W, Ho, Wo, \
+                           pad_top, pad_left, act, pool_part, wp, occd::make_fastdiv((uint32_t)wp), xps, planes)
+        if (k == 3 && stride == 1) { OCCD_DW(3, 1); }
+        else if (k == 3) { OCCD_DW(3, 2); }
+        else if (stride == 1) { OCCD_DW(5, 1); }
+        else { OCCD_DW(5, 2); }
 #undef OCCD_DW
         return occd::check_launch();
     }

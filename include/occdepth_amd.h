@@ -73,7 +73,9 @@ extern "C" {
  * 22: occd_confusion_region, occd_confusion_regions_args, occd_ssc_confusion_regions (SSC confusion counts by region --
  *     index box x camera FOV x byte masks, shared or per frame -- in one pass); added since without a change of any
  *     struct or prototype: occd_gemm_f16x2_packed_elems, occd_gemm_f16x2_pack and occd_gemm_args.pre = OCCD_GEMM_PRE_F16X2
- *     (the two-term fp16 split of the 2-D GEMMs that read pre-split weights: K16p, K21, K16 on the A image) */
+ *     (the two-term fp16 split of the 2-D GEMMs that read pre-split weights: K16p, K21, K16 on the A image); likewise
+ *     OCCD_FUSE_MAX_SOURCES, OccdFuseArgs, occd_fuse_store and occd_fuse_frames (temporal fusion of class probabilities
+ *     over a sequence, csrc/fuse.hip): a new struct and new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1257,6 +1259,46 @@ int occd_ipc_mailbox_close(void* peer);
 int occd_ipc_mailbox_free(void* mailbox);
 int occd_ipc_allreduce(const void* in, void* out, int64_t count, int32_t dtype, void* const* mailboxes, int32_t rank,
                        int32_t world, int64_t max_bytes, int32_t timeout_ms, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Temporal fusion of class probabilities over a sequence (csrc/fuse.hip).  Additive (OCCD_ABI_VERSION note).  No
+ * atomics, no allocation, no host sync (capture-safe); every output byte depends on the inputs alone.
+ *
+ * occd_fuse_store: one frame's logits (one batch item), element (c, n) at c*s_c + n*s_v floats, -> softmax rows,
+ * rows[n*pitch + c], voxel n = (x*Y + y)*Z + z.  Layouts: planes (s_v == 1, s_c >= S) and channels-last rows (s_c == 1,
+ * s_v >= C).  Channels-last rows with s_v % 4 == 0, s_v >= round4(C) and a 16-byte aligned base are read in 16-byte pieces
+ * (the floats [C, round4(C)) of a row are read and dropped); any other channels-last rows go through
+ * occd_softmax_channels.  The channels [C, round4(C)) of every output row are written as zeros (the 16-byte path and the
+ * planes: the whole pad [C, pitch)).  `rows` 16-byte aligned.  OCCD_EINVAL before any launch: a NULL pointer, C outside
+ * 1..32, S outside 1..2^28, pitch < round4(C) or pitch % 4 != 0, any other stride pair.
+ *
+ * occd_fuse_frames, one launch: for every voxel (i, j, l) of the X x Y x Z grid and every source k < K (float32; the
+ * three sums of a component are fused multiply-adds, b first, then the z, y and x terms)
+ *   s   = A_k (i + 1/2, j + 1/2, l + 1/2) + b_k        affine[k] = A_k row-major | b_k, grid units
+ *   idx = floor(s) per component;  ok = 0 <= idx < (X, Y, Z) and (masks[k] == NULL or masks[k][idx] != 0)
+ *   acc[c] += weights[k] * rows[k][idx][c],  wsum += weights[k],  n += 1        where ok, k ascending
+ * (nearest voxel, no interpolation; a non-finite s is not ok).  labels[n] = argmax_c acc[c], the lowest class on a tie;
+ * n_obs[n] = n; prob (when not NULL): rows of `pitch` floats, prob[n][c] = acc[c] / wsum for c < round4(C), channels
+ * past that are left alone.  A voxel with n == 0 gets label 0, n_obs 0 and a zero prob row.  Rows and prob 16-byte
+ * aligned; the channels [C, round4(C)) of the source rows must be finite (occd_fuse_store writes zeros).
+ * OCCD_EINVAL before any launch: a NULL argument / labels / n_obs / rows[k < K], C outside 1..32, K outside
+ * 1..OCCD_FUSE_MAX_SOURCES, a non-positive dim, X Y Z > 2^28, pitch < round4(C) (so also pitch < C) or pitch % 4 != 0.
+ * ------------------------------------------------------------------------ */
+#define OCCD_FUSE_MAX_SOURCES 8
+typedef struct OccdFuseArgs {
+    const float* rows[OCCD_FUSE_MAX_SOURCES];      /* (X Y Z, pitch) probability rows of source k; k = 0: the current frame */
+    const uint8_t* masks[OCCD_FUSE_MAX_SOURCES];   /* (X Y Z) bytes of source k, 0 = does not contribute, or NULL          */
+    float weights[OCCD_FUSE_MAX_SOURCES];
+    float affine[OCCD_FUSE_MAX_SOURCES][12];       /* target voxel centre -> source grid coordinates                       */
+    uint8_t* labels;                               /* (X Y Z)                                                              */
+    uint8_t* n_obs;                                /* (X Y Z) sources that contributed                                     */
+    float* prob;                                   /* (X Y Z, pitch), or NULL                                              */
+    int32_t X, Y, Z;
+    int32_t C, K, pitch;
+} OccdFuseArgs;
+int occd_fuse_store(const float* logits, float* rows, int64_t S, int32_t C, int64_t s_c, int64_t s_v, int32_t pitch,
+                    void* stream);
+int occd_fuse_frames(const OccdFuseArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

@@ -52,6 +52,8 @@ RenderView = abi.STRUCTS["OccdRenderView"]
 RenderArgs = abi.STRUCTS["OccdRenderArgs"]
 StereoArgs = abi.STRUCTS["OccdStereoArgs"]
 RENDER_MAX_VIEWS = abi.CONSTANTS["OCCD_RENDER_MAX_VIEWS"]
+FuseArgs = abi.STRUCTS["OccdFuseArgs"]
+FUSE_MAX_SOURCES = abi.CONSTANTS["OCCD_FUSE_MAX_SOURCES"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2021,6 +2023,64 @@ def render_voxels(labels, views, size, palette, target=None, fov=None, backgroun
         a.bg_colour[i] = int(bg_colour[i])
     _check(load().occd_render_voxels(ctypes.byref(a), _stream()), "occd_render_voxels")
     return (rgb, hit, face, depth) if aux else rgb
+
+
+# ----------------------------------------------------------------------------- temporal fusion (csrc/fuse.hip)
+def fuse_store(logits, rows):
+    """occd_fuse_store: softmax of ONE frame's logits (C, X, Y, Z) float32 -- contiguous planes or a channels-last view of
+    (X, Y, Z, cs) rows, read in place -- into `rows` (S, pitch) float32, S = X Y Z.  -> rows."""
+    if logits.dtype != torch.float32 or logits.dim() < 2 or not logits.is_cuda:
+        raise RuntimeError("fuse_store needs float32 GPU logits of shape (C, ...), got %s %s" % (tuple(logits.shape), logits.dtype))
+    C = int(logits.shape[0])
+    S = logits[0].numel()
+    if rows.dim() != 2 or rows.shape[0] != S or rows.device != logits.device:
+        raise RuntimeError("rows must be (S, pitch) = (%d, pitch) on %s, got %s on %s"
+                           % (S, logits.device, tuple(rows.shape), rows.device))
+    lay = _logit_layout(logits[None])
+    if lay is None:
+        logits = logits.contiguous()
+        lay = (C * S, S, 1)
+    _check(load().occd_fuse_store(logits.data_ptr(), _f32(rows, "rows"), S, C, lay[1], lay[2], int(rows.shape[1]), _stream()),
+           "occd_fuse_store")
+    return rows
+
+
+def fuse_frames(rows, affines, weights, dims, n_classes, masks=None, return_prob=False):
+    """occd_fuse_frames, one launch: K sources -- rows[k] (S, pitch) float32 probability rows, affines[k] the 12 float32
+    coefficients that take a target voxel centre into source k's grid, weights[k], masks[k] a (S,) uint8 / bool tensor or
+    None -- fused into the X x Y x Z target grid `dims`.  -> (labels, n_obs) uint8 (X, Y, Z) and the normalised
+    probabilities (S, pitch) float32, or None without return_prob (the contract is in include/occdepth_amd.h)."""
+    K = len(rows)
+    if not 1 <= K <= FUSE_MAX_SOURCES or len(affines) != K or len(weights) != K:
+        raise RuntimeError("fuse_frames takes 1..%d sources with one affine and one weight each" % FUSE_MAX_SOURCES)
+    X, Y, Z = (int(d) for d in dims)
+    S = X * Y * Z
+    dev = rows[0].device
+    pitch = int(rows[0].shape[1])
+    masks = [None] * K if masks is None else list(masks)
+    if len(masks) != K:
+        raise RuntimeError("masks must be None or one entry (a tensor or None) per source")
+    a = FuseArgs()
+    for k in range(K):
+        r = rows[k]
+        if r.dim() != 2 or tuple(r.shape) != (S, pitch) or r.device != dev:
+            raise RuntimeError("rows[%d] must be (%d, %d) on %s, got %s on %s" % (k, S, pitch, dev, tuple(r.shape), r.device))
+        a.rows[k] = _f32(r, "rows[%d]" % k)
+        if masks[k] is not None:
+            a.masks[k] = _ptr(_byte_mask(masks[k][None], 1, S, "masks[%d]" % k), "masks[%d]" % k)
+        a.weights[k] = float(weights[k])
+        coef = [float(v) for v in affines[k]]
+        if len(coef) != 12:
+            raise RuntimeError("affines[%d] must hold 12 values (A row-major, then b)" % k)
+        for i in range(12):
+            a.affine[k][i] = coef[i]
+    labels = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
+    n_obs = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
+    prob = torch.empty((S, pitch), dtype=torch.float32, device=dev) if return_prob else None
+    a.labels, a.n_obs, a.prob = _ptr(labels), _ptr(n_obs), _ptr(prob)
+    a.X, a.Y, a.Z, a.C, a.K, a.pitch = X, Y, Z, int(n_classes), K, pitch
+    _check(load().occd_fuse_frames(ctypes.byref(a), _stream()), "occd_fuse_frames")
+    return labels, n_obs, prob
 
 
 # ----------------------------------------------------------------------------- stereo depth targets (csrc/stereo.hip)

@@ -160,6 +160,15 @@ class OccDepth(_Base):
         if env("OCCDEPTH_RENDER_DIR", ""):
             self.enable_render(env("OCCDEPTH_RENDER_DIR"), every=int(env("OCCDEPTH_RENDER_EVERY", "1")),
                                mode=env("OCCDEPTH_RENDER_MODE", "class"))
+        # Temporal fusion of the test / validation predictions over a sequence (fuse.py), OFF by default:
+        # `enable_temporal_fusion()` -- or OCCDEPTH_FUSE=<window> OCCDEPTH_FUSE_POSES=<.../dataset/sequences>
+        # [OCCDEPTH_FUSE_DECAY=d] in the environment of an unmodified scripts/eval.py.  Off: nothing is imported, allocated
+        # or launched.
+        self.temporal_fusion = None
+        self.fused_metrics = {}
+        if env("OCCDEPTH_FUSE", "0") not in ("", "0"):
+            self.enable_temporal_fusion(env("OCCDEPTH_FUSE_POSES", ""), window=int(env("OCCDEPTH_FUSE")),
+                                        decay=float(env("OCCDEPTH_FUSE_DECAY", "1.0")))
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -711,6 +720,57 @@ class OccDepth(_Base):
             for name, h in zip(st["views"], host):
                 exp.add_image("val_render/" + name, h[0].numpy(), getattr(self, "global_step", 0), dataformats="HWC")
 
+    # ---------------------------------------------------------------- temporal fusion over a sequence (fuse.py)
+    def enable_temporal_fusion(self, poses_root, window=4, decay=1.0, max_gap=None):
+        """Fuse the prediction of every test / validation frame with up to `window - 1` earlier frames of its sequence
+        (fuse.SequenceFuser: ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt, weights decay^age, each
+        earlier frame inside its own `fov_mask_1`) and count the fused labels into a SECOND metric beside the ordinary
+        one: `val_fused/mIoU`, `val_fused/IoU` are logged and `test_epoch_end` prints a `test_fused======` block.  The
+        ordinary metrics stay on the unfused logits.  The ring holds `window` frames of probabilities on the GPU (168 MB
+        each at 256 x 256 x 32 x 20).  Frames must arrive in sequence order (no shuffling, one rank per sequence)."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("temporal fusion reads SemanticKITTI poses and is wired for the SemanticKITTI geometry "
+                                      "only; a %s model has no ego-motion to warp with" % self.dataset)
+        if not poses_root:
+            raise ValueError("temporal fusion needs the sequences directory (poses_root / OCCDEPTH_FUSE_POSES): "
+                             "<root>/<sequence>/poses.txt and calib.txt")
+        if not 1 <= int(window) <= 8:
+            raise ValueError("window must be 1..8, got %r" % (window,))
+        self.temporal_fusion = {"poses_root": str(poses_root), "window": int(window), "decay": float(decay),
+                                "max_gap": None if max_gap is None else int(max_gap), "fuser": None, "poses": {}}
+        self.fused_metrics = {}
+        return self
+
+    def _fuse_step(self, step_type, batch, ssc_pred, target):
+        """Push every batch item, in order, through the sequence fuser and count the fused labels."""
+        from .. import fuse
+        from ..loss.sscMetrics import SSCMetrics
+        st = self.temporal_fusion
+        ssc_pred = ssc_pred.detach()
+        B = ssc_pred.shape[0]
+        dims = tuple(int(d) for d in ssc_pred.shape[2:])
+        if st["fuser"] is None:
+            vs = 0.2 * float(self.full_scene_size[0]) / float(dims[0])
+            st["fuser"] = fuse.SequenceFuser(dims, self.n_classes, self._kitti_origin(batch), vs, window=st["window"],
+                                             decay=st["decay"], max_gap=st["max_gap"])
+        fov = self._report_fov(batch, target) if batch.get("fov_mask_1") is not None else None
+        fov = fov if torch.is_tensor(fov) else None
+        labels = []
+        for i in range(B):
+            seq = str(batch["sequence"][i])
+            frame = int(batch["frame_id"][i])
+            poses = st["poses"].get(seq)
+            if poses is None:
+                poses = st["poses"][seq] = fuse.read_kitti_poses(os.path.join(st["poses_root"], seq))
+            if frame not in poses:
+                raise KeyError("sequence %s has no pose for frame %d (%s)" % (seq, frame, os.path.join(st["poses_root"], seq, "poses.txt")))
+            out = st["fuser"].push(ssc_pred[i].float(), poses[frame], key=(seq, frame), fov_mask=None if fov is None else fov[i])
+            labels.append(out["y_pred"])
+        metric = self.fused_metrics.get(step_type)
+        if metric is None:
+            metric = self.fused_metrics[step_type] = SSCMetrics(self.n_classes)
+        metric.add_batch(torch.stack(labels), target)
+
     def _kitti_origin(self, batch=None):
         """SemanticKITTI voxel origin (kitti_dataset.py:82: vox_origin = (0, -25.6, -2) for the 51.2 m wide scene): the grid
         is centred on the sensor in y, whatever the scene width of a reduced test config.  A batch that carries its own
@@ -1026,6 +1086,8 @@ class OccDepth(_Base):
                 metric.add_batch(ssc_pred.detach().argmax(1).cpu().numpy(), target.cpu().numpy())
         if self.eval_report is not None and step_type in ("test", "val"):
             self._report_count(step_type, batch, ssc_pred, target)
+        if self.temporal_fusion is not None and step_type in ("test", "val"):
+            self._fuse_step(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
         if self.render is not None and step_type in ("test", "val"):
             self._render_step(step_type, batch, ssc_pred, target)     # last: its copy waits for the step's kernels
@@ -1361,6 +1423,12 @@ class OccDepth(_Base):
                 self.log("val_region/{}/mIoU".format(name), stats["iou_ssc_mean"], sync_dist=True)
                 self.log("val_region/{}/IoU".format(name), stats["iou"], sync_dist=True)
             rep.reset()
+        fused = self.fused_metrics.get("val")
+        if fused is not None:
+            stats = self._epoch_stats(fused)
+            self.log("val_fused/mIoU", stats["iou_ssc_mean"], sync_dist=True)
+            self.log("val_fused/IoU", stats["iou"], sync_dist=True)
+            fused.reset()
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -1370,7 +1438,8 @@ class OccDepth(_Base):
     def test_epoch_end(self, outputs):
         """Reference :562-580: the printed evaluation report of scripts/eval.py."""
         classes = self.class_names
-        for prefix, metric in (("test", self.test_metrics),):
+        fused = self.fused_metrics.get("test")
+        for prefix, metric in (("test", self.test_metrics),) + ((("test_fused", fused),) if fused is not None else ()):
             print("{}======".format(prefix))
             stats = self._epoch_stats(metric)
             print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(

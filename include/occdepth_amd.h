@@ -75,7 +75,9 @@ extern "C" {
  *     struct or prototype: occd_gemm_f16x2_packed_elems, occd_gemm_f16x2_pack and occd_gemm_args.pre = OCCD_GEMM_PRE_F16X2
  *     (the two-term fp16 split of the 2-D GEMMs that read pre-split weights: K16p, K21, K16 on the A image); likewise
  *     OCCD_FUSE_MAX_SOURCES, OccdFuseArgs, occd_fuse_store and occd_fuse_frames (temporal fusion of class probabilities
- *     over a sequence, csrc/fuse.hip): a new struct and new functions only */
+ *     over a sequence, csrc/fuse.hip): a new struct and new functions only; likewise OCCD_MAP_BRICK, OccdMapFrameArgs,
+ *     OccdMapExtractArgs, occd_map_integrate, occd_map_brick_labels, occd_map_count and occd_map_extract (the sequence-level
+ *     semantic voxel map, csrc/semantic_map.hip): two new structs and new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1299,6 +1301,74 @@ typedef struct OccdFuseArgs {
 int occd_fuse_store(const float* logits, float* rows, int64_t S, int32_t C, int64_t s_c, int64_t s_v, int32_t pitch,
                     void* stream);
 int occd_fuse_frames(const OccdFuseArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K30: the sequence-level semantic map (csrc/semantic_map.hip).  Additive (OCCD_ABI_VERSION note).  Every frame's labelled
+ * voxels vote into one sparse world-frame voxel map; extraction decides every voxel by its votes.  No atomics, no
+ * allocation, no host sync; every output byte depends on the inputs alone.
+ *
+ * World lattice: the map's voxel size is the frame grid's voxel size v; world voxel (I, J, L), signed, has its centre at
+ * ((I + 1/2) v, (J + 1/2) v, (L + 1/2) v) metres in the world frame of the poses (4 x 4 sensor -> world).
+ * Bricks: OCCD_MAP_BRICK^3 = 4096 voxels; brick key = floor((I, J, L) / 16) (negative coordinates floor).  The pool
+ * `votes` holds `capacity` bricks; brick `slot` is 4096 rows of `pitch` unsigned 16-bit counters, row (i*16 + j)*16 + l
+ * for the brick-local voxel (i, j, l), counter c of a row = the votes for class c.  pitch >= C and pitch % 4 == 0 (rows
+ * are read in 8-byte pieces; `votes` 8-byte aligned): 8192 * pitch bytes per brick, 163840 at C = 20.  Counters saturate
+ * at 65535.
+ *
+ * occd_map_integrate, one launch per frame, one workgroup per table row (= brick).  Row r of `table` is 16 int32:
+ *   slot | key[3] | Aq[9] row-major | cq[3]
+ * with Aq = rint(R^T 2^16) and cq = rint(c_k 2^16), c_k = (R^T ((16 k + 1/2) v - t) - o) / v for the pose [R|t], the grid
+ * origin o (metres, sensor frame) and the key k, composed by the host in float64 (|c_k| < 2^14).  For the brick-local voxel
+ * (i, j, l), in int32 only (wrapping):
+ *   gq[r] = Aq[r][0] i + Aq[r][1] j + Aq[r][2] l + cq[r];   idx[r] = gq[r] >> 16   (arithmetic shift = floor)
+ * and the voxel's counter `label` is incremented iff 0 <= idx < (X, Y, Z), (mask == NULL or mask[n] != 0) and label < C,
+ * with n = (idx0 Y + idx1) Z + idx2 and label = labels[n] read as 1 or 2 bytes (label_bytes).  So 255 never votes.  A
+ * row whose slot is outside [0, capacity) is skipped.  The slots of one launch must be distinct (one owner per counter).
+ *
+ * Extraction: label = argmax_c votes[c], the lowest class on a tie; n_obs = sum_c votes[c].  Row r of the extraction
+ * `table` is 4 int32: slot | key[3]; a slot outside [0, capacity) is a brick that is not in the map.
+ *   occd_map_brick_labels: dense[r][4096] = label, 255 where n_obs == 0 or the brick is not in the map.
+ *   occd_map_count:   counts[r] = number of kept voxels of brick r: n_obs >= min_obs (and >= 1), label != 0 unless
+ *                     include_empty.
+ *   occd_map_extract: the kept voxels of brick r, in (i, j, l) row-major order, go to the entries offsets[r] ... of
+ *                     coords (3 int32 each: 16 key + (i, j, l)), labels (uint8) and n_obs (uint16, the sum saturated at
+ *                     65535).  offsets = the exclusive prefix sum of counts (int64).  Wave ballots and an LDS hand-off
+ *                     order the writes: bit-identical from run to run.
+ * `table_host`, when not NULL, is the same table in host memory: its slots are checked before the launch (integrate: a
+ * slot outside [0, capacity); extraction: a slot >= capacity).  OCCD_EINVAL before any launch: a NULL argument or a NULL
+ * votes / table / labels / output pointer, C outside 1..32, a non-positive dim, X Y Z > 2^28, n_bricks <= 0, capacity <= 0,
+ * such a slot in table_host, label_bytes not 1 or 2, pitch < C or pitch % 4 != 0, min_obs < 0, n_out <= 0 (extract).
+ * ------------------------------------------------------------------------ */
+#define OCCD_MAP_BRICK 16
+typedef struct OccdMapFrameArgs {
+    uint16_t* votes;               /* (capacity, 4096, pitch) vote counters                                          */
+    const int32_t* table;          /* (n_bricks, 16) device                                                          */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    const void* labels;            /* (X Y Z) labels of the frame, label_bytes each                                  */
+    const uint8_t* mask;           /* (X Y Z) bytes, 0 = does not vote, or NULL                                      */
+    int32_t n_bricks, capacity;
+    int32_t X, Y, Z;
+    int32_t C, pitch, label_bytes;
+} OccdMapFrameArgs;
+typedef struct OccdMapExtractArgs {
+    const uint16_t* votes;         /* (capacity, 4096, pitch)                                                        */
+    const int32_t* table;          /* (n_bricks, 4) device                                                           */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    uint8_t* dense;                /* occd_map_brick_labels: (n_bricks, 4096)                                        */
+    int32_t* counts;               /* occd_map_count: (n_bricks)                                                     */
+    const int64_t* offsets;        /* occd_map_extract: (n_bricks) exclusive prefix sum of counts                    */
+    int32_t* coords;               /* occd_map_extract: (N, 3)                                                       */
+    uint8_t* labels;               /* occd_map_extract: (N)                                                          */
+    uint16_t* n_obs;               /* occd_map_extract: (N)                                                          */
+    int64_t n_out;                 /* occd_map_extract: N = the sum of counts; no entry at or past it is written     */
+    int32_t n_bricks, capacity;
+    int32_t C, pitch;
+    int32_t min_obs, include_empty;
+} OccdMapExtractArgs;
+int occd_map_integrate(const OccdMapFrameArgs* a, void* stream);
+int occd_map_brick_labels(const OccdMapExtractArgs* a, void* stream);
+int occd_map_count(const OccdMapExtractArgs* a, void* stream);
+int occd_map_extract(const OccdMapExtractArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

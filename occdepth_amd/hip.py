@@ -54,6 +54,9 @@ StereoArgs = abi.STRUCTS["OccdStereoArgs"]
 RENDER_MAX_VIEWS = abi.CONSTANTS["OCCD_RENDER_MAX_VIEWS"]
 FuseArgs = abi.STRUCTS["OccdFuseArgs"]
 FUSE_MAX_SOURCES = abi.CONSTANTS["OCCD_FUSE_MAX_SOURCES"]
+MapFrameArgs = abi.STRUCTS["OccdMapFrameArgs"]
+MapExtractArgs = abi.STRUCTS["OccdMapExtractArgs"]
+MAP_BRICK = abi.CONSTANTS["OCCD_MAP_BRICK"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2081,6 +2084,87 @@ def fuse_frames(rows, affines, weights, dims, n_classes, masks=None, return_prob
     a.X, a.Y, a.Z, a.C, a.K, a.pitch = X, Y, Z, int(n_classes), K, pitch
     _check(load().occd_fuse_frames(ctypes.byref(a), _stream()), "occd_fuse_frames")
     return labels, n_obs, prob
+
+
+# ----------------------------------------------------------------------------- sequence-level semantic map (csrc/semantic_map.hip)
+_MAP_BRICK_VOX = MAP_BRICK ** 3
+
+
+def _map_operands(a, votes, table, table_host, words, n_classes):
+    """Fill the fields the two argument structs share; -> the number of table rows."""
+    if votes.dtype != torch.int16 or votes.dim() != 3 or votes.shape[1] != _MAP_BRICK_VOX:
+        raise RuntimeError("votes must be an int16 (capacity, %d, pitch) pool, got %s %s"
+                           % (_MAP_BRICK_VOX, tuple(votes.shape), votes.dtype))
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != words or table.device != votes.device:
+        raise RuntimeError("table must be int32 (n_bricks, %d) on %s, got %s %s on %s"
+                           % (words, votes.device, tuple(table.shape), table.dtype, table.device))
+    a.votes, a.table = _ptr(votes, "votes"), _ptr(table, "table")
+    if table_host is not None:
+        if table_host.is_cuda or table_host.dtype != torch.int32 or table_host.shape != table.shape or \
+                not table_host.is_contiguous():
+            raise RuntimeError("table_host must be the table's contiguous int32 copy in host memory")
+        a.table_host = table_host.data_ptr()
+    a.n_bricks, a.capacity = int(table.shape[0]), int(votes.shape[0])
+    a.C, a.pitch = int(n_classes), int(votes.shape[2])
+    return a.n_bricks
+
+
+def map_integrate(votes, table, labels, dims, n_classes, mask=None, table_host=None):
+    """occd_map_integrate, one launch: the frame `labels` (X Y Z entries, uint8 / int16 / uint16) votes into the bricks
+    the (n, 16) int32 `table` names (slot | key | Aq | cq per row, semantic_map.brick_coefficients), inside `mask`
+    (X Y Z bool / uint8 entries) when given.  votes: the int16 (capacity, 4096, pitch) pool, updated in place.  The
+    contract is in include/occdepth_amd.h."""
+    X, Y, Z = (int(d) for d in dims)
+    if labels.dtype not in _LABEL_BYTES or labels.numel() != X * Y * Z:
+        raise RuntimeError("labels must hold X Y Z = %d uint8 / int16 / uint16 entries, got %s %s"
+                           % (X * Y * Z, tuple(labels.shape), labels.dtype))
+    a = MapFrameArgs()
+    _map_operands(a, votes, table, table_host, 16, n_classes)
+    a.labels, a.label_bytes = _ptr(labels, "labels"), _LABEL_BYTES[labels.dtype]
+    if mask is not None:
+        a.mask = _ptr(_byte_mask(mask.reshape(1, -1), 1, X * Y * Z, "mask"), "mask")
+    for t, name in ((labels, "labels"), (mask, "mask")):
+        if t is not None and t.device != votes.device:
+            raise RuntimeError(f"{name} is on {t.device}, votes on {votes.device}")
+    a.X, a.Y, a.Z = X, Y, Z
+    _check(load().occd_map_integrate(ctypes.byref(a), _stream()), "occd_map_integrate")
+    return votes
+
+
+def map_brick_labels(votes, table, n_classes, table_host=None):
+    """occd_map_brick_labels: the (n, 4) int32 `table` (slot | key per row; a negative slot = not in the map) ->
+    (n, 16, 16, 16) uint8 labels, 255 where a voxel has no vote or its brick is not in the map."""
+    a = MapExtractArgs()
+    n = _map_operands(a, votes, table, table_host, 4, n_classes)
+    dense = torch.empty((n, MAP_BRICK, MAP_BRICK, MAP_BRICK), dtype=torch.uint8, device=votes.device)
+    a.dense = dense.data_ptr()
+    _check(load().occd_map_brick_labels(ctypes.byref(a), _stream()), "occd_map_brick_labels")
+    return dense
+
+
+def map_extract(votes, table, n_classes, min_obs=1, include_empty=False, table_host=None):
+    """occd_map_count -> exclusive scan -> occd_map_extract: the voxels of the table's bricks with at least `min_obs`
+    votes (and a label other than 0 unless include_empty), bricks in table order, voxels in (i, j, l) order ->
+    coords (N, 3) int32 world voxel indices, labels (N,) uint8, n_obs (N,) int16 holding uint16 bits.  One host
+    synchronisation, for N."""
+    a = MapExtractArgs()
+    n = _map_operands(a, votes, table, table_host, 4, n_classes)
+    dev = votes.device
+    a.min_obs, a.include_empty = int(min_obs), int(bool(include_empty))
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    a.counts = counts.data_ptr()
+    _check(load().occd_map_count(ctypes.byref(a), _stream()), "occd_map_count")
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    offsets = (ends - counts).contiguous()
+    N = int(ends[-1])
+    coords = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    labels = torch.empty((N,), dtype=torch.uint8, device=dev)
+    n_obs = torch.empty((N,), dtype=torch.int16, device=dev)
+    if N:
+        a.offsets, a.coords, a.labels, a.n_obs, a.n_out = offsets.data_ptr(), coords.data_ptr(), labels.data_ptr(), \
+            n_obs.data_ptr(), N
+        _check(load().occd_map_extract(ctypes.byref(a), _stream()), "occd_map_extract")
+    return coords, labels, n_obs
 
 
 # ----------------------------------------------------------------------------- stereo depth targets (csrc/stereo.hip)

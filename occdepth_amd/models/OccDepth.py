@@ -169,6 +169,14 @@ class OccDepth(_Base):
         if env("OCCDEPTH_FUSE", "0") not in ("", "0"):
             self.enable_temporal_fusion(env("OCCDEPTH_FUSE_POSES", ""), window=int(env("OCCDEPTH_FUSE")),
                                         decay=float(env("OCCDEPTH_FUSE_DECAY", "1.0")))
+        # Sequence-level semantic map of the test / validation frames (semantic_map.py), OFF by default:
+        # `enable_semantic_map()` -- or OCCDEPTH_MAP_DIR=<dir> OCCDEPTH_MAP_POSES=<.../dataset/sequences> (falls back to
+        # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] in the environment of an unmodified scripts/eval.py.  Off: nothing is
+        # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
+        self.semantic_map = None
+        if env("OCCDEPTH_MAP_DIR", ""):
+            self.enable_semantic_map(env("OCCDEPTH_MAP_DIR"), env("OCCDEPTH_MAP_POSES", "") or env("OCCDEPTH_FUSE_POSES", ""),
+                                     min_obs=int(env("OCCDEPTH_MAP_MIN_OBS", "1")))
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -771,6 +779,84 @@ class OccDepth(_Base):
             metric = self.fused_metrics[step_type] = SSCMetrics(self.n_classes)
         metric.add_batch(torch.stack(labels), target)
 
+    # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
+    def enable_semantic_map(self, out_dir, poses_root, min_obs=1):
+        """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
+        ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
+        prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
+        batch has one.  At the end of the epoch every sequence's maps are written to <out_dir>/<step>_<sequence>_pred.ply
+        and _gt.ply (voxels with at least `min_obs` votes), the prediction maps are scored against the ground-truth maps
+        where both were observed -- `val_map/mIoU`, `val_map/IoU` are logged, `test_epoch_end` prints a `test_map======`
+        block -- and the maps are released.  Votes commute, so frames may arrive in any order; a sequence must stay on one
+        rank.  Memory: 163840 bytes per 16^3 brick and map at 20 classes."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("the semantic map reads SemanticKITTI poses and is wired for the SemanticKITTI geometry "
+                                      "only; a %s model has no ego-motion to lay its frames out with" % self.dataset)
+        if not poses_root:
+            raise ValueError("the semantic map needs the sequences directory (poses_root / OCCDEPTH_MAP_POSES, or "
+                             "OCCDEPTH_FUSE_POSES): <root>/<sequence>/poses.txt and calib.txt")
+        if not out_dir:
+            raise ValueError("the semantic map needs a directory to write its PLY files to (out_dir / OCCDEPTH_MAP_DIR)")
+        if int(min_obs) < 1:
+            raise ValueError("min_obs must be >= 1, got %r" % (min_obs,))
+        self.semantic_map = {"out_dir": str(out_dir), "poses_root": str(poses_root), "min_obs": int(min_obs),
+                             "maps": {}, "poses": {}, "paths": []}
+        return self
+
+    def _map_step(self, step_type, batch, ssc_pred, target):
+        """Every batch item votes into its sequence's prediction map and ground-truth map."""
+        from .. import fuse, hip, semantic_map
+        st = self.semantic_map
+        ssc_pred = ssc_pred.detach()
+        B = ssc_pred.shape[0]
+        dims = tuple(int(d) for d in ssc_pred.shape[2:])
+        vs = 0.2 * float(self.full_scene_size[0]) / float(dims[0])
+        origin = self._kitti_origin(batch)
+        fov = self._report_fov(batch, target) if batch.get("fov_mask_1") is not None else None
+        fov = fov if torch.is_tensor(fov) else None
+        items = []
+        for i in range(B):                                               # every pose first: a refusal launches nothing
+            seq = str(batch["sequence"][i])
+            frame = int(batch["frame_id"][i])
+            poses = st["poses"].get(seq)
+            if poses is None:
+                poses = st["poses"][seq] = fuse.read_kitti_poses(os.path.join(st["poses_root"], seq))
+            if frame not in poses:
+                raise KeyError("sequence %s has no pose for frame %d (%s)" % (seq, frame, os.path.join(st["poses_root"], seq, "poses.txt")))
+            items.append((seq, poses[frame]))
+        pred = hip.argmax_labels_u16(ssc_pred.float())                   # (B, X, Y, Z) uint16 bits, the unfused logits
+        gt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
+        for i, (seq, pose) in enumerate(items):
+            pair = st["maps"].get((step_type, seq))
+            if pair is None:
+                pair = st["maps"][(step_type, seq)] = tuple(semantic_map.SemanticMap(self.n_classes, vs, origin, dims)
+                                                            for _ in range(2))
+            mask = None if fov is None else fov[i]
+            pair[0].integrate(pred[i], pose, mask=mask)
+            pair[1].integrate(gt[i].reshape(dims), pose, mask=mask)
+
+    def _map_epoch_end(self, step_type):
+        """Write and score the maps of `step_type`, release them; -> the statistics over its sequences, or None."""
+        from .. import render, semantic_map
+        from ..loss.sscMetrics import SSCMetrics
+        st = self.semantic_map
+        mine = sorted(key for key in st["maps"] if key[0] == step_type)
+        if not mine:
+            return None
+        os.makedirs(st["out_dir"], exist_ok=True)
+        metric = SSCMetrics(self.n_classes)
+        colours = render.palette("kitti" if self.n_classes == 20 else int(self.n_classes))
+        for key in mine:
+            pair = st["maps"].pop(key)
+            for m, name in zip(pair, ("pred", "gt")):
+                coords, labels, n_obs = m.extract(min_obs=st["min_obs"])
+                path = os.path.join(st["out_dir"], "%s_%s_%s.ply" % (step_type, key[1], name))
+                st["paths"].append(semantic_map.write_ply(path, coords, labels, n_obs, m.voxel_size, colours))
+            semantic_map.map_confusion(pair[0], pair[1], metric)
+            for m in pair:
+                m.release()
+        return self._epoch_stats(metric)
+
     def _kitti_origin(self, batch=None):
         """SemanticKITTI voxel origin (kitti_dataset.py:82: vox_origin = (0, -25.6, -2) for the 51.2 m wide scene): the grid
         is centred on the sensor in y, whatever the scene width of a reduced test config.  A batch that carries its own
@@ -1088,6 +1174,8 @@ class OccDepth(_Base):
             self._report_count(step_type, batch, ssc_pred, target)
         if self.temporal_fusion is not None and step_type in ("test", "val"):
             self._fuse_step(step_type, batch, ssc_pred, target)
+        if getattr(self, "semantic_map", None) is not None and step_type in ("test", "val"):
+            self._map_step(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
         if self.render is not None and step_type in ("test", "val"):
             self._render_step(step_type, batch, ssc_pred, target)     # last: its copy waits for the step's kernels
@@ -1429,6 +1517,11 @@ class OccDepth(_Base):
             self.log("val_fused/mIoU", stats["iou_ssc_mean"], sync_dist=True)
             self.log("val_fused/IoU", stats["iou"], sync_dist=True)
             fused.reset()
+        if getattr(self, "semantic_map", None) is not None:
+            stats = self._map_epoch_end("val")
+            if stats is not None:
+                self.log("val_map/mIoU", stats["iou_ssc_mean"], sync_dist=True)
+                self.log("val_map/IoU", stats["iou"], sync_dist=True)
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -1449,6 +1542,15 @@ class OccDepth(_Base):
             print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
             metric.reset()
         self._print_region_report("test")
+        if getattr(self, "semantic_map", None) is not None:
+            stats = self._map_epoch_end("test")
+            if stats is not None:
+                print("test_map======")
+                print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(
+                    stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
+                print("class IoU: {}, ".format(classes))
+                print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
+                print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

@@ -1,0 +1,352 @@
+"""Sequence-level semantic map (K30): every frame's labelled voxels are laid into one sparse world-frame voxel map by
+the ego-motion and voxels seen from several frames are decided by vote (csrc/semantic_map.hip: hip.map_integrate lets a
+frame vote in one launch, hip.map_brick_labels / hip.map_extract decide).
+
+    poses = fuse.read_kitti_poses(".../dataset/sequences/08")
+    m = SemanticMap(20, 0.2, (0.0, -25.6, -2.0), (256, 256, 32))
+    m.integrate(labels, poses[frame], mask=fov_mask_1)               # (X, Y, Z) uint8 / int16 on the GPU
+    coords, labels, n_obs = m.extract(min_obs=2)
+    write_ply("08.ply", coords, labels, n_obs, 0.2, render.palette("kitti"))
+    map_confusion(pred_map, gt_map, SSCMetrics(20))                  # map mIoU where both maps were observed
+
+The world lattice has the frame grid's voxel size; voxels live in 16^3 bricks of 16-bit vote counters, one row of `pitch`
+= n_classes rounded up to 4 counters per voxel (8192 * pitch bytes per brick: 163840 at 20 classes).  The host side is
+numpy in float64 and quantises to the int32 fixed point the kernel computes in (include/occdepth_amd.h).  The effect on
+any score is not measured (no checkpoint and no dataset where this was built).
+"""
+import numpy as np
+import torch
+
+from . import hip
+
+BRICK = hip.MAP_BRICK
+FRAC = 16                                   # fractional bits of the fixed point
+C_LIMIT = float(1 << 14)                    # |c_k| below this: gq stays inside int32
+KEY_BITS = 21                               # a key component lies in [-2^20, 2^20)
+_KEY_OFF = 1 << (KEY_BITS - 1)
+_SPHERE = 8.0 * np.sqrt(3.0) + 1.0          # a brick's bounding sphere about local (7.5, 7.5, 7.5), plus one voxel
+_AXIS_MARGIN = 2.0 ** -8                    # voxels; the quantised transform is within 46 * 2^-17 of the exact one
+
+
+# ----------------------------------------------------------------------------------------------------- geometry
+def _pose(pose):
+    pose = np.asarray(pose, dtype=np.float64)
+    if pose.shape != (4, 4):
+        raise ValueError("pose must be 4 x 4 (sensor -> world), got %r" % (pose.shape,))
+    return pose[:3, :3], pose[:3, 3]
+
+
+def _brick_offsets(pose, keys, vox_origin, voxel_size):
+    """c_k = (R^T ((16 k + 1/2) v - t) - o) / v, (n, 3) float64: the grid coordinate of brick k's local voxel (0, 0, 0)."""
+    R, t = _pose(pose)
+    v = float(voxel_size)
+    keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+    org = np.asarray(vox_origin, dtype=np.float64).reshape(3)
+    world = (BRICK * keys.astype(np.float64) + 0.5) * v - t
+    return (world @ R - org) / v            # rows of (R^T world^T)^T
+
+
+def brick_coefficients(pose, keys, vox_origin, voxel_size):
+    """-> Aq (3, 3) int32 = rint(R^T 2^16) and cq (n, 3) int32 = rint(c_k 2^16) for the bricks `keys` (n, 3): brick-local
+    voxel (i, j, l) falls into the frame voxel (Aq (i, j, l) + cq) >> 16.  |c_k| >= 2^14 is refused."""
+    R, _ = _pose(pose)
+    c = _brick_offsets(pose, keys, vox_origin, voxel_size)
+    if c.size and not np.abs(c).max() < C_LIMIT:
+        raise ValueError("a brick lies %.0f voxels from the frame's grid origin: the fixed-point transform takes less "
+                         "than 2^14 = %d" % (np.abs(c).max(), int(C_LIMIT)))
+    scale = float(1 << FRAC)
+    return np.rint(R.T * scale).astype(np.int32), np.rint(c * scale).astype(np.int32)
+
+
+def frame_bricks(pose, vox_origin, voxel_size, dims):
+    """The keys (n, 3) int64, ascending, of every brick that can hold a voxel of the frame: the brick range of the
+    grid's eight corners in world voxels, less the bricks whose bounding sphere (radius 8 sqrt 3, plus a voxel of margin)
+    misses the grid box, less those whose extent along a grid axis misses it.  Over-selects; never drops a voting brick."""
+    R, t = _pose(pose)
+    v = float(voxel_size)
+    dims = np.asarray(dims, dtype=np.float64).reshape(3)
+    org = np.asarray(vox_origin, dtype=np.float64).reshape(3)
+    corners = np.array([[x, y, z] for x in (0.0, dims[0]) for y in (0.0, dims[1]) for z in (0.0, dims[2])])
+    world = ((corners * v + org) @ R.T + t) / v
+    lo = np.floor((np.floor(world.min(0)) - 1.0) / BRICK).astype(np.int64)
+    hi = np.floor((np.floor(world.max(0)) + 1.0) / BRICK).astype(np.int64)
+    k0, k1, k2 = np.meshgrid(*(np.arange(lo[a], hi[a] + 1) for a in range(3)), indexing="ij")
+    keys = np.stack([k0, k1, k2], -1).reshape(-1, 3)                      # ascending (k0, k1, k2)
+    centre = _brick_offsets(pose, keys, vox_origin, voxel_size) + 7.5 * R.T.sum(1)
+    gap = np.maximum(np.maximum(-centre, centre - dims), 0.0)
+    sphere = (gap * gap).sum(1) <= _SPHERE * _SPHERE
+    # and along each grid axis the brick's voxel centres reach 7.5 sum_c |R^T[r][c]| from its centre; the margin covers the
+    # fixed point's 3.5e-4 voxel with room to spare, and keeps a brick that merely touches the grid from the outside out
+    reach = 7.5 * np.abs(R.T).sum(1) + _AXIS_MARGIN
+    return keys[sphere & (gap <= reach).all(1)]
+
+
+def pack_keys(keys):
+    """(n, 3) keys -> (n,) int64 whose order is the ascending (k0, k1, k2) order."""
+    keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+    if keys.size and (keys.min() < -_KEY_OFF or keys.max() >= _KEY_OFF):
+        raise ValueError("brick keys must lie in [-2^20, 2^20)")
+    k = keys + _KEY_OFF
+    return (k[:, 0] << (2 * KEY_BITS)) | (k[:, 1] << KEY_BITS) | k[:, 2]
+
+
+def unpack_keys(packed):
+    p = np.asarray(packed, dtype=np.int64).reshape(-1)
+    m = (1 << KEY_BITS) - 1
+    return np.stack([p >> (2 * KEY_BITS), (p >> KEY_BITS) & m, p & m], -1) - _KEY_OFF
+
+
+# ----------------------------------------------------------------------------------------------------- the map
+class SemanticMap:
+    """A growing sparse voxel map of vote counters.
+
+    integrate() selects the bricks a frame can touch (frame_bricks), looks them up in the host directory {key -> pool
+    slot}, gives new ones zeroed slots, and sends one table -- slot, key and the 12 fixed-point coefficients per brick --
+    to the device in one asynchronous copy from a pinned buffer of its own (never one a copy in flight may still read),
+    followed by one launch.  No host synchronisation, unless the pool has to grow.
+
+    The pool `votes` is one (capacity, 16, 16, 16, pitch) int16 tensor holding uint16 bits.  The capacity is a multiple of
+    `chunk_bricks`; when it runs out, the pool is reallocated and copied at the needed size rounded up to a chunk, and by
+    at least half again, so the copies stay amortised.  `max_bricks` bounds it.  Over-selected bricks keep their slots
+    (all zero).  At 20 classes a brick is 163840 bytes; a straight drive at 256 x 256 x 32 and a 45 degree heading adds
+    2.72 MB of map per metre of new ground (profiles/map_ab.txt).
+    """
+
+    def __init__(self, n_classes, voxel_size, vox_origin, dims, max_bricks=None, chunk_bricks=1024):
+        self.n_classes = int(n_classes)
+        if not 1 <= self.n_classes <= 32:
+            raise ValueError("1..32 classes, got %r" % (n_classes,))
+        self.voxel_size = float(voxel_size)
+        if not self.voxel_size > 0.0:
+            raise ValueError("voxel_size must be positive, got %r" % (voxel_size,))
+        self.vox_origin = tuple(float(x) for x in np.asarray(vox_origin, dtype=np.float64).reshape(3))
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 1 or self.dims[0] * self.dims[1] * self.dims[2] > 1 << 28:
+            raise ValueError("dims must be (X, Y, Z) with X Y Z <= 2^28, got %r" % (dims,))
+        self.chunk_bricks = int(chunk_bricks)
+        self.max_bricks = None if max_bricks is None else int(max_bricks)
+        if self.chunk_bricks < 1 or (self.max_bricks is not None and self.max_bricks < 1):
+            raise ValueError("chunk_bricks and max_bricks must be >= 1")
+        self.pitch = hip.round_up(self.n_classes, 4)
+        self.brick_bytes = BRICK ** 3 * self.pitch * 2
+        self.votes = None                   # (capacity, 16, 16, 16, pitch) int16, with the first integrate
+        self.directory = {}                 # packed key -> slot
+        self.grown = 0                      # pool (re)allocations so far
+
+    # ------------------------------------------------------------------------------------------------ pool
+    @property
+    def n_bricks(self):
+        return len(self.directory)
+
+    @property
+    def capacity(self):
+        return 0 if self.votes is None else int(self.votes.shape[0])
+
+    @property
+    def nbytes(self):
+        return self.capacity * self.brick_bytes
+
+    def reset(self):
+        """Forget every brick; the pool keeps its memory, zeroed."""
+        self.directory = {}
+        if self.votes is not None:
+            self.votes.zero_()
+
+    def release(self):
+        """Forget every brick and give the pool's memory back."""
+        self.directory = {}
+        self.votes = None
+
+    def pool(self):
+        return self.votes.view(self.capacity, BRICK ** 3, self.pitch)
+
+    def _reserve(self, need, device):
+        if self.max_bricks is not None and need > self.max_bricks:
+            raise RuntimeError("the map needs %d bricks, max_bricks = %d allows %.1f MB of vote counters (%d bytes per "
+                               "brick at %d classes)" % (need, self.max_bricks, self.max_bricks * self.brick_bytes / 1e6,
+                                                         self.brick_bytes, self.n_classes))
+        cap = self.capacity
+        if need <= cap:
+            return
+        new_cap = hip.round_up(max(need, cap + cap // 2), self.chunk_bricks)
+        if self.max_bricks is not None:
+            new_cap = min(new_cap, self.max_bricks)
+        votes = torch.zeros((new_cap, BRICK, BRICK, BRICK, self.pitch), dtype=torch.int16, device=device)
+        if cap:
+            votes[:cap].copy_(self.votes)
+        self.votes = votes
+        self.grown += 1
+
+    def slots(self, keys, create=False, device=None):
+        """(n, 3) keys -> (n,) int32 pool slots, -1 for a key that is not in the map (create: it takes the next slot)."""
+        packed = pack_keys(keys).tolist()
+        d = self.directory
+        out = [d.get(p, -1) for p in packed]
+        if create:
+            new = [i for i, s in enumerate(out) if s < 0]
+            if new:
+                self._reserve(len(d) + len(new), device)
+                for i in new:
+                    out[i] = d[packed[i]] = len(d)
+        return np.asarray(out, dtype=np.int32).reshape(-1)
+
+    def upload(self, table, device):
+        """One table -> (device copy, host copy).  On a GPU the host copy is a fresh pinned tensor: the caching host
+        allocator hands its memory out again only after the asynchronous copy that reads it has run."""
+        host = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32))
+        if torch.device(device).type != "cuda":
+            return host, host
+        host = host.pin_memory()
+        return host.to(device, non_blocking=True), host
+
+    # ------------------------------------------------------------------------------------------------ integrate
+    def frame_table(self, pose, device):
+        """The (n, 16) int32 launch table of one frame -- slot | key | Aq | cq per brick -- with new bricks admitted."""
+        keys = frame_bricks(pose, self.vox_origin, self.voxel_size, self.dims)
+        Aq, cq = brick_coefficients(pose, keys, self.vox_origin, self.voxel_size)
+        table = np.empty((len(keys), 16), dtype=np.int32)
+        table[:, 0] = self.slots(keys, create=True, device=device)
+        table[:, 1:4] = keys
+        table[:, 4:13] = Aq.reshape(9)
+        table[:, 13:16] = cq
+        return table
+
+    def integrate(self, labels, pose, mask=None):
+        """One frame votes: labels (X, Y, Z) uint8 / int16 (uint16 bits) on the GPU, pose 4 x 4 sensor -> world, mask the
+        frame's own (X Y Z) bool / uint8 table or None.  A label >= n_classes (255) does not vote."""
+        if tuple(labels.shape) != self.dims:
+            raise ValueError("integrate takes (X, Y, Z) = %r labels, got %r" % (self.dims, tuple(labels.shape)))
+        if self.votes is not None and labels.device != self.votes.device:
+            raise ValueError("labels are on %s, the map on %s" % (labels.device, self.votes.device))
+        S = self.dims[0] * self.dims[1] * self.dims[2]
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if mask.numel() != S:
+                raise ValueError("mask must hold X Y Z = %d entries, got %r" % (S, tuple(mask.shape)))
+            mask = mask.to(labels.device)
+            if mask.dtype not in (torch.bool, torch.uint8):
+                mask = mask != 0
+        table = self.frame_table(pose, labels.device)
+        if not len(table):
+            return self
+        dev_table, host_table = self.upload(table, labels.device)
+        hip.map_integrate(self.pool(), dev_table, labels.contiguous(), self.dims, self.n_classes, mask=mask,
+                          table_host=host_table)
+        return self
+
+    # ------------------------------------------------------------------------------------------------ extraction
+    def brick_keys(self):
+        """The keys of the map's bricks, (n, 3) int64, ascending (k0, k1, k2)."""
+        return unpack_keys(np.sort(np.fromiter(self.directory.keys(), dtype=np.int64, count=len(self.directory))))
+
+    def _key_table(self, keys):
+        keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+        table = np.empty((len(keys), 4), dtype=np.int32)
+        table[:, 0] = self.slots(keys)
+        table[:, 1:4] = keys
+        return table
+
+    def brick_labels(self, keys, device=None):
+        """(n, 3) keys -> (n, 16, 16, 16) uint8 labels (argmax of the votes, the lowest class on a tie), 255 where a voxel
+        has no vote or the key is not in the map."""
+        table = self._key_table(keys)
+        if self.votes is None or not len(table):
+            return torch.full((len(table), BRICK, BRICK, BRICK), 255, dtype=torch.uint8,
+                              device=self.votes.device if self.votes is not None else (device or "cpu"))
+        dev_table, host_table = self.upload(table, self.votes.device)
+        return hip.map_brick_labels(self.pool(), dev_table, self.n_classes, table_host=host_table)
+
+    def extract(self, min_obs=1, include_empty=False):
+        """The voxels with at least `min_obs` votes (and a label other than 0, empty, unless include_empty) -> coords
+        (N, 3) int32 world voxel indices, labels (N,) uint8, n_obs (N,) int16 holding uint16 bits (the votes, saturated
+        at 65535).  Bricks by ascending key, voxels inside a brick in (i, j, l) order: the same bits on every run."""
+        if int(min_obs) < 0:
+            raise ValueError("min_obs must be >= 0, got %r" % (min_obs,))
+        if self.votes is None or not self.directory:
+            dev = self.votes.device if self.votes is not None else "cpu"
+            return (torch.empty((0, 3), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.uint8, device=dev),
+                    torch.empty((0,), dtype=torch.int16, device=dev))
+        dev_table, host_table = self.upload(self._key_table(self.brick_keys()), self.votes.device)
+        return hip.map_extract(self.pool(), dev_table, self.n_classes, min_obs=min_obs, include_empty=include_empty,
+                               table_host=host_table)
+
+
+def map_confusion(pred_map, gt_map, metric, chunk_bricks=512):
+    """Count the prediction map against the ground-truth map into `metric` (SSCMetrics.add_batch): the ground-truth
+    map's bricks in chunks, both maps' dense labels, the target set to 255 where the prediction is unobserved -- a voxel
+    counts only where both maps were observed."""
+    if pred_map.voxel_size != gt_map.voxel_size:
+        raise ValueError("the two maps have different voxel sizes (%r, %r): their lattices differ"
+                         % (pred_map.voxel_size, gt_map.voxel_size))
+    keys = gt_map.brick_keys()
+    dev = gt_map.votes.device if gt_map.votes is not None else None
+    for s in range(0, len(keys), int(chunk_bricks)):
+        part = keys[s:s + int(chunk_bricks)]
+        target = gt_map.brick_labels(part)
+        pred = pred_map.brick_labels(part, device=dev)
+        metric.add_batch(pred, torch.where(pred == 255, pred, target))
+    return metric
+
+
+# ----------------------------------------------------------------------------------------------------- PLY
+PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
+                      ("label", "u1"), ("n_obs", "<u2")])
+_PLY_PROPS = ("float x", "float y", "float z", "uchar red", "uchar green", "uchar blue", "uchar label", "ushort n_obs")
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def write_ply(path, coords, labels, n_obs, voxel_size, colours):
+    """A binary little-endian point PLY, one vertex per voxel: x y z float32 (the voxel centre in world metres),
+    red green blue uchar (colours[label]; render.palette), label uchar, n_obs ushort.  -> path."""
+    coords = _host(coords).reshape(-1, 3).astype(np.int64)
+    labels = _host(labels).reshape(-1).astype(np.uint8)
+    n_obs = _host(n_obs).reshape(-1).astype(np.int64) & 0xFFFF
+    colours = _host(colours).reshape(-1, 3).astype(np.uint8)
+    if not (len(coords) == len(labels) == len(n_obs)):
+        raise ValueError("coords, labels and n_obs must have one entry per voxel")
+    if len(labels) and int(labels.max()) >= len(colours):
+        raise ValueError("label %d has no colour (%d rows)" % (int(labels.max()), len(colours)))
+    rows = np.empty(len(labels), dtype=PLY_DTYPE)
+    centre = (coords.astype(np.float64) + 0.5) * float(voxel_size)
+    rows["x"], rows["y"], rows["z"] = centre[:, 0], centre[:, 1], centre[:, 2]
+    rgb = colours[labels]
+    rows["red"], rows["green"], rows["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    rows["label"], rows["n_obs"] = labels, n_obs
+    header = ["ply", "format binary_little_endian 1.0", "comment occdepth_amd semantic map voxel_size %r" % float(voxel_size),
+              "element vertex %d" % len(rows)] + ["property " + p for p in _PLY_PROPS] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rows.tobytes())
+    return path
+
+
+def read_ply(path):
+    """A file write_ply wrote -> {"x", "y", "z", "red", "green", "blue", "label", "n_obs"} as one structured array, plus
+    the voxel size of its comment line (None without one): (vertices, voxel_size)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("%s is not a PLY file" % path)
+    lines = data[:end].decode("ascii").splitlines()
+    if lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("%s: only binary_little_endian 1.0 is read, got %r" % (path, lines[1]))
+    count = voxel_size = None
+    props = []
+    for line in lines[2:]:
+        w = line.split()
+        if w[:2] == ["element", "vertex"]:
+            count = int(w[2])
+        elif w[0] == "property":
+            props.append(" ".join(w[1:]))
+        elif w[0] == "comment" and "voxel_size" in w:
+            voxel_size = float(w[w.index("voxel_size") + 1])
+    if count is None or tuple(props) != _PLY_PROPS:
+        raise ValueError("%s does not have the vertex layout write_ply writes" % path)
+    body = data[end + len(b"end_header\n"):]
+    if len(body) != count * PLY_DTYPE.itemsize:
+        raise ValueError("%s: %d bytes of vertices, its header announces %d" % (path, len(body), count * PLY_DTYPE.itemsize))
+    return np.frombuffer(body, dtype=PLY_DTYPE), voxel_size

@@ -1,0 +1,134 @@
+"""Build the semantic map of one sequence offline (occdepth_amd/semantic_map.py) from per-frame label volumes, write it
+as a point PLY, and score a prediction map against a ground-truth map.
+
+    python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
+        --out maps/08 [--min-obs 2] [--fov] [--every 5]
+
+--pred / --gt name a directory; what it holds decides how it is read:
+    <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
+                                         for --pred, "target" for --gt; with --fov the frame votes inside its "fov_mask_1"
+    <frame>.label                        submission files (dataset label ids, the inverse of output.KITTI_LEARNING_MAP_INV
+                                         brings them back to the 20 training classes; any other id does not vote)
+    <frame>.label with <frame>.invalid   the dataset's raw voxels, decoded on the GPU (targets.kitti_labels)
+--poses is the sequence directory with poses.txt and calib.txt.  Writes <out>_pred.ply / <out>_gt.ply and, given both
+sources, prints the map's Precision / Recall / IoU / mIoU over the voxels both maps observed.
+"""
+import argparse
+import glob
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from occdepth_amd import fuse, output, render, semantic_map as sm, targets  # noqa: E402
+
+
+def submission_inverse_lut():
+    """dataset label id -> training class, 255 for an id the submission format never writes."""
+    lut = np.full(1 << 16, 255, dtype=np.uint8)
+    for train_id, label_id in enumerate(output.KITTI_LEARNING_MAP_INV):
+        lut[label_id] = train_id
+    return lut
+
+
+def list_frames(src):
+    """-> (kind, {frame index: path without extension}); kind is "pkl", "raw" or "label"."""
+    for kind, pattern in (("pkl", "*.pkl"), ("label", "*.label")):
+        paths = sorted(glob.glob(os.path.join(src, pattern)))
+        if paths:
+            frames = {int(os.path.splitext(os.path.basename(p))[0]): os.path.splitext(p)[0] for p in paths}
+            if kind == "label" and all(os.path.exists(b + ".invalid") for b in frames.values()):
+                kind = "raw"
+            return kind, frames
+    raise FileNotFoundError("%s holds neither <frame>.pkl nor <frame>.label files" % src)
+
+
+def read_frame(kind, base, role, dims, device, use_fov=False, lut=None):
+    """-> (labels (X, Y, Z) uint8 on `device`, mask or None)."""
+    if kind == "pkl":
+        with open(base + ".pkl", "rb") as f:
+            d = pickle.load(f)
+        key = "y_pred" if role == "pred" else "target"
+        if key not in d:
+            raise KeyError("%s.pkl has no %r" % (base, key))
+        lab = np.asarray(d[key]).astype(np.uint16)
+        lab = np.where(lab > 255, 255, lab).astype(np.uint8).reshape(dims)
+        mask = None
+        if use_fov:
+            mask = torch.from_numpy(np.asarray(d["fov_mask_1"]).reshape(-1)[:lab.size] != 0).to(device)
+        return torch.from_numpy(lab).to(device), mask
+    if kind == "label":
+        raw = np.fromfile(base + ".label", dtype=np.uint16)
+        return torch.from_numpy(lut[raw].reshape(dims)).to(device), None
+    raw, invalid = targets.read_raw_kitti_voxels(os.path.dirname(base), os.path.basename(base))
+    lab = targets.kitti_labels(torch.from_numpy(raw.view(np.int16))[None].to(device), torch.from_numpy(invalid)[None].to(device),
+                               scene_size=dims)
+    return lab[0], None
+
+
+def build_map(src, role, poses, args, device):
+    kind, frames = list_frames(src)
+    lut = submission_inverse_lut() if kind == "label" else None
+    m = sm.SemanticMap(args.classes, args.voxel, args.origin, tuple(args.dims), max_bricks=args.max_bricks)
+    used = 0
+    for frame in sorted(frames)[::args.every]:
+        if frame not in poses:
+            raise KeyError("no pose for frame %d of %s (%s)" % (frame, src, os.path.join(args.poses, "poses.txt")))
+        labels, mask = read_frame(kind, frames[frame], role, tuple(args.dims), device, args.fov, lut)
+        m.integrate(labels, poses[frame], mask=mask)
+        used += 1
+    print("%s: %d %s frames of %s -> %d bricks, %.1f MB" % (role, used, kind, src, m.n_bricks, m.n_bricks * m.brick_bytes / 1e6))
+    return m
+
+
+def run(args, device=None):
+    device = device or torch.device("cuda")
+    poses = fuse.read_kitti_poses(args.poses)
+    colours = render.palette("kitti" if args.classes == 20 else args.classes)
+    maps = {}
+    for role in ("pred", "gt"):
+        src = getattr(args, role)
+        if src:
+            m = maps[role] = build_map(src, role, poses, args, device)
+            coords, labels, n_obs = m.extract(min_obs=args.min_obs)
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            path = sm.write_ply("%s_%s.ply" % (args.out, role), coords, labels, n_obs, m.voxel_size, colours)
+            print("%s: %d voxels with at least %d vote(s)" % (path, len(labels), args.min_obs))
+    if not maps:
+        raise SystemExit("give --pred, --gt or both")
+    stats = None
+    if len(maps) == 2:
+        from occdepth_amd.loss.sscMetrics import SSCMetrics
+        stats = sm.map_confusion(maps["pred"], maps["gt"], SSCMetrics(args.classes)).get_stats()
+        print("map======")
+        print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
+        print(" ".join(["{:.4f}, "] * args.classes).format(*(stats["iou_ssc"] * 100).tolist()))
+        print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+    return maps, stats
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--poses", required=True, help="the sequence directory with poses.txt and calib.txt")
+    ap.add_argument("--pred", default=None)
+    ap.add_argument("--gt", default=None)
+    ap.add_argument("--out", required=True, help="path prefix of the PLY files")
+    ap.add_argument("--min-obs", type=int, default=1)
+    ap.add_argument("--every", type=int, default=1, help="use every n-th frame")
+    ap.add_argument("--fov", action="store_true", help="pickles: vote inside the frame's fov_mask_1 only")
+    ap.add_argument("--dims", type=int, nargs=3, default=(256, 256, 32))
+    ap.add_argument("--voxel", type=float, default=0.2)
+    ap.add_argument("--origin", type=float, nargs=3, default=(0.0, -25.6, -2.0))
+    ap.add_argument("--classes", type=int, default=20)
+    ap.add_argument("--max-bricks", type=int, default=None)
+    return ap
+
+
+if __name__ == "__main__":
+    if not torch.cuda.is_available():
+        raise SystemExit("map_sequence.py builds the map on the GPU; there is none here")
+    run(parser().parse_args())

@@ -537,6 +537,20 @@ int occd_wino_output_transform_nchw(const float* M, const float* scale, const fl
                                     float* y, int32_t batch, int32_t Cout, int32_t H, int32_t W, int32_t ty0,
                                     int32_t ths, int32_t act, float slope, int32_t res_first, void* stream);
 
+/* The same transforms in CHANNEL-MAJOR form, for the product with the weights as the LEFT operand:
+ *   (caller): M^T[xi] (Cout, T) = U^T[xi] (Cout, Cin) . V^T[xi] (Cin, T) -- one occd_gemm_f32x3 launch of batch 16 with
+ *             U^T as the image of occd_gemm_f16x2_pack (pre = OCCD_GEMM_PRE_F16X2), ldb = ldc = Tp.
+ *   input : x (B, Cin, H, W) -> V^T (16, Cin, Tp);   output: M^T (16, Cout, Tp) -> y (B, Cout, H, W), epilogue as above.
+ * Tp >= T is the row pitch in floats, a multiple of 32 (rows on 128-byte lines); columns [T, Tp) are neither written by the
+ * input transform nor read by the output transform.  Whole images only (no strips).  Values, operation by operation, are
+ * those of the _nchw pair.  OCCD_EINVAL: null x / V^T / M^T / y, Tp < T, Tp % 32 != 0, act outside 0 .. 3, or more than
+ * 4 * 65535 channels.                                                                                             */
+int occd_wino_input_transform_cm(const float* x, float* Vt, int32_t batch, int32_t Cin, int32_t H, int32_t W,
+                                 int64_t Tp, void* stream);
+int occd_wino_output_transform_cm(const float* Mt, const float* scale, const float* shift, const float* res,
+                                  float* y, int32_t batch, int32_t Cout, int32_t H, int32_t W, int64_t Tp,
+                                  int32_t act, float slope, int32_t res_first, void* stream);
+
 /* K10: FUSED Winograd F(2x2, 3x3) convolution on the fp32 matrix pipe -- replaces
  * nn.Conv2d(k=3, s=1, p=1) + BatchNorm2d (eval) + activation of the 2-D decoder (occdepth/models/unet2d.py:24-46)
  * and the 3x3 convolutions of DepthNet / BasicBlock (occdepth/models/flosp_depth/flosp_depth.py:201-257):

@@ -132,8 +132,11 @@ _SWITCHES = {
     #                               within the bounds of tests/test_gemm_f16x2.py; finite activations |x| >= 32760 overflow to
     #                               non-finite outputs; matrices with a non-finite weight keep bf16x3
     #   OCCDEPTH_GEMM_SPLIT=bf16x3  the three-term bf16 image as before (the bit-for-bit previous path)
-    # Explicit hip.GemmPacked(w, role) / hip.matmul_operand(w, role) callers, the on-the-fly K16 launches (Winograd-domain products,
-    # project convolutions with gate and residual), role-"b" images and training are unchanged by this switch.
+    # Under f16x2 the builders also put the Winograd-domain products of the decoder on the channel-major form (hip.WinoCM, where
+    # hip.wino_cm_wins says so) and the K16 launches below 256 rows (project convolutions with gate and residual, the 192-row
+    # expand) on the image (hip.tile_f16x2_wins); bf16x3 keeps their float32 operands, bit for bit as before.
+    # Explicit hip.GemmPacked(w, role) / hip.matmul_operand(w, role) callers, role-"b" images and training are unchanged by this
+    # switch.
     "GEMM_SPLIT": ("OCCDEPTH_GEMM_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
 }
 

@@ -774,6 +774,23 @@ def splitk_f16x2_wins(M, N, K, batch):
     return -(-(-(-M // 32)) // rr) * per >= SPLITK_F16X2_MIN_TILE_STEPS
 
 
+# K16's tile variants on the f16x2 image below PANEL_MIN_ROWS rows, per launch geometry (tools/bench_gemm_rest.py,
+# profiles/gemm_f16x2_rest_ab.txt, replayed graphs, spreads <= 3 %): every such launch of the config-2 frame wins under the
+# library's own hint-0 pick -- project convolutions with gate and skip 48 x 28365 x 288 1.30x and 80 x 7191 x 480 1.29x, the first
+# projects of a stage 48 x 28365 x 192 1.28x, 80 x 7191 x 288 1.40x, 160 x 1848 x 480 1.61x, the expand 192 x 112850 x 32 1.21x
+# (batch 2 each; forcing a variant gains nothing beyond the spread: hint 4 within 2 % of hint 0 where it leads).  The rule covers
+# what was measured: 48 ... 255 rows on at least 3000 columns over the batch; anything else keeps float32 operands.
+# OCCDEPTH_GEMM_TILE_F16X2=0 -> float32 operands on all of them for A/B.
+TILE_F16X2 = os.environ.get("OCCDEPTH_GEMM_TILE_F16X2", "1") == "1"
+TILE_F16X2_MIN_ROWS, TILE_F16X2_MIN_COLS = 48, 3000
+
+
+def tile_f16x2_wins(M, N, K, batch):
+    """The host rule of K16's tile variants on the f16x2 image for matrices below PANEL_MIN_ROWS rows (project convolutions with
+    their gate and skip, the 192-row expand): does the image beat float32 operands split on the fly on this launch?"""
+    return TILE_F16X2 and M >= TILE_F16X2_MIN_ROWS and N * batch >= TILE_F16X2_MIN_COLS
+
+
 def gemm_packed_a(w, split):
     """The role-"a" image of `w` under `split`; a matrix the f16x2 pack refuses (a non-finite weight) keeps bf16x3."""
     if split == "f16x2":
@@ -784,12 +801,19 @@ def gemm_packed_a(w, split):
     return GemmPacked(w, "a")
 
 
-def matmul_operand(w, role, split=None):
+def matmul_operand(w, role, split=None, small=False):
     """A static operand (weights) in the form hip.matmul wants it: (the float32 tensor, its GemmPacked image or None).
-    split: None = the three-term bf16 image; the model's builders pass `gemm_split()` (role "a" only)."""
+    split: None = the three-term bf16 image; the model's builders pass `gemm_split()` (role "a" only).
+    small: under split "f16x2" a matrix below PANEL_MIN_ROWS rows gets its f16x2 image as well (the project convolutions and the
+    192-row expand: K16's tile variants on the A image, where `tile_f16x2_wins` says so); a non-finite matrix stays float32."""
     w = w.detach().float().contiguous()
     if GEMM_X3 and w.is_cuda and (GEMM_X3_PACK or _panel_operand(w, role)):
         return w, (gemm_packed_a(w, split) if split is not None and role == "a" else GemmPacked(w, role))
+    if GEMM_X3 and w.is_cuda and small and split == "f16x2" and role == "a" and w.dim() == 2 and GEMM_X3_PANEL:
+        try:
+            return w, GemmPacked(w, "a", split="f16x2")
+        except ValueError:
+            pass
     return w, None
 
 
@@ -816,8 +840,13 @@ def matmul(a, b, bias=None, act=None, slope=0.01, res=None, k_scale=None, out=No
     tb, pb = b if isinstance(b, tuple) else (b, None)
     if GEMM_X3:
         # (a panel-only image serves the plain epilogue; with a residual / a k scale the float32 operand goes to K16)
-        a_img = pa is not None and (GEMM_X3_PACK or (res is None and k_scale is None and
-                                                     (_panel_launch(pa, tb) or _presplit_launch(pa, tb))))
+        if pa is not None and pa.rows < PANEL_MIN_ROWS and not GEMM_X3_PACK:
+            # an image `matmul_operand(..., small=True)` built: K16's tile variants on it, residual / k scale included
+            n, batch = tb.shape[-1], (tb.shape[0] if tb.dim() == 3 else 1)
+            a_img = pa.split == "f16x2" and tile_f16x2_wins(pa.rows, n, pa.K, batch)
+        else:
+            a_img = pa is not None and (GEMM_X3_PACK or (res is None and k_scale is None and
+                                                         (_panel_launch(pa, tb) or _presplit_launch(pa, tb))))
         xa, xb = (pa if a_img else ta), (pb if pb is not None and k_scale is None else tb)
         if gemm_x3_supported(xa, xb):
             return gemm_x3(xa, xb, bias=bias, act=act, slope=slope, res=res, k_scale=k_scale, out=out)
@@ -1261,13 +1290,98 @@ def wino_output_transform(M, shape, scale=None, shift=None, act=None, slope=0.01
     return y
 
 
-def conv2d_3x3_winograd(x, U, scale=None, shift=None, act=None, slope=0.01, res=None, res_first=False, strip_rows=None):
+class WinoCM:
+    """The weight operand of the channel-major Winograd-domain product: U^T (16, Cout, Cin) as the batch-16 f16x2 image of
+    `GemmPacked(..., "a", split="f16x2")`.  `make_u` builds the operand of the present form (the `matmul_operand(U, "b")` pair)
+    the first time a launch needs it (a geometry `wino_cm_wins` turns down, the strip mode): the 16 * Cin * Cout float32 U does
+    not stay alive beside the image otherwise.  Raises ValueError on a non-finite weight (no f16x2 image)."""
+
+    def __init__(self, w, make_u):
+        self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
+        ut = winograd_weights(w).transpose(1, 2).contiguous()             # (16, Cout, Cin)
+        self.image = GemmPacked(ut, "a", split="f16x2")
+        self._make_u, self._u = make_u, None
+
+    def u(self):
+        if self._u is None:
+            self._u = self._make_u()
+        return self._u
+
+
+# The channel-major form per launch geometry (tools/bench_gemm_rest.py, profiles/gemm_f16x2_rest_ab.txt; replayed graphs, ms):
+#   1280 -> 1280 @2x24x77  (T =  936): whole convolution 0.407 -> 0.245 (1.66x); product 0.333 -> 0.194 (147 -> 253 TF/s)
+#    640 ->  640 @2x47x153 (T = 3696): whole convolution 0.421 -> 0.314 (1.34x); product 0.313 -> 0.221 (155 -> 219 TF/s)
+# the input transforms 1.72x / 1.47x, the output transforms 1.43x / 1.25x; spreads <= 7 %.  Both are long-K launches that fill
+# the chip with 256 x 128 tiles -- the regime in which K16's pre-split form leads on the tap GEMMs (`_presplit_launch`, the same
+# two limits).  Anything smaller is unmeasured and stays on the present form.  OCCDEPTH_WINO_CM=0 -> the present form for A/B.
+WINO_CM = os.environ.get("OCCDEPTH_WINO_CM", "1") == "1"
+WINO_CM_MIN_CIN, WINO_CM_MIN_WORKGROUPS = 512, 320
+
+
+def wino_cm_wins(B, cin, cout, H, W):
+    """The host rule of the channel-major Winograd-domain product: does transforms_cm + K16 on the f16x2 image of U^T beat the
+    present transforms + K16 on float32 operands on this launch?"""
+    T = B * ((H + 1) // 2) * ((W + 1) // 2)
+    return WINO_CM and cin >= WINO_CM_MIN_CIN and cin % 8 == 0 and T >= 4 and \
+        16 * -(-cout // 256) * -(-T // 128) >= WINO_CM_MIN_WORKGROUPS
+
+
+def wino_input_transform_cm(x, Tp=None):
+    """x (B, C, H, W) -> V^T (16, C, T) as a view of (16, C, Tp), Tp = T rounded up to 32 floats (columns [T, Tp) unwritten)."""
+    B, C, H, W = x.shape
+    T = B * ((H + 1) // 2) * ((W + 1) // 2)
+    Tp = round_up(T, 32) if Tp is None else Tp
+    Vt = torch.empty((16, C, Tp), device=x.device, dtype=torch.float32)
+    xc = x if x.is_contiguous() else x.contiguous()
+    if _PROFILING:
+        set_tag("%d @%dx%dx%d" % (C, B, H, W))
+    _check(load().occd_wino_input_transform_cm(_f32(xc, "x"), Vt.data_ptr(), B, C, H, W, Tp, _stream()),
+           "occd_wino_input_transform_cm")
+    return Vt[..., :T]
+
+
+def wino_output_transform_cm(Mt, shape, scale=None, shift=None, act=None, slope=0.01, res=None, res_first=False):
+    """M^T (16, C, T) with rows on a pitch of Tp = Mt.stride(1) floats (Tp % 32 == 0) -> y (B, C, H, W)."""
+    B, C, H, W = shape
+    T = B * ((H + 1) // 2) * ((W + 1) // 2)
+    if Mt.dtype != torch.float32 or tuple(Mt.shape) != (16, C, T) or Mt.stride(2) != 1 or Mt.stride(0) != C * Mt.stride(1):
+        raise RuntimeError("wino_output_transform_cm: M^T must be (16, C, T) float32 over dense padded rows")
+    y = torch.empty(shape, device=Mt.device, dtype=torch.float32)
+    if res is not None and not res.is_contiguous():
+        res = res.contiguous()
+    if _PROFILING:
+        set_tag("%d @%dx%dx%d" % (C, B, H, W))
+    if not Mt.is_cuda or Mt.stride(1) < T or Mt.stride(1) % 32:
+        raise RuntimeError("wino_output_transform_cm: M^T must be a GPU tensor with rows on a pitch of 32 floats")
+    _check(load().occd_wino_output_transform_cm(Mt.data_ptr(), _f32(scale, "scale") if scale is not None else None,
+                                                _f32(shift, "shift") if shift is not None else None,
+                                                _f32(res, "res") if res is not None else None, _f32(y, "y"), B, C, H, W,
+                                                Mt.stride(1), ACT2D[act], float(slope), 1 if res_first else 0, _stream()),
+           "occd_wino_output_transform_cm")
+    return y
+
+
+def conv2d_3x3_winograd(x, U, scale=None, shift=None, act=None, slope=0.01, res=None, res_first=False, strip_rows=None,
+                        cm=None):
     """act(scale * conv3x3(x, g, pad 1) + shift) (+res) with U = winograd_weights(g) (or the `matmul_operand(U, "b")` pair):
     HIP transforms around 16 batched GEMMs (K16; the library with OCCDEPTH_GEMM_X3=0).  `strip_rows` tile rows per pass keep
-    V / M cache-sized on big images."""
+    V / M cache-sized on big images.
+    U a `WinoCM`: the channel-major form -- channel-major transforms around ONE K16 launch on the f16x2 image of U^T (three fp16
+    MFMAs per K step; finite |x| >= 8190 overflow the staged fp16 operand, |V| <= 4 max|x|) -- where `wino_cm_wins` says so
+    (cm: None = ask the rule, True / False = force) and the whole image is one pass; else the present form on `U.u()`."""
     B, Cin, H, W = x.shape
-    cout = (U[0] if isinstance(U, tuple) else U).shape[2]
     th = (H + 1) // 2
+    if isinstance(U, WinoCM):
+        whole = strip_rows is None or strip_rows >= th
+        if GEMM_X3 and whole and x.is_cuda and (wino_cm_wins(B, Cin, U.cout, H, W) if cm is None else cm):
+            if U.cin != Cin:
+                raise RuntimeError("conv2d_3x3_winograd: the WinoCM operand does not match the input channels")
+            Vt = wino_input_transform_cm(x)
+            Mt = torch.empty((16, U.cout, Vt.stride(1)), device=x.device, dtype=torch.float32)[..., :Vt.shape[2]]
+            gemm_x3(U.image, Vt, out=Mt)
+            return wino_output_transform_cm(Mt, (B, U.cout, H, W), scale, shift, act, slope, res, res_first)
+        U = U.u()
+    cout = (U[0] if isinstance(U, tuple) else U).shape[2]
     if strip_rows is None or strip_rows >= th:
         V = wino_input_transform(x)
         return wino_output_transform(matmul(V, U), (B, cout, H, W), scale, shift, act, slope, res, res_first)

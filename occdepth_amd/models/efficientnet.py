@@ -82,7 +82,8 @@ def gemm_operands(owner, conv, bn):
         w = conv.weight.detach().float().flatten(1) * scale.view(-1, 1)
         if conv.bias is not None:
             shift = conv.bias.detach().float() * scale + shift
-        hit = (key, hip.matmul_operand(w, "a", split=key[1]), shift.contiguous())
+        # (small: below 256 rows too -- the project convolutions and the 192-row expand on K16's tile variants, hip.tile_f16x2_wins)
+        hit = (key, hip.matmul_operand(w, "a", split=key[1], small=True), shift.contiguous())
         cache[id(conv)] = hit
     return hit[1], hit[2]
 

@@ -53,14 +53,25 @@ class UpSampleBN(nn.Module):
     WINOGRAD_MIN_CIN = int(os.environ.get("OCCDEPTH_WINOGRAD_MIN_CIN", "256"))
 
     def _wino_operands(self, conv, bn):
-        key = _stamp(conv, bn)
+        key = (_stamp(conv, bn), hip.gemm_split())
         cache = self.__dict__.setdefault("_wino_cache", {})
         hit = cache.get(id(conv))
         if hit is None or hit[0] != key:
             scale, shift = bn_affine_cached(bn)
             if conv.bias is not None:
                 shift = shift + scale * conv.bias.detach().float()
-            hit = (key, hip.matmul_operand(hip.winograd_weights(conv.weight), "b"), scale.contiguous(), shift.contiguous())
+
+            def make_u():
+                return hip.matmul_operand(hip.winograd_weights(conv.weight), "b")
+
+            U = None
+            if key[1] == "f16x2" and hip.GEMM_X3 and conv.weight.is_cuda:
+                # the weights as the LEFT operand, pre-split (hip.WinoCM); the float32 U only if a launch asks for it
+                try:
+                    U = hip.WinoCM(conv.weight.detach().float(), make_u)
+                except ValueError:
+                    pass                                     # a non-finite weight has no f16x2 image: the present form
+            hit = (key, make_u() if U is None else U, scale.contiguous(), shift.contiguous())
             cache[id(conv)] = hit
         return hit[1:]
 

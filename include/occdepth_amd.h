@@ -983,7 +983,12 @@ int occd_pack_weights_bf16x3(const float* w, const float* scale, void* wpk,
  * OCCD_EINVAL.  Finite activations with |x| >= 32760 overflow the fp16 operand and make the outputs they reach non-finite.
  * Its weight image (occd_packed_weight_f16x2_bytes() bytes, 16-byte aligned) comes from occd_pack_weights_f16x2: three fp16
  * images hi | hs | lo of w' = 2^k[co] w (layout of occd_pack_weights_bf16) and 32 * ceil(cout / 32) float epilogue factors.
- * Weights must be finite.
+ * Weights must be finite.  K2s3h keeps the hi and lo images in LDS for its lifetime and forms hs = hi 2^-11 in registers (the
+ * stored hs image is read only by the ring form below; the image's format is unchanged).
+ * occd_conv3d_head_set_lo: where K2s3h takes lo from -- 1 (the default) the resident LDS image; 0 the form before: hi | hs in
+ * LDS, lo streamed from L2 through a register ring.  The outputs of both are bit-identical.  OCCD_HEAD_LO=0 in the environment
+ * (read once) selects 0 as well; returns the previous setting; a value outside 0..1 selects 1.  (Added without a change of any
+ * struct or prototype: no ABI bump.)
  * OCCD_CONV_F16X2 of occd_conv3d_bf16_fwd and occd_conv3d_bf16_fwd_phases = the same numerics and weight image on the generic kernel
  * (K2bh: any geometry OCCD_CONV_BF16X3 takes; act_in NONE or RELU only): only the hi and lo images are streamed, hs = hi 2^-11 is formed
  * in registers, the epilogue reads the factors of each phase's own image.  Same overflow contract as OCCD_CONV_F16X2_HEAD.               */
@@ -991,6 +996,7 @@ int64_t occd_packed_weight_f16x2_bytes(int32_t cout, int32_t cin, int32_t taps);
 int occd_pack_weights_f16x2(const float* w, const float* scale, void* wpk,
                             int32_t cout, int32_t cin, int32_t kx, int32_t ky, int32_t kz,
                             int32_t layout, void* stream);
+int32_t occd_conv3d_head_set_lo(int32_t form);
 int64_t occd_conv3d_wgrad_bf16_workspace_floats(const occd_conv3d_wgrad_args* a, int32_t dtype);
 int occd_conv3d_wgrad_bf16(const occd_conv3d_wgrad_args* a, int32_t dtype, void* stream);
 

@@ -490,8 +490,14 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_kernel(const SlideP s
 //   * activations: x' = 2^kF2XExp x = hi + 2^-11 lo' with hi = fp16(x'), lo' = fp16((x' - hi) 2^11) (22 significant bits
 //     while |x'| >= 2^-13); two fp16 planes in LDS, rows of 2 x 32 B + 16 B pad = 5 sixteen-byte slots (odd: conflict-free);
 //   * weights (occd_pack_weights_f16x2): per output channel scaled by 2^k so that max |w'| lies in [2^13, 2^14) (exact);
-//     hi = fp16(w'), lo = fp16(w' - hi) at natural scale, hs = hi 2^-11 (exact while normal).  hi and hs stay in LDS (the
-//     two 55,296 B images K2s3 keeps), lo streams from L2 through the same two-step ring;
+//     hi = fp16(w'), lo = fp16(w' - hi) at natural scale, hs = hi 2^-11 (exact while normal).  `LOL` (the default,
+//     occd_conv3d_head_set_lo): hi and lo stay in LDS (the two 55,296 B image slots K2s3 keeps) and hs is formed in
+//     registers, four v_pk_mul_f16 per fragment, as K2bh / K10h / the f16x2 GEMMs do (fp16 denormals are on and the packer
+//     rounds its stored hs the same way: the same bits) -- the kernel streams no weights, and the ring's 24 VGPRs, its
+//     8 waves x 27 KB of L2 reads per half-slab and its place in the in-order vmcnt queue between the staging loads and
+//     the residual prefetch are gone (172 / 191 / 209 VGPRs at NRES = 0 / 1 / 2 against 216 / 234 / 252; 23 - 57 us of
+//     0.35 - 0.43 ms per 256 x 256 x 32 launch, profiles/head_lo_lds_ab.txt).  !LOL, the form before and the bit-for-bit
+//     reference: hi and the stored hs image in LDS, lo streams from L2 through the same two-step ring as K2s3's;
 //   * per sub-step acc += lo * hi_x + hs * lo'_x + hi * hi_x (smallest first; the dropped lo * lo'_x term is <= 2^-22
 //     relative); the epilogue multiplies by 2^-(k + kF2XExp) (per channel, exact) before the bias;
 //   * range: an activation with |x'| >= 65520 (|x| >= 32760) stages as +-Inf and poisons the outputs it reaches (never a
@@ -508,9 +514,10 @@ constexpr int kX3WImg = kWTaps * 2 * 64;  // u32x4 per split image of the weight
 
 // NRES: residual operands compiled in (0: neither, 1: res1, 2: res1 and res2) -- their prefetch registers (16 per
 // operand) are what the 5 of 7 head launches without residuals do not pay for.  F16: the K2s3h numerics (see above).
-template <bool F16, int D, int NRES, bool ZH, int TYV>
+template <bool F16, int D, int NRES, bool ZH, int TYV, bool LOL = false>
 __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
     static_assert(TYV >= 1 && TYV <= kTY, "output rows per y tile: one wave each");
+    static_assert(F16 || !LOL, "resident lo image: the two-term fp16 split only (bf16x3 has three images)");
     const PersistP& p = sp.base;
     constexpr int RowB = F16 ? kF2RowB : kX3RowB; // bytes per slab entry
     constexpr int ZW = ZH ? kTZ + 2 * D : kX3ZW;  // entries per y row: the tile + its z halo (ZH), or the tile + the zero entry
@@ -519,17 +526,17 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
     constexpr int NITEM = YIN * ZST * 2;          // staging items: (y row, z, 8-channel chunk of the 16-channel half)
     constexpr int NLOAD = (NITEM + 511) / 512;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    u32x4* const w4 = reinterpret_cast<u32x4*>(lds_raw);                 // hi image | mid image (F16: hi | hs)
+    u32x4* const w4 = reinterpret_cast<u32x4*>(lds_raw);                 // hi image | mid image (F16: hi | hs, LOL: hi | lo)
     unsigned char* const slab = lds_raw + 2 * kX3WImg * 16;
     int* const mailbox = reinterpret_cast<int*>(slab + ROWS * RowB);
     f32x4* const bias4 = reinterpret_cast<f32x4*>(slab + ROWS * RowB + 16);
     f32x4* const wsc4 = bias4 + 8;                                      // F16: per-channel 2^-(k + kF2XExp)
-    // lo image: read through a buffer descriptor (voffset = lane * 16, soffset = a compile-time constant per fragment, so
-    // the 54 fragment addresses cost no address VGPRs)
-    const auto wlo_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+    // lo image (unless LOL): read through a buffer descriptor (voffset = lane * 16, soffset = a compile-time constant per
+    // fragment, so the 54 fragment addresses cost no address VGPRs)
+    [[maybe_unused]] const auto wlo_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(reinterpret_cast<const u32x4*>(p.wpk) + 2 * kX3WImg)), 0,
         kX3WImg * 16, 0x00020000);
-    auto wlo_load = [&](int frag) {
+    [[maybe_unused]] auto wlo_load = [&](int frag) {
         return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wlo_rsrc, (unsigned)(threadIdx.x & 63) * 16u, frag * 1024, 0));
     };
 
@@ -538,7 +545,8 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, kk = lane >> 5;
 
-    {   // hi | mid weight images: global -> LDS, once (6912 u32x4 = 13.5 x 512, 7 loads in flight per thread)
+    {   // hi | mid weight images (LOL: hi | lo, images 0 and 2 of the buffer): global -> LDS, once (6912 u32x4 = 13.5 x 512,
+        // 7 loads in flight per thread)
         static_assert(2 * kX3WImg == 13 * 512 + 256, "weight staging loop");
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -546,7 +554,7 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
 #pragma unroll
             for (int u = 0; u < 7; ++u) {
                 const int i = tid + (half * 7 + u) * 512;
-                if (i < 2 * kX3WImg) wv[u] = reinterpret_cast<const u32x4*>(p.wpk)[i];
+                if (i < 2 * kX3WImg) wv[u] = reinterpret_cast<const u32x4*>(p.wpk)[LOL && i >= kX3WImg ? i + kX3WImg : i];
             }
 #pragma unroll
             for (int u = 0; u < 7; ++u) {
@@ -632,12 +640,16 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
     asm volatile("" : "+v"(mid_img));            //  exceed the 16-bit ds_read immediate and every fragment costs an address VGPR)
 
     // lo-weight ring: [step parity][kx], two steps ahead of the MFMAs (a younger load must not be waited for while the
-    // next slab's staging loads -- issued at the top of the slab -- are still in flight: vmcnt retires in order)
-    u32x4 ring[2][3];
+    // next slab's staging loads -- issued at the top of the slab -- are still in flight: vmcnt retires in order).
+    // LOL: no ring -- lo is the second LDS image, hs = hi 2^-11 is formed in registers (exact: fp16 denormals are on, and
+    // the packer rounds its stored hs the same way), the kernel streams no weights at all.
+    [[maybe_unused]] u32x4 ring[2][3];
+    if constexpr (!LOL) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) ring[t][kx] = wlo_load((kx * 9 + t) * 2 + 0);
+            for (int kx = 0; kx < 3; ++kx) ring[t][kx] = wlo_load((kx * 9 + t) * 2 + 0);
+    }
 
 #define OCCD_X3_MFMA(ACC, W, A) \
     ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, W), __builtin_bit_cast(bf16x8, A), ACC, 0, 0, 0)
@@ -682,9 +694,15 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
                 bhn = whi[((kxn * 9 + tn) * 2) * 64];
                 bmn = wmid[((kxn * 9 + tn) * 2) * 64];
             }
-            const u32x4 bl = ring[par][kx];
+            u32x4 bl;
+            if constexpr (!LOL) bl = ring[par][kx];
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (F16) {            // bh = hi, bm = hs = hi 2^-11, bl = lo of w'; a0 = hi, a1 = lo' of x'
+            if constexpr (LOL) {            // bh = hi, bm = lo of w' (both from LDS), hs = hi 2^-11 here; a0 = hi, a1 = lo' of x'
+                const u32x4 hs = __builtin_bit_cast(u32x4, __builtin_bit_cast(f16x8, bh) * (_Float16)(1.f / 2048.f));
+                if (kx == 0) { OCCD_F2_MFMA(acc0, bm, a0); OCCD_F2_MFMA(acc0, hs, a1); OCCD_F2_MFMA(acc0, bh, a0); }
+                else if (kx == 1) { OCCD_F2_MFMA(acc1, bm, a0); OCCD_F2_MFMA(acc1, hs, a1); OCCD_F2_MFMA(acc1, bh, a0); }
+                else { OCCD_F2_MFMA(acc2, bm, a0); OCCD_F2_MFMA(acc2, hs, a1); OCCD_F2_MFMA(acc2, bh, a0); }
+            } else if constexpr (F16) {     // bh = hi, bm = hs = hi 2^-11, bl = lo of w'; a0 = hi, a1 = lo' of x'
                 if (kx == 0) { OCCD_F2_MFMA(acc0, bl, a0); OCCD_F2_MFMA(acc0, bm, a1); OCCD_F2_MFMA(acc0, bh, a0); }
                 else if (kx == 1) { OCCD_F2_MFMA(acc1, bl, a0); OCCD_F2_MFMA(acc1, bm, a1); OCCD_F2_MFMA(acc1, bh, a0); }
                 else { OCCD_F2_MFMA(acc2, bl, a0); OCCD_F2_MFMA(acc2, bm, a1); OCCD_F2_MFMA(acc2, bh, a0); }
@@ -699,7 +717,7 @@ __device__ __forceinline__ void slide_split_body(const SlideP& sp) {
                 OCCD_X3_MFMA(acc2, bh, a1); OCCD_X3_MFMA(acc2, bm, a0); OCCD_X3_MFMA(acc2, bh, a0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (i % NA == NA - 1) {
+            if (!LOL && i % NA == NA - 1) {
                 // step t done: refill its ring parity with step t + 2 (of this slab, or t + 2 - 9 of the next one, whose
                 // half is always the other one) for ALL kx -- the next slab may feed accumulators this one skipped
                 const int t2 = t + 2 < 9 ? t + 2 : t + 2 - 9;
@@ -858,9 +876,9 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_x3_kernel(const Slide
     slide_split_body<false, D, NRES, ZH, TYV>(sp);
 }
 
-template <int D, int NRES, bool ZH = false, int TYV = kTY>
+template <int D, int NRES, bool ZH = false, int TYV = kTY, bool LOL = false>
 __global__ void __launch_bounds__(512, 2) conv3d_c32_slide_f16x2_kernel(const SlideP sp) {
-    slide_split_body<true, D, NRES, ZH, TYV>(sp);
+    slide_split_body<true, D, NRES, ZH, TYV, LOL>(sp);
 }
 
 // Per-DEVICE launch state (work-list counters live in that device's memory, CU count and the large-LDS function
@@ -872,7 +890,7 @@ struct DevState {
     int* counter = nullptr;
     int num_cu = 0;
     bool slide_attr[4] = {};
-    bool slide_x3_attr[2][4][3][3] = {};   // [F16][D][NRES][form]
+    bool slide_x3_attr[3][4][3][3] = {};   // [bf16x3, f16x2 ring, f16x2 resident lo][D][NRES][form]
     bool attr_done[4] = {};
 };
 DevState g_dev[kMaxDevices];
@@ -948,7 +966,7 @@ int launch_slide(const PersistP& base, hipStream_t st, DevState* ds) {
     return occd::check_launch();
 }
 
-template <int D, int NRES, bool ZH, int TYV = kTY, bool F16 = false>
+template <int D, int NRES, bool ZH, int TYV = kTY, bool F16 = false, bool LOL = false>
 int launch_slide_x3(const PersistP& base0, hipStream_t st, DevState* ds) {
     PersistP base = base0;
     if (TYV != kTY) {                                     // the work list is cut in y tiles of TYV rows
@@ -960,24 +978,27 @@ int launch_slide_x3(const PersistP& base0, hipStream_t st, DevState* ds) {
     constexpr size_t lds = (size_t)2 * kX3WImg * 16 + (size_t)ROWS * (F16 ? kF2RowB : kX3RowB) + 16 + 128 + (F16 ? 128 : 0);
     static_assert(lds <= 160 * 1024, "K2s3 LDS budget (Z > 32: D <= 2 only)");
     const void* kern;
-    if constexpr (F16) kern = reinterpret_cast<const void*>(conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV>);
+    if constexpr (F16) kern = reinterpret_cast<const void*>(conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV, LOL>);
     else kern = reinterpret_cast<const void*>(conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>);
     {
         std::lock_guard<std::mutex> lock(ds->mu);
         constexpr int VAR = ZH ? (TYV == kTY ? 1 : 2) : 0;
-        if (!ds->slide_x3_attr[F16][D][NRES][VAR]) {
+        constexpr int KIND = F16 ? (LOL ? 2 : 1) : 0;
+        if (!ds->slide_x3_attr[KIND][D][NRES][VAR]) {
             if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
                 return OCCD_ELAUNCH;
-            ds->slide_x3_attr[F16][D][NRES][VAR] = true;
+            ds->slide_x3_attr[KIND][D][NRES][VAR] = true;
         }
     }
     SlideP sp;
     const int rc = plan_slide<D>(base, ds, &sp);
     if (rc != OCCD_OK) return rc;
     static const bool res_early = occd::env_flag("OCCD_C32X3_RES_EARLY", true);      // A/B switch (0: in front of the second half)
-    sp.res_early = res_early ? 1 : 0;
+    // resident lo: no weight stream behind the residual loads any more, the switch was timed again (OCCD_C32X3H_RES_EARLY)
+    static const bool res_early_lol = occd::env_flag("OCCD_C32X3H_RES_EARLY", true);
+    sp.res_early = (LOL ? res_early_lol : res_early) ? 1 : 0;
     const int grid = ds->num_cu < sp.total_segs ? ds->num_cu : sp.total_segs;
-    if constexpr (F16) hipLaunchKernelGGL((conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV>), dim3((unsigned)grid), dim3(512), lds, st, sp);
+    if constexpr (F16) hipLaunchKernelGGL((conv3d_c32_slide_f16x2_kernel<D, NRES, ZH, TYV, LOL>), dim3((unsigned)grid), dim3(512), lds, st, sp);
     else hipLaunchKernelGGL((conv3d_c32_slide_x3_kernel<D, NRES, ZH, TYV>), dim3((unsigned)grid), dim3(512), lds, st, sp);
     return occd::check_launch();
 }
@@ -1034,6 +1055,13 @@ bool c32_geometry(const occd_conv3d_args* a, PersistP* p, double* flops, double*
 }
 }  // namespace
 
+// Where K2s3h takes the lo weight image from: 1 (the default) resident in LDS beside hi, hs formed in registers; 0 streamed
+// from L2 through the ring beside the stored hi | hs images (the form before).  Both feed the same operands to the same
+// MFMAs in the same order: bit-identical outputs.  OCCD_HEAD_LO=0 in the environment (read once) or
+// occd_conv3d_head_set_lo(0) select the ring.
+static std::atomic<int> g_head_lo{occd::env_flag("OCCD_HEAD_LO", true) ? 1 : 0};
+extern "C" int32_t occd_conv3d_head_set_lo(int32_t form) { return g_head_lo.exchange(form < 0 || form > 1 ? 1 : form); }
+
 namespace occd {
 
 // Returns 1 when the launch was taken by the persistent kernel, 0 when the geometry does not qualify,
@@ -1078,10 +1106,16 @@ int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream, bool 
     }
     const int nres = (p.res1 != nullptr) + (p.res2 != nullptr);
     int rc;
-#define OCCD_X3_LAUNCH(DD, ZZ, TT, FF)                                                                          \
-    (nres == 0 ? launch_slide_x3<DD, 0, ZZ, TT, FF>(p, stream, ds) : nres == 1 ? launch_slide_x3<DD, 1, ZZ, TT, FF>(p, stream, ds) \
-               : launch_slide_x3<DD, 2, ZZ, TT, FF>(p, stream, ds))
-    if (f16x2) {
+#define OCCD_X3_LAUNCH_L(DD, ZZ, TT, FF, LL)                                                                            \
+    (nres == 0 ? launch_slide_x3<DD, 0, ZZ, TT, FF, LL>(p, stream, ds) : nres == 1 ? launch_slide_x3<DD, 1, ZZ, TT, FF, LL>(p, stream, ds) \
+               : launch_slide_x3<DD, 2, ZZ, TT, FF, LL>(p, stream, ds))
+#define OCCD_X3_LAUNCH(DD, ZZ, TT, FF) OCCD_X3_LAUNCH_L(DD, ZZ, TT, FF, false)
+    if (f16x2 && g_head_lo.load() != 0) {       // resident lo (the default)
+        if (a->Z == kTZ) rc = d == 1 ? OCCD_X3_LAUNCH_L(1, false, kTY, true, true) : d == 2 ? OCCD_X3_LAUNCH_L(2, false, kTY, true, true)
+                                                                                  : OCCD_X3_LAUNCH_L(3, false, kTY, true, true);
+        else rc = d == 1 ? OCCD_X3_LAUNCH_L(1, true, kTY, true, true) : d == 2 ? OCCD_X3_LAUNCH_L(2, true, kTY, true, true)
+                                                                              : OCCD_X3_LAUNCH_L(3, true, 6, true, true);
+    } else if (f16x2) {                         // lo through the ring: the form before, bit for bit the same results
         // (dilation 3 at Z > 32: the 8-row y tile would fit LDS with 80-byte entries, but its third staging load per thread
         //  spills at NRES = 2 -- the six-row tile of K2s3 it is)
         if (a->Z == kTZ) rc = d == 1 ? OCCD_X3_LAUNCH(1, false, kTY, true) : d == 2 ? OCCD_X3_LAUNCH(2, false, kTY, true)
@@ -1093,6 +1127,7 @@ int try_conv3d_c32_slide_x3(const occd_conv3d_args* a, hipStream_t stream, bool 
     else if (d < 3) rc = d == 1 ? OCCD_X3_LAUNCH(1, true, kTY, false) : OCCD_X3_LAUNCH(2, true, kTY, false);
     else rc = OCCD_X3_LAUNCH(3, true, 6, false);
 #undef OCCD_X3_LAUNCH
+#undef OCCD_X3_LAUNCH_L
     return rc == OCCD_OK ? 1 : rc;
 }
 

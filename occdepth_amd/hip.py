@@ -388,6 +388,15 @@ def conv3d_f16x2(x, wpk, bias, cout, kernel, out, o_off=(0, 0, 0), **kw):
                              bias, cout, out, **kw)
 
 
+def set_head_lo(form):
+    """Where K2s3h (`conv3d_f16x2`) takes the lo weight image from: 1 (the default) resident in LDS beside hi, hs = hi 2^-11
+    formed in registers; 0 the form before (hi | hs in LDS, lo streamed from L2 through a register ring).  Bit-identical
+    outputs.  Returns the previous setting; anything but 0 / 1 is refused."""
+    if isinstance(form, bool) or not isinstance(form, int) or form not in (0, 1):
+        raise ValueError(f"set_head_lo: 0 (ring) or 1 (LDS), got {form!r}")
+    return load().occd_conv3d_head_set_lo(form)
+
+
 def conv3d_bf16(x, wpk, bias, cout, kernel, out, stride=(1, 1, 1), dilation=(1, 1, 1), padding=(0, 0, 0),
                 res1=None, res2=None, act_in=ACT_NONE, act_out=ACT_NONE, out_pos=None, o_stride=(1, 1, 1),
                 o_off=(0, 0, 0), cin=None, tile_hint=0, split3=False, f16x2=False):

@@ -5,6 +5,9 @@
 with no / one / two residual operands, plus the error of each against ATen float64 on a 16-plane slab of the same data.
 
     python tools/bench_head_x3.py
+    python tools/bench_head_x3.py --lo-ab     K2s3h only: lo weights through the L2 ring (hip.set_head_lo(0)) against resident in
+                                              LDS (1, the default), the five (D, NRES) launches of the frame and 32 -> 22; best of
+                                              three interleaved rounds and their spread, outputs compared bit for bit
 """
 import os
 import sys
@@ -62,5 +65,48 @@ def main():
                   f"rms rel {float((got - ref).norm() / ref.norm()):.3e}", flush=True)
 
 
+def lo_ab(rounds=3, iters=10):
+    torch.manual_seed(0)
+    x = hip.Vox(torch.randn(1, *DIMS, 32, device="cuda"), 32)
+    r1 = hip.Vox(torch.randn(1, *DIMS, 32, device="cuda"), 32)
+    r2 = hip.Vox(torch.randn(1, *DIMS, 32, device="cuda"), 32)
+    bias = torch.randn(32, device="cuda")
+    cases = [(1, 0, 32), (2, 0, 32), (3, 0, 32), (2, 1, 32), (3, 2, 32), (1, 0, 22)]
+    epi = {0: {}, 1: dict(res1=r1, act_out=hip.ACT_RELU), 2: dict(res1=r1, res2=r2, act_in=hip.ACT_RELU, act_out=hip.ACT_RELU)}
+    print(f"# K2s3h, 32 -> cout 3x3x3 @ {DIMS}, N(0,1) data; ms per launch: best of {rounds} rounds of {iters} launches "
+          f"(spread = max - min of the rounds), ring = set_head_lo(0), lds = set_head_lo(1)")
+    for d, nres, cout in cases:
+        w = torch.randn(cout, 32, 3, 3, 3, device="cuda") / (32 * 27) ** 0.5
+        wpk = hip.pack_weights_f16x2(w)
+        out = hip.Vox.empty(1, DIMS, cout, "cuda")
+        run = lambda: hip.conv3d_f16x2(x, wpk, bias, cout, (3, 3, 3), out, dilation=(d,) * 3, padding=(d,) * 3, **epi[nres])
+        ms, bits = {0: [], 1: []}, {}
+        for form in (0, 1):
+            old = hip.set_head_lo(form)
+            try:
+                run()
+                torch.cuda.synchronize()
+                bits[form] = out.buf.clone()
+            finally:
+                hip.set_head_lo(old)
+        for _ in range(rounds):
+            for form in (0, 1):
+                old = hip.set_head_lo(form)
+                try:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(iters):
+                        run()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[form].append(e0.elapsed_time(e1) / iters)
+                finally:
+                    hip.set_head_lo(old)
+        b0, b1 = min(ms[0]), min(ms[1])
+        print(f"head 32>{cout} d={d} nres={nres}: ring {b0:.4f} ms (spread {max(ms[0]) - b0:.4f})  lds {b1:.4f} ms "
+              f"(spread {max(ms[1]) - b1:.4f})  delta {1e3 * (b1 - b0):+.1f} us  {b0 / b1:.3f}x  "
+              f"bit-identical {torch.equal(bits[0], bits[1])}", flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    lo_ab() if "--lo-ab" in sys.argv[1:] else main()

@@ -77,7 +77,9 @@ extern "C" {
  *     OCCD_FUSE_MAX_SOURCES, OccdFuseArgs, occd_fuse_store and occd_fuse_frames (temporal fusion of class probabilities
  *     over a sequence, csrc/fuse.hip): a new struct and new functions only; likewise OCCD_MAP_BRICK, OccdMapFrameArgs,
  *     OccdMapExtractArgs, occd_map_integrate, occd_map_brick_labels, occd_map_count and occd_map_extract (the sequence-level
- *     semantic voxel map, csrc/semantic_map.hip): two new structs and new functions only */
+ *     semantic voxel map, csrc/semantic_map.hip): two new structs and new functions only; likewise OccdMapRenderArgs and
+ *     occd_map_render (K31, the sparse two-level ray cast over the map's bricks, csrc/map_render.hip): one new struct and
+ *     one new function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1389,6 +1391,56 @@ int occd_map_integrate(const OccdMapFrameArgs* a, void* stream);
 int occd_map_brick_labels(const OccdMapExtractArgs* a, void* stream);
 int occd_map_count(const OccdMapExtractArgs* a, void* stream);
 int occd_map_extract(const OccdMapExtractArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K31: render the sequence map (csrc/map_render.hip).  Additive (OCCD_ABI_VERSION note).  One ray per pixel through the
+ * sparse brick map, two levels: a directory `cells` of 16^3-voxel bricks over a window of (gx, gy, gz) bricks, and one
+ * 4096-byte row of labels per brick.  One launch for n_views x H x W pixels, one thread per pixel, a wave per 8 x 8
+ * pixel tile.  No atomics, no allocation, no host sync (capture-safe).
+ *
+ * Window: the box [0, 16 gx] x [0, 16 gy] x [0, 16 gz] in voxels; `views` are OccdRenderViews in these window voxel
+ * units.  cells[(cx gy + cy) gz + cz] is the row of the brick at that cell; negative (or >= n_rows): the brick is absent.  Voxel
+ * (x, y, z) of a present brick reads labels[row][((x & 15) 16 + (y & 15)) 16 + (z & 15)] (and target likewise).
+ *
+ * Contract: for t_max = +inf every pixel's (voxel, face, t, colour) equals, bit for bit, what occd_render_voxels gives
+ * for the same view on the dense (16 gx, 16 gy, 16 gz) uint8 volume of the same labels in which every voxel of an absent
+ * brick is 255 (target 255), without fov; hit = row * 4096 + the brick-local index of that voxel.  For a finite t_max
+ * every hit of depth > t_max is a miss.  The ray set-up, the visibility rule and the colour rule are those of
+ * occd_render_voxels above; every boundary time is m_a(i) = ((float)(i + (dir_a > 0)) - origin_a) * (1 / dir_a).
+ * Inside a present brick the walk steps voxel by voxel.  An absent brick is left in one step: with last_a the brick's
+ * last voxel index along each moving axis and M_a = m_a(last_a), the exit axis a has the smallest (M_a, a) (x before y
+ * before z on ties); the ray ends when M_a > t_max or M_a is not below +inf; on every other moving axis b the index
+ * becomes the first one whose crossing does not precede (M_a, a) in the voxel walk's merge order (m_b <= M_a for b < a,
+ * m_b < M_a for b > a), found from the estimate floor(origin_b + dir_b M_a) clamped into the brick by single steps against
+ * that predicate; then index_a = last_a + sign(dir_a), face = a, t = M_a.  The crossing times of an axis are monotone
+ * in the index, so the voxel walk is a merge of three sorted sequences and the skip lands on a point of that merge.
+ * flags bit 0: absent bricks are walked voxel by voxel (without label loads) instead -- same result, for A/B runs.
+ * At most 16 (gx + gy + gz) + 3 iterations per ray (never reached: each moves at least one index one way).
+ * OCCD_EINVAL without a launch: NULL labels / cells / views / palette / rgb, gx, gy or gz outside 1..65536,
+ * gx gy gz > 2^27, n_rows <= 0, non-positive H or W, n_views outside 1..OCCD_RENDER_MAX_VIEWS, alpha outside 0..256,
+ * n_palette < 1 (4 with a target) or > 65536, a view rectangle larger than the canvas, t_max negative or NaN, an
+ * unknown flag.
+ * ------------------------------------------------------------------------ */
+typedef struct OccdMapRenderArgs {
+    const uint8_t* labels;         /* (n_rows, 4096) device                                                   */
+    const uint8_t* target;         /* (n_rows, 4096), or NULL: class mode                                     */
+    const int32_t* cells;          /* (gx, gy, gz) row of the brick, negative = absent                        */
+    const OccdRenderView* views;   /* (n_views) device, window voxel units                                    */
+    const uint8_t* palette;        /* (n_palette, 3) device                                                   */
+    const uint8_t* background;     /* (n_views, H, W, 3), or NULL                                             */
+    uint8_t* rgb;                  /* (n_views, H, W, 3)                                                      */
+    int64_t* hit;                  /* (n_views, H, W) row * 4096 + local voxel or -1, or NULL                 */
+    uint8_t* face;                 /* (n_views, H, W) as OccdRenderArgs.face, or NULL                         */
+    float* depth;                  /* (n_views, H, W) t at the hit, +inf on a miss, or NULL                   */
+    int32_t gx, gy, gz, n_rows;
+    int32_t n_views, H, W;
+    int32_t n_palette, alpha;
+    int32_t flags;
+    float t_max;                   /* +inf: no limit                                                          */
+    int32_t view_w[OCCD_RENDER_MAX_VIEWS], view_h[OCCD_RENDER_MAX_VIEWS];
+    uint8_t bg_colour[4];
+} OccdMapRenderArgs;
+int occd_map_render(const OccdMapRenderArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

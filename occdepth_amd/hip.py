@@ -57,6 +57,7 @@ FUSE_MAX_SOURCES = abi.CONSTANTS["OCCD_FUSE_MAX_SOURCES"]
 MapFrameArgs = abi.STRUCTS["OccdMapFrameArgs"]
 MapExtractArgs = abi.STRUCTS["OccdMapExtractArgs"]
 MAP_BRICK = abi.CONSTANTS["OCCD_MAP_BRICK"]
+MapRenderArgs = abi.STRUCTS["OccdMapRenderArgs"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2288,6 +2289,62 @@ def map_extract(votes, table, n_classes, min_obs=1, include_empty=False, table_h
             n_obs.data_ptr(), N
         _check(load().occd_map_extract(ctypes.byref(a), _stream()), "occd_map_extract")
     return coords, labels, n_obs
+
+
+def map_render(labels, cells, views, size, palette, target=None, background=None, alpha=256, bg_colour=(255, 255, 255),
+               view_sizes=None, t_max=float("inf"), skip=True, aux=False):
+    """Ray-cast a brick map to images in one launch (occd_map_render, K31; the contract is in include/occdepth_amd.h).
+    labels (n, 4096) (or (n, 16, 16, 16)) uint8 brick rows; cells (gx, gy, gz) int32 directory, the row of the brick at
+    that cell or -1; views (V, 18) float32 ray generators in window voxel units; size = (H, W) of the canvas and
+    view_sizes an optional list of V (h, w) rectangles inside it; palette (P, 3) uint8; target like labels (error mode);
+    background (V, H, W, 3) uint8 blended with `alpha` (0..256); t_max: hits deeper than this are misses; skip=False
+    walks absent bricks voxel by voxel (the same images, for A/B runs).  All on the GPU and contiguous.  -> rgb
+    (V, H, W, 3) uint8, and with aux also hit int64 (row * 4096 + local voxel or -1), face uint8, depth float32 (V, H, W)."""
+    if labels.dtype != torch.uint8 or labels.dim() not in (2, 4) or labels.shape[0] < 1 or labels[0].numel() != _MAP_BRICK_VOX:
+        raise RuntimeError("labels must be uint8 (n, %d) brick rows, got %s %s" % (_MAP_BRICK_VOX, tuple(labels.shape), labels.dtype))
+    if cells.dtype != torch.int32 or cells.dim() != 3:
+        raise RuntimeError("cells must be an int32 (gx, gy, gz) directory, got %s %s" % (tuple(cells.shape), cells.dtype))
+    if views.dtype != torch.float32 or views.dim() != 2 or views.shape[1] != 18:
+        raise RuntimeError("views must be float32 (V, 18), got %s %s" % (tuple(views.shape), views.dtype))
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3:
+        raise RuntimeError("palette must be uint8 (P, 3)")
+    V = int(views.shape[0])
+    H, W = int(size[0]), int(size[1])
+    dev = labels.device
+    a = MapRenderArgs()
+    a.labels, a.cells, a.views, a.palette = _ptr(labels, "labels"), _ptr(cells, "cells"), _ptr(views, "views"), _ptr(palette, "palette")
+    if target is not None:
+        if target.dtype != torch.uint8 or target.shape != labels.shape:
+            raise RuntimeError("target must be uint8 brick rows with the shape of labels")
+        a.target = _ptr(target, "target")
+    if background is not None:
+        if background.dtype != torch.uint8 or tuple(background.shape) != (V, H, W, 3):
+            raise RuntimeError("background must be uint8 (V, H, W, 3) = %s" % ((V, H, W, 3),))
+        a.background = _ptr(background, "background")
+    for t, name in ((cells, "cells"), (views, "views"), (palette, "palette"), (target, "target"), (background, "background")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, labels on {dev}")
+    if view_sizes is not None:
+        if len(view_sizes) != V:
+            raise RuntimeError("view_sizes needs one (h, w) per view")
+        for i, (h, w) in enumerate(view_sizes):
+            a.view_h[i], a.view_w[i] = int(h), int(w)
+    rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+    a.rgb = rgb.data_ptr()
+    hit = face = depth = None
+    if aux:
+        hit = torch.empty((V, H, W), dtype=torch.int64, device=dev)
+        face = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+        depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+        a.hit, a.face, a.depth = hit.data_ptr(), face.data_ptr(), depth.data_ptr()
+    a.gx, a.gy, a.gz = (int(d) for d in cells.shape)
+    a.n_rows, a.n_views, a.H, a.W = int(labels.shape[0]), V, H, W
+    a.n_palette, a.alpha = int(palette.shape[0]), int(alpha)
+    a.t_max, a.flags = float(t_max), 0 if skip else 1
+    for i in range(3):
+        a.bg_colour[i] = int(bg_colour[i])
+    _check(load().occd_map_render(ctypes.byref(a), _stream()), "occd_map_render")
+    return (rgb, hit, face, depth) if aux else rgb
 
 
 # ----------------------------------------------------------------------------- stereo depth targets (csrc/stereo.hip)

@@ -171,12 +171,13 @@ class OccDepth(_Base):
                                         decay=float(env("OCCDEPTH_FUSE_DECAY", "1.0")))
         # Sequence-level semantic map of the test / validation frames (semantic_map.py), OFF by default:
         # `enable_semantic_map()` -- or OCCDEPTH_MAP_DIR=<dir> OCCDEPTH_MAP_POSES=<.../dataset/sequences> (falls back to
-        # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] in the environment of an unmodified scripts/eval.py.  Off: nothing is
+        # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] [OCCDEPTH_MAP_VIEWS=bev,oblique] in the environment of an unmodified scripts/eval.py.  Off: nothing is
         # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
         self.semantic_map = None
         if env("OCCDEPTH_MAP_DIR", ""):
             self.enable_semantic_map(env("OCCDEPTH_MAP_DIR"), env("OCCDEPTH_MAP_POSES", "") or env("OCCDEPTH_FUSE_POSES", ""),
-                                     min_obs=int(env("OCCDEPTH_MAP_MIN_OBS", "1")))
+                                     min_obs=int(env("OCCDEPTH_MAP_MIN_OBS", "1")),
+                                     views=tuple(v for v in env("OCCDEPTH_MAP_VIEWS", "").split(",") if v))
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -780,7 +781,7 @@ class OccDepth(_Base):
         metric.add_batch(torch.stack(labels), target)
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
-    def enable_semantic_map(self, out_dir, poses_root, min_obs=1):
+    def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=()):
         """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
         ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
         prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
@@ -788,7 +789,9 @@ class OccDepth(_Base):
         and _gt.ply (voxels with at least `min_obs` votes), the prediction maps are scored against the ground-truth maps
         where both were observed -- `val_map/mIoU`, `val_map/IoU` are logged, `test_epoch_end` prints a `test_map======`
         block -- and the maps are released.  Votes commute, so frames may arrive in any order; a sequence must stay on one
-        rank.  Memory: 163840 bytes per 16^3 brick and map at 20 classes."""
+        rank.  Memory: 163840 bytes per 16^3 brick and map at 20 classes.  views: any of "bev", "oblique" -- before the
+        maps are released every sequence is also drawn (render.render_map on semantic_map.MapVolume(pred, gt, min_obs))
+        to <out_dir>/<step>_<sequence>_{pred,gt,err}_{view}.png; () draws nothing and imports nothing more."""
         if self.dataset != "kitti":
             raise NotImplementedError("the semantic map reads SemanticKITTI poses and is wired for the SemanticKITTI geometry "
                                       "only; a %s model has no ego-motion to lay its frames out with" % self.dataset)
@@ -799,8 +802,11 @@ class OccDepth(_Base):
             raise ValueError("the semantic map needs a directory to write its PLY files to (out_dir / OCCDEPTH_MAP_DIR)")
         if int(min_obs) < 1:
             raise ValueError("min_obs must be >= 1, got %r" % (min_obs,))
+        views = tuple(str(v) for v in views)
+        if any(v not in ("bev", "oblique") for v in views):
+            raise ValueError("a map view is 'bev' or 'oblique' (views / OCCDEPTH_MAP_VIEWS), got %r" % (views,))
         self.semantic_map = {"out_dir": str(out_dir), "poses_root": str(poses_root), "min_obs": int(min_obs),
-                             "maps": {}, "poses": {}, "paths": []}
+                             "maps": {}, "poses": {}, "paths": [], "views": views}
         return self
 
     def _map_step(self, step_type, batch, ssc_pred, target):
@@ -853,6 +859,10 @@ class OccDepth(_Base):
                 path = os.path.join(st["out_dir"], "%s_%s_%s.ply" % (step_type, key[1], name))
                 st["paths"].append(semantic_map.write_ply(path, coords, labels, n_obs, m.voxel_size, colours))
             semantic_map.map_confusion(pair[0], pair[1], metric)
+            if st.get("views"):
+                volume = semantic_map.MapVolume(pair[0], pair[1], st["min_obs"])
+                prefix = os.path.join(st["out_dir"], "%s_%s" % (step_type, key[1]))
+                st["paths"] += render.write_map_pictures(volume, prefix, st["views"], palette=colours)
             for m in pair:
                 m.release()
         return self._epoch_stats(metric)

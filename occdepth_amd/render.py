@@ -197,6 +197,116 @@ def render_logits(ssc_logit, views, size, **kw):
     return render_labels(hip.argmax_labels_u16(ssc_logit), views, size, **kw)
 
 
+# --------------------------------------------------------------------------------------------------- the sequence map
+MAP_BEV_SIDE = 2048
+
+
+def render_map(volume, views, size, mode="class", background=None, alpha=160, palette=None, t_max=None, return_aux=False,
+               skip=True):
+    """Draw a sequence map (semantic_map.MapVolume) by ray-casting its bricks directly (csrc/map_render.hip, one launch).
+    views: (18,), (V, 18) or a list of (18,) tensors in the volume's window voxel units (`map_camera_view`,
+    `map_bev_view`, `map_oblique_view`).  size: (H, W) for every view -> rgb (V, H, W, 3) uint8; or one (h, w) per view
+    -> a list of V tensors (h, w, 3) rendered in the same launch.  mode "error" colours the prediction against the
+    ground-truth map and needs a volume built with `gt`.  background (V, H, W, 3) uint8 + alpha (0..256): the voxels are
+    blended over it.  palette: as for `render_labels` (default: the volume's class count).  t_max: hits deeper than this
+    (in the unit of the view's t: metres for a camera, voxels otherwise) are misses; None = no limit.  return_aux: also
+    hit (row * 4096 + brick-local voxel, or -1; int64), face, depth.  The images are, bit for bit, what `render_labels`
+    draws from the window's dense volume.  skip=False walks absent bricks voxel by voxel (the same images; for A/B runs)."""
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s, got %r" % (MODES, mode))
+    if mode == "error" and volume.target is None:
+        raise ValueError("mode='error' needs a MapVolume built with a ground-truth map (gt)")
+    dev = volume.labels.device
+    views = _stack_views(views, 1, dev)[0].contiguous()
+    V = views.shape[0]
+    per_view = not isinstance(size[0], int)
+    sizes = [tuple(int(s) for s in hw) for hw in size] if per_view else None
+    if per_view and len(sizes) != V:
+        raise ValueError("%d sizes for %d views" % (len(sizes), V))
+    H, W = (max(s[0] for s in sizes), max(s[1] for s in sizes)) if per_view else (int(size[0]), int(size[1]))
+    out = hip.map_render(volume.labels, volume.cells, views, (H, W), _device_palette(palette, volume.n_classes, dev),
+                         target=volume.target if mode == "error" else None, background=background, alpha=alpha,
+                         bg_colour=BACKGROUND, view_sizes=sizes, t_max=float("inf") if t_max is None else float(t_max),
+                         skip=skip, aux=return_aux)
+    if not per_view:
+        return out
+    crop = lambda t: [t[i, :h, :w] for i, (h, w) in enumerate(sizes)]
+    return tuple(crop(t) for t in out) if return_aux else crop(out)
+
+
+def map_camera_view(cam_k, T_velo_2_cam, pose, volume, flip=False, width=None):
+    """The map seen through a frame's camera: cam_k (3, 3), T_velo_2_cam (4, 4) (sensor -> camera) and the frame's `pose`
+    (4 x 4 sensor -> world, as fuse.read_kitti_poses returns) -> (18,) float32 in the volume's window voxel units, t =
+    camera depth in metres.  Equals camera_view(cam_k, T_velo_2_cam @ rigid_inverse(pose), volume.origin_metres,
+    volume.voxel_size), but composed in float64 relative to the window origin: the camera centre is formed as
+    R_pose c + (t_pose - origin), so a pose kilometres from world zero keeps the float32 ray origins small."""
+    k = torch.as_tensor(cam_k).to(torch.float64).cpu()
+    E = torch.as_tensor(T_velo_2_cam).to(torch.float64).cpu()
+    P = torch.as_tensor(np.asarray(pose, dtype=np.float64)) if not torch.is_tensor(pose) else pose.to(torch.float64).cpu()
+    org = torch.as_tensor(np.asarray(volume.origin_metres, dtype=np.float64))
+    R = P[:3, :3]
+    world_2_cam = torch.eye(4, dtype=torch.float64)                    # world' -> camera, world' = world - window origin
+    world_2_cam[:3, :3] = E[:3, :3] @ R.T
+    world_2_cam[:3, 3] = E[:3, 3] - E[:3, :3] @ (R.T @ (P[:3, 3] - org))
+    view = camera_view(k, world_2_cam, (0.0, 0.0, 0.0), volume.voxel_size, flip=flip, width=width)
+    return view.to(volume.labels.device)
+
+
+def map_bev_view(volume, max_side=MAP_BEV_SIDE):
+    """Orthographic view from above over the whole window -> (view (18,), (h, w)): `bev_view` at the largest whole number
+    of pixels per voxel whose image fits `max_side`.  Where the window is longer than `max_side` voxels, one pixel per n =
+    ceil(side / max_side) voxels instead: the pixel draws the column under its centre and the n^2 - 1 others are not
+    looked at -- point sampling, not an average; thin structures can drop out of such a picture."""
+    X, Y = int(volume.dims[0]), int(volume.dims[1])
+    side, max_side = max(X, Y), int(max_side)
+    if max_side < 1:
+        raise ValueError("max_side must be >= 1, got %r" % (max_side,))
+    dev = volume.labels.device
+    if side <= max_side:
+        ppv = max_side // side
+        return bev_view(volume.dims, ppv, device=dev), bev_size(volume.dims, ppv)
+    n = -(-side // max_side)
+    return bev_view(volume.dims, 1.0 / n, device=dev), (-(-X // n), -(-Y // n))
+
+
+def map_oblique_view(volume, size, azimuth=-60.0, elevation=35.0):
+    """`oblique_view` over the volume's window."""
+    return oblique_view(volume.dims, size, azimuth, elevation, device=volume.labels.device)
+
+
+MAP_VIEW_NAMES = ("bev", "oblique")
+
+
+def map_standard_views(names, volume, bev_side=None):
+    """The views the model hook and tools/map_sequence.py draw of a map -> ([(18,) tensors], [(h, w)])."""
+    views, sizes = [], []
+    for name in names:
+        if name == "bev":
+            view, size = map_bev_view(volume, MAP_BEV_SIDE if bev_side is None else bev_side)
+        elif name == "oblique":
+            view, size = map_oblique_view(volume, OBLIQUE_SIZE), OBLIQUE_SIZE
+        else:
+            raise ValueError("unknown map view %r (have %s)" % (name, MAP_VIEW_NAMES))
+        views.append(view)
+        sizes.append((int(size[0]), int(size[1])))
+    return views, sizes
+
+
+def write_map_pictures(volume, prefix, names, bev_side=None, palette=None):
+    """<prefix>_{pred,gt,err}_{view}.png of a MapVolume (pred alone when it was built without gt) -> the paths.  The gt
+    picture draws the volume with the target as labels."""
+    views, sizes = map_standard_views(names, volume, bev_side)
+    kinds = [("pred", volume, "class")]
+    if volume.target is not None:
+        kinds += [("gt", volume.target_volume(), "class"), ("err", volume, "error")]
+    paths = []
+    for kind, vol, mode in kinds:
+        images = render_map(vol, views, sizes, mode=mode, palette=palette)
+        for name, img in zip(names, images):
+            paths.append(write_png("%s_%s_%s.png" % (prefix, kind, name), img))
+    return paths
+
+
 # --------------------------------------------------------------------------------------------------------------- png
 def write_png(path, rgb):
     """(H, W, 3) or (H, W) uint8 array / tensor -> an 8-bit PNG (filter 0 on every row; zlib and struct only)."""

@@ -288,6 +288,103 @@ def map_confusion(pred_map, gt_map, metric, chunk_bricks=512):
     return metric
 
 
+# ----------------------------------------------------------------------------------------------------- drawable form
+MAX_CELLS = 1 << 27                         # directory entries of a MapVolume (512 MB of int32)
+MAX_GRID = 1 << 16                          # bricks along one axis of its window
+
+
+class MapVolume:
+    """A map in the form render.render_map draws (K31, csrc/map_render.hip): one 4096-byte row of labels per brick and a
+    dense directory of the bricks over the map's bounding window.
+
+    Rows: the brick keys of `pred`, united with those of `gt` when given, clipped to the inclusive brick-key box
+    key_range = (lo(3), hi(3)) when given, ascending in (k0, k1, k2).  labels (n, 4096) uint8 = pred.brick_labels(keys),
+    with min_obs > 1 set to 255 where a voxel has fewer votes; target (n, 4096) uint8 = gt.brick_labels(keys), set to 255
+    where the prediction is 255 (map_confusion's rule: a voxel counts only where both maps were observed), or None.
+    Window: key_min / key_max over the rows, grid = key_max - key_min + 1 bricks, dims = 16 grid voxels, origin_voxels =
+    16 key_min (int64), origin_metres = origin_voxels * voxel_size (float64); world voxel I spans [I v, (I + 1) v).
+    Directory: cells (Gx, Gy, Gz) int32 on the device, the row of the brick at that cell, -1 where there is none and,
+    with drop_empty, where the brick holds no drawable voxel (its row stays: row indices are stable).  Drawable: label in
+    1..254 (what class mode draws); with a target also target != 255 and (label in 1..254 or target != 0) (what error mode
+    draws, and a class-mode picture of the target) -- a brick is dropped only when no mode would draw any of its voxels,
+    so one volume serves the prediction, ground-truth and error pictures.  No host synchronisation.
+
+        def target_volume(): the same window with the target as labels (the ground-truth picture)."""
+
+    def __init__(self, pred, gt=None, min_obs=1, key_range=None, drop_empty=True, chunk_bricks=512):
+        if gt is not None and (pred.voxel_size != gt.voxel_size or pred.n_classes != gt.n_classes):
+            raise ValueError("the two maps differ in voxel size (%r, %r) or classes (%r, %r)"
+                             % (pred.voxel_size, gt.voxel_size, pred.n_classes, gt.n_classes))
+        if int(min_obs) < 1:
+            raise ValueError("min_obs must be >= 1, got %r" % (min_obs,))
+        self.voxel_size, self.n_classes, self.min_obs = pred.voxel_size, pred.n_classes, int(min_obs)
+        packed = set(pred.directory) | (set(gt.directory) if gt is not None else set())
+        keys = unpack_keys(np.sort(np.fromiter(packed, dtype=np.int64, count=len(packed))))
+        if key_range is not None:
+            lo, hi = (np.asarray(k, dtype=np.int64).reshape(3) for k in key_range)
+            keys = keys[((keys >= lo) & (keys <= hi)).all(1)]
+        if not len(keys):
+            raise ValueError("the map has no brick to draw" + ("" if key_range is None else " inside key_range = %r" % (key_range,))
+                             + " (key_range selects an inclusive box of brick keys)")
+        self.keys = keys
+        self.key_min, self.key_max = keys.min(0), keys.max(0)
+        grid = self.key_max - self.key_min + 1
+        if grid.max() > MAX_GRID or int(grid[0]) * int(grid[1]) * int(grid[2]) > MAX_CELLS:
+            raise ValueError("the map's window is %d x %d x %d bricks: more than 2^16 along an axis or more than 2^27 cells; "
+                             "draw a part of it with key_range" % tuple(grid))
+        self.grid = tuple(int(g) for g in grid)
+        self.dims = tuple(BRICK * g for g in self.grid)
+        self.origin_voxels = BRICK * self.key_min
+        self.origin_metres = self.origin_voxels.astype(np.float64) * self.voxel_size
+        dev = next((m.votes.device for m in (pred, gt) if m is not None and m.votes is not None), torch.device("cpu"))
+        labels, target, drawn = [], [], []
+        for s in range(0, len(keys), int(chunk_bricks)):
+            part = keys[s:s + int(chunk_bricks)]
+            lab = pred.brick_labels(part, device=dev).reshape(len(part), BRICK ** 3)
+            if self.min_obs > 1 and pred.votes is not None:
+                slots = torch.from_numpy(pred.slots(part).astype(np.int64))
+                have = slots >= 0
+                n_obs = torch.zeros(lab.shape, dtype=torch.int32, device=dev)
+                if bool(have.any()):
+                    votes = pred.pool()[slots[have].to(dev)]
+                    n_obs[have.to(dev)] = (votes.to(torch.int32) & 0xFFFF).sum(-1, dtype=torch.int32)
+                lab = torch.where(n_obs < self.min_obs, torch.full_like(lab, 255), lab)
+            occ = (lab > 0) & (lab < 255)
+            if gt is not None:
+                tg = gt.brick_labels(part, device=dev).reshape(len(part), BRICK ** 3)
+                tg = torch.where(lab == 255, lab, tg)
+                target.append(tg)
+                occ = occ | ((tg != 255) & (tg != 0))                       # class mode's rule or error mode's
+            labels.append(lab)
+            drawn.append(occ.any(1))
+        self.labels = torch.cat(labels).contiguous()
+        self.target = torch.cat(target).contiguous() if gt is not None else None
+        self.drawable = torch.cat(drawn)                                     # (n,) bool: the brick holds something to draw
+        rows = torch.arange(len(keys), dtype=torch.int32, device=dev)
+        if drop_empty:
+            rows = torch.where(self.drawable, rows, torch.full_like(rows, -1))
+        at = torch.from_numpy(keys - self.key_min).to(dev)
+        self.cells = torch.full(self.grid, -1, dtype=torch.int32, device=dev)
+        self.cells[at[:, 0], at[:, 1], at[:, 2]] = rows
+
+    def target_volume(self):
+        """The same rows and directory with the target as labels and no target: class mode draws the ground truth."""
+        if self.target is None:
+            raise ValueError("the volume was built without a ground-truth map")
+        import copy
+        v = copy.copy(self)
+        v.labels, v.target = self.target, None
+        return v
+
+    @property
+    def n_rows(self):
+        return int(self.labels.shape[0])
+
+    @property
+    def device(self):
+        return self.labels.device
+
+
 # ----------------------------------------------------------------------------------------------------- PLY
 PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
                       ("label", "u1"), ("n_obs", "<u2")])

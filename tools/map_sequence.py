@@ -2,7 +2,7 @@
 as a point PLY, and score a prediction map against a ground-truth map.
 
     python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
-        --out maps/08 [--min-obs 2] [--fov] [--every 5]
+        --out maps/08 [--min-obs 2] [--fov] [--every 5] [--views bev oblique] [--png-side 2048] [--camera-every 50 --t-max 80]
 
 --pred / --gt name a directory; what it holds decides how it is read:
     <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
@@ -11,7 +11,9 @@ as a point PLY, and score a prediction map against a ground-truth map.
                                          brings them back to the 20 training classes; any other id does not vote)
     <frame>.label with <frame>.invalid   the dataset's raw voxels, decoded on the GPU (targets.kitti_labels)
 --poses is the sequence directory with poses.txt and calib.txt.  Writes <out>_pred.ply / <out>_gt.ply and, given both
-sources, prints the map's Precision / Recall / IoU / mIoU over the voxels both maps observed.
+sources, prints the map's Precision / Recall / IoU / mIoU over the voxels both maps observed.  --views also draws the maps
+(render.render_map, the bricks ray-cast on the GPU) to <out>_{pred,gt,err}_{view}.png; --camera-every N draws them through
+the left colour camera (P2 and Tr of calib.txt) of every N-th posed frame to <out>_{pred,gt,err}_camera_<frame>.png.
 """
 import argparse
 import glob
@@ -85,6 +87,52 @@ def build_map(src, role, poses, args, device):
     return m
 
 
+def read_camera(seq_dir):
+    """calib.txt -> (cam_k (3, 3), sensor -> left colour camera (4, 4)), float64: cam_k = P2[:, :3] and the extrinsic is
+    Tr shifted by K^-1 P2[:, 3] (P2 projects from the rectified camera 0 frame, which Tr maps the sensor into)."""
+    rows = {}
+    with open(os.path.join(seq_dir, "calib.txt")) as f:
+        for line in f:
+            name, _, rest = line.partition(":")
+            if rest.strip():
+                rows[name.strip()] = np.array([float(x) for x in rest.split()], dtype=np.float64)
+    missing = [k for k in ("P2", "Tr") if k not in rows or rows[k].size != 12]
+    if missing:
+        raise KeyError("%s has no %s row of 12 numbers" % (os.path.join(seq_dir, "calib.txt"), " / ".join(missing)))
+    P2 = rows["P2"].reshape(3, 4)
+    E = np.eye(4)
+    E[:3] = rows["Tr"].reshape(3, 4)
+    E[:3, 3] += np.linalg.solve(P2[:, :3], P2[:, 3])
+    return P2[:, :3].copy(), E
+
+
+def draw(maps, poses, args, colours):
+    """The pictures of --views and --camera-every, next to the PLYs -> the paths."""
+    pred = maps.get("pred") or maps["gt"]
+    volume = sm.MapVolume(pred, maps.get("gt") if "pred" in maps else None, args.min_obs)
+    paths = []
+    if args.views:
+        if "pred" in maps:
+            paths += render.write_map_pictures(volume, args.out, args.views, bev_side=args.png_side, palette=colours)
+        else:                                                              # a ground-truth map alone
+            views, sizes = render.map_standard_views(args.views, volume, args.png_side)
+            for name, img in zip(args.views, render.render_map(volume, views, sizes, palette=colours)):
+                paths.append(render.write_png("%s_gt_%s.png" % (args.out, name), img))
+    if args.camera_every:
+        cam_k, E = read_camera(args.poses)
+        size = tuple(args.camera_size)
+        kinds = [("pred" if "pred" in maps else "gt", volume, "class")]
+        if volume.target is not None:
+            kinds += [("gt", volume.target_volume(), "class"), ("err", volume, "error")]
+        for frame in sorted(poses)[::args.camera_every]:
+            view = render.map_camera_view(cam_k, E, poses[frame], volume)
+            for kind, vol, mode in kinds:
+                img = render.render_map(vol, view, size, mode=mode, palette=colours, t_max=args.t_max)[0]
+                paths.append(render.write_png("%s_%s_camera_%06d.png" % (args.out, kind, frame), img))
+    print("%d pictures, window %d x %d x %d voxels, %d bricks" % ((len(paths),) + volume.dims + (volume.n_rows,)))
+    return paths
+
+
 def run(args, device=None):
     device = device or torch.device("cuda")
     poses = fuse.read_kitti_poses(args.poses)
@@ -100,6 +148,8 @@ def run(args, device=None):
             print("%s: %d voxels with at least %d vote(s)" % (path, len(labels), args.min_obs))
     if not maps:
         raise SystemExit("give --pred, --gt or both")
+    if args.views or args.camera_every:
+        draw(maps, poses, args, colours)
     stats = None
     if len(maps) == 2:
         from occdepth_amd.loss.sscMetrics import SSCMetrics
@@ -125,6 +175,13 @@ def parser():
     ap.add_argument("--origin", type=float, nargs=3, default=(0.0, -25.6, -2.0))
     ap.add_argument("--classes", type=int, default=20)
     ap.add_argument("--max-bricks", type=int, default=None)
+    ap.add_argument("--views", nargs="*", default=[], choices=render.MAP_VIEW_NAMES,
+                    help="draw the map: <out>_{pred,gt,err}_{view}.png (render.render_map)")
+    ap.add_argument("--png-side", type=int, default=render.MAP_BEV_SIDE, help="longest side of the bev picture, pixels")
+    ap.add_argument("--camera-every", type=int, default=0,
+                    help="draw the map through the left colour camera (P2, Tr of calib.txt) of every n-th posed frame")
+    ap.add_argument("--camera-size", type=int, nargs=2, default=(370, 1220), help="H W of the camera pictures")
+    ap.add_argument("--t-max", type=float, default=80.0, help="camera pictures: voxels deeper than this (m) are not drawn")
     return ap
 
 

@@ -79,7 +79,9 @@ extern "C" {
  *     OccdMapExtractArgs, occd_map_integrate, occd_map_brick_labels, occd_map_count and occd_map_extract (the sequence-level
  *     semantic voxel map, csrc/semantic_map.hip): two new structs and new functions only; likewise OccdMapRenderArgs and
  *     occd_map_render (K31, the sparse two-level ray cast over the map's bricks, csrc/map_render.hip): one new struct and
- *     one new function only */
+ *     one new function only; likewise OCCD_MAP_SAMPLE_EXCLUDE_SELF, OCCD_MAP_SAMPLE_KEEP_OWN, OccdMapSampleArgs and
+ *     occd_map_sample (K32, the map read back into a frame's voxels, csrc/semantic_map.hip): one new struct and one new
+ *     function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1391,6 +1393,61 @@ int occd_map_integrate(const OccdMapFrameArgs* a, void* stream);
 int occd_map_brick_labels(const OccdMapExtractArgs* a, void* stream);
 int occd_map_count(const OccdMapExtractArgs* a, void* stream);
 int occd_map_extract(const OccdMapExtractArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K32: read the sequence map back into a frame (occd_map_sample, csrc/semantic_map.hip).  Additive (OCCD_ABI_VERSION
+ * note).  One launch per frame, one thread per frame voxel (z fastest): every voxel of the frame's (X, Y, Z) grid looks
+ * up the world voxel its centre falls into and decides it by the votes the whole sequence left there.  The pool is only
+ * read.  No atomics, no allocation, no host sync (capture-safe); every output byte depends on the inputs alone.
+ *
+ * Window: the inclusive brick-key box key_min .. key_max of the frame's candidate bricks (the brick range of the grid's
+ * eight corners in world voxels, one voxel wider on every side); grid = key_max - key_min + 1 bricks, W0 = 16 key_min.
+ * cells[(cx gy + cy) gz + cz] is the row in `table` of the brick at that cell, or negative where the map has no such brick.
+ * `table` has integrate's layout, 16 int32 per row: slot | key[3] | Aq[9] | cq[3] (Aq, cq of THIS frame's pose).
+ *
+ * Geometry, int32 fixed point with 16 fractional bits (unsigned wrapping arithmetic; the host keeps |wq| < 2^31: it
+ * refuses X + Y + Z >= 2^14 and |d| >= 2^14).  For the frame voxel g = (x, y, z), n = (x Y + y) Z + z:
+ *   wq[r] = Bq[r][0] x + Bq[r][1] y + Bq[r][2] z + dq[r];   idx[r] = wq[r] >> 16   (arithmetic shift = floor)
+ * with Bq = rint(R 2^16), dq = rint(d 2^16), d = R (1/2 + o / v) + t / v - W0 composed by the host in float64: idx is the
+ * world voxel relative to W0.  cell = idx >> 4, local = idx & 15.  The brick is ABSENT when cell is outside grid, the
+ * cell's row is outside [0, n_bricks) or that row's slot is outside [0, capacity); otherwise the voxel's counters are
+ * the row (local0 * 16 + local1) * 16 + local2 of brick `slot`, read in 8-byte pieces.
+ *
+ * Decision per voxel.  flags & OCCD_MAP_SAMPLE_EXCLUDE_SELF takes this frame's own vote out: with the row's Aq | cq the
+ * frame voxel n' that occd_map_integrate maps this world voxel to is computed (same formula, same wrapping), and the
+ * counter own[n'] counts one less iff n' is inside (X, Y, Z), (own_mask == NULL or own_mask[n'] != 0), own[n'] < C, and
+ * the counter is neither 0 nor 65535 (a saturated counter has forgotten how many votes it dropped and is not retracted).
+ * n' need not be n: the two nearest-voxel maps are not inverses.  Then n_obs = the sum of the counters, label = their
+ * arg-max, the lowest class on a tie.  flags & OCCD_MAP_SAMPLE_KEEP_OWN: if own[n] < C and its counter equals the
+ * maximum and the maximum is > 0, label = own[n].  Outputs:
+ *   labels[n] = label where n_obs >= max(min_obs, 1); elsewhere own[n] (a value >= 255 becomes 255) when own is given,
+ *               else 255.  An absent brick has n_obs = 0.
+ *   n_obs[n]  = the sum saturated at 65535, always written.
+ * own is read as 1 or 2 bytes per voxel (label_bytes), as in occd_map_integrate.
+ * OCCD_EINVAL before any launch: a NULL argument, NULL votes / table / cells / labels / n_obs, C outside 1..32, pitch < C
+ * or pitch % 4 != 0 or votes not 8-byte aligned, non-positive dims, grid, n_bricks or capacity, X Y Z > 2^28,
+ * gx gy gz > 2^27, a flag without own or an unknown flag, min_obs < 0, label_bytes not 1 or 2, a slot >= capacity in
+ * table_host (a negative one is a brick that is not in the map).
+ * ------------------------------------------------------------------------ */
+#define OCCD_MAP_SAMPLE_EXCLUDE_SELF 1
+#define OCCD_MAP_SAMPLE_KEEP_OWN 2
+typedef struct OccdMapSampleArgs {
+    const uint16_t* votes;         /* (capacity, 4096, pitch) vote counters, read only                               */
+    const int32_t* table;          /* (n_bricks, 16) device                                                          */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    const int32_t* cells;          /* (gx, gy, gz) device: row of the brick, negative = absent                       */
+    const void* own;               /* (X Y Z) labels of the frame itself, label_bytes each, or NULL                  */
+    const uint8_t* own_mask;       /* (X Y Z) bytes, the mask the frame voted with, or NULL                          */
+    uint8_t* labels;               /* (X Y Z) out                                                                    */
+    uint16_t* n_obs;               /* (X Y Z) out                                                                    */
+    int32_t n_bricks, capacity;
+    int32_t X, Y, Z;
+    int32_t gx, gy, gz;
+    int32_t C, pitch, label_bytes;
+    int32_t min_obs, flags;
+    int32_t Bq[9], dq[3];          /* row-major rint(R 2^16), rint(d 2^16)                                           */
+} OccdMapSampleArgs;
+int occd_map_sample(const OccdMapSampleArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * K31: render the sequence map (csrc/map_render.hip).  Additive (OCCD_ABI_VERSION note).  One ray per pixel through the

@@ -1,4 +1,5 @@
-// K30: the sequence-level semantic map (occd_map_integrate, occd_map_brick_labels, occd_map_count, occd_map_extract).
+// K30: the sequence-level semantic map (occd_map_integrate, occd_map_brick_labels, occd_map_count, occd_map_extract), and
+// K32: the map read back into a frame's voxels (occd_map_sample).
 // Contract: include/occdepth_amd.h.
 //
 // The map is a pool of 16^3 bricks of unsigned 16-bit vote counters, one row of `pitch` counters per voxel, row
@@ -27,6 +28,7 @@ constexpr int kBrick = OCCD_MAP_BRICK;
 constexpr int kBrickVox = kBrick * kBrick * kBrick;     // 4096
 constexpr int kThreads = kBrick * kBrick;               // 256: the (j, l) plane, or one pass of the extraction
 constexpr int64_t kMaxVox = (int64_t)1 << 28;           // flat frame indices stay far inside int32
+constexpr int64_t kMaxCells = (int64_t)1 << 27;         // directory entries of a sample window
 static_assert(kBrick == 16, "the thread layouts below are written for 16^3 bricks");
 
 template <int BYTES>
@@ -65,12 +67,16 @@ __global__ void __launch_bounds__(kThreads) map_integrate_kernel(const OccdMapFr
     }
 }
 
-// argmax (the lowest class on a tie) and sum of the C counters of one row, read in 8-byte pieces
-__device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t& label, uint32_t& nobs) {
+// argmax (the lowest class on a tie) and sum of the C counters of one row, read in 8-byte pieces.  The counter of class
+// `dec` counts one less unless it is 0 or 65535 (sample's exclude_self; ~0u: none); best = the maximum, at = the counter
+// of class `ask` (0 when there is no such class)
+__device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t dec, uint32_t ask, uint32_t& label, uint32_t& nobs,
+                                       uint32_t& best, uint32_t& at) {
     const u32x2* q = reinterpret_cast<const u32x2*>(row);
-    uint32_t best = 0;
+    best = 0;
     label = 0;
     nobs = 0;
+    at = 0;
     const int nq = (C + 3) >> 2;                        // <= 8, and 4 nq <= pitch
     for (int k = 0; k < nq; ++k) {
         const u32x2 w = q[k];
@@ -79,11 +85,18 @@ __device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t& lab
         for (int e = 0; e < 4; ++e) {
             const int c = 4 * k + e;
             if (c < C) {
-                nobs += v[e];
-                if (v[e] > best) { best = v[e]; label = (uint32_t)c; }
+                const uint32_t n = v[e] - (uint32_t)((uint32_t)c == dec && v[e] != 0u && v[e] != 0xffffu);
+                nobs += n;
+                if ((uint32_t)c == ask) at = n;
+                if (n > best) { best = n; label = (uint32_t)c; }
             }
         }
     }
+}
+
+__device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t& label, uint32_t& nobs) {
+    uint32_t best, at;
+    decide(row, C, ~0u, ~0u, label, nobs, best, at);
 }
 
 __global__ void __launch_bounds__(kThreads) map_brick_labels_kernel(const OccdMapExtractArgs a) {
@@ -145,6 +158,66 @@ __global__ void __launch_bounds__(kThreads) map_scan_kernel(const OccdMapExtract
     if (!WRITE && tid == 0) a.counts[blockIdx.x] = total;
 }
 
+// K32: one thread per frame voxel, z fastest.  The transposed access pattern of integrate: there a brick's (j, l) plane
+// reads labels that are scattered over the frame, here a z-column of the frame reads vote rows -- under a pure yaw z runs
+// along the brick's l, so the 16 lanes of a z-run read 16 consecutive rows (16 * pitch * 2 contiguous bytes, 640 at pitch
+// 20) and a wave touches as few 128-byte lines per load as the frame's heading allows; labels and n_obs are written
+// coalesced.  (A thread per (x, y) column walking z puts the lanes of a wave 16 rows or more apart, the argument of
+// integrate's header with the roles swapped.)
+template <int LB>
+__global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampleArgs a) {
+    const uint32_t S = (uint32_t)a.X * (uint32_t)a.Y * (uint32_t)a.Z;          // <= 2^28
+    const uint32_t n = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
+    if (n >= S) return;
+    const uint32_t z = n % (uint32_t)a.Z, xy = n / (uint32_t)a.Z;
+    const uint32_t y = xy % (uint32_t)a.Y, x = xy / (uint32_t)a.Y;
+    // unsigned arithmetic wraps; the host keeps |wq| < 2^31, and whatever bad coefficients give is range-checked below
+    int32_t cell[3];
+    uint32_t loc[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const uint32_t wq = (uint32_t)a.Bq[3 * r] * x + (uint32_t)a.Bq[3 * r + 1] * y + (uint32_t)a.Bq[3 * r + 2] * z + (uint32_t)a.dq[r];
+        const int32_t idx = (int32_t)wq >> 16;
+        cell[r] = idx >> 4;
+        loc[r] = (uint32_t)idx & 15u;
+    }
+    const uint32_t own = a.own != nullptr ? load_label<LB>(a.own, n) : 255u;
+    uint32_t label = 0, nobs = 0;
+    if (cell[0] >= 0 && cell[0] < a.gx && cell[1] >= 0 && cell[1] < a.gy && cell[2] >= 0 && cell[2] < a.gz) {
+        const int32_t r = a.cells[((size_t)cell[0] * (size_t)a.gy + (size_t)cell[1]) * (size_t)a.gz + (size_t)cell[2]];
+        if (r >= 0 && r < a.n_bricks) {
+            const int32_t* row = a.table + (size_t)r * 16;
+            const int32_t slot = row[0];
+            if (slot >= 0 && slot < a.capacity) {
+                uint32_t dec = ~0u;
+                if (a.flags & OCCD_MAP_SAMPLE_EXCLUDE_SELF) {              // the frame voxel integrate maps this world voxel to
+                    int32_t g[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const uint32_t gq = (uint32_t)row[4 + 3 * k] * loc[0] + (uint32_t)row[4 + 3 * k + 1] * loc[1] +
+                                            (uint32_t)row[4 + 3 * k + 2] * loc[2] + (uint32_t)row[13 + k];
+                        g[k] = (int32_t)gq >> 16;
+                    }
+                    if (g[0] >= 0 && g[0] < a.X && g[1] >= 0 && g[1] < a.Y && g[2] >= 0 && g[2] < a.Z) {
+                        const uint32_t m = ((uint32_t)g[0] * (uint32_t)a.Y + (uint32_t)g[1]) * (uint32_t)a.Z + (uint32_t)g[2];
+                        if (a.own_mask == nullptr || a.own_mask[m] != 0) {
+                            const uint32_t voted = load_label<LB>(a.own, m);
+                            if (voted < (uint32_t)a.C) dec = voted;
+                        }
+                    }
+                }
+                const uint32_t v = (loc[0] * kBrick + loc[1]) * kBrick + loc[2];
+                uint32_t best, at;
+                decide(a.votes + ((size_t)slot * kBrickVox + (size_t)v) * (size_t)a.pitch, a.C, dec, own, label, nobs, best, at);
+                if ((a.flags & OCCD_MAP_SAMPLE_KEEP_OWN) && own < (uint32_t)a.C && at == best && best > 0u) label = own;
+            }
+        }
+    }
+    const uint32_t need = a.min_obs > 1 ? (uint32_t)a.min_obs : 1u;
+    a.labels[n] = (uint8_t)(nobs >= need ? label : (own < 255u ? own : 255u));
+    a.n_obs[n] = (uint16_t)(nobs < 0xffffu ? nobs : 0xffffu);
+}
+
 bool pool_ok(const void* votes, const int32_t* table, int32_t n_bricks, int32_t capacity, int32_t C, int32_t pitch) {
     if (!votes || !table || n_bricks <= 0 || capacity <= 0 || C < 1 || C > 32) return false;
     return pitch >= C && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(votes) & 7) == 0;
@@ -200,5 +273,23 @@ extern "C" int occd_map_extract(const OccdMapExtractArgs* a, void* stream) {
     if (!extract_ok(a) || !a->offsets || !a->coords || !a->labels || !a->n_obs || a->n_out <= 0) return OCCD_EINVAL;
     occd::ProfScope prof("map_extract", (hipStream_t)stream, 0.0, pool_bytes(a->n_bricks, a->pitch) + 15.0 * (double)a->n_out);
     hipLaunchKernelGGL(map_scan_kernel<true>, dim3((unsigned)a->n_bricks), dim3(kThreads), 0, (hipStream_t)stream, *a);
+    return occd::check_launch();
+}
+
+extern "C" int occd_map_sample(const OccdMapSampleArgs* a, void* stream) {
+    if (!a || !a->cells || !a->labels || !a->n_obs || !pool_ok(a->votes, a->table, a->n_bricks, a->capacity, a->C, a->pitch))
+        return OCCD_EINVAL;
+    if (a->X <= 0 || a->Y <= 0 || a->Z <= 0 || (int64_t)a->X * a->Y * a->Z > kMaxVox) return OCCD_EINVAL;
+    if (a->gx <= 0 || a->gy <= 0 || a->gz <= 0 || (int64_t)a->gx * a->gy * a->gz > kMaxCells) return OCCD_EINVAL;
+    if ((a->flags & ~(OCCD_MAP_SAMPLE_EXCLUDE_SELF | OCCD_MAP_SAMPLE_KEEP_OWN)) != 0 || (a->flags != 0 && !a->own)) return OCCD_EINVAL;
+    if (a->min_obs < 0 || (a->label_bytes != 1 && a->label_bytes != 2)) return OCCD_EINVAL;
+    if (!slots_ok(a->table_host, a->n_bricks, 16, a->capacity, false)) return OCCD_EINVAL;
+    const double S = (double)a->X * a->Y * a->Z;
+    // every voxel reads its vote row and writes 3 bytes; its own label, the mask and the directory come on top
+    occd::ProfScope prof("map_sample", (hipStream_t)stream, 0.0,
+                         S * (a->pitch * 2.0 + 3.0 + (a->own ? a->label_bytes : 0)) + (double)a->gx * a->gy * a->gz * 4.0);
+    const dim3 grid((unsigned)(((int64_t)a->X * a->Y * a->Z + kThreads - 1) / kThreads));
+    if (a->label_bytes == 1) hipLaunchKernelGGL(map_sample_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL(map_sample_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
     return occd::check_launch();
 }

@@ -58,6 +58,9 @@ MapFrameArgs = abi.STRUCTS["OccdMapFrameArgs"]
 MapExtractArgs = abi.STRUCTS["OccdMapExtractArgs"]
 MAP_BRICK = abi.CONSTANTS["OCCD_MAP_BRICK"]
 MapRenderArgs = abi.STRUCTS["OccdMapRenderArgs"]
+MapSampleArgs = abi.STRUCTS["OccdMapSampleArgs"]
+MAP_SAMPLE_EXCLUDE_SELF = abi.CONSTANTS["OCCD_MAP_SAMPLE_EXCLUDE_SELF"]
+MAP_SAMPLE_KEEP_OWN = abi.CONSTANTS["OCCD_MAP_SAMPLE_KEEP_OWN"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2289,6 +2292,53 @@ def map_extract(votes, table, n_classes, min_obs=1, include_empty=False, table_h
             n_obs.data_ptr(), N
         _check(load().occd_map_extract(ctypes.byref(a), _stream()), "occd_map_extract")
     return coords, labels, n_obs
+
+
+def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask=None, min_obs=1, exclude_self=False,
+               keep_own=False, table_host=None):
+    """occd_map_sample (K32), one launch: every voxel of the (X, Y, Z) = `dims` frame reads the map back.  votes: the
+    int16 (capacity, 4096, pitch) pool (only read); table (n, 16) int32 (slot | key | Aq | cq per row, the frame's own
+    coefficients); cells (gx, gy, gz) = `grid` int32, the table row of the brick at each cell of the frame's window or
+    -1; own: the frame's own labels (X Y Z entries, uint8 / int16 / uint16) or None; own_mask: the (X Y Z) bool / uint8
+    mask it voted with or None; Bq (3, 3), dq (3,) from semantic_map.sample_coefficients.  exclude_self / keep_own need
+    `own`.  -> labels (X, Y, Z) uint8, n_obs (X, Y, Z) int16 holding uint16 bits.  The contract is in
+    include/occdepth_amd.h."""
+    X, Y, Z = (int(d) for d in dims)
+    S = X * Y * Z
+    if cells.dtype != torch.int32 or cells.dim() != 3 or tuple(cells.shape) != tuple(int(g) for g in grid):
+        raise RuntimeError("cells must be an int32 (gx, gy, gz) = %r directory, got %s %s" % (tuple(grid), tuple(cells.shape), cells.dtype))
+    if own is not None and (own.dtype not in _LABEL_BYTES or own.numel() != S):
+        raise RuntimeError("own must hold X Y Z = %d uint8 / int16 / uint16 entries, got %s %s" % (S, tuple(own.shape), own.dtype))
+    if own is None and (exclude_self or keep_own):
+        raise RuntimeError("exclude_self and keep_own need the frame's own labels")
+    Bq, dq = [int(v) for r in Bq for v in r], [int(v) for v in dq]
+    if len(Bq) != 9 or len(dq) != 3 or not all(-(1 << 31) <= v < 1 << 31 for v in Bq + dq):
+        raise RuntimeError("Bq must be a 3 x 3 and dq a 3-vector of int32 (semantic_map.sample_coefficients)")
+    a = MapSampleArgs()
+    _map_operands(a, votes, table, table_host, 16, n_classes)
+    a.cells = _ptr(cells, "cells")
+    if own is not None:
+        a.own, a.label_bytes = _ptr(own, "own"), _LABEL_BYTES[own.dtype]
+    else:
+        a.label_bytes = 1
+    if own_mask is not None:
+        a.own_mask = _ptr(_byte_mask(own_mask.reshape(1, -1), 1, S, "own_mask"), "own_mask")
+    for t, name in ((cells, "cells"), (own, "own"), (own_mask, "own_mask")):
+        if t is not None and t.device != votes.device:
+            raise RuntimeError(f"{name} is on {t.device}, votes on {votes.device}")
+    labels = torch.empty((X, Y, Z), dtype=torch.uint8, device=votes.device)
+    n_obs = torch.empty((X, Y, Z), dtype=torch.int16, device=votes.device)
+    a.labels, a.n_obs = labels.data_ptr(), n_obs.data_ptr()
+    a.X, a.Y, a.Z = X, Y, Z
+    a.gx, a.gy, a.gz = (int(g) for g in cells.shape)
+    a.min_obs = int(min_obs)
+    a.flags = (MAP_SAMPLE_EXCLUDE_SELF if exclude_self else 0) | (MAP_SAMPLE_KEEP_OWN if keep_own else 0)
+    for i, v in enumerate(Bq):
+        a.Bq[i] = v
+    for i, v in enumerate(dq):
+        a.dq[i] = v
+    _check(load().occd_map_sample(ctypes.byref(a), _stream()), "occd_map_sample")
+    return labels, n_obs
 
 
 def map_render(labels, cells, views, size, palette, target=None, background=None, alpha=256, bg_colour=(255, 255, 255),

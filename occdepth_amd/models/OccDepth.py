@@ -171,13 +171,17 @@ class OccDepth(_Base):
                                         decay=float(env("OCCDEPTH_FUSE_DECAY", "1.0")))
         # Sequence-level semantic map of the test / validation frames (semantic_map.py), OFF by default:
         # `enable_semantic_map()` -- or OCCDEPTH_MAP_DIR=<dir> OCCDEPTH_MAP_POSES=<.../dataset/sequences> (falls back to
-        # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] [OCCDEPTH_MAP_VIEWS=bev,oblique] in the environment of an unmodified scripts/eval.py.  Off: nothing is
+        # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] [OCCDEPTH_MAP_VIEWS=bev,oblique] [OCCDEPTH_MAP_FRAMES=1 [OCCDEPTH_MAP_FRAMES_SELF=0]
+        # [OCCDEPTH_MAP_SUBMISSION=<dir>]: the map read back into every frame] in the environment of an unmodified scripts/eval.py.  Off: nothing is
         # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
         self.semantic_map = None
         if env("OCCDEPTH_MAP_DIR", ""):
             self.enable_semantic_map(env("OCCDEPTH_MAP_DIR"), env("OCCDEPTH_MAP_POSES", "") or env("OCCDEPTH_FUSE_POSES", ""),
                                      min_obs=int(env("OCCDEPTH_MAP_MIN_OBS", "1")),
-                                     views=tuple(v for v in env("OCCDEPTH_MAP_VIEWS", "").split(",") if v))
+                                     views=tuple(v for v in env("OCCDEPTH_MAP_VIEWS", "").split(",") if v),
+                                     frames=env("OCCDEPTH_MAP_FRAMES", "0") == "1",
+                                     submission_dir=env("OCCDEPTH_MAP_SUBMISSION", "") or None,
+                                     exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0")
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -781,7 +785,8 @@ class OccDepth(_Base):
         metric.add_batch(torch.stack(labels), target)
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
-    def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=()):
+    def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
+                            exclude_self=False, max_frames=1024):
         """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
         ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
         prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
@@ -791,7 +796,18 @@ class OccDepth(_Base):
         block -- and the maps are released.  Votes commute, so frames may arrive in any order; a sequence must stay on one
         rank.  Memory: 163840 bytes per 16^3 brick and map at 20 classes.  views: any of "bev", "oblique" -- before the
         maps are released every sequence is also drawn (render.render_map on semantic_map.MapVolume(pred, gt, min_obs))
-        to <out_dir>/<step>_<sequence>_{pred,gt,err}_{view}.png; () draws nothing and imports nothing more."""
+        to <out_dir>/<step>_<sequence>_{pred,gt,err}_{view}.png; () draws nothing and imports nothing more.
+
+        frames (or a submission_dir, which switches it on): the map is also read back into every frame (K32,
+        SemanticMap.sample).  Every frame's prediction (uint8), target (uint8), the FOV mask it voted with, its pose,
+        sequence and frame id are kept on the GPU until the epoch ends -- three bytes per voxel, 6.3 MB per frame at
+        256 x 256 x 32, about 5 GB for the 815 validation frames of sequence 08; more than `max_frames` kept frames
+        raise instead of running the allocator dry.  Before the maps are released each kept frame is sampled from its
+        sequence's PREDICTION map (own = its prediction, own_mask = its mask, min_obs, keep_own; exclude_self takes the
+        frame's own vote out) and counted against its target into a third metric: `val_mapped/mIoU`, `val_mapped/IoU`
+        are logged and `test_epoch_end` prints a `test_mapped======` block.  With submission_dir the mapped labels are
+        written as <submission_dir>/sequences/<seq>/predictions/<frame>.label (output.write_kitti_submission_labels).
+        Off: nothing more is kept, imported or launched.  The effect on any score is not measured."""
         if self.dataset != "kitti":
             raise NotImplementedError("the semantic map reads SemanticKITTI poses and is wired for the SemanticKITTI geometry "
                                       "only; a %s model has no ego-motion to lay its frames out with" % self.dataset)
@@ -805,8 +821,12 @@ class OccDepth(_Base):
         views = tuple(str(v) for v in views)
         if any(v not in ("bev", "oblique") for v in views):
             raise ValueError("a map view is 'bev' or 'oblique' (views / OCCDEPTH_MAP_VIEWS), got %r" % (views,))
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1, got %r" % (max_frames,))
         self.semantic_map = {"out_dir": str(out_dir), "poses_root": str(poses_root), "min_obs": int(min_obs),
-                             "maps": {}, "poses": {}, "paths": [], "views": views}
+                             "maps": {}, "poses": {}, "paths": [], "views": views,
+                             "frames": bool(frames) or bool(submission_dir), "submission_dir": str(submission_dir) if submission_dir else None,
+                             "exclude_self": bool(exclude_self), "max_frames": int(max_frames), "kept": {}, "mapped_stats": {}}
         return self
 
     def _map_step(self, step_type, batch, ssc_pred, target):
@@ -830,6 +850,12 @@ class OccDepth(_Base):
             if frame not in poses:
                 raise KeyError("sequence %s has no pose for frame %d (%s)" % (seq, frame, os.path.join(st["poses_root"], seq, "poses.txt")))
             items.append((seq, poses[frame]))
+        if st.get("frames"):
+            kept = sum(len(v) for v in st["kept"].values())
+            if kept + B > st["max_frames"]:
+                raise RuntimeError("the map read-back would keep %d frames on the GPU, max_frames = %d (%.1f MB per frame: "
+                                   "prediction, target and mask); raise max_frames or evaluate fewer frames per epoch"
+                                   % (kept + B, st["max_frames"], 3e-6 * dims[0] * dims[1] * dims[2]))
         pred = hip.argmax_labels_u16(ssc_pred.float())                   # (B, X, Y, Z) uint16 bits, the unfused logits
         gt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
         for i, (seq, pose) in enumerate(items):
@@ -840,6 +866,10 @@ class OccDepth(_Base):
             mask = None if fov is None else fov[i]
             pair[0].integrate(pred[i], pose, mask=mask)
             pair[1].integrate(gt[i].reshape(dims), pose, mask=mask)
+            if st.get("frames"):
+                st["kept"].setdefault((step_type, seq), []).append(      # copies: the batch's tensors are not held on to
+                    (pred[i].to(torch.uint8), gt[i].reshape(dims).clone(), None if mask is None else mask != 0, pose,
+                     str(batch["frame_id"][i])))
 
     def _map_epoch_end(self, step_type):
         """Write and score the maps of `step_type`, release them; -> the statistics over its sequences, or None."""
@@ -852,8 +882,16 @@ class OccDepth(_Base):
         os.makedirs(st["out_dir"], exist_ok=True)
         metric = SSCMetrics(self.n_classes)
         colours = render.palette("kitti" if self.n_classes == 20 else int(self.n_classes))
+        mapped = SSCMetrics(self.n_classes) if st.get("frames") else None
         for key in mine:
             pair = st["maps"].pop(key)
+            for own, gt, own_mask, pose, frame_id in (st["kept"].pop(key, ()) if mapped is not None else ()):
+                labels, _ = pair[0].sample(pose, own=own, own_mask=own_mask, min_obs=st["min_obs"],
+                                           exclude_self=st["exclude_self"], keep_own=True)
+                mapped.add_batch(labels[None], gt[None])
+                if st["submission_dir"]:
+                    from .. import output
+                    st["paths"].append(output.write_kitti_submission_labels(labels, key[1], frame_id, st["submission_dir"]))
             for m, name in zip(pair, ("pred", "gt")):
                 coords, labels, n_obs = m.extract(min_obs=st["min_obs"])
                 path = os.path.join(st["out_dir"], "%s_%s_%s.ply" % (step_type, key[1], name))
@@ -865,6 +903,8 @@ class OccDepth(_Base):
                 st["paths"] += render.write_map_pictures(volume, prefix, st["views"], palette=colours)
             for m in pair:
                 m.release()
+        if mapped is not None:
+            st["mapped_stats"][step_type] = self._epoch_stats(mapped)
         return self._epoch_stats(metric)
 
     def _kitti_origin(self, batch=None):
@@ -1532,6 +1572,10 @@ class OccDepth(_Base):
             if stats is not None:
                 self.log("val_map/mIoU", stats["iou_ssc_mean"], sync_dist=True)
                 self.log("val_map/IoU", stats["iou"], sync_dist=True)
+            stats = self.semantic_map.get("mapped_stats", {}).pop("val", None)
+            if stats is not None:
+                self.log("val_mapped/mIoU", stats["iou_ssc_mean"], sync_dist=True)
+                self.log("val_mapped/IoU", stats["iou"], sync_dist=True)
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -1554,13 +1598,14 @@ class OccDepth(_Base):
         self._print_region_report("test")
         if getattr(self, "semantic_map", None) is not None:
             stats = self._map_epoch_end("test")
-            if stats is not None:
-                print("test_map======")
-                print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(
-                    stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
-                print("class IoU: {}, ".format(classes))
-                print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
-                print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+            for prefix, stats in (("test_map", stats), ("test_mapped", self.semantic_map.get("mapped_stats", {}).pop("test", None))):
+                if stats is not None:
+                    print("{}======".format(prefix))
+                    print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(
+                        stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
+                    print("class IoU: {}, ".format(classes))
+                    print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
+                    print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

@@ -72,6 +72,21 @@ def write_outputs(ssc_logit, batch, root, dataset):
     return paths
 
 
+def write_kitti_submission_labels(labels, sequence, frame_id, root):
+    """One frame of TRAINING-class labels ((X, Y, Z) tensor or array, values 0..19; anything else, 255 included, is
+    written as 0 = unlabeled) in the submission layout of write_kitti_submission:
+    <root>/sequences/<sequence>/predictions/<frame_id>.label, uint16 dataset ids in (X, Y, Z) order.  -> the path."""
+    lut = np.zeros(1 << 16, dtype=np.uint16)
+    lut[:len(KITTI_LEARNING_MAP_INV)] = KITTI_LEARNING_MAP_INV
+    lab = _np(labels)
+    lab = lab.view(np.uint16) if lab.dtype == np.int16 else lab.astype(np.uint16)
+    d = os.path.join(root, "sequences", str(sequence), "predictions")
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, str(frame_id) + ".label")
+    lut[lab.reshape(-1)].tofile(path)
+    return path
+
+
 def write_kitti_submission(ssc_logit, batch, root):
     """generate_kitti_submission.py's inner loop: <root>/sequences/<seq>/predictions/<frame>.label, uint16 labels in
     the dataset's own ids, flattened in (X, Y, Z) order."""

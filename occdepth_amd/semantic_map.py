@@ -8,6 +8,7 @@ frame vote in one launch, hip.map_brick_labels / hip.map_extract decide).
     coords, labels, n_obs = m.extract(min_obs=2)
     write_ply("08.ply", coords, labels, n_obs, 0.2, render.palette("kitti"))
     map_confusion(pred_map, gt_map, SSCMetrics(20))                  # map mIoU where both maps were observed
+    labels, n_obs = m.sample(poses[frame], own=labels, own_mask=fov_mask_1, keep_own=True)   # the map read back into a frame (K32)
 
 The world lattice has the frame grid's voxel size; voxels live in 16^3 bricks of 16-bit vote counters, one row of `pitch`
 = n_classes rounded up to 4 counters per voxel (8192 * pitch bytes per brick: 163840 at 20 classes).  The host side is
@@ -58,10 +59,9 @@ def brick_coefficients(pose, keys, vox_origin, voxel_size):
     return np.rint(R.T * scale).astype(np.int32), np.rint(c * scale).astype(np.int32)
 
 
-def frame_bricks(pose, vox_origin, voxel_size, dims):
-    """The keys (n, 3) int64, ascending, of every brick that can hold a voxel of the frame: the brick range of the
-    grid's eight corners in world voxels, less the bricks whose bounding sphere (radius 8 sqrt 3, plus a voxel of margin)
-    misses the grid box, less those whose extent along a grid axis misses it.  Over-selects; never drops a voting brick."""
+def frame_brick_box(pose, vox_origin, voxel_size, dims):
+    """-> (lo, hi), int64 (3,): the inclusive brick-key box of the frame's candidate bricks, the brick range of the
+    grid's eight corners in world voxels, one voxel wider on every side."""
     R, t = _pose(pose)
     v = float(voxel_size)
     dims = np.asarray(dims, dtype=np.float64).reshape(3)
@@ -70,6 +70,16 @@ def frame_bricks(pose, vox_origin, voxel_size, dims):
     world = ((corners * v + org) @ R.T + t) / v
     lo = np.floor((np.floor(world.min(0)) - 1.0) / BRICK).astype(np.int64)
     hi = np.floor((np.floor(world.max(0)) + 1.0) / BRICK).astype(np.int64)
+    return lo, hi
+
+
+def frame_bricks(pose, vox_origin, voxel_size, dims):
+    """The keys (n, 3) int64, ascending, of every brick that can hold a voxel of the frame: the brick range of the
+    grid's eight corners in world voxels, less the bricks whose bounding sphere (radius 8 sqrt 3, plus a voxel of margin)
+    misses the grid box, less those whose extent along a grid axis misses it.  Over-selects; never drops a voting brick."""
+    R, t = _pose(pose)
+    dims = np.asarray(dims, dtype=np.float64).reshape(3)
+    lo, hi = frame_brick_box(pose, vox_origin, voxel_size, dims)
     k0, k1, k2 = np.meshgrid(*(np.arange(lo[a], hi[a] + 1) for a in range(3)), indexing="ij")
     keys = np.stack([k0, k1, k2], -1).reshape(-1, 3)                      # ascending (k0, k1, k2)
     centre = _brick_offsets(pose, keys, vox_origin, voxel_size) + 7.5 * R.T.sum(1)
@@ -79,6 +89,25 @@ def frame_bricks(pose, vox_origin, voxel_size, dims):
     # fixed point's 3.5e-4 voxel with room to spare, and keeps a brick that merely touches the grid from the outside out
     reach = 7.5 * np.abs(R.T).sum(1) + _AXIS_MARGIN
     return keys[sphere & (gap <= reach).all(1)]
+
+
+def sample_coefficients(pose, vox_origin, voxel_size, key_min, dims=None):
+    """-> Bq (3, 3) int32 = rint(R 2^16) and dq (3,) int32 = rint(d 2^16), d = R (1/2 + o / v) + t / v - 16 key_min: the
+    frame voxel (x, y, z) falls into the world voxel 16 key_min + ((Bq (x, y, z) + dq) >> 16) (occd_map_sample, K32).
+    |d| >= 2^14 is refused, and with `dims` a grid of X + Y + Z >= 2^14: the fixed point stays inside int32."""
+    R, t = _pose(pose)
+    v = float(voxel_size)
+    org = np.asarray(vox_origin, dtype=np.float64).reshape(3)
+    W0 = BRICK * np.asarray(key_min, dtype=np.float64).reshape(3)
+    if dims is not None and not sum(int(d) for d in dims) < int(C_LIMIT):
+        raise ValueError("a frame of X + Y + Z = %d voxels: the fixed-point transform takes less than 2^14 = %d"
+                         % (sum(int(d) for d in dims), int(C_LIMIT)))
+    d = R @ (0.5 + org / v) + t / v - W0
+    if not np.abs(d).max() < C_LIMIT:
+        raise ValueError("the frame's grid origin lies %.0f voxels from its window's: the fixed-point transform takes less "
+                         "than 2^14 = %d" % (np.abs(d).max(), int(C_LIMIT)))
+    scale = float(1 << FRAC)
+    return np.rint(R * scale).astype(np.int32), np.rint(d * scale).astype(np.int32)
 
 
 def pack_keys(keys):
@@ -233,6 +262,77 @@ class SemanticMap:
         hip.map_integrate(self.pool(), dev_table, labels.contiguous(), self.dims, self.n_classes, mask=mask,
                           table_host=host_table)
         return self
+
+    # ------------------------------------------------------------------------------------------------ read-back
+    def frame_cells(self, pose, device):
+        """The window of one frame for sample() -> (cells, table, key_min): the inclusive brick-key box of the frame's
+        candidates (frame_brick_box; every brick of the box, not only those frame_bricks keeps), table (n, 16) int32 in
+        integrate's layout -- slot | key | Aq | cq -- for the n bricks of the box that the map holds (none is admitted,
+        the pool never grows), and cells (gx, gy, gz) int32, the table row of the brick at each cell or -1.  Both are
+        numpy arrays; `device` is where they will go (kept for symmetry with frame_table)."""
+        lo, hi = frame_brick_box(pose, self.vox_origin, self.voxel_size, self.dims)
+        grid = tuple(int(g) for g in hi - lo + 1)
+        k0, k1, k2 = np.meshgrid(*(np.arange(lo[a], hi[a] + 1) for a in range(3)), indexing="ij")
+        keys = np.stack([k0, k1, k2], -1).reshape(-1, 3)
+        slots = self.slots(keys, create=False)
+        have = slots >= 0
+        keys = keys[have]
+        Aq, cq = brick_coefficients(pose, keys, self.vox_origin, self.voxel_size)
+        table = np.empty((len(keys), 16), dtype=np.int32)
+        table[:, 0] = slots[have]
+        table[:, 1:4] = keys
+        table[:, 4:13] = Aq.reshape(9)
+        table[:, 13:16] = cq
+        cells = np.full(grid, -1, dtype=np.int32)
+        at = keys - lo
+        cells[at[:, 0], at[:, 1], at[:, 2]] = np.arange(len(keys), dtype=np.int32)
+        return cells, table, lo
+
+    def sample(self, pose, own=None, own_mask=None, min_obs=1, exclude_self=False, keep_own=False):
+        """What the whole map says about the voxels of the frame at `pose` (K32, one launch) -> labels (X, Y, Z) uint8,
+        n_obs (X, Y, Z) int16 holding uint16 bits (the votes at the world voxel the frame voxel's centre falls into,
+        saturated at 65535).  labels = the arg-max of those votes (the lowest class on a tie) where n_obs >= max(min_obs,
+        1); elsewhere `own` (the frame's own labels, (X, Y, Z) uint8 / int16 on the map's device; >= 255 -> 255) when
+        given, else 255.  exclude_self takes the frame's own vote out first: `own` and `own_mask` must be what it was
+        integrated with (a counter saturated at 65535 is not retracted).  keep_own: a tie that own's class is part of
+        goes to own.  An empty map, or a frame that meets none of its bricks, gives the fallback volume and zeros
+        without a launch."""
+        if int(min_obs) < 0:
+            raise ValueError("min_obs must be >= 0, got %r" % (min_obs,))
+        if own is None and (exclude_self or keep_own):
+            raise ValueError("exclude_self and keep_own need the frame's own labels (own)")
+        if not sum(self.dims) < int(C_LIMIT):
+            raise ValueError("a frame of X + Y + Z = %d voxels: the fixed-point transform takes less than 2^14" % sum(self.dims))
+        dev = self.votes.device if self.votes is not None else (own.device if own is not None else torch.device("cpu"))
+        S = self.dims[0] * self.dims[1] * self.dims[2]
+        if own is not None:
+            if tuple(own.shape) != self.dims:
+                raise ValueError("sample takes own (X, Y, Z) = %r labels, got %r" % (self.dims, tuple(own.shape)))
+            if own.device != dev:
+                raise ValueError("own is on %s, the map on %s" % (own.device, dev))
+        if own_mask is not None:
+            own_mask = torch.as_tensor(own_mask)
+            if own_mask.numel() != S:
+                raise ValueError("own_mask must hold X Y Z = %d entries, got %r" % (S, tuple(own_mask.shape)))
+            own_mask = own_mask.to(dev)
+            if own_mask.dtype not in (torch.bool, torch.uint8):
+                own_mask = own_mask != 0
+        table = None
+        if self.votes is not None and self.directory:
+            cells, table, key_min = self.frame_cells(pose, dev)
+        if table is None or not len(table):
+            if own is None:
+                labels = torch.full(self.dims, 255, dtype=torch.uint8, device=dev)
+            else:
+                wide = own.to(torch.int32) & 0xFFFF
+                labels = torch.where(wide < 255, wide, torch.full_like(wide, 255)).to(torch.uint8)
+            return labels, torch.zeros(self.dims, dtype=torch.int16, device=dev)
+        Bq, dq = sample_coefficients(pose, self.vox_origin, self.voxel_size, key_min, self.dims)
+        dev_table, host_table = self.upload(table, dev)
+        dev_cells, _ = self.upload(cells, dev)
+        return hip.map_sample(self.pool(), dev_table, dev_cells, None if own is None else own.contiguous(), self.dims,
+                              self.n_classes, Bq, dq, cells.shape, own_mask=own_mask, min_obs=int(min_obs),
+                              exclude_self=bool(exclude_self), keep_own=bool(keep_own), table_host=host_table)
 
     # ------------------------------------------------------------------------------------------------ extraction
     def brick_keys(self):

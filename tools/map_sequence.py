@@ -3,6 +3,7 @@ as a point PLY, and score a prediction map against a ground-truth map.
 
     python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
         --out maps/08 [--min-obs 2] [--fov] [--every 5] [--views bev oblique] [--png-side 2048] [--camera-every 50 --t-max 80]
+        [--frames-out DIR [--exclude-self] [--keep-own]]
 
 --pred / --gt name a directory; what it holds decides how it is read:
     <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
@@ -14,6 +15,11 @@ as a point PLY, and score a prediction map against a ground-truth map.
 sources, prints the map's Precision / Recall / IoU / mIoU over the voxels both maps observed.  --views also draws the maps
 (render.render_map, the bricks ray-cast on the GPU) to <out>_{pred,gt,err}_{view}.png; --camera-every N draws them through
 the left colour camera (P2 and Tr of calib.txt) of every N-th posed frame to <out>_{pred,gt,err}_camera_<frame>.png.
+--frames-out DIR reads the finished prediction map back into every --pred frame (SemanticMap.sample, K32: own = the
+frame's labels, inside its mask with --fov; --exclude-self takes the frame's own vote out, --keep-own lets a tie go to the
+frame's label) and writes DIR/sequences/<sequence>/predictions/<frame>.label, submission files (<sequence> is the name of
+the --poses directory).  When --gt holds per-frame targets it also prints a `frames======` block (the frames' own labels
+against their targets) and a `mapped======` block (the sampled labels against the same targets).
 """
 import argparse
 import glob
@@ -87,6 +93,45 @@ def build_map(src, role, poses, args, device):
     return m
 
 
+def _print_block(name, stats, classes):
+    print("%s======" % name)
+    print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
+    print(" ".join(["{:.4f}, "] * classes).format(*(stats["iou_ssc"] * 100).tolist()))
+    print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+
+
+def sample_frames(pred_map, poses, args, device):
+    """--frames-out: every --pred frame sampled back from the finished prediction map and written as a submission file;
+    with per-frame targets in --gt also scored -> (paths, {"frames": stats, "mapped": stats} or None)."""
+    from occdepth_amd.loss.sscMetrics import SSCMetrics
+    dims = tuple(args.dims)
+    kind, frames = list_frames(args.pred)
+    lut = submission_inverse_lut() if kind == "label" else None
+    gt_kind, gt_frames = list_frames(args.gt) if args.gt else (None, {})
+    gt_lut = submission_inverse_lut() if gt_kind == "label" else None
+    metrics = {"frames": SSCMetrics(args.classes), "mapped": SSCMetrics(args.classes)} if gt_frames else None
+    sequence = os.path.basename(os.path.normpath(args.poses))
+    paths, scored = [], 0
+    for frame in sorted(frames)[::args.every]:
+        own, mask = read_frame(kind, frames[frame], "pred", dims, device, args.fov, lut)
+        mapped, _ = pred_map.sample(poses[frame], own=own, own_mask=mask, min_obs=args.min_obs,
+                                    exclude_self=args.exclude_self, keep_own=args.keep_own)
+        paths.append(output.write_kitti_submission_labels(mapped, sequence, "%06d" % frame, args.frames_out))
+        if frame in gt_frames:
+            target, _ = read_frame(gt_kind, gt_frames[frame], "gt", dims, device, False, gt_lut)
+            for name, labels in (("frames", own), ("mapped", mapped)):          # a voxel without a label or a target is not counted
+                void = (labels >= args.classes) | (target >= args.classes)
+                metrics[name].add_batch(labels[None], torch.where(void, torch.full_like(target, 255), target)[None])
+            scored += 1
+    print("%d frames sampled from the prediction map -> %s" % (len(paths), os.path.join(args.frames_out, "sequences", sequence, "predictions")))
+    if not scored:
+        return paths, None
+    stats = {name: m.get_stats() for name, m in metrics.items()}
+    for name in ("frames", "mapped"):
+        _print_block(name, stats[name], args.classes)
+    return paths, stats
+
+
 def read_camera(seq_dir):
     """calib.txt -> (cam_k (3, 3), sensor -> left colour camera (4, 4)), float64: cam_k = P2[:, :3] and the extrinsic is
     Tr shifted by K^-1 P2[:, 3] (P2 projects from the rectified camera 0 frame, which Tr maps the sensor into)."""
@@ -158,6 +203,10 @@ def run(args, device=None):
         print("Precision={:.4f}, Recall={:.4f}, IoU={:.4f}".format(stats["precision"] * 100, stats["recall"] * 100, stats["iou"] * 100))
         print(" ".join(["{:.4f}, "] * args.classes).format(*(stats["iou_ssc"] * 100).tolist()))
         print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+    if args.frames_out:
+        if "pred" not in maps:
+            raise SystemExit("--frames-out samples the prediction map: give --pred")
+        sample_frames(maps["pred"], poses, args, device)
     return maps, stats
 
 
@@ -182,6 +231,10 @@ def parser():
                     help="draw the map through the left colour camera (P2, Tr of calib.txt) of every n-th posed frame")
     ap.add_argument("--camera-size", type=int, nargs=2, default=(370, 1220), help="H W of the camera pictures")
     ap.add_argument("--t-max", type=float, default=80.0, help="camera pictures: voxels deeper than this (m) are not drawn")
+    ap.add_argument("--frames-out", default=None,
+                    help="read the prediction map back into every --pred frame: DIR/sequences/<seq>/predictions/<frame>.label")
+    ap.add_argument("--exclude-self", action="store_true", help="--frames-out: take the frame's own vote out of the map first")
+    ap.add_argument("--keep-own", action="store_true", help="--frames-out: a tie that the frame's own label is part of goes to it")
     return ap
 
 

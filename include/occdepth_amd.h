@@ -81,7 +81,8 @@ extern "C" {
  *     occd_map_render (K31, the sparse two-level ray cast over the map's bricks, csrc/map_render.hip): one new struct and
  *     one new function only; likewise OCCD_MAP_SAMPLE_EXCLUDE_SELF, OCCD_MAP_SAMPLE_KEEP_OWN, OccdMapSampleArgs and
  *     occd_map_sample (K32, the map read back into a frame's voxels, csrc/semantic_map.hip): one new struct and one new
- *     function only */
+ *     function only; likewise OccdMapMergeArgs and occd_map_merge (K33, the counter-wise saturating sum of two sets of
+ *     bricks, csrc/semantic_map.hip): one new struct and one new function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1448,6 +1449,35 @@ typedef struct OccdMapSampleArgs {
     int32_t Bq[9], dq[3];          /* row-major rint(R 2^16), rint(d 2^16)                                           */
 } OccdMapSampleArgs;
 int occd_map_sample(const OccdMapSampleArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K33: the sum of two sets of bricks (occd_map_merge, csrc/semantic_map.hip).  Additive (OCCD_ABI_VERSION note).  Votes
+ * are counters and commute: the map of a set of frames is the counter-wise saturating sum of the maps of any partition
+ * of the set, and min(a + b + c, 65535) on non-negative counters depends on neither order nor grouping.
+ *
+ * `votes` is the destination pool of `capacity` bricks, `src` holds `src_capacity` bricks in the same layout (4096 rows
+ * of `pitch` counters each: another map's pool, or a staging buffer of received rows); both 16-byte aligned, so every
+ * brick and every 16-byte piece of one (512 * pitch per brick) is.  Row r of `table` is 2 int32: destination slot |
+ * source row.  For every table row and every counter c of the brick, the padding counters included:
+ *   votes[slot][c] = min(votes[slot][c] + src[row][c], 65535)
+ * A table row whose slot is outside [0, capacity) or whose source row is outside [0, src_capacity) is skipped.  The
+ * slots of one launch must be distinct, and `src` must not overlap the destination bricks (one owner per counter: no
+ * atomics, the bytes written do not depend on the schedule).  One launch of n x split workgroups: a brick is cut into
+ * `split` equal runs of pieces (1, 2, 4 or 8; 0 = the library's choice).  `table_host`, when not NULL, is the same
+ * table in host memory: a row of it that the kernel would skip is refused instead.
+ * n == 0 returns OCCD_OK without a launch.  OCCD_EINVAL before any launch: a NULL argument or NULL votes / src / table,
+ * n < 0, capacity or src_capacity <= 0, pitch outside 4..32 or pitch % 4 != 0, votes or src not 16-byte aligned, a split
+ * other than 0, 1, 2, 4, 8, such a row in table_host.
+ * ------------------------------------------------------------------------ */
+typedef struct OccdMapMergeArgs {
+    uint16_t* votes;               /* (capacity, 4096, pitch) destination counters                                   */
+    const uint16_t* src;           /* (src_capacity, 4096, pitch) source counters, read only                         */
+    const int32_t* table;          /* (n, 2) device: destination slot | source row                                   */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    int32_t n, capacity, src_capacity;
+    int32_t pitch, split;
+} OccdMapMergeArgs;
+int occd_map_merge(const OccdMapMergeArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * K31: render the sequence map (csrc/map_render.hip).  Additive (OCCD_ABI_VERSION note).  One ray per pixel through the

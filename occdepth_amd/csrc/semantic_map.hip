@@ -1,5 +1,6 @@
 // K30: the sequence-level semantic map (occd_map_integrate, occd_map_brick_labels, occd_map_count, occd_map_extract), and
-// K32: the map read back into a frame's voxels (occd_map_sample).
+// K32: the map read back into a frame's voxels (occd_map_sample), and
+// K33: the counter-wise saturating sum of two sets of bricks (occd_map_merge).
 // Contract: include/occdepth_amd.h.
 //
 // The map is a pool of 16^3 bricks of unsigned 16-bit vote counters, one row of `pitch` counters per voxel, row
@@ -218,6 +219,53 @@ __global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampl
     a.n_obs[n] = (uint16_t)(nobs < 0xffffu ? nobs : 0xffffu);
 }
 
+// K33: dst = min(dst + src, 65535) over the bricks a table pairs up.  A brick is 512 * pitch 16-byte pieces and nothing
+// in it depends on anything but the same piece of the other operand, so this is a stream: a workgroup takes a 1 / split
+// part of one table row (blockIdx.x = row, blockIdx.y = part; whole multiples of 256 pieces), a thread takes pieces
+// 256 apart (a wave reads 1 KiB contiguous per load), issues the 2 * kMergeUnroll 16-byte loads of a round before the
+// first add, and adds two counters per 32-bit lane with the packed clamped add.  Every counter has one owner.
+constexpr int kMergeUnroll = 4;
+constexpr int kMergeSplit = 8;                          // parts per brick when the caller does not ask, for a launch of fewer
+constexpr int kMergeWhole = 1024;                       // bricks than this; whole bricks from there on (measured: DESIGN.md K33)
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t add_sat_u16x2(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
+__global__ void __launch_bounds__(kThreads) map_merge_kernel(const OccdMapMergeArgs a, const int pieces) {
+    const int32_t* row = a.table + (size_t)blockIdx.x * 2;
+    const int32_t slot = row[0], from = row[1];
+    if (slot < 0 || slot >= a.capacity || from < 0 || from >= a.src_capacity) return;      // the whole workgroup
+    const size_t brick = (size_t)kBrickVox / 8 * (size_t)a.pitch;                          // 16-byte pieces per brick
+    const size_t part = (size_t)blockIdx.y * (size_t)pieces + threadIdx.x;
+    u32x4* dst = reinterpret_cast<u32x4*>(a.votes) + (size_t)slot * brick + part;
+    const u32x4* src = reinterpret_cast<const u32x4*>(a.src) + (size_t)from * brick + part;
+    for (int base = 0; base < pieces; base += kMergeUnroll * kThreads) {
+        u32x4 d[kMergeUnroll], s[kMergeUnroll];
+#pragma unroll
+        for (int u = 0; u < kMergeUnroll; ++u) {
+            const int p = base + u * kThreads;          // pieces is a multiple of 256: p < pieces holds for a whole workgroup
+            if (p < pieces) {
+                d[u] = dst[p];
+                s[u] = __builtin_nontemporal_load(src + p);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kMergeUnroll; ++u) {
+            const int p = base + u * kThreads;
+            if (p < pieces) {
+                u32x4 r;
+                r.x = add_sat_u16x2(d[u].x, s[u].x);
+                r.y = add_sat_u16x2(d[u].y, s[u].y);
+                r.z = add_sat_u16x2(d[u].z, s[u].z);
+                r.w = add_sat_u16x2(d[u].w, s[u].w);
+                dst[p] = r;
+            }
+        }
+    }
+}
+
 bool pool_ok(const void* votes, const int32_t* table, int32_t n_bricks, int32_t capacity, int32_t C, int32_t pitch) {
     if (!votes || !table || n_bricks <= 0 || capacity <= 0 || C < 1 || C > 32) return false;
     return pitch >= C && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(votes) & 7) == 0;
@@ -291,5 +339,24 @@ extern "C" int occd_map_sample(const OccdMapSampleArgs* a, void* stream) {
     const dim3 grid((unsigned)(((int64_t)a->X * a->Y * a->Z + kThreads - 1) / kThreads));
     if (a->label_bytes == 1) hipLaunchKernelGGL(map_sample_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(map_sample_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    return occd::check_launch();
+}
+
+extern "C" int occd_map_merge(const OccdMapMergeArgs* a, void* stream) {
+    if (!a || !a->votes || !a->src || !a->table || a->n < 0 || a->capacity <= 0 || a->src_capacity <= 0) return OCCD_EINVAL;
+    if (a->pitch < 4 || a->pitch > 32 || (a->pitch & 3) != 0) return OCCD_EINVAL;
+    if (((reinterpret_cast<uintptr_t>(a->votes) | reinterpret_cast<uintptr_t>(a->src)) & 15) != 0) return OCCD_EINVAL;
+    const int split = a->split != 0 ? a->split : (a->n < kMergeWhole ? kMergeSplit : 1);
+    if (split != 1 && split != 2 && split != 4 && split != 8) return OCCD_EINVAL;
+    if (a->table_host) {
+        for (int32_t r = 0; r < a->n; ++r) {
+            const int32_t slot = a->table_host[(size_t)r * 2], from = a->table_host[(size_t)r * 2 + 1];
+            if (slot < 0 || slot >= a->capacity || from < 0 || from >= a->src_capacity) return OCCD_EINVAL;
+        }
+    }
+    if (a->n == 0) return OCCD_OK;
+    occd::ProfScope prof("map_merge", (hipStream_t)stream, 0.0, 3.0 * pool_bytes(a->n, a->pitch));
+    const int pieces = kBrickVox / 8 * a->pitch / split;            // 512 * pitch / split: a multiple of 256 for every pitch
+    hipLaunchKernelGGL(map_merge_kernel, dim3((unsigned)a->n, (unsigned)split), dim3(kThreads), 0, (hipStream_t)stream, *a, pieces);
     return occd::check_launch();
 }

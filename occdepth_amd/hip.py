@@ -61,6 +61,7 @@ MapRenderArgs = abi.STRUCTS["OccdMapRenderArgs"]
 MapSampleArgs = abi.STRUCTS["OccdMapSampleArgs"]
 MAP_SAMPLE_EXCLUDE_SELF = abi.CONSTANTS["OCCD_MAP_SAMPLE_EXCLUDE_SELF"]
 MAP_SAMPLE_KEEP_OWN = abi.CONSTANTS["OCCD_MAP_SAMPLE_KEEP_OWN"]
+MapMergeArgs = abi.STRUCTS["OccdMapMergeArgs"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2339,6 +2340,36 @@ def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask
         a.dq[i] = v
     _check(load().occd_map_sample(ctypes.byref(a), _stream()), "occd_map_sample")
     return labels, n_obs
+
+
+def map_merge(votes, src, table, table_host=None, split=0):
+    """occd_map_merge (K33), one launch: votes[slot] = min(votes[slot] + src[row], 65535), counter by counter, for every
+    (slot, row) of the (n, 2) int32 `table`.  votes: the int16 (capacity, 4096, pitch) pool, updated in place; src: int16
+    (rows, 4096, pitch) in the same layout on the same device (another map's pool or a buffer of received rows; it must
+    not overlap the destination bricks).  split: workgroups per brick, 0 = the library's choice.  n == 0 launches
+    nothing.  The contract is in include/occdepth_amd.h."""
+    for t, name in ((votes, "votes"), (src, "src")):
+        if t.dtype != torch.int16 or t.dim() != 3 or t.shape[1] != _MAP_BRICK_VOX:
+            raise RuntimeError("%s must be int16 (bricks, %d, pitch), got %s %s" % (name, _MAP_BRICK_VOX, tuple(t.shape), t.dtype))
+    if src.shape[2] != votes.shape[2] or src.device != votes.device:
+        raise RuntimeError("src has pitch %d on %s, votes pitch %d on %s" % (src.shape[2], src.device, votes.shape[2], votes.device))
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 2 or table.device != votes.device:
+        raise RuntimeError("table must be int32 (n, 2) on %s, got %s %s on %s"
+                           % (votes.device, tuple(table.shape), table.dtype, table.device))
+    a = MapMergeArgs()
+    a.votes, a.src = _ptr(votes, "votes"), _ptr(src, "src")
+    if table_host is not None:
+        if table_host.is_cuda or table_host.dtype != torch.int32 or table_host.shape != table.shape or \
+                not table_host.is_contiguous():
+            raise RuntimeError("table_host must be the table's contiguous int32 copy in host memory")
+        a.table_host = table_host.data_ptr()
+    a.n, a.capacity, a.src_capacity = int(table.shape[0]), int(votes.shape[0]), int(src.shape[0])
+    a.pitch, a.split = int(votes.shape[2]), int(split)
+    if a.n == 0:
+        return votes
+    a.table = _ptr(table, "table")
+    _check(load().occd_map_merge(ctypes.byref(a), _stream()), "occd_map_merge")
+    return votes
 
 
 def map_render(labels, cells, views, size, palette, target=None, background=None, alpha=256, bg_colour=(255, 255, 255),

@@ -172,7 +172,7 @@ class OccDepth(_Base):
         # Sequence-level semantic map of the test / validation frames (semantic_map.py), OFF by default:
         # `enable_semantic_map()` -- or OCCDEPTH_MAP_DIR=<dir> OCCDEPTH_MAP_POSES=<.../dataset/sequences> (falls back to
         # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] [OCCDEPTH_MAP_VIEWS=bev,oblique] [OCCDEPTH_MAP_FRAMES=1 [OCCDEPTH_MAP_FRAMES_SELF=0]
-        # [OCCDEPTH_MAP_SUBMISSION=<dir>]: the map read back into every frame] in the environment of an unmodified scripts/eval.py.  Off: nothing is
+        # [OCCDEPTH_MAP_SUBMISSION=<dir>]: the map read back into every frame] [OCCDEPTH_MAP_GATHER=0] [OCCDEPTH_MAP_SAVE=1] in the environment of an unmodified scripts/eval.py.  Off: nothing is
         # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
         self.semantic_map = None
         if env("OCCDEPTH_MAP_DIR", ""):
@@ -181,7 +181,8 @@ class OccDepth(_Base):
                                      views=tuple(v for v in env("OCCDEPTH_MAP_VIEWS", "").split(",") if v),
                                      frames=env("OCCDEPTH_MAP_FRAMES", "0") == "1",
                                      submission_dir=env("OCCDEPTH_MAP_SUBMISSION", "") or None,
-                                     exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0")
+                                     exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0",
+                                     gather=env("OCCDEPTH_MAP_GATHER", "1") != "0", save_maps=env("OCCDEPTH_MAP_SAVE", "0") == "1")
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -786,15 +787,27 @@ class OccDepth(_Base):
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
     def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
-                            exclude_self=False, max_frames=1024):
+                            exclude_self=False, max_frames=1024, gather=True, save_maps=False):
         """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
         ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
         prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
         batch has one.  At the end of the epoch every sequence's maps are written to <out_dir>/<step>_<sequence>_pred.ply
         and _gt.ply (voxels with at least `min_obs` votes), the prediction maps are scored against the ground-truth maps
         where both were observed -- `val_map/mIoU`, `val_map/IoU` are logged, `test_epoch_end` prints a `test_map======`
-        block -- and the maps are released.  Votes commute, so frames may arrive in any order; a sequence must stay on one
-        rank.  Memory: 163840 bytes per 16^3 brick and map at 20 classes.  views: any of "bev", "oblique" -- before the
+        block -- and the maps are released.  Votes commute, so frames may arrive in any order and on any rank: with gather
+        (the default; OCCDEPTH_MAP_GATHER=0 or gather=False turns it off) and a torch.distributed process group of more
+        than one rank, the epoch end first sums every sequence's maps over the ranks (semantic_map.merge_over_ranks, K33:
+        the ranks agree on the (step, sequence) keys, a rank without a frame of a sequence brings an empty pair, the
+        prediction map and then the ground-truth map of every key in sorted order), so every rank holds the map of all
+        frames.  Then PLYs, PNGs and .occmap files are written by rank 0 alone; `val_map/*` is computed on every rank
+        from the identical maps and never summed over ranks, not even with metrics_allreduce; `val_mapped/*` counts each
+        rank's own kept frames against the merged prediction map and follows the ordinary metric's metrics_allreduce
+        rule; every rank writes the submission files of the frames it kept (their names differ by frame).  A frame that
+        voted on more than one rank (DistributedSampler pads by repeating frames) votes twice, as the ordinary metric
+        counts it twice: one warning gives their number.  With one rank, or gather off, every rank does what a single
+        process does.  save_maps (OCCDEPTH_MAP_SAVE=1): before the maps are released their vote counters are kept as
+        <out_dir>/<step>_<sequence>_{pred,gt}.occmap (SemanticMap.save; SemanticMap.load and merge resume from them).
+        Memory: 163840 bytes per 16^3 brick and map at 20 classes.  views: any of "bev", "oblique" -- before the
         maps are released every sequence is also drawn (render.render_map on semantic_map.MapVolume(pred, gt, min_obs))
         to <out_dir>/<step>_<sequence>_{pred,gt,err}_{view}.png; () draws nothing and imports nothing more.
 
@@ -826,7 +839,8 @@ class OccDepth(_Base):
         self.semantic_map = {"out_dir": str(out_dir), "poses_root": str(poses_root), "min_obs": int(min_obs),
                              "maps": {}, "poses": {}, "paths": [], "views": views,
                              "frames": bool(frames) or bool(submission_dir), "submission_dir": str(submission_dir) if submission_dir else None,
-                             "exclude_self": bool(exclude_self), "max_frames": int(max_frames), "kept": {}, "mapped_stats": {}}
+                             "exclude_self": bool(exclude_self), "max_frames": int(max_frames), "kept": {}, "mapped_stats": {},
+                             "gather": bool(gather), "save_maps": bool(save_maps), "seen": {}}
         return self
 
     def _map_step(self, step_type, batch, ssc_pred, target):
@@ -866,6 +880,7 @@ class OccDepth(_Base):
             mask = None if fov is None else fov[i]
             pair[0].integrate(pred[i], pose, mask=mask)
             pair[1].integrate(gt[i].reshape(dims), pose, mask=mask)
+            st.setdefault("seen", {}).setdefault(step_type, []).append((seq, int(batch["frame_id"][i])))
             if st.get("frames"):
                 st["kept"].setdefault((step_type, seq), []).append(      # copies: the batch's tensors are not held on to
                     (pred[i].to(torch.uint8), gt[i].reshape(dims).clone(), None if mask is None else mask != 0, pose,
@@ -877,6 +892,36 @@ class OccDepth(_Base):
         from ..loss.sscMetrics import SSCMetrics
         st = self.semantic_map
         mine = sorted(key for key in st["maps"] if key[0] == step_type)
+        seen = st.setdefault("seen", {}).pop(step_type, [])
+        gathered, writer = False, True
+        if st.get("gather", True):
+            import torch.distributed as dist
+            gathered = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if gathered:
+            # every rank issues the same collectives in the same order: the keys, then per key the two maps
+            said = [None] * dist.get_world_size()
+            shapes = {key: (st["maps"][key][0].voxel_size, st["maps"][key][0].vox_origin, st["maps"][key][0].dims) for key in mine}
+            dist.all_gather_object(said, (shapes, sorted(set(seen))))
+            writer = dist.get_rank() == 0
+            held = {}
+            for shapes_r, seen_r in said:
+                for frame in seen_r:
+                    held[frame] = held.get(frame, 0) + 1
+            twice = sum(1 for n in held.values() if n > 1)
+            if twice:
+                import warnings
+                warnings.warn("occdepth_amd: %d frame(s) of the %s epoch voted on more than one rank (the sampler pads by "
+                              "repeating frames): they vote twice, as the ordinary metric counts them twice" % (twice, step_type))
+            known = {}
+            for shapes_r, _ in said:
+                known.update(shapes_r)
+            mine = sorted(known)
+            for key in mine:
+                if key not in st["maps"]:
+                    vs, origin, dims = known[key]
+                    st["maps"][key] = tuple(semantic_map.SemanticMap(self.n_classes, vs, origin, dims) for _ in range(2))
+                for m in st["maps"][key]:
+                    semantic_map.merge_over_ranks(m)
         if not mine:
             return None
         os.makedirs(st["out_dir"], exist_ok=True)
@@ -892,12 +937,14 @@ class OccDepth(_Base):
                 if st["submission_dir"]:
                     from .. import output
                     st["paths"].append(output.write_kitti_submission_labels(labels, key[1], frame_id, st["submission_dir"]))
-            for m, name in zip(pair, ("pred", "gt")):
+            for m, name in zip(pair, ("pred", "gt")) if writer else ():
                 coords, labels, n_obs = m.extract(min_obs=st["min_obs"])
                 path = os.path.join(st["out_dir"], "%s_%s_%s.ply" % (step_type, key[1], name))
                 st["paths"].append(semantic_map.write_ply(path, coords, labels, n_obs, m.voxel_size, colours))
+                if st.get("save_maps"):
+                    st["paths"].append(m.save(os.path.join(st["out_dir"], "%s_%s_%s.occmap" % (step_type, key[1], name))))
             semantic_map.map_confusion(pair[0], pair[1], metric)
-            if st.get("views"):
+            if st.get("views") and writer:
                 volume = semantic_map.MapVolume(pair[0], pair[1], st["min_obs"])
                 prefix = os.path.join(st["out_dir"], "%s_%s" % (step_type, key[1]))
                 st["paths"] += render.write_map_pictures(volume, prefix, st["views"], palette=colours)
@@ -905,7 +952,8 @@ class OccDepth(_Base):
                 m.release()
         if mapped is not None:
             st["mapped_stats"][step_type] = self._epoch_stats(mapped)
-        return self._epoch_stats(metric)
+        # after the exchange every rank counted the same maps: their statistics are never summed over the ranks
+        return metric.get_stats() if gathered else self._epoch_stats(metric)
 
     def _kitti_origin(self, batch=None):
         """SemanticKITTI voxel origin (kitti_dataset.py:82: vox_origin = (0, -25.6, -2) for the 51.2 m wide scene): the grid

@@ -9,12 +9,15 @@ frame vote in one launch, hip.map_brick_labels / hip.map_extract decide).
     write_ply("08.ply", coords, labels, n_obs, 0.2, render.palette("kitti"))
     map_confusion(pred_map, gt_map, SSCMetrics(20))                  # map mIoU where both maps were observed
     labels, n_obs = m.sample(poses[frame], own=labels, own_mask=fov_mask_1, keep_own=True)   # the map read back into a frame (K32)
+    m.merge(other); m.save("08.occmap"); SemanticMap.load("08.occmap"); merge_over_ranks(m)   # maps summed: runs, files, ranks (K33)
 
 The world lattice has the frame grid's voxel size; voxels live in 16^3 bricks of 16-bit vote counters, one row of `pitch`
 = n_classes rounded up to 4 counters per voxel (8192 * pitch bytes per brick: 163840 at 20 classes).  The host side is
 numpy in float64 and quantises to the int32 fixed point the kernel computes in (include/occdepth_amd.h).  The effect on
 any score is not measured (no checkpoint and no dataset where this was built).
 """
+import os
+
 import numpy as np
 import torch
 
@@ -369,6 +372,197 @@ class SemanticMap:
         dev_table, host_table = self.upload(self._key_table(self.brick_keys()), self.votes.device)
         return hip.map_extract(self.pool(), dev_table, self.n_classes, min_obs=min_obs, include_empty=include_empty,
                                table_host=host_table)
+
+
+    # ------------------------------------------------------------------------------------------------ merge (K33)
+    def occupied_keys(self, chunk_bricks=512):
+        """The keys, (n, 3) int64 ascending, of the bricks that hold at least one vote: frame_bricks over-selects, and
+        an all-zero brick need neither travel nor be written.  Torch operators on the pool; one host synchronisation."""
+        keys = self.brick_keys()
+        if not len(keys):
+            return keys
+        slots = torch.from_numpy(self.slots(keys).astype(np.int64)).to(self.votes.device)
+        words = self.pool().view(self.capacity, -1).view(torch.int64)       # a brick is 2048 * pitch 8-byte words
+        flags = [words.index_select(0, slots[s:s + int(chunk_bricks)]).ne(0).any(1)
+                 for s in range(0, len(keys), int(chunk_bricks))]
+        return keys[torch.cat(flags).cpu().numpy()]
+
+    def _merge_from(self, keys, src, src_rows, device):
+        """votes[slot of keys[i]] += src[src_rows[i]], saturating; keys the map lacks are admitted in ascending order."""
+        keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+        packed = pack_keys(keys)
+        if len(np.unique(packed)) != len(packed):
+            raise ValueError("merge_rows takes every brick key once: %d of %d keys are repeats"
+                             % (len(packed) - len(np.unique(packed)), len(packed)))
+        if not len(keys):
+            return self
+        new = np.sort(np.fromiter((p for p in packed.tolist() if p not in self.directory), dtype=np.int64))
+        if len(new):
+            self.slots(unpack_keys(new), create=True, device=device)       # refuses before it changes anything
+        table = np.stack([self.slots(keys), np.asarray(src_rows, dtype=np.int32).reshape(-1)], 1)
+        dev_table, host_table = self.upload(table, self.votes.device)
+        hip.map_merge(self.pool(), src, dev_table, table_host=host_table)
+        return self
+
+    def merge_rows(self, keys, rows, device=None):
+        """Add bricks of counters to the map (K33, one launch): keys (n, 3) int64, each once; rows (n, 4096, pitch)
+        int16 holding uint16 bits, row i the brick keys[i] -- used as it is on the map's device, copied there from
+        anywhere else (an empty map takes `device`, else the rows' device).  votes = min(votes + rows, 65535).  Keys the
+        map lacks are admitted, new bricks taking slots in ascending key order.  No host synchronisation unless the pool
+        has to grow; max_bricks is checked before anything changes."""
+        rows = torch.as_tensor(rows)
+        keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+        if rows.dtype != torch.int16 or tuple(rows.shape) != (len(keys), BRICK ** 3, self.pitch):
+            raise ValueError("merge_rows takes int16 rows (%d, %d, %d) for its %d keys, got %s %r"
+                             % (len(keys), BRICK ** 3, self.pitch, len(keys), rows.dtype, tuple(rows.shape)))
+        dev = self.votes.device if self.votes is not None else torch.device(device if device is not None else rows.device)
+        if rows.device != dev:
+            rows = rows.to(dev)                                             # blocking: the caller may reuse its buffer
+        return self._merge_from(keys, rows.contiguous(), np.arange(len(keys)), dev)
+
+    def merge(self, other):
+        """Add another map's votes to this one: the map of a set of frames is the counter-wise saturating sum of the
+        maps of any partition of the set.  One launch straight from other.pool(), without a copy when both maps share a
+        device.  n_classes and voxel_size must agree; vox_origin and dims may differ: they describe the frames a map
+        integrates, not the world lattice, which the voxel size alone fixes.  An empty `other` changes nothing."""
+        if other is self:
+            raise ValueError("a map cannot be merged into itself (every counter would have two owners)")
+        if other.n_classes != self.n_classes or other.voxel_size != self.voxel_size:
+            raise ValueError("the maps differ in classes (%d, %d) or voxel size (%r, %r): their counters or lattices differ"
+                             % (self.n_classes, other.n_classes, self.voxel_size, other.voxel_size))
+        if other.votes is None or not other.directory:
+            return self
+        keys = other.brick_keys()
+        rows = other.slots(keys)
+        dev = self.votes.device if self.votes is not None else other.votes.device
+        src = other.pool()
+        if src.device != dev:
+            src = src[:other.n_bricks].to(dev)                              # only the bricks in use travel; slots are 0 .. n - 1
+        return self._merge_from(keys, src, rows, dev)
+
+    # ------------------------------------------------------------------------------------------------ save / load
+    def _staging(self, chunk, device):
+        buf = torch.empty((chunk, BRICK ** 3, self.pitch), dtype=torch.int16)
+        return buf.pin_memory() if torch.device(device).type == "cuda" else buf
+
+    def save(self, path, chunk_bricks=None):
+        """Write the occupied bricks to `path` (the .occmap format): MAP_MAGIC, the header MAP_HEADER,
+        the keys (n, 3) little-endian int32 ascending, then the n bricks' counter rows in that order.  The rows pass
+        through one pinned buffer of `chunk_bricks` bricks (default: the map's): the map never needs a host copy.  -> path."""
+        keys = self.occupied_keys()
+        chunk = max(1, int(chunk_bricks or self.chunk_bricks))
+        header = np.zeros((), dtype=MAP_HEADER)
+        header["n_classes"], header["pitch"], header["brick"] = self.n_classes, self.pitch, BRICK
+        header["voxel_size"], header["vox_origin"], header["dims"] = self.voxel_size, self.vox_origin, self.dims
+        header["n_bricks"] = len(keys)
+        with open(path, "wb") as f:
+            f.write(MAP_MAGIC)
+            f.write(header.tobytes())
+            f.write(keys.astype("<i4").tobytes())
+            if len(keys):
+                dev = self.votes.device
+                slots = torch.from_numpy(self.slots(keys).astype(np.int64)).to(dev)
+                buf = self._staging(min(chunk, len(keys)), dev)
+                for s in range(0, len(keys), chunk):
+                    part = buf[:len(slots[s:s + chunk])]
+                    part.copy_(self.pool().index_select(0, slots[s:s + chunk]))          # blocking
+                    f.write(memoryview(part.numpy()).cast("B"))
+        return path
+
+    @classmethod
+    def load(cls, path, device=None, max_bricks=None, chunk_bricks=None):
+        """A file save() wrote -> a new map on `device` (default: the GPU when there is one) holding its bricks, in
+        slots 0 .. n - 1 by ascending key.  Read `chunk_bricks` bricks at a time through one pinned buffer.  Refuses a
+        wrong magic or version, a brick edge other than this build's, and a file whose length disagrees with its header."""
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            magic = f.read(len(MAP_MAGIC))
+            if magic != MAP_MAGIC:
+                raise ValueError("%s is not an occdepth_amd map file of this version: it starts with %r, not %r"
+                                 % (path, magic, MAP_MAGIC))
+            raw = f.read(MAP_HEADER.itemsize)
+            if len(raw) != MAP_HEADER.itemsize:
+                raise ValueError("%s: %d bytes, its header alone takes %d" % (path, size, len(MAP_MAGIC) + MAP_HEADER.itemsize))
+            h = np.frombuffer(raw, dtype=MAP_HEADER)[0]
+            if int(h["brick"]) != BRICK:
+                raise ValueError("%s holds bricks of edge %d, this build has %d" % (path, int(h["brick"]), BRICK))
+            n, pitch = int(h["n_bricks"]), int(h["pitch"])
+            m = cls(int(h["n_classes"]), float(h["voxel_size"]), tuple(h["vox_origin"].tolist()), tuple(h["dims"].tolist()),
+                    max_bricks=max_bricks, **({} if chunk_bricks is None else {"chunk_bricks": int(chunk_bricks)}))
+            if n < 0 or pitch != m.pitch:
+                raise ValueError("%s: a header of %d bricks at pitch %d for %d classes" % (path, n, pitch, m.n_classes))
+            want = len(MAP_MAGIC) + MAP_HEADER.itemsize + n * (12 + m.brick_bytes)
+            if size != want:
+                raise ValueError("%s: %d bytes, its header announces %d" % (path, size, want))
+            keys = np.frombuffer(f.read(12 * n), dtype="<i4").reshape(n, 3).astype(np.int64)
+            if n and (np.diff(pack_keys(keys)) <= 0).any():
+                raise ValueError("%s: its brick keys are not ascending" % path)
+            if not n:
+                return m
+            dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+            slots = m.slots(keys, create=True, device=dev)                  # 0 .. n - 1; max_bricks refuses here
+            buf = m._staging(min(m.chunk_bricks, n), dev)
+            for s in range(0, n, m.chunk_bricks):
+                part = buf[:len(slots[s:s + m.chunk_bricks])]
+                f.readinto(memoryview(part.numpy()).cast("B"))
+                m.pool()[s:s + len(part)].copy_(part)                       # blocking: the buffer is read into again
+        return m
+
+
+MAP_MAGIC = b"OCCDMAP1"                     # the last byte is the format version
+MAP_HEADER = np.dtype([("n_classes", "<i4"), ("pitch", "<i4"), ("brick", "<i4"), ("reserved", "<i4"), ("voxel_size", "<f8"),
+                       ("vox_origin", "<f8", (3,)), ("dims", "<i4", (3,)), ("reserved2", "<i4"), ("n_bricks", "<i8")])
+
+
+def merge_over_ranks(m, group=None, chunk_bricks=256, device=None):
+    """A collective over a torch.distributed group: leaves on every rank the same map, counter for counter -- the sum of
+    all ranks' maps.  The ranks exchange their occupied_keys(), admit the union in ascending order (so the directories
+    agree too), and for source rank r = 0 .. W - 1 the rows of r's bricks are broadcast `chunk_bricks` at a time and
+    merged (merge_rows) by every other rank.  The buffer lives on the device when the backend moves device tensors
+    (RCCL, which torch calls nccl), else in pinned host memory (gloo).  A rank other than the first keeps a copy of its
+    own occupied rows from before the first merge: what it sends must not hold what it received.  Each rank receives
+    W - 1 maps' worth of rows.  All ranks must agree on n_classes, pitch and voxel_size.  A world of one, or no
+    process group, returns at once.  An empty map takes `device` (default: the current GPU when there is one)."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return m
+    W = dist.get_world_size(group)
+    if W < 2:
+        return m
+    rank = dist.get_rank(group)
+    chunk = max(1, int(chunk_bricks))
+    mine = pack_keys(m.occupied_keys())
+    shape = (m.n_classes, m.pitch, m.voxel_size)
+    said = [None] * W
+    dist.all_gather_object(said, (shape, mine), group=group)
+    if any(s[0] != shape for s in said):
+        raise ValueError("the ranks' maps differ in (n_classes, pitch, voxel_size): %r" % ([s[0] for s in said],))
+    union = np.unique(np.concatenate([s[1] for s in said]))
+    if not len(union):
+        return m
+    dev = m.votes.device if m.votes is not None else torch.device(
+        device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+    m.slots(unpack_keys(union), create=True, device=dev)
+    on_device = dist.get_backend(group) == "nccl" and dev.type == "cuda"
+    n_max = max(len(s[1]) for s in said)
+    buf = (torch.empty((min(chunk, n_max), BRICK ** 3, m.pitch), dtype=torch.int16, device=dev) if on_device
+           else m._staging(min(chunk, n_max), dev))
+    own_slots = torch.from_numpy(m.slots(unpack_keys(mine)).astype(np.int64)).to(dev)
+    own = None
+    if rank > 0 and len(mine):                                              # rank 0 has sent before it merges
+        own = m.pool().index_select(0, own_slots) if on_device else torch.cat(
+            [m.pool().index_select(0, own_slots[s:s + chunk]).cpu() for s in range(0, len(mine), chunk)])
+    for r in range(W):
+        keys_r = said[r][1]
+        src = dist.get_global_rank(group, r) if group is not None else r
+        for s in range(0, len(keys_r), chunk):
+            part = buf[:len(keys_r[s:s + chunk])]
+            if r == rank:
+                part.copy_(m.pool().index_select(0, own_slots[s:s + chunk]) if own is None else own[s:s + len(part)])
+            dist.broadcast(part.view(torch.int32), src, group=group)       # gloo moves no 16-bit integers
+            if r != rank:
+                m.merge_rows(unpack_keys(keys_r[s:s + chunk]), part)
+    return m
 
 
 def map_confusion(pred_map, gt_map, metric, chunk_bricks=512):

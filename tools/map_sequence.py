@@ -3,7 +3,7 @@ as a point PLY, and score a prediction map against a ground-truth map.
 
     python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
         --out maps/08 [--min-obs 2] [--fov] [--every 5] [--views bev oblique] [--png-side 2048] [--camera-every 50 --t-max 80]
-        [--frames-out DIR [--exclude-self] [--keep-own]]
+        [--frames-out DIR [--exclude-self] [--keep-own]] [--frame-range FIRST LAST] [--save-map PREFIX] [--load-map PREFIX ...]
 
 --pred / --gt name a directory; what it holds decides how it is read:
     <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
@@ -20,6 +20,10 @@ frame's labels, inside its mask with --fov; --exclude-self takes the frame's own
 frame's label) and writes DIR/sequences/<sequence>/predictions/<frame>.label, submission files (<sequence> is the name of
 the --poses directory).  When --gt holds per-frame targets it also prints a `frames======` block (the frames' own labels
 against their targets) and a `mapped======` block (the sampled labels against the same targets).
+--save-map PREFIX keeps the finished maps as PREFIX_pred.occmap / PREFIX_gt.occmap (SemanticMap.save: the vote counters, which
+can be voted into again, unlike the PLY); --load-map PREFIX [PREFIX ...] merges such files in (SemanticMap.load, then merge,
+K33) before the frames are integrated, and --frame-range FIRST LAST (inclusive) keeps a run to a part of the sequence: one
+run over frames 0..1999 with --save-map and a second over 2000..4070 with --load-map give the map of the whole drive.
 """
 import argparse
 import glob
@@ -82,8 +86,13 @@ def build_map(src, role, poses, args, device):
     kind, frames = list_frames(src)
     lut = submission_inverse_lut() if kind == "label" else None
     m = sm.SemanticMap(args.classes, args.voxel, args.origin, tuple(args.dims), max_bricks=args.max_bricks)
+    for prefix in args.load_map or ():                                     # votes commute: earlier runs' maps come first or last alike
+        path = "%s_%s.occmap" % (prefix, role)
+        m.merge(sm.SemanticMap.load(path, device=device))
+        print("%s: merged %s -> %d bricks" % (role, path, m.n_bricks))
     used = 0
-    for frame in sorted(frames)[::args.every]:
+    first, last = args.frame_range if args.frame_range else (min(frames), max(frames))
+    for frame in [f for f in sorted(frames) if first <= f <= last][::args.every]:
         if frame not in poses:
             raise KeyError("no pose for frame %d of %s (%s)" % (frame, src, os.path.join(args.poses, "poses.txt")))
         labels, mask = read_frame(kind, frames[frame], role, tuple(args.dims), device, args.fov, lut)
@@ -191,6 +200,9 @@ def run(args, device=None):
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             path = sm.write_ply("%s_%s.ply" % (args.out, role), coords, labels, n_obs, m.voxel_size, colours)
             print("%s: %d voxels with at least %d vote(s)" % (path, len(labels), args.min_obs))
+            if args.save_map:
+                os.makedirs(os.path.dirname(os.path.abspath(args.save_map)), exist_ok=True)
+                print("%s: the vote counters" % m.save("%s_%s.occmap" % (args.save_map, role)))
     if not maps:
         raise SystemExit("give --pred, --gt or both")
     if args.views or args.camera_every:
@@ -235,6 +247,10 @@ def parser():
                     help="read the prediction map back into every --pred frame: DIR/sequences/<seq>/predictions/<frame>.label")
     ap.add_argument("--exclude-self", action="store_true", help="--frames-out: take the frame's own vote out of the map first")
     ap.add_argument("--keep-own", action="store_true", help="--frames-out: a tie that the frame's own label is part of goes to it")
+    ap.add_argument("--frame-range", type=int, nargs=2, default=None, metavar=("FIRST", "LAST"), help="use these frames only (inclusive)")
+    ap.add_argument("--save-map", default=None, metavar="PREFIX", help="keep the maps' vote counters: PREFIX_{pred,gt}.occmap")
+    ap.add_argument("--load-map", nargs="+", default=None, metavar="PREFIX",
+                    help="merge PREFIX_{pred,gt}.occmap of earlier runs in before the frames are integrated")
     return ap
 
 

@@ -82,7 +82,8 @@ extern "C" {
  *     one new function only; likewise OCCD_MAP_SAMPLE_EXCLUDE_SELF, OCCD_MAP_SAMPLE_KEEP_OWN, OccdMapSampleArgs and
  *     occd_map_sample (K32, the map read back into a frame's voxels, csrc/semantic_map.hip): one new struct and one new
  *     function only; likewise OccdMapMergeArgs and occd_map_merge (K33, the counter-wise saturating sum of two sets of
- *     bricks, csrc/semantic_map.hip): one new struct and one new function only */
+ *     bricks, csrc/semantic_map.hip): one new struct and one new function only; likewise OCCD_GEMM_KERNEL_* and
+ *     occd_gemm_f32x3_route (the hint-0 kernel choice of occd_gemm_f32x3 as a host query): one new function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -326,6 +327,17 @@ typedef struct occd_gemm_args {
     int64_t stride_bias_n;                 /* floats between the batch items of bias_n (0: shared)                              */
 } occd_gemm_args;
 int occd_gemm_f32x3(const occd_gemm_args* a, void* stream);
+/* Which kernel occd_gemm_f32x3 launches for a problem, from shapes alone (host code, no device needed): the one rule the
+ * launch itself follows, for callers that keep one weight image per route.  pre, tile_hint: as in occd_gemm_args; plain:
+ * 1 = no res, no scale_k, no act_a, no bias_n.  *kernel = OCCD_GEMM_KERNEL_*; *variant = the panel width in 32-column
+ * units (PANEL: 1 / 2) or the tile variant 0 .. 4 = 256 x 128, 128 x 128, 128 x 64, 64 x 64, 64 x 256 (TILE; WS is
+ * always 0, KSPLIT always 3).  OCCD_EINVAL for shapes and hint / pre combinations occd_gemm_f32x3 rejects.              */
+#define OCCD_GEMM_KERNEL_TILE 0   /* the barrier-phased tile kernels (K16)                   */
+#define OCCD_GEMM_KERNEL_PANEL 1  /* K16p: the panel-stationary kernel on a pre-split A      */
+#define OCCD_GEMM_KERNEL_WS 2     /* K16w: the wave-specialised 256 x 128 kernel             */
+#define OCCD_GEMM_KERNEL_KSPLIT 3 /* the 64 x 64 tile with in-workgroup split-K              */
+int occd_gemm_f32x3_route(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t pre, int32_t plain, int32_t tile_hint,
+                          int32_t* kernel, int32_t* variant);
 /* K21 (round 6), the skinny long-K GEMMs -- the MBConv project convolutions of the 1/16 and 1/32 EfficientNet stages,
  * `bn3(conv_pwl(x * se_gate)) + skip` (geffnet InvertedResidual behind occdepth/models/unet2d.py:188-196): K16p's
  * panel-stationary loop with K cut into `nz` chunks over the grid's z dimension, float32 partial tiles in `workspace`, and a

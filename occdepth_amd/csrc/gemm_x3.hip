@@ -1443,6 +1443,101 @@ extern "C" int occd_gemm_x3_pack(const float* w, void* out, int32_t rows, int32_
     return occd::check_launch();
 }
 
+// The hint-0 decision of occd_gemm_f32x3 (and what a forcing hint turns it into), from shapes alone: which kernel family
+// (OCCD_GEMM_KERNEL_*) and which variant of it -- PANEL: the panel width in 32-column units (1 / 2); TILE, WS, KSPLIT: the
+// index into kVariantsG.  pre: occd_gemm_args.pre; plain: no res, no scale_k, no act_a, no bias_n.  OCCD_EINVAL for a shape
+// or a hint / pre combination occd_gemm_f32x3 rejects.  Host code only: occd_gemm_f32x3 launches what this returns, and
+// occd_gemm_f32x3_route answers callers that pack weight images per route (occdepth_amd/hip.py).
+static int gemm_route(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t pre, int32_t plain, int32_t tile_hint,
+                      int32_t* kernel, int32_t* variant) {
+    if (M <= 0 || N < 4 || K <= 0 || (K & 7) || batch <= 0 || batch > 65535) return OCCD_EINVAL;
+    if (pre < 0 || pre > OCCD_GEMM_PRE_F16X2 || tile_hint < 0 || tile_hint > kNumVariantsG + 3) return OCCD_EINVAL;
+    const bool img_a = pre == 1 || pre == OCCD_GEMM_PRE_F16X2;
+    {
+        // K16p: pre-split A, the whole-K panel of 32 / 64 B columns fits LDS, plain epilogue.  hint 8 forces it, hint 0 picks it
+        // for matrices of >= 256 rows -- one row tile for each of the 8 waves (OCCD_GEMM_PANEL=0 keeps the barrier-phased
+        // PRE = 1 kernel for A/B)
+        static const bool panel_off = !occd::env_flag("OCCD_GEMM_PANEL", true);
+        const int KP = ((K + 15) / 16) * 16;
+        const bool fits1 = img_a && plain && (size_t)KP * panel_row_bytes(1) <= 160 * 1024;      // K <= 848
+        const bool fits2 = img_a && plain && (size_t)KP * panel_row_bytes(2) <= 160 * 1024;      // K <= 352
+        if (tile_hint == kNumVariantsG + 3 && !fits1) return OCCD_EINVAL;
+        // (hint 0, K > 352 -- the 32-column form only: just the few-pixel launches of the 1/16 and 1/32 stages, where it leads by
+        //  ~15 %; the 1/4-level tap GEMM, 2880 x 7191 x 640, measured 0.45 ms on it against K16's 0.35)
+        const long small_launch = (long)((N + 63) / 64) * batch * (((M + 31) / 32 + 7) / 8);
+        const bool auto_ok = tile_hint == 0 && !panel_off && M >= 256 && (fits2 || small_launch <= 512);
+        if (fits1 && (tile_hint == kNumVariantsG + 3 || auto_ok)) {
+            // panel width: 64 columns while two workgroups fit a CU's LDS with them (K <= 176), else 32 (measured, kernel trace,
+            // profiles/r05_gemm_panel.txt: tap 1/2 (K = 320) 332 against 362 us, 224 -> 1344 on 1848 pixels 22 against 27 us; the
+            // 64-column form ahead by 3 ... 10 % on K = 48 ... 160): a second resident workgroup stages its panel under the
+            // first one's MFMAs, which is worth more than half the weight-fragment traffic
+            int nt = (fits2 && (size_t)KP * panel_row_bytes(2) <= 80 * 1024) ? 2 : 1;
+            static const int dev_nt = getenv("OCCD_GEMM_PANEL_NT") ? atoi(getenv("OCCD_GEMM_PANEL_NT")) : 0;     // (development A/B)
+            if ((dev_nt == 1 || dev_nt == 2) && (dev_nt == 1 || fits2)) nt = dev_nt;
+            *kernel = OCCD_GEMM_KERNEL_PANEL;
+            *variant = nt;
+            return OCCD_OK;
+        }
+    }
+    int pick = tile_hint - 1;
+    if (tile_hint == kNumVariantsG + 1) {
+        if (pre != 0) return OCCD_EINVAL;
+        pick = 0;
+    }
+    if (tile_hint == kNumVariantsG + 2) {
+        if (pre != 0) return OCCD_EINVAL;
+        pick = 3;
+    }
+    if (pick < 0) {
+        // Long K (>= 1024: tap GEMMs, Winograd-domain products): the largest tile that still leaves >= 160 workgroups
+        // (measured, profiles/r04_gemm_x3_v3_ws.txt: the large tiles win down to ~0.6 workgroups per CU).  Short K (the MBConv
+        // expand convolutions, 32 ... 640 input channels = 1 ... 20 k-steps): a workgroup is mostly prologue + epilogue and only
+        // several resident workgroups per CU hide it -- 64 x 64 tiles unless the problem is so large that even 256 x 128 tiles
+        // give 8 workgroups per CU (profiles/r04_gemm_x3_v5_shortk.txt: 48 -> 288 on 28365 pixels 54 -> 34 us, 384 -> 2304 on
+        // 468 pixels 27 -> 23 us; the tap GEMMs of the 1/1 and 1/2 levels, K = 160 / 320, keep 256 x 128); in between
+        // (K = 512 ... 1023) the largest tile with >= 320 workgroups.  A matrix of <= 64 rows (project convolutions of the
+        // high-resolution stages in training: M = 32 ... 64, N = 10^4 ... 10^5 pixels) takes the 64-row tiles instead of
+        // wasting 3/4 of a 256-row one.
+        auto wgs_of = [&](int i) {
+            const VariantG& v = kVariantsG[i];
+            const long tm = v.MT * v.WM * 32, tn = v.NT * v.WN * 32;
+            return ((M + tm - 1) / tm) * ((N + tn - 1) / tn) * batch;
+        };
+        if (M <= 64) {
+            // (short K: 64 x 64 again -- 288 -> 48 on 2 x 28365 pixels 30 us against 42 with 64 x 256 tiles)
+            pick = (K >= 512 && (long)((N + 255) / 256) * batch >= 160) ? 4 : 3;
+        } else if (K < 512) {
+            pick = wgs_of(0) >= 2048 ? 0 : 3;
+        } else {
+            const long need = K < 1024 ? 320 : 160;
+            pick = 3;
+            for (int i = 0; i < 4; ++i)
+                if (wgs_of(i) >= need) { pick = i; break; }
+        }
+    }
+    // the wave-specialised 256 x 128 kernel takes the launches the 256 x 128 tile would (float32 operands): hint 6 forces it,
+    // hint 0 picks it (OCCD_GEMM_WS=0 in the environment keeps the barrier-phased kernels for A/B)
+    static const bool ws_off = !occd::env_flag("OCCD_GEMM_WS", true);
+    // measured (profiles/r04_gemm_x3_v4_fast.txt): with the tail-free fast path the barrier-phased kernel leads everywhere but on
+    // the longest K (tap GEMM of the 1/16 level, K = 2560: 0.438 against 0.462 ms); K16w keeps that launch
+    const bool ws = pre == 0 && plain && (tile_hint == kNumVariantsG + 1 || (tile_hint == 0 && pick == 0 && !ws_off && K >= 2048));
+    // in-workgroup split-K (64 x 64 tile, 4 K groups = 16 waves) when the 64 x 64 tiling leaves CUs without a workgroup and K is
+    // long: the project convolutions of the 1/16 and 1/32 stages (tile_hint 7 forces it; OCCD_GEMM_KS=0 disables it for A/B)
+    static const bool ks_off = !occd::env_flag("OCCD_GEMM_KS", true);
+    const long wgs64 = (long)((M + 63) / 64) * ((N + 63) / 64) * batch;
+    const bool ksplit = pre == 0 && !ws && (tile_hint == kNumVariantsG + 2 ||
+                                            (tile_hint == 0 && pick == 3 && !ks_off && K >= 768 && wgs64 <= 320));
+    *kernel = ws ? OCCD_GEMM_KERNEL_WS : ksplit ? OCCD_GEMM_KERNEL_KSPLIT : OCCD_GEMM_KERNEL_TILE;
+    *variant = pick;
+    return OCCD_OK;
+}
+
+extern "C" int occd_gemm_f32x3_route(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t pre, int32_t plain, int32_t tile_hint,
+                                     int32_t* kernel, int32_t* variant) {
+    if (!kernel || !variant) return OCCD_EINVAL;
+    return gemm_route(M, N, K, batch, pre, plain, tile_hint, kernel, variant);
+}
+
 // a->tile_hint: 0 = pick (see below), 1 .. 5 = force a tile variant, 6 = force K16w, 7 = force the 64 x 64 split-K form,
 // 8 = force K16p (pre = 1, K <= 848, no res / scale_k).
 // a->pre: 0 = A and B float32; 1 = a->A is the role-0 image of occd_gemm_x3_pack (lda ignored, stride_a = bf16 elements
@@ -1468,128 +1563,63 @@ extern "C" int occd_gemm_f32x3(const occd_gemm_args* a, void* stream) {
     if (a->bias_n != nullptr && ((reinterpret_cast<uintptr_t>(a->bias_n) & 3) || a->stride_bias_n < 0 ||
                                  a->tile_hint == kNumVariantsG + 1 || a->tile_hint == kNumVariantsG + 3))
         return OCCD_EINVAL;                              // (the wave-specialised and the panel kernels have no column bias)
-    {
-        // K16p: pre-split A, the whole-K panel of 32 / 64 B columns fits LDS, plain epilogue.  hint 8 forces it, hint 0 picks it
-        // for matrices of >= 256 rows -- one row tile for each of the 8 waves (OCCD_GEMM_PANEL=0 keeps the barrier-phased
-        // PRE = 1 kernel for A/B)
-        static const bool panel_off = !occd::env_flag("OCCD_GEMM_PANEL", true);
-        const int KP = ((a->K + 15) / 16) * 16;
-        const bool plain = img_a && a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr;
-        const bool fits1 = plain && (size_t)KP * panel_row_bytes(1) <= 160 * 1024;      // K <= 848
-        const bool fits2 = plain && (size_t)KP * panel_row_bytes(2) <= 160 * 1024;      // K <= 352
-        if (a->tile_hint == kNumVariantsG + 3 && !fits1) return OCCD_EINVAL;
-        // (hint 0, K > 352 -- the 32-column form only: just the few-pixel launches of the 1/16 and 1/32 stages, where it leads by
-        //  ~15 %; the 1/4-level tap GEMM, 2880 x 7191 x 640, measured 0.45 ms on it against K16's 0.35)
-        const long small_launch = (long)((a->N + 63) / 64) * a->batch * (((a->M + 31) / 32 + 7) / 8);
-        const bool auto_ok = a->tile_hint == 0 && !panel_off && a->M >= 256 && (fits2 || small_launch <= 512);
-        if (fits1 && (a->tile_hint == kNumVariantsG + 3 || auto_ok)) {
-            GemmP p;
-            p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.res = nullptr; p.kscale = nullptr;
-            p.M = a->M; p.N = a->N; p.K = a->K;
-            p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.sA = a->stride_a / 8; p.sB = a->stride_b; p.sC = a->stride_c;
-            p.act = a->act; p.slope = a->slope; p.act_a = 0; p.n_fast = 1;
-            const int tiles = (a->M + 31) / 32, r8 = (tiles + 7) / 8;
-            if (f16x2) {
-                p.fac = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a->A) + f16x2_image_elems(a->M, a->K));
-                p.s_fac = a->stride_a / 2;
-            }
-            // panel width: 64 columns while two workgroups fit a CU's LDS with them (K <= 176), else 32 (measured, kernel trace,
-            // profiles/r05_gemm_panel.txt: tap 1/2 (K = 320) 332 against 362 us, 224 -> 1344 on 1848 pixels 22 against 27 us; the
-            // 64-column form ahead by 3 ... 10 % on K = 48 ... 160): a second resident workgroup stages its panel under the
-            // first one's MFMAs, which is worth more than half the weight-fragment traffic
-            int nt = (fits2 && (size_t)KP * panel_row_bytes(2) <= 80 * 1024) ? 2 : 1;
-            static const int dev_nt = getenv("OCCD_GEMM_PANEL_NT") ? atoi(getenv("OCCD_GEMM_PANEL_NT")) : 0;     // (development A/B)
-            if ((dev_nt == 1 || dev_nt == 2) && (dev_nt == 1 || fits2)) nt = dev_nt;
-            p.ntiles = (a->N + 32 * nt - 1) / (32 * nt);
-            const long panels = (long)p.ntiles * a->batch;
-            // row ranges: ranges of 8 row tiles (one per wave) while that gives at most ~4 workgroups per CU; a large launch
-            // walks all its row tiles in every workgroup (the panel is staged once), cut only as far as 256 CUs need it
-            long ranges = panels * r8 <= 1024 ? r8 : panels >= 256 ? 1 : 256 / panels;
-            if (ranges > r8) ranges = r8;
-            if (ranges < 1) ranges = 1;
-            static const int dev_ranges = getenv("OCCD_GEMM_PANEL_RANGES") ? atoi(getenv("OCCD_GEMM_PANEL_RANGES")) : 0;
-            if (dev_ranges >= 1 && dev_ranges <= tiles) ranges = dev_ranges;
-            p.mr_tiles = (int)((tiles + ranges - 1) / ranges);
-            p.mtiles = (tiles + p.mr_tiles - 1) / p.mr_tiles;
-            // row tiles per wave and round (MT): 1.  Measured (profiles/r05_gemm_panel.txt): 2 / 3 tiles per wave halve / third
-            // the LDS fragment reads but lose on every launch of the frame (tap 1/1 460 -> 471 / 487 us, 48 -> 288 on 28365
-            // pixels 29 -> 37 / 45 us): several short rounds per wave overlap one wave's stores with the other's MFMAs; raising
-            // the priority of one wave per SIMD to force that alternation changed nothing.
-            const long nwg = (long)p.mtiles * p.ntiles;
-            if (nwg >= (1L << 31)) return OCCD_EINVAL;
-            p.nwg = (unsigned)nwg;
-            // weight fragments ONE step ahead; two on the 32-column form with a long K (K >= 512: 42.8 -> 40.0 us, 40.2 -> 37.8).
-            // Measured with the branch-free loop below, i.e. with the loads really in flight (ISA: vmcnt(10) ... vmcnt(1)):
-            // deeper is slower on every other launch (tap 1/1 369 -> 384 / 382 / 412 us at 2 / 4 / 6 steps, 48 -> 288 27 -> 31 -> 41)
-            // -- tools/panel_timeline.cpp shows a 16-k step at ~700 cycles (32 columns) / ~950 (64) whatever the depth: the two
-            // waves of a SIMD keep the matrix pipe 55 - 70 % busy INSIDE the loop; the launch-level 22 - 35 % is prologue (kernel
-            // arguments + panel staging: 7k cycles of a 29k-cycle workgroup at 384 -> 2304 on 468 pixels), epilogue and dispatch.
-            // f16x2: the same widths and depths (the routing limits above are those of the three-term rows, so that a launch takes
-            // the same route under either split; the 64-column row of 320 B would leave two workgroups per CU up to K = 256 --
-            // not measured, K <= 176 kept)
-            void (*kern)(const GemmP) = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2> : gemm_x3_panel_kernel<1, 1, 1>;
-            if (f16x2) kern = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1, 2> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2, 2> : gemm_x3_panel_kernel<1, 1, 1, 2>;
-            const size_t plds = (size_t)KP * panel_row_bytes(nt, f16x2 ? 2 : 3);
-            if (plds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
-            const double flops = 2.0 * a->M * a->N * a->K * a->batch;
-            const double bytes = 4.0 * ((double)a->M * a->K * (a->stride_a != 0 ? a->batch : 1) + ((double)a->K + a->M) * a->N * a->batch);
-            occd::ProfScope prof("gemm_f32x3_panel", (hipStream_t)stream, flops, bytes);
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg, (unsigned)a->batch), dim3(512), plds, (hipStream_t)stream, p);
-            return occd::check_launch();
-        }
-    }
-    int pick = a->tile_hint - 1;
-    if (a->tile_hint == kNumVariantsG + 1) pick = 0;
-    if (a->tile_hint == kNumVariantsG + 2) {
-        if (a->pre != 0) return OCCD_EINVAL;
-        pick = 3;
-    }
-    if (pick < 0) {
-        // Long K (>= 1024: tap GEMMs, Winograd-domain products): the largest tile that still leaves >= 160 workgroups
-        // (measured, profiles/r04_gemm_x3_v3_ws.txt: the large tiles win down to ~0.6 workgroups per CU).  Short K (the MBConv
-        // expand convolutions, 32 ... 640 input channels = 1 ... 20 k-steps): a workgroup is mostly prologue + epilogue and only
-        // several resident workgroups per CU hide it -- 64 x 64 tiles unless the problem is so large that even 256 x 128 tiles
-        // give 8 workgroups per CU (profiles/r04_gemm_x3_v5_shortk.txt: 48 -> 288 on 28365 pixels 54 -> 34 us, 384 -> 2304 on
-        // 468 pixels 27 -> 23 us; the tap GEMMs of the 1/1 and 1/2 levels, K = 160 / 320, keep 256 x 128); in between
-        // (K = 512 ... 1023) the largest tile with >= 320 workgroups.  A matrix of <= 64 rows (project convolutions of the
-        // high-resolution stages in training: M = 32 ... 64, N = 10^4 ... 10^5 pixels) takes the 64-row tiles instead of
-        // wasting 3/4 of a 256-row one.
-        auto wgs_of = [&](int i) {
-            const VariantG& v = kVariantsG[i];
-            const long tm = v.MT * v.WM * 32, tn = v.NT * v.WN * 32;
-            return ((a->M + tm - 1) / tm) * ((a->N + tn - 1) / tn) * a->batch;
-        };
-        if (a->M <= 64) {
-            // (short K: 64 x 64 again -- 288 -> 48 on 2 x 28365 pixels 30 us against 42 with 64 x 256 tiles)
-            pick = (a->K >= 512 && (long)((a->N + 255) / 256) * a->batch >= 160) ? 4 : 3;
-        } else if (a->K < 512) {
-            pick = wgs_of(0) >= 2048 ? 0 : 3;
-        } else {
-            const long need = a->K < 1024 ? 320 : 160;
-            pick = 3;
-            for (int i = 0; i < 4; ++i)
-                if (wgs_of(i) >= need) { pick = i; break; }
-        }
-    }
-    // the wave-specialised 256 x 128 kernel takes the launches the 256 x 128 tile would (float32 operands): hint 5 forces it,
-    // hint 0 picks it (OCCD_GEMM_WS=0 in the environment keeps the barrier-phased kernels for A/B)
-    static const bool ws_off = !occd::env_flag("OCCD_GEMM_WS", true);
-    // measured (profiles/r04_gemm_x3_v4_fast.txt): with the tail-free fast path the barrier-phased kernel leads everywhere but on
-    // the longest K (tap GEMM of the 1/16 level, K = 2560: 0.438 against 0.462 ms); K16w keeps that launch
     if ((a->res != nullptr || a->scale_k != nullptr) && (a->tile_hint == kNumVariantsG + 1 || a->pre == 2)) return OCCD_EINVAL;
-    if (a->res != nullptr && (reinterpret_cast<uintptr_t>(a->res) & 3)) return OCCD_EINVAL;
     if (a->act_a != 0 && (a->act_a != 1 || img_a || a->pre == 3 || a->tile_hint == kNumVariantsG + 1)) return OCCD_EINVAL;
-    const bool ws = a->pre == 0 && a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr &&
-                    (a->tile_hint == kNumVariantsG + 1 || (a->tile_hint == 0 && pick == 0 && !ws_off && a->K >= 2048));
-    if (a->tile_hint == kNumVariantsG + 1 && a->pre != 0) return OCCD_EINVAL;
+    const bool plain = a->res == nullptr && a->scale_k == nullptr && a->act_a == 0 && a->bias_n == nullptr;
+    int32_t route = 0, pick = 0;
+    if (gemm_route(a->M, a->N, a->K, a->batch, a->pre, plain, a->tile_hint, &route, &pick) != OCCD_OK) return OCCD_EINVAL;
+    if (route == OCCD_GEMM_KERNEL_PANEL) {
+        const int nt = pick, KP = ((a->K + 15) / 16) * 16;
+        GemmP p;
+        p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.res = nullptr; p.kscale = nullptr;
+        p.M = a->M; p.N = a->N; p.K = a->K;
+        p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.sA = a->stride_a / 8; p.sB = a->stride_b; p.sC = a->stride_c;
+        p.act = a->act; p.slope = a->slope; p.act_a = 0; p.n_fast = 1;
+        const int tiles = (a->M + 31) / 32, r8 = (tiles + 7) / 8;
+        if (f16x2) {
+            p.fac = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(a->A) + f16x2_image_elems(a->M, a->K));
+            p.s_fac = a->stride_a / 2;
+        }
+        p.ntiles = (a->N + 32 * nt - 1) / (32 * nt);
+        const long panels = (long)p.ntiles * a->batch;
+        // row ranges: ranges of 8 row tiles (one per wave) while that gives at most ~4 workgroups per CU; a large launch
+        // walks all its row tiles in every workgroup (the panel is staged once), cut only as far as 256 CUs need it
+        long ranges = panels * r8 <= 1024 ? r8 : panels >= 256 ? 1 : 256 / panels;
+        if (ranges > r8) ranges = r8;
+        if (ranges < 1) ranges = 1;
+        static const int dev_ranges = getenv("OCCD_GEMM_PANEL_RANGES") ? atoi(getenv("OCCD_GEMM_PANEL_RANGES")) : 0;
+        if (dev_ranges >= 1 && dev_ranges <= tiles) ranges = dev_ranges;
+        p.mr_tiles = (int)((tiles + ranges - 1) / ranges);
+        p.mtiles = (tiles + p.mr_tiles - 1) / p.mr_tiles;
+        // row tiles per wave and round (MT): 1.  Measured (profiles/r05_gemm_panel.txt): 2 / 3 tiles per wave halve / third
+        // the LDS fragment reads but lose on every launch of the frame (tap 1/1 460 -> 471 / 487 us, 48 -> 288 on 28365
+        // pixels 29 -> 37 / 45 us): several short rounds per wave overlap one wave's stores with the other's MFMAs; raising
+        // the priority of one wave per SIMD to force that alternation changed nothing.
+        const long nwg = (long)p.mtiles * p.ntiles;
+        if (nwg >= (1L << 31)) return OCCD_EINVAL;
+        p.nwg = (unsigned)nwg;
+        // weight fragments ONE step ahead; two on the 32-column form with a long K (K >= 512: 42.8 -> 40.0 us, 40.2 -> 37.8).
+        // Measured with the branch-free loop below, i.e. with the loads really in flight (ISA: vmcnt(10) ... vmcnt(1)):
+        // deeper is slower on every other launch (tap 1/1 369 -> 384 / 382 / 412 us at 2 / 4 / 6 steps, 48 -> 288 27 -> 31 -> 41)
+        // -- tools/panel_timeline.cpp shows a 16-k step at ~700 cycles (32 columns) / ~950 (64) whatever the depth: the two
+        // waves of a SIMD keep the matrix pipe 55 - 70 % busy INSIDE the loop; the launch-level 22 - 35 % is prologue (kernel
+        // arguments + panel staging: 7k cycles of a 29k-cycle workgroup at 384 -> 2304 on 468 pixels), epilogue and dispatch.
+        // f16x2: the same widths and depths (the routing limits of gemm_route are those of the three-term rows, so that a launch
+        // takes the same route under either split; the 64-column row of 320 B would leave two workgroups per CU up to K = 256 --
+        // not measured, K <= 176 kept)
+        void (*kern)(const GemmP) = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2> : gemm_x3_panel_kernel<1, 1, 1>;
+        if (f16x2) kern = nt == 2 ? gemm_x3_panel_kernel<1, 2, 1, 2> : a->K >= 512 ? gemm_x3_panel_kernel<1, 1, 2, 2> : gemm_x3_panel_kernel<1, 1, 1, 2>;
+        const size_t plds = (size_t)KP * panel_row_bytes(nt, f16x2 ? 2 : 3);
+        if (plds > 64 * 1024 && occd::ensure_big_lds(reinterpret_cast<const void*>(kern)) != OCCD_OK) return OCCD_ELAUNCH;
+        const double flops = 2.0 * a->M * a->N * a->K * a->batch;
+        const double bytes = 4.0 * ((double)a->M * a->K * (a->stride_a != 0 ? a->batch : 1) + ((double)a->K + a->M) * a->N * a->batch);
+        occd::ProfScope prof("gemm_f32x3_panel", (hipStream_t)stream, flops, bytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg, (unsigned)a->batch), dim3(512), plds, (hipStream_t)stream, p);
+        return occd::check_launch();
+    }
+    const bool ws = route == OCCD_GEMM_KERNEL_WS, ksplit = route == OCCD_GEMM_KERNEL_KSPLIT;
     const VariantG& v = kVariantsG[pick];
     const int TM = v.MT * v.WM * 32, TN = v.NT * v.WN * 32;
-    // in-workgroup split-K (64 x 64 tile, 4 K groups = 16 waves) when the 64 x 64 tiling leaves CUs without a workgroup and K is
-    // long: the project convolutions of the 1/16 and 1/32 stages (tile_hint 7 forces it; OCCD_GEMM_KS=0 disables it for A/B)
-    static const bool ks_off = !occd::env_flag("OCCD_GEMM_KS", true);
-    const long wgs64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64) * a->batch;
-    const bool ksplit = a->pre == 0 && !ws && (a->tile_hint == kNumVariantsG + 2 ||
-                                               (a->tile_hint == 0 && pick == 3 && !ks_off && a->K >= 768 && wgs64 <= 320));
     GemmP p;
     p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.res = a->res; p.kscale = a->scale_k;
     p.M = a->M; p.N = a->N; p.K = a->K;

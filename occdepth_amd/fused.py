@@ -124,7 +124,7 @@ _SWITCHES = {
     # The head launches (OCCDEPTH_HEAD_SPLIT), the OCCDEPTH_BF16X3=1 experiment, the opt-in 1x1x1 / sigmoid route and training
     # are unchanged by this switch.
     "K2B_SPLIT": ("OCCDEPTH_K2B_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
-    # Which weight image the 2-D network's operand builders (efficientnet.gemm_operands / splitk_operands, the tap-GEMM and the
+    # Which weight image the 2-D network's operand holders (hip.GemmWeights of efficientnet.gemm_operands, the tap-GEMM and the
     # merged conv_head o conv2 operands of unet2d.py) make for the GEMMs that read pre-split weights -- K16p, K21 and K16's
     # pre-split form (csrc/gemm_x3.hip):
     #   OCCDEPTH_GEMM_SPLIT=f16x2   (default) the image of occd_gemm_f16x2_pack: three v_mfma_f32_32x32x16_f16 per K step and 4
@@ -135,7 +135,7 @@ _SWITCHES = {
     # Under f16x2 the builders also put the Winograd-domain products of the decoder on the channel-major form (hip.WinoCM, where
     # hip.wino_cm_wins says so) and the K16 launches below 256 rows (project convolutions with gate and residual, the 192-row
     # expand) on the image (hip.tile_f16x2_wins); bf16x3 keeps their float32 operands, bit for bit as before.
-    # Explicit hip.GemmPacked(w, role) / hip.matmul_operand(w, role) callers, role-"b" images and training are unchanged by this
+    # Explicit hip.GemmPacked(w, role) / hip.GemmWeights(w, role) callers, role-"b" images and training are unchanged by this
     # switch.
     "GEMM_SPLIT": ("OCCDEPTH_GEMM_SPLIT", "f16x2", "f16x2", _same("f16x2", "bf16x3"), "f16x2 or bf16x3"),
 }

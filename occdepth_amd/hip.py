@@ -5,6 +5,7 @@ every function takes torch CUDA(=HIP) tensors, passes raw pointers + sizes
 through the C ABI and launches on torch's current stream.  There is NO fallback:
 a missing / unloadable library or a CPU tensor raises.
 """
+import collections
 import ctypes
 import os
 from ctypes import c_int32, c_int64, c_void_p
@@ -497,6 +498,29 @@ def gemm_x3_supported(a, b):
     return nb_a is None or nb_b is None or nb_a == nb_b
 
 
+def _gemm_args(who, a, b, out, M, N, K, batch, bias, act, slope, res, k_scale):
+    """The occd_gemm_args that K16 and K21 share: operand addresses, sizes, the output's strides and the epilogue operands
+    (checked); the operand strides, tile_hint and pre are the caller's."""
+    q = GemmArgs()
+    q.A, q.B, q.C = a.data_ptr(), b.data_ptr(), out.data_ptr()
+    if bias is not None:
+        if bias.numel() != M or not bias.is_contiguous():
+            raise RuntimeError(who + ": bias must be M contiguous floats")
+        q.bias = _f32(bias, "bias")
+    q.M, q.N, q.K, q.batch = M, N, K, batch
+    q.ldc, q.stride_c = out.stride(-2), (out.stride(0) if out.dim() == 3 else 0)
+    q.act, q.slope = GEMM_ACT[act], slope
+    if res is not None:
+        if res.dtype != torch.float32 or res.shape != out.shape or res.stride() != out.stride():
+            raise RuntimeError(who + ": res must be laid out like out")
+        q.res = res.data_ptr()
+    if k_scale is not None:
+        if k_scale.dtype != torch.float32 or tuple(k_scale.shape) != (batch, K) or not k_scale.is_contiguous():
+            raise RuntimeError(who + ": k_scale must be (batch, K) contiguous floats")
+        q.scale_k = k_scale.data_ptr()
+    return q
+
+
 def gemm_x3(a, b, bias=None, act=None, slope=0.01, out=None, tile_hint=0, plain_bf16=False, res=None, k_scale=None,
             sigmoid_a=False, bias_n=None):
     """K16 (occd_gemm_f32x3): out[i] = act(a[i] @ (b[i] * k_scale[i][:, None]) + bias[:, None]) + res[i] in float32-level
@@ -527,35 +551,20 @@ def gemm_x3(a, b, bias=None, act=None, slope=0.01, out=None, tile_hint=0, plain_
         # end / once per batch item on top of itself
         raise RuntimeError("gemm_x3: out must be (batch, M, N) with batch = %d (2-D only when neither operand is batched)"
                            % batch)
-    q = GemmArgs()
-    q.A = a.buf.data_ptr() if pa else a.data_ptr()       # (strided views: the strides travel as lda / ldb / ldc)
-    q.B = b.buf.data_ptr() if pb else b.data_ptr()
-    q.C = out.data_ptr()
-    q.bias = _f32(bias, "bias") if bias is not None else None
-    if bias is not None and (bias.numel() != M or not bias.is_contiguous()):
-        raise RuntimeError("gemm_x3: bias must be M contiguous floats")
-    q.M, q.N, q.K, q.batch = M, N, K, batch
-    q.lda = K if pa else a.stride(-2)
+    q = _gemm_args("gemm_x3", a.buf if pa else a, b.buf if pb else b, out, M, N, K, batch, bias, act, slope, res, k_scale)
+    q.lda = K if pa else a.stride(-2)                    # (strided views: the strides travel as lda / ldb / ldc)
     q.ldb = N if pb else b.stride(-2)
-    q.ldc = out.stride(-2)
     q.stride_a = (a.per if nb_a else 0) if pa else (a.stride(0) if a.dim() == 3 else 0)
     q.stride_b = (b.per if nb_b else 0) if pb else (b.stride(0) if b.dim() == 3 else 0)
-    q.stride_c = out.stride(0) if out.dim() == 3 else 0
-    q.act, q.slope, q.tile_hint = GEMM_ACT[act], slope, tile_hint
+    q.tile_hint = tile_hint
     f16x2 = pa and a.split == "f16x2"
     q.pre = (GEMM_PRE_F16X2 if f16x2 else 1) if pa else 2 if pb else (3 if plain_bf16 else 0)
     if plain_bf16 and (pa or pb):
         raise RuntimeError("gemm_x3: plain_bf16 takes float32 tensor operands")
     if f16x2 and bias_n is not None:
         raise RuntimeError("gemm_x3: an f16x2 image takes no column bias")
-    if res is not None:
-        if res.dtype != torch.float32 or res.shape != out.shape or res.stride() != out.stride():
-            raise RuntimeError("gemm_x3: res must be laid out like out")
-        q.res = res.data_ptr()
-    if k_scale is not None:
-        if pb or k_scale.dtype != torch.float32 or tuple(k_scale.shape) != (batch, K) or not k_scale.is_contiguous():
-            raise RuntimeError("gemm_x3: k_scale must be (batch, K) contiguous floats and b a float32 tensor")
-        q.scale_k = k_scale.data_ptr()
+    if k_scale is not None and pb:
+        raise RuntimeError("gemm_x3: k_scale must be (batch, K) contiguous floats and b a float32 tensor")
     if sigmoid_a:
         if pa or plain_bf16:
             raise RuntimeError("gemm_x3: sigmoid_a takes a float32 tensor A and the split arithmetic")
@@ -606,24 +615,10 @@ def gemm_x3_splitk(a, b, bias=None, act=None, slope=0.01, out=None, res=None, k_
     if ws is None or ws.numel() < need:
         ws = torch.empty(max(need, 1 << 22), device=b.device, dtype=torch.float32)
         _SPLITK_WS[b.device] = ws
-    q = GemmArgs()
-    q.A, q.B, q.C = a.buf.data_ptr(), b.data_ptr(), out.data_ptr()
-    if bias is not None:
-        if bias.numel() != M or not bias.is_contiguous():
-            raise RuntimeError("gemm_x3_splitk: bias must be M contiguous floats")
-        q.bias = _f32(bias, "bias")
-    q.M, q.N, q.K, q.batch = M, N, K, batch
-    q.lda, q.ldb, q.ldc = K, b.stride(-2), out.stride(-2)
-    q.stride_a, q.stride_b, q.stride_c = 0, (b.stride(0) if b.dim() == 3 else 0), out.stride(0)
-    q.act, q.slope, q.tile_hint, q.pre = GEMM_ACT[act], slope, 0, (GEMM_PRE_F16X2 if a.split == "f16x2" else 1)
-    if res is not None:
-        if res.dtype != torch.float32 or res.shape != out.shape or res.stride() != out.stride():
-            raise RuntimeError("gemm_x3_splitk: res must be laid out like out")
-        q.res = res.data_ptr()
-    if k_scale is not None:
-        if k_scale.dtype != torch.float32 or tuple(k_scale.shape) != (batch, K) or not k_scale.is_contiguous():
-            raise RuntimeError("gemm_x3_splitk: k_scale must be (batch, K) contiguous floats")
-        q.scale_k = k_scale.data_ptr()
+    q = _gemm_args("gemm_x3_splitk", a.buf, b, out, M, N, K, batch, bias, act, slope, res, k_scale)
+    q.lda, q.ldb = K, b.stride(-2)
+    q.stride_a, q.stride_b = 0, (b.stride(0) if b.dim() == 3 else 0)
+    q.tile_hint, q.pre = 0, (GEMM_PRE_F16X2 if a.split == "f16x2" else 1)
     if _PROFILING:
         set_tag("%dx%dx%d b%d z%d%s" % (M, N, K, batch, nz, " f16x2" if a.split == "f16x2" else ""))
     _check(load().occd_gemm_f32x3_splitk(ctypes.byref(q), per, nz, rr, ws.data_ptr(), ws.numel(), _stream()),
@@ -734,43 +729,33 @@ GEMM_X3_PACK = os.environ.get("OCCDEPTH_GEMM_X3_PACK", "0") == "1"
 
 # K16p (round 5): the SHORT-K left operands (expand convolutions, the 1/1 and 1/2 tap GEMMs: K <= 848, >= 256 rows) ARE pre-split, for
 # the panel-stationary kernel that keeps a 64-column panel of B over the whole K in LDS (csrc/gemm_x3.hip).  OCCDEPTH_GEMM_X3_PANEL=0
-# -> the barrier-phased K16 on float32 operands as in round 4.
+# -> the barrier-phased K16 on float32 operands as in round 4.  Whether a launch takes K16p is the library's own answer
+# (`gemm_x3_route`: K <= 352, or K <= 848 on a few-pixel launch); matrices below PANEL_MIN_ROWS rows never do (one row tile for
+# each of the 8 waves).
 GEMM_X3_PANEL = os.environ.get("OCCDEPTH_GEMM_X3_PANEL", "1") == "1"
-PANEL_MAX_K, PANEL_MIN_ROWS = 848, 256
+PANEL_MIN_ROWS = 256
 
 
-def _panel_operand(w, role):
-    # (any K: beyond K16p's reach the image feeds K16's pre-split form on the large launches, `_presplit_launch`)
-    return GEMM_X3_PANEL and role == "a" and w.dim() == 2 and w.shape[0] >= PANEL_MIN_ROWS
+# K16 on the pre-split weight image (PRE = 1, fragments requested a full 32-k step ahead since late round 5): the long-K
+# GEMMs that fill the chip with 256 x 128 tiles -- the tap GEMMs of the 1/4, 1/8 and 1/16 levels: 425 -> 368, 397 -> 355, 438 ->
+# 422 us against float32 operands (profiles/r05_gemm_panel.txt); small launches and the Winograd-domain products do not gain.
+PRESPLIT_MIN_K, PRESPLIT_MIN_WORKGROUPS = 512, 320
 
 
-def _panel_launch(pa, b):
-    """The host-side mirror of occd_gemm_f32x3's hint-0 rule for K16p: K <= 352, or (K <= 848) a few-pixel launch."""
-    if pa.K <= 352:
-        return True
-    if pa.K > PANEL_MAX_K:
-        return False
-    n, batch = b.shape[-1], (b.shape[0] if b.dim() == 3 else 1)
-    return -(-n // 64) * batch * -(-(-(-pa.rows // 32)) // 8) <= 512
-
-
-def _presplit_launch(pa, b):
-    """K16 on the pre-split weight image (PRE = 1, fragments requested a full 32-k step ahead since late round 5): the long-K
-    GEMMs that fill the chip with 256 x 128 tiles -- the tap GEMMs of the 1/4, 1/8 and 1/16 levels: 425 -> 368, 397 -> 355, 438 ->
-    422 us against float32 operands (profiles/r05_gemm_panel.txt); small launches and the Winograd-domain products do not gain."""
-    n, batch = b.shape[-1], (b.shape[0] if b.dim() == 3 else 1)
-    return pa.K >= 512 and -(-pa.rows // 256) * -(-n // 128) * batch >= 320
+def presplit_wins(M, N, K, batch):
+    """The host rule of K16's pre-split form: does the weight image beat float32 operands split on the fly on this launch?"""
+    return K >= PRESPLIT_MIN_K and -(-M // 256) * -(-N // 128) * batch >= PRESPLIT_MIN_WORKGROUPS
 
 
 def gemm_split():
-    """'f16x2' / 'bf16x3': which image the model's operand builders make for the GEMMs that read pre-split weights (K16p, K21,
-    K16's pre-split form) -- OCCDEPTH_GEMM_SPLIT, or the last `set_gemm_split` (the switch is declared in fused.py)."""
+    """'f16x2' / 'bf16x3': which image a `GemmWeights(..., split="switch")` packs for the launches that read pre-split weights
+    (K16p, K21, K16's pre-split form) -- OCCDEPTH_GEMM_SPLIT, or the last `set_gemm_split` (the switch is declared in fused.py)."""
     from . import fused
     return fused.GEMM_SPLIT
 
 
 def set_gemm_split(v):
-    """'f16x2' / 'bf16x3'; the builders' caches carry the switch in their keys: the next launch packs the other image."""
+    """'f16x2' / 'bf16x3'; read at every launch (`gemm_route`): the next one packs the other image if it has none yet."""
     from . import fused
     fused.set_gemm_split(v)
 
@@ -805,30 +790,120 @@ def tile_f16x2_wins(M, N, K, batch):
     return TILE_F16X2 and M >= TILE_F16X2_MIN_ROWS and N * batch >= TILE_F16X2_MIN_COLS
 
 
-def gemm_packed_a(w, split):
-    """The role-"a" image of `w` under `split`; a matrix the f16x2 pack refuses (a non-finite weight) keeps bf16x3."""
-    if split == "f16x2":
-        try:
-            return GemmPacked(w, "a", split="f16x2")
-        except ValueError:
-            pass
-    return GemmPacked(w, "a")
+GEMM_KERNELS = {abi.CONSTANTS["OCCD_GEMM_KERNEL_" + n.upper()]: n for n in ("tile", "panel", "ws", "ksplit")}
 
 
-def matmul_operand(w, role, split=None, small=False):
-    """A static operand (weights) in the form hip.matmul wants it: (the float32 tensor, its GemmPacked image or None).
-    split: None = the three-term bf16 image; the model's builders pass `gemm_split()` (role "a" only).
-    small: under split "f16x2" a matrix below PANEL_MIN_ROWS rows gets its f16x2 image as well (the project convolutions and the
-    192-row expand: K16's tile variants on the A image, where `tile_f16x2_wins` says so); a non-finite matrix stays float32."""
-    w = w.detach().float().contiguous()
-    if GEMM_X3 and w.is_cuda and (GEMM_X3_PACK or _panel_operand(w, role)):
-        return w, (gemm_packed_a(w, split) if split is not None and role == "a" else GemmPacked(w, role))
-    if GEMM_X3 and w.is_cuda and small and split == "f16x2" and role == "a" and w.dim() == 2 and GEMM_X3_PANEL:
-        try:
-            return w, GemmPacked(w, "a", split="f16x2")
-        except ValueError:
-            pass
-    return w, None
+def gemm_x3_route(M, N, K, batch, pre=0, plain=True, tile_hint=0):
+    """(kernel, variant) occd_gemm_f32x3 launches on this problem -- 'panel' (variant: the panel width in 32-column units),
+    'tile' / 'ws' / 'ksplit' (variant: 0 .. 4 = 256 x 128, 128 x 128, 128 x 64, 64 x 64, 64 x 256) -- or None where it refuses.
+    The library's own rule (occd_gemm_f32x3_route: the function the launch itself follows); host code, no GPU needed."""
+    kernel, variant = c_int32(), c_int32()
+    if load().occd_gemm_f32x3_route(M, N, K, batch, pre, 1 if plain else 0, tile_hint, ctypes.byref(kernel), ctypes.byref(variant)):
+        return None
+    return GEMM_KERNELS[kernel.value], variant.value
+
+
+class GemmWeights:
+    """A static operand (weights) of the 2-D network's GEMMs: the folded float32 matrix `w` (role "a": (M, K) / (batch, M, K);
+    role "b": (K, N) / (batch, K, N)) and the images of it that launches have asked for, each packed the first time a launch
+    routes to it (`gemm_route`): "bf16x3" / "f16x2" (`GemmPacked`) and "k11" (`pw_pack_weights`, role "a").
+    split: which image the pre-split routes read -- None = the three-term bf16 image whatever the switch says (explicit callers),
+    "switch" = `gemm_split()` at every launch (the model's builders), or a fixed "bf16x3" / "f16x2".
+    small: a matrix below PANEL_MIN_ROWS rows may take K16's tile variants on its f16x2 image (`tile_f16x2_wins`).
+    A matrix the f16x2 pack refuses (a non-finite weight) remembers that: `image("f16x2")` is None from then on."""
+
+    def __init__(self, w, role, split=None, small=False):
+        if role not in ("a", "b") or split not in (None, "switch", "bf16x3", "f16x2"):
+            raise RuntimeError("GemmWeights: role 'a' or 'b'; split None, 'switch', 'bf16x3' or 'f16x2'")
+        self.w = w.detach().float().contiguous()
+        self.role, self.split, self.small = role, split, small
+        self.images, self.kernels = {}, {}
+
+    @property
+    def shape(self):
+        return self.w.shape
+
+    @property
+    def is_cuda(self):
+        return self.w.is_cuda
+
+    def dim(self):
+        return self.w.dim()
+
+    def split_now(self):
+        return gemm_split() if self.split == "switch" else (self.split or "bf16x3")
+
+    def image(self, kind):
+        if kind not in self.images:
+            if kind == "k11":
+                self.images[kind] = pw_pack_weights(self.w)
+            elif kind == "f16x2":
+                try:
+                    self.images[kind] = GemmPacked(self.w, self.role, split="f16x2")
+                except ValueError:
+                    self.images[kind] = None
+            else:
+                self.images[kind] = GemmPacked(self.w, self.role)
+        return self.images[kind]
+
+
+def _library_kernel(holder, *query):
+    """`gemm_x3_route(*query)`, asked once per (M, N, K, batch, pre, plain) and held on the launch's static operand (the library's
+    rule reads the shapes and its own process-wide environment only, none of the switches of this module): asked at every
+    launch it cost the eager frame 0.06 - 0.09 ms of 14.02, three times the parent's run-to-run spread."""
+    memo = getattr(holder, "kernels", None)
+    if memo is None:
+        return gemm_x3_route(*query)
+    if query not in memo:
+        memo[query] = gemm_x3_route(*query)
+    return memo[query]
+
+
+# entry: "lib" (torch.matmul + tensor ops), "k16" (gemm_x3), "k21" (gemm_x3_splitk) or "k11" (conv1x1: the caller's, NCHW);
+# a / b: the form of each operand, "f32" / "bf16x3" / "f16x2"; kernel: for "k16" the library's (kernel, variant), else None
+GemmRoute = collections.namedtuple("GemmRoute", "entry a b kernel")
+
+
+def gemm_route(M, N, K, batch, a=None, b=None, res=False, k_scale=False, supported=True, project=None, cuda=True):
+    """The ONE decision of an eval-path 2-D GEMM launch act(a @ (b * k_scale) + bias) + res: entry point and operand forms, from
+    the shapes, the epilogue, the static operands' properties (a / b: `GemmWeights` or None for a plain tensor; nothing is
+    packed here), `supported` (`gemm_x3_supported` on the float32 operands) and the switches as they stand now.  Nothing is
+    memoised but the library's answer (`_library_kernel`).  project: (k21, k16) for an MBConv project convolution on dense
+    operands (y, gate, skip contiguous) -- what the site's measured limits (efficientnet.PW_PROJECT_*) admit on this map; the
+    route is K21, K16 or the caller's K11."""
+    split = a.split_now() if a is not None else None
+    if project:
+        k21, k16 = project
+        if k21 and GEMM_X3 and cuda and K % 8 == 0 and N >= 4:
+            return GemmRoute("k21", split if split == "bf16x3" or splitk_f16x2_wins(M, N, K, batch) else "bf16x3", "f32", None)
+        if not (k16 and GEMM_X3 and K % 8 == 0):
+            return GemmRoute("k11", "f32", "f32", None)
+    if not GEMM_X3 or not supported:
+        return GemmRoute("lib", "f32", "f32", None)
+    fa = fb = "f32"
+    kernel = None
+    plain = not res and not k_scale
+    if b is not None and b.is_cuda and GEMM_X3_PACK and not k_scale:
+        fb = "bf16x3"
+    if a is not None and a.is_cuda:
+        if GEMM_X3_PACK:
+            fa = split
+            if fb != "f32":
+                fa = fb = "f32"                                          # (K16 reads ONE image: two static operands stay float32)
+        elif GEMM_X3_PANEL and a.dim() == 2 and M >= PANEL_MIN_ROWS:
+            # (a panel-only image serves the plain epilogue; with a residual / a k scale the float32 operand goes to K16)
+            if plain:
+                kernel = _library_kernel(a, M, N, K, batch, GEMM_PRE_F16X2 if split == "f16x2" else 1, True)
+                if (kernel is not None and kernel[0] == "panel") or presplit_wins(M, N, K, batch):
+                    fa = split
+                else:
+                    kernel = None
+        elif GEMM_X3_PANEL and a.dim() == 2 and a.small and split == "f16x2" and tile_f16x2_wins(M, N, K, batch):
+            fa = "f16x2"                                                 # K16's tile variants on the image, residual / k scale included
+    if kernel is None:
+        pre = (GEMM_PRE_F16X2 if fa == "f16x2" else 1) if fa != "f32" else 2 if fb != "f32" else 0
+        kernel = _library_kernel(a if a is not None else b, M, N, K, batch, pre, plain)
+    return GemmRoute("k16", fa, fb, kernel)
 
 
 # Rows of a K16 result that start on 128-byte boundaries are WRITTEN 2.2x faster than rows of an odd pixel count (H * W floats:
@@ -846,26 +921,25 @@ def padded_rows(shape, device):
     return torch.empty(tuple(shape[:-1]) + (pitch,), device=device, dtype=torch.float32)[..., :n]
 
 
-def matmul(a, b, bias=None, act=None, slope=0.01, res=None, k_scale=None, out=None):
-    """act(a @ (b * k_scale[..., None]) + bias[:, None]) + res for the eval path: K16 when it applies, else the library + plain
-    tensor ops.  a / b may be the (tensor, GemmPacked or None) pair of `matmul_operand`; out: an optional (batch, M, N) result
-    tensor (rows may be padded: `padded_rows`)."""
-    ta, pa = a if isinstance(a, tuple) else (a, None)
-    tb, pb = b if isinstance(b, tuple) else (b, None)
-    if GEMM_X3:
-        # (a panel-only image serves the plain epilogue; with a residual / a k scale the float32 operand goes to K16)
-        if pa is not None and pa.rows < PANEL_MIN_ROWS and not GEMM_X3_PACK:
-            # an image `matmul_operand(..., small=True)` built: K16's tile variants on it, residual / k scale included
-            n, batch = tb.shape[-1], (tb.shape[0] if tb.dim() == 3 else 1)
-            a_img = pa.split == "f16x2" and tile_f16x2_wins(pa.rows, n, pa.K, batch)
-        else:
-            a_img = pa is not None and (GEMM_X3_PACK or (res is None and k_scale is None and
-                                                         (_panel_launch(pa, tb) or _presplit_launch(pa, tb))))
-        xa, xb = (pa if a_img else ta), (pb if pb is not None and k_scale is None else tb)
-        if gemm_x3_supported(xa, xb):
-            return gemm_x3(xa, xb, bias=bias, act=act, slope=slope, res=res, k_scale=k_scale, out=out)
-        if gemm_x3_supported(ta, tb):
-            return gemm_x3(ta, tb, bias=bias, act=act, slope=slope, res=res, k_scale=k_scale, out=out)
+def matmul(a, b, bias=None, act=None, slope=0.01, res=None, k_scale=None, out=None, route=None):
+    """act(a @ (b * k_scale[..., None]) + bias[:, None]) + res for the eval path, on the route `gemm_route` names (route: the
+    caller's, if it asked already): K16 / K21 on the operand forms it says, else the library + plain tensor ops.  a / b: tensors,
+    or `GemmWeights` for static operands; out: an optional (batch, M, N) result tensor (rows may be padded: `padded_rows`)."""
+    wa, wb = (a if isinstance(a, GemmWeights) else None), (b if isinstance(b, GemmWeights) else None)
+    ta, tb = (a.w if wa is not None else a), (b.w if wb is not None else b)
+    M, K, N = ta.shape[-2], ta.shape[-1], tb.shape[-1]
+    if route is None:
+        batch = ta.shape[0] if ta.dim() == 3 else tb.shape[0] if tb.dim() == 3 else 1
+        route = gemm_route(M, N, K, batch, wa, wb, res is not None, k_scale is not None, GEMM_X3 and gemm_x3_supported(ta, tb))
+    if route.entry != "lib":
+        xa, xb = ta, (wb.image(route.b) if route.b != "f32" else tb)
+        if route.a != "f32":
+            xa = wa.image(route.a)
+            if xa is None:       # the f16x2 pack refused a non-finite weight: bf16x3 -- float32 on the tile route, which has no other image
+                xa = wa.image("bf16x3") if route.entry == "k21" or GEMM_X3_PACK or M >= PANEL_MIN_ROWS else ta
+        if route.entry == "k21":
+            return gemm_x3_splitk(xa, tb, bias=bias, act=act, slope=slope, res=res, k_scale=k_scale, out=out)
+        return gemm_x3(xa, xb, bias=bias, act=act, slope=slope, res=res, k_scale=k_scale, out=out)
     if k_scale is not None:
         tb = tb * k_scale.unsqueeze(-1)
     y = torch.matmul(ta, tb)
@@ -1306,7 +1380,7 @@ def wino_output_transform(M, shape, scale=None, shift=None, act=None, slope=0.01
 
 class WinoCM:
     """The weight operand of the channel-major Winograd-domain product: U^T (16, Cout, Cin) as the batch-16 f16x2 image of
-    `GemmPacked(..., "a", split="f16x2")`.  `make_u` builds the operand of the present form (the `matmul_operand(U, "b")` pair)
+    `GemmPacked(..., "a", split="f16x2")`.  `make_u` builds the operand of the present form (`GemmWeights(U, "b")`)
     the first time a launch needs it (a geometry `wino_cm_wins` turns down, the strip mode): the 16 * Cin * Cout float32 U does
     not stay alive beside the image otherwise.  Raises ValueError on a non-finite weight (no f16x2 image)."""
 
@@ -1326,7 +1400,7 @@ class WinoCM:
 #   1280 -> 1280 @2x24x77  (T =  936): whole convolution 0.407 -> 0.245 (1.66x); product 0.333 -> 0.194 (147 -> 253 TF/s)
 #    640 ->  640 @2x47x153 (T = 3696): whole convolution 0.421 -> 0.314 (1.34x); product 0.313 -> 0.221 (155 -> 219 TF/s)
 # the input transforms 1.72x / 1.47x, the output transforms 1.43x / 1.25x; spreads <= 7 %.  Both are long-K launches that fill
-# the chip with 256 x 128 tiles -- the regime in which K16's pre-split form leads on the tap GEMMs (`_presplit_launch`, the same
+# the chip with 256 x 128 tiles -- the regime in which K16's pre-split form leads on the tap GEMMs (`presplit_wins`, the same
 # two limits).  Anything smaller is unmeasured and stays on the present form.  OCCDEPTH_WINO_CM=0 -> the present form for A/B.
 WINO_CM = os.environ.get("OCCDEPTH_WINO_CM", "1") == "1"
 WINO_CM_MIN_CIN, WINO_CM_MIN_WORKGROUPS = 512, 320
@@ -1377,7 +1451,7 @@ def wino_output_transform_cm(Mt, shape, scale=None, shift=None, act=None, slope=
 
 def conv2d_3x3_winograd(x, U, scale=None, shift=None, act=None, slope=0.01, res=None, res_first=False, strip_rows=None,
                         cm=None):
-    """act(scale * conv3x3(x, g, pad 1) + shift) (+res) with U = winograd_weights(g) (or the `matmul_operand(U, "b")` pair):
+    """act(scale * conv3x3(x, g, pad 1) + shift) (+res) with U = winograd_weights(g) (or `GemmWeights(U, "b")`):
     HIP transforms around 16 batched GEMMs (K16; the library with OCCDEPTH_GEMM_X3=0).  `strip_rows` tile rows per pass keep
     V / M cache-sized on big images.
     U a `WinoCM`: the channel-major form -- channel-major transforms around ONE K16 launch on the f16x2 image of U^T (three fp16
@@ -1395,7 +1469,7 @@ def conv2d_3x3_winograd(x, U, scale=None, shift=None, act=None, slope=0.01, res=
             gemm_x3(U.image, Vt, out=Mt)
             return wino_output_transform_cm(Mt, (B, U.cout, H, W), scale, shift, act, slope, res, res_first)
         U = U.u()
-    cout = (U[0] if isinstance(U, tuple) else U).shape[2]
+    cout = U.shape[2]
     if strip_rows is None or strip_rows >= th:
         V = wino_input_transform(x)
         return wino_output_transform(matmul(V, U), (B, cout, H, W), scale, shift, act, slope, res, res_first)

@@ -72,9 +72,9 @@ def pw_operands(owner, conv, bn=None):
 
 
 def gemm_operands(owner, conv, bn):
-    """(W * BatchNorm scale as a (Cout, Cin) matrix, shift) of a 1x1 convolution + BatchNorm for K16 (hip.matmul), cached on
-    `owner` until a source tensor changes."""
-    key = (_stamp(conv, bn), hip.gemm_split())
+    """(W * BatchNorm scale as the `hip.GemmWeights` of a (Cout, Cin) left operand, shift) of a 1x1 convolution + BatchNorm for
+    hip.matmul, cached on `owner` until a source tensor changes.  Images are packed by the launches that route to them."""
+    key = _stamp(conv, bn)
     cache = owner.__dict__.setdefault("_gemm_cache", {})
     hit = cache.get(id(conv))
     if hit is None or hit[0] != key:
@@ -83,7 +83,7 @@ def gemm_operands(owner, conv, bn):
         if conv.bias is not None:
             shift = conv.bias.detach().float() * scale + shift
         # (small: below 256 rows too -- the project convolutions and the 192-row expand on K16's tile variants, hip.tile_f16x2_wins)
-        hit = (key, hip.matmul_operand(w, "a", split=key[1], small=True), shift.contiguous())
+        hit = (key, hip.GemmWeights(w, "a", split="switch", small=True), shift.contiguous())
         cache[id(conv)] = hit
     return hit[1], hit[2]
 
@@ -95,7 +95,7 @@ def expand_gemm(owner, conv, bn, x, act, pad_out=False):
     if hip.GEMM_X3 and C % 8 == 0 and H * W >= 4 and x.is_contiguous():
         w, shift = gemm_operands(owner, conv, bn)
         # (the expanded planes on a 128-byte pitch: written 2x faster; the depthwise kernel that consumes them takes the stride)
-        out = hip.padded_rows((B, w[0].shape[0], H * W), x.device) if pad_out else None
+        out = hip.padded_rows((B, w.shape[0], H * W), x.device) if pad_out else None
         return hip.matmul(w, x.view(B, C, H * W), bias=shift, act=act, out=out).view(B, -1, H, W)
     return hip.affine_act(F.conv2d(x, conv.weight), *bn_affine_cached(bn), act)
 
@@ -120,44 +120,21 @@ PW_PROJECT_SPLITK_MIN_K = int(os.environ.get("OCCDEPTH_PW_PROJECT_SPLITK_MIN_K",
 PW_PROJECT_SPLITK_MAX_PIXELS = int(os.environ.get("OCCDEPTH_PW_PROJECT_SPLITK_MAX_PIXELS", "8000"))
 
 
-def splitk_operands(owner, conv, bn, pixels=None, batch=1):
-    """(GemmPacked image of W * BatchNorm scale, shift) for K21, cached on `owner` until a source tensor, the switch or the
-    verdict of the host rule changes.  The image is f16x2 when hip.gemm_split() says so and hip.splitk_f16x2_wins does for a
-    launch on batch x pixels columns (pixels None: no launch geometry, the switch alone); else bf16x3."""
-    split = hip.gemm_split()
-    if split == "f16x2" and pixels is not None and not hip.splitk_f16x2_wins(conv.out_channels, pixels, conv.in_channels, batch):
-        split = "bf16x3"
-    key = (_stamp(conv, bn), split)
-    cache = owner.__dict__.setdefault("_splitk_cache", {})
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        scale, shift = bn_affine_cached(bn)
-        w = (conv.weight.detach().float().flatten(1) * scale.view(-1, 1)).contiguous()
-        if conv.bias is not None:
-            shift = conv.bias.detach().float() * scale + shift
-        hit = (key, hip.gemm_packed_a(w, key[1]), shift.contiguous())
-        cache[id(conv)] = hit
-    return hit[1], hit[2]
-
-
 def project_conv(owner, conv, bn, y, gate, res):
-    """bn(conv1x1(y * gate)) (+ res): K21 on the few-pixel long-K stages (two launches), else one launch of K16 (hip.matmul)
-    where it applies, else K11 / K11s."""
+    """bn(conv1x1(y * gate)) (+ res) on the route hip.gemm_route names: K21 on the few-pixel long-K stages (two launches), one
+    launch of K16 where it applies (both through hip.matmul), else K11 / K11s (hip.conv1x1, on the NCHW tensors as they lie)."""
     B, C, H, W = y.shape
     cout = conv.out_channels
-    if (PW_PROJECT_SPLITK and hip.GEMM_X3 and y.is_cuda and C % 8 == 0 and C >= PW_PROJECT_SPLITK_MIN_K and H * W >= 4
-            and B * H * W <= PW_PROJECT_SPLITK_MAX_PIXELS and y.is_contiguous() and gate.is_contiguous()
-            and tuple(gate.shape) == (B, C) and (res is None or res.is_contiguous())):
-        pa, shift = splitk_operands(owner, conv, bn, H * W, B)
-        out = hip.gemm_x3_splitk(pa, y.view(B, C, H * W), bias=shift, k_scale=gate,
-                                 res=res.view(B, cout, H * W) if res is not None else None)
-        return out.view(B, cout, H, W)
-    if (PW_PROJECT_K16 and hip.GEMM_X3 and C % 8 == 0 and B * H * W >= PW_PROJECT_K16_MIN_PIXELS and y.is_contiguous()
-            and cout >= PW_PROJECT_K16_MIN_COUT and gate.is_contiguous() and tuple(gate.shape) == (B, C) and (res is None or res.is_contiguous())):
+    if y.is_contiguous() and gate.is_contiguous() and tuple(gate.shape) == (B, C) and (res is None or res.is_contiguous()):
         w, shift = gemm_operands(owner, conv, bn)
-        out = hip.matmul(w, y.view(B, C, H * W), bias=shift, k_scale=gate,
-                         res=res.view(B, cout, H * W) if res is not None else None)
-        return out.view(B, cout, H, W)
+        yb = y.view(B, C, H * W)
+        k21 = PW_PROJECT_SPLITK and C >= PW_PROJECT_SPLITK_MIN_K and B * H * W <= PW_PROJECT_SPLITK_MAX_PIXELS
+        k16 = PW_PROJECT_K16 and B * H * W >= PW_PROJECT_K16_MIN_PIXELS and cout >= PW_PROJECT_K16_MIN_COUT
+        route = hip.gemm_route(cout, H * W, C, B, a=w, res=res is not None, k_scale=True, project=(k21, k16), cuda=y.is_cuda,
+                               supported=hip.GEMM_X3 and hip.gemm_x3_supported(w.w, yb))
+        if route.entry != "k11":
+            out = hip.matmul(w, yb, bias=shift, k_scale=gate, res=res.view(B, cout, H * W) if res is not None else None, route=route)
+            return out.view(B, cout, H, W)
     wpk, shift = pw_operands(owner, conv, bn)
     return hip.conv1x1(y, wpk, cout, shift, None, gate=gate, res=res)
 

@@ -62,7 +62,7 @@ class UpSampleBN(nn.Module):
                 shift = shift + scale * conv.bias.detach().float()
 
             def make_u():
-                return hip.matmul_operand(hip.winograd_weights(conv.weight), "b")
+                return hip.GemmWeights(hip.winograd_weights(conv.weight), "b")
 
             U = None
             if key[1] == "f16x2" and hip.GEMM_X3 and conv.weight.is_cuda:
@@ -118,7 +118,7 @@ class UpSampleBN(nn.Module):
     UPCONV_FUSE_SKIP = os.environ.get("OCCDEPTH_UPCONV_FUSE_SKIP", "1") == "1"
 
     def _upconv_operands(self, conv, bn, cup):
-        key = (_stamp(conv, bn), cup, _fused.WINO_SPLIT, hip.gemm_split())
+        key = (_stamp(conv, bn), cup, _fused.WINO_SPLIT)
         hit = self.__dict__.get("_upconv_cache")
         if hit is None or hit[0] != key:
             scale, shift = bn_affine_cached(bn)
@@ -129,7 +129,8 @@ class UpSampleBN(nn.Module):
             # rows t * Cout + co (t = ky * 3 + kx) of the tap GEMM, BatchNorm scale folded in
             w9 = (w[:, :cup] * scale.view(-1, 1, 1, 1)).permute(2, 3, 0, 1).reshape(9 * cout, cup).contiguous()
             wskip = (w[:, cup:] * scale.view(-1, 1, 1, 1)).contiguous()
-            hit = (key, hip.pw_pack_weights(w9), hip.matmul_operand(w9, "a", split=key[3]),
+            # (the tap matrix's images -- K16's, or the K11 pack under OCCDEPTH_UPCONV_LIB_BELOW -- are packed by the launches)
+            hit = (key, hip.GemmWeights(w9, "a", split="switch"),
                    _fused.wino_pack(w[:, cup:].contiguous(), scale), shift.contiguous(), wskip)
             self.__dict__["_upconv_cache"] = hit
         return hit[1:]
@@ -141,7 +142,7 @@ class UpSampleBN(nn.Module):
         return hip.padded_rows(shape, device) if hip.GEMM_X3 else None
 
     def _first_conv_upconv(self, x, skip, conv, bn, act):
-        wpk9, w9, upk_skip, shift, wskip = self._upconv_operands(conv, bn, x.shape[1])
+        w9, upk_skip, shift, wskip = self._upconv_operands(conv, bn, x.shape[1])
         cout = conv.out_channels
         B, cup, h, w = x.shape
         if B > 1 and B * h * w <= self.UPCONV_FOLD_BELOW:
@@ -156,7 +157,7 @@ class UpSampleBN(nn.Module):
                 # K16 (csrc/gemm_x3.hip) into tap planes on a 128-byte pitch (written 2x faster; K12 takes the strides)
                 z = hip.matmul(w9, xc.view(B, cup, h * w), out=self._tap_planes((B, 9 * cout, h * w), x.device)).view(B, 9 * cout, h, w)
             else:
-                z = hip.conv1x1(x, wpk9, 9 * cout)
+                z = hip.conv1x1(x, w9.image("k11"), 9 * cout)
         rw = (w - 1) / max(skip.shape[3] - 1, 1)
         if self.UPCONV_FUSE_SKIP and skip.shape[1] <= 4 and rw * 258.0 + 3.0 <= 191.0:
             # few skip channels (the 1/1 level: the raw image): their 3x3 convolution, the shift and the LeakyReLU ride in
@@ -244,13 +245,13 @@ class DecoderBN(nn.Module):
         """conv2(conv_head(f)) as ONE convolution: both are 1x1 and nothing sits between them (the reference taps
         features[11] = conv_head's raw output, unet2d.py:146,183), so W = W_conv2 . W_head (formed once in float64) and the
         2560 -> 2560 GEMM on the 1/32 map disappears: 640 -> 2560 with conv2's bias and conv2's padding=1 frame."""
-        key = (_stamp(self.conv2, conv_head), hip.gemm_split())
+        key = _stamp(self.conv2, conv_head)
         hit = self.__dict__.get("_merged_head")
         if hit is None or hit[0] != key:
             w2 = self.conv2.weight.detach().double().flatten(1)
             wh = conv_head.weight.detach().double().flatten(1)
             w = (w2 @ wh).float().reshape(w2.shape[0], wh.shape[1], 1, 1).contiguous()
-            hit = (key, w, hip.matmul_operand(w.view(w.shape[0], -1), "a", split=key[1]) if w.is_cuda else None)
+            hit = (key, w, hip.GemmWeights(w.view(w.shape[0], -1), "a", split="switch") if w.is_cuda else None)
             self.__dict__["_merged_head"] = hit
         pad = self.conv2.padding
         if (hip.GEMM_X3 and _fused.on_gpu(f) and self.conv2.stride == (1, 1) and self.conv2.bias is not None

@@ -262,12 +262,14 @@ def test_non_finite_weight_is_refused_and_builder_keeps_bf16x3(hip):
         wb[200, 3] = bad
         with pytest.raises(ValueError):
             hip.GemmPacked(wb, "a", split="f16x2")
-        pa = hip.matmul_operand(wb, "a", split="f16x2")[1]
-        assert pa is not None and pa.split == "bf16x3" and hip.gemm_packed_a(wb, "f16x2").split == "bf16x3"
+        gw = hip.GemmWeights(wb, "a", split="f16x2")
+        assert hip.gemm_route(256, 100, 64, 2, a=gw).a == "f16x2" and gw.image("f16x2") is None      # refused, and remembered
         with hip.profile() as prof:
-            hip.gemm_x3(pa, torch.randn(2, 64, 100, device=DEV))
-        assert "f16x2" not in list(prof.rows)[0], prof.rows.keys()
-    assert hip.matmul_operand(w, "a", split="f16x2")[1].split == "f16x2"
+            hip.matmul(gw, torch.randn(2, 64, 100, device=DEV))
+        launched = [k for k in prof.rows if "pack" not in k]
+        assert len(launched) == 1 and "f16x2" not in launched[0] and launched[0].startswith("gemm_f32x3_panel"), prof.rows.keys()
+        assert set(gw.images) == {"f16x2", "bf16x3"} and gw.images["bf16x3"].split == "bf16x3"
+    assert hip.GemmWeights(w, "a", split="f16x2").image("f16x2").split == "f16x2"
 
 
 @pytest.mark.gpu

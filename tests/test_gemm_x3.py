@@ -146,13 +146,14 @@ def test_gemm_x3_panel_limits(hip):
     with pytest.raises(RuntimeError):
         hip.gemm_x3(hip.GemmPacked(a2, "a"), b2, tile_hint=8, res=torch.zeros(2, 256, 100, device=DEV))
     # hip.matmul hands the image to K16 only where the panel kernel applies
-    w = hip.matmul_operand(a2, "a")
-    assert w[1] is not None and hip.matmul_operand(a2[:64].contiguous(), "a")[1] is None        # (fewer than 256 rows: never)
-    wbig = hip.matmul_operand(a, "a")                        # K = 856: beyond K16p; the image exists for K16's pre-split form ...
-    assert wbig[1] is not None
+    w = hip.GemmWeights(a2, "a")
+    assert hip.gemm_route(256, 100, 64, 2, a=w).a == "bf16x3" and w.image("bf16x3") is not None     # (packed here, not under the profile)
+    assert hip.gemm_route(64, 100, 64, 2, a=hip.GemmWeights(a2[:64].contiguous(), "a")).a == "f32"     # (fewer than 256 rows: never)
+    wbig = hip.GemmWeights(a, "a")                           # K = 856: beyond K16p; the image serves K16's pre-split form ...
+    assert hip.gemm_route(a.shape[0], 128 * 160, 856, 2, a=wbig).a == "bf16x3"
     with hip.profile() as prof:
         yb = hip.matmul(wbig, b)                             # ... which only the chip-filling launches take: this one stays float32
-    assert [k.split(":")[0] for k in prof.rows] == ["gemm_f32x3"]
+    assert [k.split(":")[0] for k in prof.rows] == ["gemm_f32x3"] and not wbig.images
     assert float((yb - torch.matmul(a, b)).abs().max()) < 1e-3
     res = torch.randn(2, 256, 100, device=DEV)
     with hip.profile() as prof:
@@ -171,8 +172,10 @@ def test_matmul_takes_the_presplit_form_on_large_long_k_launches(hip):
     M, N, K, batch = 5760, 1848, 1280, 2
     a = (torch.randn(M, K, generator=g) / K ** 0.5).to(DEV)
     b = torch.randn(batch, K, N, generator=g).to(DEV)
-    w = hip.matmul_operand(a, "a")
-    assert w[1] is not None and hip._presplit_launch(w[1], b) and not hip._panel_launch(w[1], b)
+    w = hip.GemmWeights(a, "a")
+    route = hip.gemm_route(M, N, K, batch, a=w)
+    assert route.a == "bf16x3" and hip.presplit_wins(M, N, K, batch) and route.kernel == ("tile", 0)    # (not the panel kernel)
+    assert w.image("bf16x3") is not None                     # (packed here, not under the profile)
     with hip.profile() as prof:
         y = hip.matmul(w, b)
     assert [k.split(":")[0] for k in prof.rows] == ["gemm_f32x3_preA"], prof.rows.keys()

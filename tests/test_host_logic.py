@@ -174,8 +174,8 @@ def test_synthetic_inputs_match_survey_statistics():
 
 def test_padded_rows_and_the_panel_launch_rule(monkeypatch):
     """hip.padded_rows: results whose rows start on 128-byte boundaries (a view of a buffer with the last dimension rounded up
-    to 32 floats; dense under OCCDEPTH_PAD_ROWS=0), and the host-side mirror of occd_gemm_f32x3's rule for the panel-stationary
-    kernel: K <= 352 always, K <= 848 only on the few-pixel launches."""
+    to 32 floats; dense under OCCDEPTH_PAD_ROWS=0), and hip.gemm_route on the library's rule for the panel-stationary kernel
+    (occd_gemm_f32x3_route: K <= 352 always, K <= 848 only on the few-pixel launches)."""
     import torch
     from occdepth_amd import hip
     monkeypatch.setattr(hip, "PAD_ROWS", True)
@@ -187,17 +187,20 @@ def test_padded_rows_and_the_panel_launch_rule(monkeypatch):
     monkeypatch.setattr(hip, "PAD_ROWS", False)
     assert hip.padded_rows((2, 18, 35), "cpu").is_contiguous()
 
-    class Img:                                                              # what _panel_launch reads of a GemmPacked
-        def __init__(self, rows, K):
-            self.rows, self.K = rows, K
-    b = lambda batch, K, N: torch.empty(batch, K, N, device="meta")
-    assert hip._panel_launch(Img(720, 160), b(2, 160, 112850))             # tap GEMM 1/1
-    assert hip._panel_launch(Img(1440, 320), b(2, 320, 28365))             # tap GEMM 1/2
-    assert hip._panel_launch(Img(2304, 384), b(2, 384, 468))               # expand convolution of the 1/32 stage
-    assert hip._panel_launch(Img(3840, 640), b(2, 640, 468))
-    assert not hip._panel_launch(Img(2880, 640), b(2, 640, 7191))          # tap GEMM 1/4: K16 is faster ...
-    assert hip._presplit_launch(Img(2880, 640), b(2, 640, 7191))           # ... on its pre-split form (chip-filling, K >= 512)
-    assert hip._presplit_launch(Img(11520, 2560), b(2, 2560, 574)) and not hip._panel_launch(Img(11520, 2560), b(2, 2560, 574))
-    assert not hip._presplit_launch(Img(2304, 384), b(2, 384, 468)) and not hip._presplit_launch(Img(2560, 640), b(2, 640, 574))
+    class W:                                                                # what gemm_route reads of a GemmWeights on the GPU
+        is_cuda, small, dim, split_now = True, False, staticmethod(lambda: 2), staticmethod(lambda: "bf16x3")
+    route = lambda M, N, K, batch=2: hip.gemm_route(M, N, K, batch, a=W())
+    panel = lambda *g: route(*g).kernel[0] == "panel"
+    presplit = lambda *g: route(*g).a == "bf16x3" and not panel(*g)
+    assert panel(720, 112850, 160)                                          # tap GEMM 1/1
+    assert panel(1440, 28365, 320)                                          # tap GEMM 1/2
+    assert panel(2304, 468, 384)                                            # expand convolution of the 1/32 stage
+    assert panel(3840, 468, 640)
+    assert not panel(2880, 7191, 640)                                       # tap GEMM 1/4: K16 is faster ...
+    assert presplit(2880, 7191, 640)                                        # ... on its pre-split form (chip-filling, K >= 512)
+    assert presplit(11520, 574, 2560) and not panel(11520, 574, 2560)
+    assert not presplit(2304, 468, 384) and not presplit(2560, 574, 640)
     w = torch.empty(2880, 640)
-    assert hip.matmul_operand(w, "a")[1] is None                            # (CPU tensors are never pre-split)
+    cpu = hip.GemmWeights(w, "a")                                           # (CPU tensors are never pre-split)
+    assert hip.gemm_route(2880, 7191, 640, 2, a=cpu, supported=hip.gemm_x3_supported(w, torch.empty(2, 640, 7191, device="meta"))) \
+        == hip.GemmRoute("lib", "f32", "f32", None) and not cpu.images

@@ -42,7 +42,8 @@ def main():
                 gate, res = torch.rand(batch, K, device=dev), torch.randn(batch, M, N, device=dev)
                 run = lambda pa: hip.gemm_x3_splitk(pa, b, bias=bias, k_scale=gate, res=res)
             else:
-                assert (hip._panel_launch if family == "panel" else hip._presplit_launch)(p3, b)
+                route = hip.gemm_route(M, N, K, batch, a=hip.GemmWeights(w, "a"))
+                assert route.a == "bf16x3" and (route.kernel[0] == "panel") == (family == "panel")
                 run = lambda pa: hip.gemm_x3(pa, b, bias=bias, act="swish", out=out)
             iters = 20 if M * N * K > 1 << 32 else 100
             r3 = rounds(lambda: run(p3), iters)

@@ -83,7 +83,11 @@ extern "C" {
  *     occd_map_sample (K32, the map read back into a frame's voxels, csrc/semantic_map.hip): one new struct and one new
  *     function only; likewise OccdMapMergeArgs and occd_map_merge (K33, the counter-wise saturating sum of two sets of
  *     bricks, csrc/semantic_map.hip): one new struct and one new function only; likewise OCCD_GEMM_KERNEL_* and
- *     occd_gemm_f32x3_route (the hint-0 kernel choice of occd_gemm_f32x3 as a host query): one new function only */
+ *     occd_gemm_f32x3_route (the hint-0 kernel choice of occd_gemm_f32x3 as a host query): one new function only; likewise
+ *     OccdVisibilityArgs and occd_frame_visibility (K34, the voxels of a frame the camera's pixel rays reach,
+ *     csrc/visibility.hip) and OccdMapWeightedArgs, occd_map_integrate_weighted, OccdMapSampleWeightedArgs and
+ *     occd_map_sample_weighted (votes of a weight per voxel, csrc/semantic_map.hip): three new structs and three new
+ *     functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1540,6 +1544,84 @@ typedef struct OccdMapRenderArgs {
     uint8_t bg_colour[4];
 } OccdMapRenderArgs;
 int occd_map_render(const OccdMapRenderArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K34: which voxels of a frame the camera could see (occd_frame_visibility, csrc/visibility.hip).  Additive
+ * (OCCD_ABI_VERSION note).  One ray per pixel of ONE view through ONE frame's label volume, one thread per pixel, a wave
+ * per 8 x 8 pixel tile.  `view` is one OccdRenderView in grid-voxel units, read exactly as occd_render_voxels reads it,
+ * and the walk is that of occd_render_voxels in class mode (same ray set-up, slab entry, clamped first voxel, boundary
+ * times ((float)(i + (dir > 0)) - origin) * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32
+ * without fma).  Every voxel n the walk visits, up to and including the first occupied one (0 < label < 255), gets
+ * visible[n] = 1; a ray that leaves the grid has marked all it crossed; a ray that misses the box marks nothing.  Every
+ * other byte of visible is 0: the entry point zeroes the volume itself with a fill kernel on the same stream (no memset
+ * node).  All writers of a byte write the same value (plain byte stores, a byte that already reads 1 is not written
+ * again), so the result depends on the inputs alone.  No read-modify-write atomics, no allocation, no host sync
+ * (capture-safe).  Visibility is pixel-centric on purpose: a voxel is visible when some pixel's ray reaches it, not when
+ * the ray to its centre is free (that rule hides nearly all distant ground behind the ground in front of it).
+ * hit, when not NULL: hit[v W + u] = the first occupied voxel (x Y + y) Z + z of pixel (u, v), or -1 -- what
+ * occd_render_voxels writes to its hit for the same view.
+ * OCCD_EINVAL before any launch: a NULL argument, NULL labels / view / visible, non-positive H, W, X, Y or Z,
+ * X Y Z > 2^28, label_bytes not 1 or 2.
+ * ------------------------------------------------------------------------ */
+typedef struct OccdVisibilityArgs {
+    const void* labels;            /* (X Y Z) labels of the frame, label_bytes each                           */
+    const OccdRenderView* view;    /* one view, device, grid-voxel units                                      */
+    uint8_t* visible;              /* (X Y Z) out: 1 = a pixel ray reached the voxel, else 0                  */
+    int32_t* hit;                  /* (H, W) out: first occupied voxel or -1, or NULL                         */
+    int32_t H, W;
+    int32_t X, Y, Z;
+    int32_t label_bytes;
+} OccdVisibilityArgs;
+int occd_frame_visibility(const OccdVisibilityArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * Weighted votes for the sequence map (csrc/semantic_map.hip).  Additive (OCCD_ABI_VERSION note): the unweighted
+ * entry points and their structs are unchanged, and both kinds of vote may go into one pool -- saturating sums of
+ * non-negative weights commute, so extraction, merge, save / load and render apply as they are.
+ *
+ * occd_map_integrate_weighted is occd_map_integrate with a REQUIRED (X Y Z) uint8 `weight` volume where that one has its
+ * optional mask: the frame voxel n votes with w = weight[n], the counter becomes min(v + w, 65535), and w == 0 casts no
+ * vote.  Every other rule (geometry, label < C, slots, table_host) is occd_map_integrate's.  With weights in {0, 1} the
+ * pool bytes equal those of occd_map_integrate with that volume as the mask.
+ *
+ * occd_map_sample_weighted is occd_map_sample with `own_weight` where that one has own_mask.  OCCD_MAP_SAMPLE_EXCLUDE_SELF
+ * retracts w = own_weight[n'] from the counter own[n'] iff n' is inside (X, Y, Z), own[n'] < C, w > 0, and the counter v
+ * has v != 65535 and v >= w (a saturated counter has forgotten what it dropped; a counter below w cannot hold that
+ * vote); for w = 1 this is occd_map_sample's rule.  own_weight is read only under that flag and is then required.
+ * n_obs and min_obs are sums of counters, so with weighted votes they are in VOTE UNITS (a frame that voted with
+ * weight 8 adds 8), not in frames.
+ * OCCD_EINVAL before any launch: what the unweighted entry refuses, a NULL weight (integrate), EXCLUDE_SELF without
+ * own_weight (sample).
+ * ------------------------------------------------------------------------ */
+typedef struct OccdMapWeightedArgs {
+    uint16_t* votes;               /* (capacity, 4096, pitch) vote counters                                          */
+    const int32_t* table;          /* (n_bricks, 16) device                                                          */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    const void* labels;            /* (X Y Z) labels of the frame, label_bytes each                                  */
+    const uint8_t* weight;         /* (X Y Z) bytes, the weight of each voxel's vote, 0 = does not vote              */
+    int32_t n_bricks, capacity;
+    int32_t X, Y, Z;
+    int32_t C, pitch, label_bytes;
+} OccdMapWeightedArgs;
+int occd_map_integrate_weighted(const OccdMapWeightedArgs* a, void* stream);
+
+typedef struct OccdMapSampleWeightedArgs {
+    const uint16_t* votes;         /* (capacity, 4096, pitch) vote counters, read only                               */
+    const int32_t* table;          /* (n_bricks, 16) device                                                          */
+    const int32_t* table_host;     /* the same rows in host memory, or NULL                                          */
+    const int32_t* cells;          /* (gx, gy, gz) device: row of the brick, negative = absent                       */
+    const void* own;               /* (X Y Z) labels of the frame itself, label_bytes each, or NULL                  */
+    const uint8_t* own_weight;     /* (X Y Z) bytes, the weights the frame voted with; NULL without EXCLUDE_SELF     */
+    uint8_t* labels;               /* (X Y Z) out                                                                    */
+    uint16_t* n_obs;               /* (X Y Z) out, vote units                                                        */
+    int32_t n_bricks, capacity;
+    int32_t X, Y, Z;
+    int32_t gx, gy, gz;
+    int32_t C, pitch, label_bytes;
+    int32_t min_obs, flags;        /* min_obs in vote units                                                          */
+    int32_t Bq[9], dq[3];          /* row-major rint(R 2^16), rint(d 2^16)                                           */
+} OccdMapSampleWeightedArgs;
+int occd_map_sample_weighted(const OccdMapSampleWeightedArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

@@ -20,6 +20,12 @@
 // Extraction reads every row in 8-byte pieces.  The compacted list is count per brick -> exclusive scan (the caller's)
 // -> ordered write: inside a workgroup the 4096 voxels go in 16 passes of 256, a wave orders its lanes with a ballot and
 // mbcnt, the waves hand their totals over through LDS (two buffers, one barrier per pass).
+//
+// Weighted votes (occd_map_integrate_weighted, occd_map_sample_weighted) are the same two kernels instantiated with
+// WEIGHTED = true: a byte of weight per frame voxel where the unweighted form has a yes / no mask.
+#include <stddef.h>
+#include <string.h>
+
 #include "common.h"
 #include "device.h"
 
@@ -38,7 +44,9 @@ __device__ __forceinline__ uint32_t load_label(const void* base, uint32_t n) {
     return static_cast<const uint16_t*>(base)[n];
 }
 
-template <int LB>
+// WEIGHTED (occd_map_integrate_weighted): a.mask is the required weight volume, the vote counts weight[n] and the counter
+// saturates at 65535; otherwise a.mask is the optional yes / no mask and a vote counts one
+template <int LB, bool WEIGHTED>
 __global__ void __launch_bounds__(kThreads) map_integrate_kernel(const OccdMapFrameArgs a) {
     const int32_t* row = a.table + (size_t)blockIdx.x * 16;
     const int32_t slot = row[0];
@@ -59,20 +67,29 @@ __global__ void __launch_bounds__(kThreads) map_integrate_kernel(const OccdMapFr
         for (int r = 0; r < 3; ++r) gq[r] += step[r];
         if (ix < 0 || ix >= a.X || iy < 0 || iy >= a.Y || iz < 0 || iz >= a.Z) continue;
         const uint32_t n = ((uint32_t)ix * (uint32_t)a.Y + (uint32_t)iy) * (uint32_t)a.Z + (uint32_t)iz;   // < X Y Z <= 2^28
-        if (a.mask != nullptr && a.mask[n] == 0) continue;
+        uint32_t w = 1u;
+        if (WEIGHTED) {
+            w = a.mask[n];
+            if (w == 0u) continue;
+        } else if (a.mask != nullptr && a.mask[n] == 0) continue;
         const uint32_t label = load_label<LB>(a.labels, n);
         if (label >= (uint32_t)a.C) continue;           // C <= pitch: the counter lies inside the row
         uint16_t* c = rows + (size_t)i * kThreads * (size_t)a.pitch + label;
         const uint16_t v = *c;
-        if (v != 0xffffu) *c = (uint16_t)(v + 1);
+        if (WEIGHTED) {
+            const uint32_t sum = (uint32_t)v + w;
+            if (v != 0xffffu) *c = (uint16_t)(sum < 0xffffu ? sum : 0xffffu);
+        } else if (v != 0xffffu) *c = (uint16_t)(v + 1);
     }
 }
 
 // argmax (the lowest class on a tie) and sum of the C counters of one row, read in 8-byte pieces.  The counter of class
 // `dec` counts one less unless it is 0 or 65535 (sample's exclude_self; ~0u: none); best = the maximum, at = the counter
-// of class `ask` (0 when there is no such class)
+// of class `ask` (0 when there is no such class).  WEIGHTED (occd_map_sample_weighted): the counter of class `dec` counts
+// `amount` (> 0) less unless it is 65535 or below `amount` -- for amount = 1 the same rule
+template <bool WEIGHTED = false>
 __device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t dec, uint32_t ask, uint32_t& label, uint32_t& nobs,
-                                       uint32_t& best, uint32_t& at) {
+                                       uint32_t& best, uint32_t& at, uint32_t amount = 1u) {
     const u32x2* q = reinterpret_cast<const u32x2*>(row);
     best = 0;
     label = 0;
@@ -86,7 +103,8 @@ __device__ __forceinline__ void decide(const uint16_t* row, int C, uint32_t dec,
         for (int e = 0; e < 4; ++e) {
             const int c = 4 * k + e;
             if (c < C) {
-                const uint32_t n = v[e] - (uint32_t)((uint32_t)c == dec && v[e] != 0u && v[e] != 0xffffu);
+                const uint32_t n = WEIGHTED ? v[e] - ((uint32_t)c == dec && v[e] != 0xffffu && v[e] >= amount ? amount : 0u)
+                                            : v[e] - (uint32_t)((uint32_t)c == dec && v[e] != 0u && v[e] != 0xffffu);
                 nobs += n;
                 if ((uint32_t)c == ask) at = n;
                 if (n > best) { best = n; label = (uint32_t)c; }
@@ -165,7 +183,9 @@ __global__ void __launch_bounds__(kThreads) map_scan_kernel(const OccdMapExtract
 // 20) and a wave touches as few 128-byte lines per load as the frame's heading allows; labels and n_obs are written
 // coalesced.  (A thread per (x, y) column walking z puts the lanes of a wave 16 rows or more apart, the argument of
 // integrate's header with the roles swapped.)
-template <int LB>
+// WEIGHTED (occd_map_sample_weighted): a.own_mask is the weight volume the frame voted with, and exclude_self retracts that
+// weight
+template <int LB, bool WEIGHTED>
 __global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampleArgs a) {
     const uint32_t S = (uint32_t)a.X * (uint32_t)a.Y * (uint32_t)a.Z;          // <= 2^28
     const uint32_t n = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
@@ -190,7 +210,7 @@ __global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampl
             const int32_t* row = a.table + (size_t)r * 16;
             const int32_t slot = row[0];
             if (slot >= 0 && slot < a.capacity) {
-                uint32_t dec = ~0u;
+                uint32_t dec = ~0u, amount = 1u;
                 if (a.flags & OCCD_MAP_SAMPLE_EXCLUDE_SELF) {              // the frame voxel integrate maps this world voxel to
                     int32_t g[3];
 #pragma unroll
@@ -201,7 +221,8 @@ __global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampl
                     }
                     if (g[0] >= 0 && g[0] < a.X && g[1] >= 0 && g[1] < a.Y && g[2] >= 0 && g[2] < a.Z) {
                         const uint32_t m = ((uint32_t)g[0] * (uint32_t)a.Y + (uint32_t)g[1]) * (uint32_t)a.Z + (uint32_t)g[2];
-                        if (a.own_mask == nullptr || a.own_mask[m] != 0) {
+                        if (WEIGHTED) amount = a.own_mask[m];              // required under this flag (the entry point checks)
+                        if (WEIGHTED ? amount != 0u : (a.own_mask == nullptr || a.own_mask[m] != 0)) {
                             const uint32_t voted = load_label<LB>(a.own, m);
                             if (voted < (uint32_t)a.C) dec = voted;
                         }
@@ -209,7 +230,8 @@ __global__ void __launch_bounds__(kThreads) map_sample_kernel(const OccdMapSampl
                 }
                 const uint32_t v = (loc[0] * kBrick + loc[1]) * kBrick + loc[2];
                 uint32_t best, at;
-                decide(a.votes + ((size_t)slot * kBrickVox + (size_t)v) * (size_t)a.pitch, a.C, dec, own, label, nobs, best, at);
+                decide<WEIGHTED>(a.votes + ((size_t)slot * kBrickVox + (size_t)v) * (size_t)a.pitch, a.C, dec, own, label, nobs, best, at,
+                                 amount);
                 if ((a.flags & OCCD_MAP_SAMPLE_KEEP_OWN) && own < (uint32_t)a.C && at == best && best > 0u) label = own;
             }
         }
@@ -288,19 +310,59 @@ bool extract_ok(const OccdMapExtractArgs* a) {
 
 double pool_bytes(int32_t n_bricks, int32_t pitch) { return (double)n_bricks * kBrickVox * pitch * 2.0; }
 
-}  // namespace
+// the weighted structs are the unweighted ones with one field renamed: the kernels take the unweighted struct either way
+static_assert(sizeof(OccdMapWeightedArgs) == sizeof(OccdMapFrameArgs) &&
+              offsetof(OccdMapWeightedArgs, weight) == offsetof(OccdMapFrameArgs, mask) &&
+              offsetof(OccdMapWeightedArgs, label_bytes) == offsetof(OccdMapFrameArgs, label_bytes), "OccdMapWeightedArgs");
+static_assert(sizeof(OccdMapSampleWeightedArgs) == sizeof(OccdMapSampleArgs) &&
+              offsetof(OccdMapSampleWeightedArgs, own_weight) == offsetof(OccdMapSampleArgs, own_mask) &&
+              offsetof(OccdMapSampleWeightedArgs, dq) == offsetof(OccdMapSampleArgs, dq), "OccdMapSampleWeightedArgs");
 
-extern "C" int occd_map_integrate(const OccdMapFrameArgs* a, void* stream) {
+template <bool WEIGHTED>
+int map_integrate(const OccdMapFrameArgs* a, void* stream) {
     if (!a || !a->labels || !pool_ok(a->votes, a->table, a->n_bricks, a->capacity, a->C, a->pitch)) return OCCD_EINVAL;
+    if (WEIGHTED && !a->mask) return OCCD_EINVAL;
     if (a->X <= 0 || a->Y <= 0 || a->Z <= 0 || (int64_t)a->X * a->Y * a->Z > kMaxVox) return OCCD_EINVAL;
     if (a->label_bytes != 1 && a->label_bytes != 2) return OCCD_EINVAL;
     if (!slots_ok(a->table_host, a->n_bricks, 16, a->capacity, true)) return OCCD_EINVAL;
     const double frame = (double)a->X * a->Y * a->Z * (a->label_bytes + (a->mask ? 1 : 0));
-    occd::ProfScope prof("map_integrate", (hipStream_t)stream, 0.0, 2.0 * pool_bytes(a->n_bricks, a->pitch) + frame);
+    occd::ProfScope prof(WEIGHTED ? "map_integrate_weighted" : "map_integrate", (hipStream_t)stream, 0.0,
+                         2.0 * pool_bytes(a->n_bricks, a->pitch) + frame);
     const dim3 grid((unsigned)a->n_bricks);
-    if (a->label_bytes == 1) hipLaunchKernelGGL(map_integrate_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
-    else hipLaunchKernelGGL(map_integrate_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    if (a->label_bytes == 1) hipLaunchKernelGGL((map_integrate_kernel<1, WEIGHTED>), grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL((map_integrate_kernel<2, WEIGHTED>), grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
     return occd::check_launch();
+}
+
+template <bool WEIGHTED>
+int map_sample(const OccdMapSampleArgs* a, void* stream) {
+    if (!a || !a->cells || !a->labels || !a->n_obs || !pool_ok(a->votes, a->table, a->n_bricks, a->capacity, a->C, a->pitch))
+        return OCCD_EINVAL;
+    if (a->X <= 0 || a->Y <= 0 || a->Z <= 0 || (int64_t)a->X * a->Y * a->Z > kMaxVox) return OCCD_EINVAL;
+    if (a->gx <= 0 || a->gy <= 0 || a->gz <= 0 || (int64_t)a->gx * a->gy * a->gz > kMaxCells) return OCCD_EINVAL;
+    if ((a->flags & ~(OCCD_MAP_SAMPLE_EXCLUDE_SELF | OCCD_MAP_SAMPLE_KEEP_OWN)) != 0 || (a->flags != 0 && !a->own)) return OCCD_EINVAL;
+    if (WEIGHTED && (a->flags & OCCD_MAP_SAMPLE_EXCLUDE_SELF) && !a->own_mask) return OCCD_EINVAL;
+    if (a->min_obs < 0 || (a->label_bytes != 1 && a->label_bytes != 2)) return OCCD_EINVAL;
+    if (!slots_ok(a->table_host, a->n_bricks, 16, a->capacity, false)) return OCCD_EINVAL;
+    const double S = (double)a->X * a->Y * a->Z;
+    // every voxel reads its vote row and writes 3 bytes; its own label, the mask and the directory come on top
+    occd::ProfScope prof(WEIGHTED ? "map_sample_weighted" : "map_sample", (hipStream_t)stream, 0.0,
+                         S * (a->pitch * 2.0 + 3.0 + (a->own ? a->label_bytes : 0)) + (double)a->gx * a->gy * a->gz * 4.0);
+    const dim3 grid((unsigned)(((int64_t)a->X * a->Y * a->Z + kThreads - 1) / kThreads));
+    if (a->label_bytes == 1) hipLaunchKernelGGL((map_sample_kernel<1, WEIGHTED>), grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL((map_sample_kernel<2, WEIGHTED>), grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
+    return occd::check_launch();
+}
+
+}  // namespace
+
+extern "C" int occd_map_integrate(const OccdMapFrameArgs* a, void* stream) { return map_integrate<false>(a, stream); }
+
+extern "C" int occd_map_integrate_weighted(const OccdMapWeightedArgs* a, void* stream) {
+    if (!a) return OCCD_EINVAL;
+    OccdMapFrameArgs f;
+    memcpy(&f, a, sizeof(f));                           // the same layout (asserted above), weight where mask is
+    return map_integrate<true>(&f, stream);
 }
 
 extern "C" int occd_map_brick_labels(const OccdMapExtractArgs* a, void* stream) {
@@ -324,22 +386,13 @@ extern "C" int occd_map_extract(const OccdMapExtractArgs* a, void* stream) {
     return occd::check_launch();
 }
 
-extern "C" int occd_map_sample(const OccdMapSampleArgs* a, void* stream) {
-    if (!a || !a->cells || !a->labels || !a->n_obs || !pool_ok(a->votes, a->table, a->n_bricks, a->capacity, a->C, a->pitch))
-        return OCCD_EINVAL;
-    if (a->X <= 0 || a->Y <= 0 || a->Z <= 0 || (int64_t)a->X * a->Y * a->Z > kMaxVox) return OCCD_EINVAL;
-    if (a->gx <= 0 || a->gy <= 0 || a->gz <= 0 || (int64_t)a->gx * a->gy * a->gz > kMaxCells) return OCCD_EINVAL;
-    if ((a->flags & ~(OCCD_MAP_SAMPLE_EXCLUDE_SELF | OCCD_MAP_SAMPLE_KEEP_OWN)) != 0 || (a->flags != 0 && !a->own)) return OCCD_EINVAL;
-    if (a->min_obs < 0 || (a->label_bytes != 1 && a->label_bytes != 2)) return OCCD_EINVAL;
-    if (!slots_ok(a->table_host, a->n_bricks, 16, a->capacity, false)) return OCCD_EINVAL;
-    const double S = (double)a->X * a->Y * a->Z;
-    // every voxel reads its vote row and writes 3 bytes; its own label, the mask and the directory come on top
-    occd::ProfScope prof("map_sample", (hipStream_t)stream, 0.0,
-                         S * (a->pitch * 2.0 + 3.0 + (a->own ? a->label_bytes : 0)) + (double)a->gx * a->gy * a->gz * 4.0);
-    const dim3 grid((unsigned)(((int64_t)a->X * a->Y * a->Z + kThreads - 1) / kThreads));
-    if (a->label_bytes == 1) hipLaunchKernelGGL(map_sample_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
-    else hipLaunchKernelGGL(map_sample_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a);
-    return occd::check_launch();
+extern "C" int occd_map_sample(const OccdMapSampleArgs* a, void* stream) { return map_sample<false>(a, stream); }
+
+extern "C" int occd_map_sample_weighted(const OccdMapSampleWeightedArgs* a, void* stream) {
+    if (!a) return OCCD_EINVAL;
+    OccdMapSampleArgs f;
+    memcpy(&f, a, sizeof(f));                           // the same layout (asserted above), own_weight where own_mask is
+    return map_sample<true>(&f, stream);
 }
 
 extern "C" int occd_map_merge(const OccdMapMergeArgs* a, void* stream) {

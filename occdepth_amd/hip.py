@@ -63,6 +63,9 @@ MapSampleArgs = abi.STRUCTS["OccdMapSampleArgs"]
 MAP_SAMPLE_EXCLUDE_SELF = abi.CONSTANTS["OCCD_MAP_SAMPLE_EXCLUDE_SELF"]
 MAP_SAMPLE_KEEP_OWN = abi.CONSTANTS["OCCD_MAP_SAMPLE_KEEP_OWN"]
 MapMergeArgs = abi.STRUCTS["OccdMapMergeArgs"]
+VisibilityArgs = abi.STRUCTS["OccdVisibilityArgs"]
+MapWeightedArgs = abi.STRUCTS["OccdMapWeightedArgs"]
+MapSampleWeightedArgs = abi.STRUCTS["OccdMapSampleWeightedArgs"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2230,6 +2233,33 @@ def render_voxels(labels, views, size, palette, target=None, fov=None, backgroun
     return (rgb, hit, face, depth) if aux else rgb
 
 
+def frame_visibility(labels, view, size, return_hit=False):
+    """occd_frame_visibility (K34): which voxels of ONE frame the pixel rays of ONE view reach.  labels (X, Y, Z) uint8 /
+    int16 / uint16; view (18,) float32 ray generator in grid-voxel units (render.camera_view); size = (H, W) pixels.  All
+    on the GPU and contiguous.  -> visible (X, Y, Z) uint8: 1 for every voxel a ray visits up to and including its first
+    occupied one (0 < label < 255), else 0; with return_hit also hit (H, W) int32, the first occupied voxel or -1 (what
+    render_voxels reports).  Zeroed by the entry point itself: capture-safe.  The contract is in include/occdepth_amd.h."""
+    if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
+        raise RuntimeError("labels must be one (X, Y, Z) uint8 / int16 / uint16 volume, got %s %s" % (tuple(labels.shape), labels.dtype))
+    if view.dtype != torch.float32 or view.numel() != 18:
+        raise RuntimeError("view must be one float32 (18,) ray generator, got %s %s" % (tuple(view.shape), view.dtype))
+    if view.device != labels.device:
+        raise RuntimeError(f"view is on {view.device}, labels on {labels.device}")
+    H, W = int(size[0]), int(size[1])
+    a = VisibilityArgs()
+    a.labels, a.view, a.label_bytes = _ptr(labels, "labels"), _ptr(view, "view"), _LABEL_BYTES[labels.dtype]
+    visible = torch.empty(tuple(labels.shape), dtype=torch.uint8, device=labels.device)
+    a.visible = visible.data_ptr()
+    hit = None
+    if return_hit:
+        hit = torch.empty((max(H, 0), max(W, 0)), dtype=torch.int32, device=labels.device)
+        a.hit = hit.data_ptr()
+    a.H, a.W = H, W
+    a.X, a.Y, a.Z = (int(d) for d in labels.shape)
+    _check(load().occd_frame_visibility(ctypes.byref(a), _stream()), "occd_frame_visibility")
+    return (visible, hit) if return_hit else visible
+
+
 # ----------------------------------------------------------------------------- temporal fusion (csrc/fuse.hip)
 def fuse_store(logits, rows):
     """occd_fuse_store: softmax of ONE frame's logits (C, X, Y, Z) float32 -- contiguous planes or a channels-last view of
@@ -2316,21 +2346,46 @@ def map_integrate(votes, table, labels, dims, n_classes, mask=None, table_host=N
     the (n, 16) int32 `table` names (slot | key | Aq | cq per row, semantic_map.brick_coefficients), inside `mask`
     (X Y Z bool / uint8 entries) when given.  votes: the int16 (capacity, 4096, pitch) pool, updated in place.  The
     contract is in include/occdepth_amd.h."""
+    return _map_integrate(votes, table, labels, dims, n_classes, mask, None, table_host)
+
+
+def _check_weight(t, S, name):
+    """A weight volume as the kernels read it: X Y Z uint8 entries."""
+    if t is not None and (not torch.is_tensor(t) or t.dtype != torch.uint8 or t.numel() != S):
+        raise RuntimeError("%s must hold X Y Z = %d uint8 weights, got %s %s"
+                           % (name, S, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__, getattr(t, "dtype", None)))
+
+
+def _map_integrate(votes, table, labels, dims, n_classes, mask, weight, table_host):
     X, Y, Z = (int(d) for d in dims)
     if labels.dtype not in _LABEL_BYTES or labels.numel() != X * Y * Z:
         raise RuntimeError("labels must hold X Y Z = %d uint8 / int16 / uint16 entries, got %s %s"
                            % (X * Y * Z, tuple(labels.shape), labels.dtype))
-    a = MapFrameArgs()
+    _check_weight(weight, X * Y * Z, "weight")
+    a = MapFrameArgs() if weight is None else MapWeightedArgs()
     _map_operands(a, votes, table, table_host, 16, n_classes)
     a.labels, a.label_bytes = _ptr(labels, "labels"), _LABEL_BYTES[labels.dtype]
-    if mask is not None:
+    if weight is not None:
+        a.weight = _ptr(weight, "weight")
+    elif mask is not None:
         a.mask = _ptr(_byte_mask(mask.reshape(1, -1), 1, X * Y * Z, "mask"), "mask")
-    for t, name in ((labels, "labels"), (mask, "mask")):
+    for t, name in ((labels, "labels"), (mask, "mask"), (weight, "weight")):
         if t is not None and t.device != votes.device:
             raise RuntimeError(f"{name} is on {t.device}, votes on {votes.device}")
     a.X, a.Y, a.Z = X, Y, Z
-    _check(load().occd_map_integrate(ctypes.byref(a), _stream()), "occd_map_integrate")
+    if weight is None:
+        _check(load().occd_map_integrate(ctypes.byref(a), _stream()), "occd_map_integrate")
+    else:
+        _check(load().occd_map_integrate_weighted(ctypes.byref(a), _stream()), "occd_map_integrate_weighted")
     return votes
+
+
+def map_integrate_weighted(votes, table, labels, dims, n_classes, weight, table_host=None):
+    """occd_map_integrate_weighted, one launch: map_integrate with a required `weight` volume (X Y Z uint8 entries) in
+    place of the mask -- voxel n votes with weight[n], counters become min(v + w, 65535), weight 0 casts no vote."""
+    if weight is None:
+        raise RuntimeError("map_integrate_weighted needs the weight volume (map_integrate takes an optional mask)")
+    return _map_integrate(votes, table, labels, dims, n_classes, None, weight, table_host)
 
 
 def map_brick_labels(votes, table, n_classes, table_host=None):
@@ -2378,6 +2433,23 @@ def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask
     mask it voted with or None; Bq (3, 3), dq (3,) from semantic_map.sample_coefficients.  exclude_self / keep_own need
     `own`.  -> labels (X, Y, Z) uint8, n_obs (X, Y, Z) int16 holding uint16 bits.  The contract is in
     include/occdepth_amd.h."""
+    return _map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask, None, min_obs, exclude_self, keep_own,
+                       table_host)
+
+
+def map_sample_weighted(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_weight=None, min_obs=1,
+                        exclude_self=False, keep_own=False, table_host=None):
+    """occd_map_sample_weighted, one launch: map_sample for a map of weighted votes.  own_weight: the (X Y Z) uint8
+    weights the frame voted with, required by exclude_self (which retracts them) and read by nothing else.  min_obs and
+    the returned n_obs are in vote units."""
+    if exclude_self and own_weight is None:
+        raise RuntimeError("exclude_self retracts the frame's own weights: own_weight is needed")
+    return _map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, None, own_weight, min_obs, exclude_self, keep_own,
+                       table_host, weighted=True)
+
+
+def _map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask, own_weight, min_obs, exclude_self, keep_own,
+                table_host, weighted=False):
     X, Y, Z = (int(d) for d in dims)
     S = X * Y * Z
     if cells.dtype != torch.int32 or cells.dim() != 3 or tuple(cells.shape) != tuple(int(g) for g in grid):
@@ -2386,10 +2458,11 @@ def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask
         raise RuntimeError("own must hold X Y Z = %d uint8 / int16 / uint16 entries, got %s %s" % (S, tuple(own.shape), own.dtype))
     if own is None and (exclude_self or keep_own):
         raise RuntimeError("exclude_self and keep_own need the frame's own labels")
+    _check_weight(own_weight, S, "own_weight")
     Bq, dq = [int(v) for r in Bq for v in r], [int(v) for v in dq]
     if len(Bq) != 9 or len(dq) != 3 or not all(-(1 << 31) <= v < 1 << 31 for v in Bq + dq):
         raise RuntimeError("Bq must be a 3 x 3 and dq a 3-vector of int32 (semantic_map.sample_coefficients)")
-    a = MapSampleArgs()
+    a = MapSampleWeightedArgs() if weighted else MapSampleArgs()
     _map_operands(a, votes, table, table_host, 16, n_classes)
     a.cells = _ptr(cells, "cells")
     if own is not None:
@@ -2398,7 +2471,9 @@ def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask
         a.label_bytes = 1
     if own_mask is not None:
         a.own_mask = _ptr(_byte_mask(own_mask.reshape(1, -1), 1, S, "own_mask"), "own_mask")
-    for t, name in ((cells, "cells"), (own, "own"), (own_mask, "own_mask")):
+    if own_weight is not None:
+        a.own_weight = _ptr(own_weight, "own_weight")
+    for t, name in ((cells, "cells"), (own, "own"), (own_mask, "own_mask"), (own_weight, "own_weight")):
         if t is not None and t.device != votes.device:
             raise RuntimeError(f"{name} is on {t.device}, votes on {votes.device}")
     labels = torch.empty((X, Y, Z), dtype=torch.uint8, device=votes.device)
@@ -2412,7 +2487,10 @@ def map_sample(votes, table, cells, own, dims, n_classes, Bq, dq, grid, own_mask
         a.Bq[i] = v
     for i, v in enumerate(dq):
         a.dq[i] = v
-    _check(load().occd_map_sample(ctypes.byref(a), _stream()), "occd_map_sample")
+    if weighted:
+        _check(load().occd_map_sample_weighted(ctypes.byref(a), _stream()), "occd_map_sample_weighted")
+    else:
+        _check(load().occd_map_sample(ctypes.byref(a), _stream()), "occd_map_sample")
     return labels, n_obs
 
 

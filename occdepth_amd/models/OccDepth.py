@@ -174,15 +174,18 @@ class OccDepth(_Base):
         # OCCDEPTH_FUSE_POSES) [OCCDEPTH_MAP_MIN_OBS=n] [OCCDEPTH_MAP_VIEWS=bev,oblique] [OCCDEPTH_MAP_FRAMES=1 [OCCDEPTH_MAP_FRAMES_SELF=0]
         # [OCCDEPTH_MAP_SUBMISSION=<dir>]: the map read back into every frame] [OCCDEPTH_MAP_GATHER=0] [OCCDEPTH_MAP_SAVE=1] in the environment of an unmodified scripts/eval.py.  Off: nothing is
         # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
+        # [OCCDEPTH_MAP_VISIBILITY=<w_vis>,<w_hid>]: the prediction map takes occlusion-aware votes (visibility.py, K34).
         self.semantic_map = None
         if env("OCCDEPTH_MAP_DIR", ""):
+            weights = env("OCCDEPTH_MAP_VISIBILITY", "")
             self.enable_semantic_map(env("OCCDEPTH_MAP_DIR"), env("OCCDEPTH_MAP_POSES", "") or env("OCCDEPTH_FUSE_POSES", ""),
                                      min_obs=int(env("OCCDEPTH_MAP_MIN_OBS", "1")),
                                      views=tuple(v for v in env("OCCDEPTH_MAP_VIEWS", "").split(",") if v),
                                      frames=env("OCCDEPTH_MAP_FRAMES", "0") == "1",
                                      submission_dir=env("OCCDEPTH_MAP_SUBMISSION", "") or None,
                                      exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0",
-                                     gather=env("OCCDEPTH_MAP_GATHER", "1") != "0", save_maps=env("OCCDEPTH_MAP_SAVE", "0") == "1")
+                                     gather=env("OCCDEPTH_MAP_GATHER", "1") != "0", save_maps=env("OCCDEPTH_MAP_SAVE", "0") == "1",
+                                     visibility=tuple(int(w) for w in weights.split(",")) if weights else None)
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -787,7 +790,7 @@ class OccDepth(_Base):
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
     def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
-                            exclude_self=False, max_frames=1024, gather=True, save_maps=False):
+                            exclude_self=False, max_frames=1024, gather=True, save_maps=False, visibility=None):
         """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
         ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
         prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
@@ -820,7 +823,21 @@ class OccDepth(_Base):
         frame's own vote out) and counted against its target into a third metric: `val_mapped/mIoU`, `val_mapped/IoU`
         are logged and `test_epoch_end` prints a `test_mapped======` block.  With submission_dir the mapped labels are
         written as <submission_dir>/sequences/<seq>/predictions/<frame>.label (output.write_kitti_submission_labels).
-        Off: nothing more is kept, imported or launched.  The effect on any score is not measured."""
+        Off: nothing more is kept, imported or launched.  The effect on any score is not measured.
+
+        visibility = (w_visible, w_hidden) (OCCDEPTH_MAP_VISIBILITY=<w_vis>,<w_hid>; integers, 1 <= w_visible <= 255,
+        0 <= w_hidden <= 255): occlusion-aware votes.  The pixel rays of the batch's left camera (`cam_k`,
+        `T_velo_2_cam`, the size of `img`) are cast through every PREDICTED volume (visibility.visible_voxels, K34); a
+        voxel a ray reaches, up to and including the first occupied one, votes into the prediction map with w_visible,
+        every other voxel inside the FOV mask with w_hidden, so a frame that only guessed a voxel no longer outvotes one
+        that saw it.  The ground-truth map is unchanged.  Kept frames hold that weight volume where they held the mask
+        (the same bytes), the read-back retracts it under exclude_self, and min_obs counts vote units.  None (the
+        default): nothing more is imported or launched.  The effect on mIoU is not measured."""
+        if visibility is not None:
+            if len(tuple(visibility)) != 2:
+                raise ValueError("visibility is (w_visible, w_hidden) (OCCDEPTH_MAP_VISIBILITY=<w_vis>,<w_hid>), got %r" % (visibility,))
+            from ..visibility import check_weights
+            visibility = check_weights(*visibility)
         if self.dataset != "kitti":
             raise NotImplementedError("the semantic map reads SemanticKITTI poses and is wired for the SemanticKITTI geometry "
                                       "only; a %s model has no ego-motion to lay its frames out with" % self.dataset)
@@ -840,7 +857,7 @@ class OccDepth(_Base):
                              "maps": {}, "poses": {}, "paths": [], "views": views,
                              "frames": bool(frames) or bool(submission_dir), "submission_dir": str(submission_dir) if submission_dir else None,
                              "exclude_self": bool(exclude_self), "max_frames": int(max_frames), "kept": {}, "mapped_stats": {},
-                             "gather": bool(gather), "save_maps": bool(save_maps), "seen": {}}
+                             "gather": bool(gather), "save_maps": bool(save_maps), "seen": {}, "visibility": visibility}
         return self
 
     def _map_step(self, step_type, batch, ssc_pred, target):
@@ -872,19 +889,32 @@ class OccDepth(_Base):
                                    % (kept + B, st["max_frames"], 3e-6 * dims[0] * dims[1] * dims[2]))
         pred = hip.argmax_labels_u16(ssc_pred.float())                   # (B, X, Y, Z) uint16 bits, the unfused logits
         gt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
+        weights = st.get("visibility")
+        if weights:                                                      # the left camera's pixel rays, one view per item
+            from .. import render, visibility
+            missing = [k for k in ("cam_k", "T_velo_2_cam", "img") if k not in batch]
+            if missing:
+                raise KeyError("occlusion-aware map votes need the camera of every frame: the batch has no %s" % ", ".join(missing))
+            cam_k, cam_E, _ = render.batch_camera(batch, self.dataset, origin, pred.device)
+            rays, rays_hw = visibility.camera_rays(cam_k, cam_E, origin, vs, tuple(batch["img"].shape[-2:]))
         for i, (seq, pose) in enumerate(items):
             pair = st["maps"].get((step_type, seq))
             if pair is None:
                 pair = st["maps"][(step_type, seq)] = tuple(semantic_map.SemanticMap(self.n_classes, vs, origin, dims)
                                                             for _ in range(2))
             mask = None if fov is None else fov[i]
-            pair[0].integrate(pred[i], pose, mask=mask)
+            weight = None
+            if weights:
+                weight = visibility.vote_weights(visibility.visible_voxels(pred[i], rays[i], rays_hw), mask, *weights)
+                pair[0].integrate(pred[i], pose, weight=weight)
+            else:
+                pair[0].integrate(pred[i], pose, mask=mask)
             pair[1].integrate(gt[i].reshape(dims), pose, mask=mask)
             st.setdefault("seen", {}).setdefault(step_type, []).append((seq, int(batch["frame_id"][i])))
-            if st.get("frames"):
+            if st.get("frames"):                                         # the weight volume takes the mask's place: the same bytes
+                voted = weight if weights else (None if mask is None else mask != 0)
                 st["kept"].setdefault((step_type, seq), []).append(      # copies: the batch's tensors are not held on to
-                    (pred[i].to(torch.uint8), gt[i].reshape(dims).clone(), None if mask is None else mask != 0, pose,
-                     str(batch["frame_id"][i])))
+                    (pred[i].to(torch.uint8), gt[i].reshape(dims).clone(), voted, pose, str(batch["frame_id"][i])))
 
     def _map_epoch_end(self, step_type):
         """Write and score the maps of `step_type`, release them; -> the statistics over its sequences, or None."""
@@ -931,8 +961,9 @@ class OccDepth(_Base):
         for key in mine:
             pair = st["maps"].pop(key)
             for own, gt, own_mask, pose, frame_id in (st["kept"].pop(key, ()) if mapped is not None else ()):
-                labels, _ = pair[0].sample(pose, own=own, own_mask=own_mask, min_obs=st["min_obs"],
-                                           exclude_self=st["exclude_self"], keep_own=True)
+                voted = {"own_weight": own_mask} if st.get("visibility") else {"own_mask": own_mask}
+                labels, _ = pair[0].sample(pose, own=own, min_obs=st["min_obs"], exclude_self=st["exclude_self"], keep_own=True,
+                                           **voted)
                 mapped.add_batch(labels[None], gt[None])
                 if st["submission_dir"]:
                     from .. import output

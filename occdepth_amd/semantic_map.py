@@ -10,6 +10,7 @@ frame vote in one launch, hip.map_brick_labels / hip.map_extract decide).
     map_confusion(pred_map, gt_map, SSCMetrics(20))                  # map mIoU where both maps were observed
     labels, n_obs = m.sample(poses[frame], own=labels, own_mask=fov_mask_1, keep_own=True)   # the map read back into a frame (K32)
     m.merge(other); m.save("08.occmap"); SemanticMap.load("08.occmap"); merge_over_ranks(m)   # maps summed: runs, files, ranks (K33)
+    m.integrate(labels, poses[frame], weight=w); m.sample(poses[frame], own=labels, own_weight=w)   # a uint8 weight per voxel (visibility.py, K34)
 
 The world lattice has the frame grid's voxel size; voxels live in 16^3 bricks of 16-bit vote counters, one row of `pitch`
 = n_classes rounded up to 4 counters per voxel (8192 * pitch bytes per brick: 163840 at 20 classes).  The host side is
@@ -243,13 +244,28 @@ class SemanticMap:
         table[:, 13:16] = cq
         return table
 
-    def integrate(self, labels, pose, mask=None):
+    def _weight(self, weight, device, name):
+        """A weight volume as the weighted kernels take it: X Y Z uint8 entries on `device`."""
+        weight = torch.as_tensor(weight)
+        S = self.dims[0] * self.dims[1] * self.dims[2]
+        if weight.dtype != torch.uint8 or weight.numel() != S:
+            raise ValueError("%s must hold X Y Z = %d uint8 weights (visibility.vote_weights), got %s %r"
+                             % (name, S, weight.dtype, tuple(weight.shape)))
+        return weight.to(device).contiguous()
+
+    def integrate(self, labels, pose, mask=None, weight=None):
         """One frame votes: labels (X, Y, Z) uint8 / int16 (uint16 bits) on the GPU, pose 4 x 4 sensor -> world, mask the
-        frame's own (X Y Z) bool / uint8 table or None.  A label >= n_classes (255) does not vote."""
+        frame's own (X Y Z) bool / uint8 table or None.  A label >= n_classes (255) does not vote.  weight: instead of a
+        mask (a frame takes one or the other), the (X Y Z) uint8 weight of each voxel's vote, 0 = no vote
+        (visibility.vote_weights); counters saturate at 65535 either way, and frames of both kinds may share a map."""
         if tuple(labels.shape) != self.dims:
             raise ValueError("integrate takes (X, Y, Z) = %r labels, got %r" % (self.dims, tuple(labels.shape)))
         if self.votes is not None and labels.device != self.votes.device:
             raise ValueError("labels are on %s, the map on %s" % (labels.device, self.votes.device))
+        if mask is not None and weight is not None:
+            raise ValueError("a frame votes inside a mask or with a weight per voxel, not both (a weight of 0 is the mask)")
+        if weight is not None:
+            weight = self._weight(weight, labels.device, "weight")
         S = self.dims[0] * self.dims[1] * self.dims[2]
         if mask is not None:
             mask = torch.as_tensor(mask)
@@ -262,6 +278,10 @@ class SemanticMap:
         if not len(table):
             return self
         dev_table, host_table = self.upload(table, labels.device)
+        if weight is not None:
+            hip.map_integrate_weighted(self.pool(), dev_table, labels.contiguous(), self.dims, self.n_classes, weight,
+                                       table_host=host_table)
+            return self
         hip.map_integrate(self.pool(), dev_table, labels.contiguous(), self.dims, self.n_classes, mask=mask,
                           table_host=host_table)
         return self
@@ -291,7 +311,7 @@ class SemanticMap:
         cells[at[:, 0], at[:, 1], at[:, 2]] = np.arange(len(keys), dtype=np.int32)
         return cells, table, lo
 
-    def sample(self, pose, own=None, own_mask=None, min_obs=1, exclude_self=False, keep_own=False):
+    def sample(self, pose, own=None, own_mask=None, min_obs=1, exclude_self=False, keep_own=False, own_weight=None):
         """What the whole map says about the voxels of the frame at `pose` (K32, one launch) -> labels (X, Y, Z) uint8,
         n_obs (X, Y, Z) int16 holding uint16 bits (the votes at the world voxel the frame voxel's centre falls into,
         saturated at 65535).  labels = the arg-max of those votes (the lowest class on a tie) where n_obs >= max(min_obs,
@@ -299,9 +319,13 @@ class SemanticMap:
         given, else 255.  exclude_self takes the frame's own vote out first: `own` and `own_mask` must be what it was
         integrated with (a counter saturated at 65535 is not retracted).  keep_own: a tie that own's class is part of
         goes to own.  An empty map, or a frame that meets none of its bricks, gives the fallback volume and zeros
-        without a launch."""
+        without a launch.  own_weight (instead of own_mask, never both): the (X Y Z) uint8 weights the frame was
+        integrated with; exclude_self then retracts that weight (not from a counter saturated at 65535, nor from one
+        below the weight), and n_obs and min_obs count vote units, as they do for any map that took weighted votes."""
         if int(min_obs) < 0:
             raise ValueError("min_obs must be >= 0, got %r" % (min_obs,))
+        if own_mask is not None and own_weight is not None:
+            raise ValueError("a frame voted inside own_mask or with own_weight, not both")
         if own is None and (exclude_self or keep_own):
             raise ValueError("exclude_self and keep_own need the frame's own labels (own)")
         if not sum(self.dims) < int(C_LIMIT):
@@ -320,6 +344,8 @@ class SemanticMap:
             own_mask = own_mask.to(dev)
             if own_mask.dtype not in (torch.bool, torch.uint8):
                 own_mask = own_mask != 0
+        if own_weight is not None:
+            own_weight = self._weight(own_weight, dev, "own_weight")
         table = None
         if self.votes is not None and self.directory:
             cells, table, key_min = self.frame_cells(pose, dev)
@@ -333,6 +359,11 @@ class SemanticMap:
         Bq, dq = sample_coefficients(pose, self.vox_origin, self.voxel_size, key_min, self.dims)
         dev_table, host_table = self.upload(table, dev)
         dev_cells, _ = self.upload(cells, dev)
+        if own_weight is not None:
+            return hip.map_sample_weighted(self.pool(), dev_table, dev_cells, None if own is None else own.contiguous(),
+                                           self.dims, self.n_classes, Bq, dq, cells.shape, own_weight=own_weight,
+                                           min_obs=int(min_obs), exclude_self=bool(exclude_self), keep_own=bool(keep_own),
+                                           table_host=host_table)
         return hip.map_sample(self.pool(), dev_table, dev_cells, None if own is None else own.contiguous(), self.dims,
                               self.n_classes, Bq, dq, cells.shape, own_mask=own_mask, min_obs=int(min_obs),
                               exclude_self=bool(exclude_self), keep_own=bool(keep_own), table_host=host_table)

@@ -4,6 +4,7 @@ as a point PLY, and score a prediction map against a ground-truth map.
     python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
         --out maps/08 [--min-obs 2] [--fov] [--every 5] [--views bev oblique] [--png-side 2048] [--camera-every 50 --t-max 80]
         [--frames-out DIR [--exclude-self] [--keep-own]] [--frame-range FIRST LAST] [--save-map PREFIX] [--load-map PREFIX ...]
+        [--visibility W_VIS W_HID]
 
 --pred / --gt name a directory; what it holds decides how it is read:
     <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
@@ -24,6 +25,10 @@ against their targets) and a `mapped======` block (the sampled labels against th
 can be voted into again, unlike the PLY); --load-map PREFIX [PREFIX ...] merges such files in (SemanticMap.load, then merge,
 K33) before the frames are integrated, and --frame-range FIRST LAST (inclusive) keeps a run to a part of the sequence: one
 run over frames 0..1999 with --save-map and a second over 2000..4070 with --load-map give the map of the whole drive.
+--visibility W_VIS W_HID makes the prediction map's votes occlusion-aware (occdepth_amd/visibility.py, K34): the pixel rays of
+the left colour camera (P2 and Tr of calib.txt, --camera-size) are cast through every --pred frame's own labels; a voxel a ray
+reaches, up to and including the first occupied one, votes with W_VIS, any other (inside the mask with --fov) with W_HID.  The
+ground-truth map votes as before; --frames-out hands each frame's weights back to the read-back.
 """
 import argparse
 import glob
@@ -82,6 +87,20 @@ def read_frame(kind, base, role, dims, device, use_fov=False, lut=None):
     return lab[0], None
 
 
+def visibility_weight(labels, mask, args):
+    """--visibility: the vote weights of one prediction frame from its own labels -- the pixel rays of the left colour
+    camera (calib.txt, --camera-size) carve the volume (occdepth_amd.visibility, K34) -- or None without the switch."""
+    if not args.visibility:
+        return None
+    from occdepth_amd import visibility
+    if getattr(args, "_rays", None) is None:                               # one view for the whole sequence
+        cam_k, E = read_camera(args.poses)
+        args._rays = visibility.camera_rays(torch.from_numpy(cam_k), torch.from_numpy(E), tuple(args.origin), args.voxel,
+                                            tuple(args.camera_size))
+    view, size = args._rays
+    return visibility.vote_weights(visibility.visible_voxels(labels, view, size), mask, *args.visibility)
+
+
 def build_map(src, role, poses, args, device):
     kind, frames = list_frames(src)
     lut = submission_inverse_lut() if kind == "label" else None
@@ -96,7 +115,11 @@ def build_map(src, role, poses, args, device):
         if frame not in poses:
             raise KeyError("no pose for frame %d of %s (%s)" % (frame, src, os.path.join(args.poses, "poses.txt")))
         labels, mask = read_frame(kind, frames[frame], role, tuple(args.dims), device, args.fov, lut)
-        m.integrate(labels, poses[frame], mask=mask)
+        weight = visibility_weight(labels, mask, args) if role == "pred" else None
+        if weight is not None:
+            m.integrate(labels, poses[frame], weight=weight)
+        else:
+            m.integrate(labels, poses[frame], mask=mask)
         used += 1
     print("%s: %d %s frames of %s -> %d bricks, %.1f MB" % (role, used, kind, src, m.n_bricks, m.n_bricks * m.brick_bytes / 1e6))
     return m
@@ -123,8 +146,10 @@ def sample_frames(pred_map, poses, args, device):
     paths, scored = [], 0
     for frame in sorted(frames)[::args.every]:
         own, mask = read_frame(kind, frames[frame], "pred", dims, device, args.fov, lut)
-        mapped, _ = pred_map.sample(poses[frame], own=own, own_mask=mask, min_obs=args.min_obs,
-                                    exclude_self=args.exclude_self, keep_own=args.keep_own)
+        weight = visibility_weight(own, mask, args)                        # what the frame voted with, made again
+        voted = {"own_mask": mask} if weight is None else {"own_weight": weight}
+        mapped, _ = pred_map.sample(poses[frame], own=own, min_obs=args.min_obs, exclude_self=args.exclude_self,
+                                    keep_own=args.keep_own, **voted)
         paths.append(output.write_kitti_submission_labels(mapped, sequence, "%06d" % frame, args.frames_out))
         if frame in gt_frames:
             target, _ = read_frame(gt_kind, gt_frames[frame], "gt", dims, device, False, gt_lut)
@@ -247,6 +272,9 @@ def parser():
                     help="read the prediction map back into every --pred frame: DIR/sequences/<seq>/predictions/<frame>.label")
     ap.add_argument("--exclude-self", action="store_true", help="--frames-out: take the frame's own vote out of the map first")
     ap.add_argument("--keep-own", action="store_true", help="--frames-out: a tie that the frame's own label is part of goes to it")
+    ap.add_argument("--visibility", type=int, nargs=2, default=None, metavar=("W_VIS", "W_HID"),
+                    help="occlusion-aware votes of the prediction map: a voxel the left camera's pixel rays reach in the frame's "
+                         "own labels votes with W_VIS (1..255), any other with W_HID (0..255); camera from calib.txt and --camera-size")
     ap.add_argument("--frame-range", type=int, nargs=2, default=None, metavar=("FIRST", "LAST"), help="use these frames only (inclusive)")
     ap.add_argument("--save-map", default=None, metavar="PREFIX", help="keep the maps' vote counters: PREFIX_{pred,gt}.occmap")
     ap.add_argument("--load-map", nargs="+", default=None, metavar="PREFIX",

@@ -472,7 +472,10 @@ int occd_softmax_channels(const float* src, float* dst, int64_t rows,
  *   out[v][o] = part[v][o] + sum_{tap<27, c<2} softmax(part[v+tap][occ_off : occ_off+2])[c] * wn[o][c][tap]
  * part: (B, X, Y, Z, part_cs) rows with the wide-half class logits at [0, nbr) and the 2 occupancy logits at
  * occ_off; wn: (nbr, 2, 3, 3, 3) = conv_classes.weight[:, planes:]; out: (B, X, Y, Z, out_cs); zero padding
- * applies to the softmax output.  VALU kernel (K = 54 is too thin for MFMA).                        */
+ * applies to the softmax output.  VALU kernel (K = 54 is too thin for MFMA).
+ * Only lanes [0, nbr) of an out row are written: lanes [nbr, out_cs) and whatever follows the last row are left
+ * untouched.  The kernels are built for 3, 5 and 8 float4 groups of outputs (nbr <= 12, <= 20, <= 32) and load that
+ * many floats of every part row, so part_cs must be at least 12, 20 or 32 (OCCD_EINVAL otherwise).  */
 int occd_cascade_tail_fwd(const float* part, const float* wn, float* out, int32_t batch, int32_t X,
                           int32_t Y, int32_t Z, int32_t part_cs, int32_t occ_off, int32_t out_cs,
                           int32_t nbr, void* stream);

@@ -1477,10 +1477,12 @@ extern "C" int occd_cascade_tail_fwd(const float* part, const float* wn, float* 
     if (nbr <= 0 || nbr > kTailMaxOut || (part_cs & 3) || (out_cs & 3) || (occ_off & 1) || occ_off + 2 > part_cs ||
         ((nbr + 3) & ~3) > part_cs || nbr > out_cs)
         return OCCD_EINVAL;
+    const int ng = (nbr + 3) >> 2;
+    // the variants exist for NG = 3, 5 and 8 only and load 4 * NG floats of every part row, whatever nbr is
+    if (4 * (ng <= 3 ? 3 : ng <= 5 ? 5 : 8) > part_cs) return OCCD_EINVAL;
     const long total = (long)batch * X * Y * Z;
     occd::ProfScope prof("cascade_tail", (hipStream_t)stream, 2.0 * total * 54 * nbr, 4.0 * total * (2.0 * nbr + 2));
     const dim3 grid((unsigned)((total + 255) / 256));
-    const int ng = (nbr + 3) >> 2;
     hipStream_t st = (hipStream_t)stream;
     if (Z <= 64 && X <= 65535 && batch <= 65535) {
         const int TY = 256 / Z;

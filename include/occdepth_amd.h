@@ -87,7 +87,9 @@ extern "C" {
  *     OccdVisibilityArgs and occd_frame_visibility (K34, the voxels of a frame the camera's pixel rays reach,
  *     csrc/visibility.hip) and OccdMapWeightedArgs, occd_map_integrate_weighted, OccdMapSampleWeightedArgs and
  *     occd_map_sample_weighted (votes of a weight per voxel, csrc/semantic_map.hip): three new structs and three new
- *     functions only */
+ *     functions only; likewise OCCD_RAY_MAX_THRESHOLDS, OCCD_RAY_MAX_CLASSES, OCCD_RAY_UNKNOWN_*, OCCD_RAY_COUNTERS,
+ *     OccdRayMetricArgs and occd_ray_metric (K35, the ray-wise counters of RayIoU, csrc/ray_metric.hip): one new struct
+ *     and one new function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1625,6 +1627,59 @@ typedef struct OccdMapSampleWeightedArgs {
     int32_t Bq[9], dq[3];          /* row-major rint(R 2^16), rint(d 2^16)                                           */
 } OccdMapSampleWeightedArgs;
 int occd_map_sample_weighted(const OccdMapSampleWeightedArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K35: score a prediction along sensor rays (occd_ray_metric, csrc/ray_metric.hip): the counters of RayIoU ("Fully
+ * Sparse 3D Occupancy Prediction", Liu et al., 2024).  Additive (OCCD_ABI_VERSION note).  One thread per (frame b,
+ * origin k, ray r), 64 consecutive rays a wave: ray r of origin k of frame b is origins[b, k] + t dirs[r], in grid-voxel
+ * units (voxel (i, j, l) is the cube [i, i + 1) x [j, j + 1) x [l, l + 1)), through pred[b] and target[b], both
+ * (X, Y, Z) with z fastest.
+ * The walk is that of occd_render_voxels in class mode (slab entry, clamped first voxel, boundary times
+ * ((float)(i + (dir > 0)) - origin) * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32
+ * without fma), ONE walk for both volumes: every visited voxel is tested in whichever volume has not hit yet, and the
+ * walk ends when both have hit or the ray leaves the grid -- the voxel sequence depends on the ray alone, so the outcome
+ * is that of two independent casts.  A hit is the first voxel with 0 < label < 255; its depth is the t at which the ray
+ * entered that voxel (0 when the origin lies in it): what occd_render_voxels writes to `depth`.  A non-finite origin
+ * or direction component makes the ray a miss in both volumes.
+ * Target label 255 (unknown): with unknown_mode OCCD_RAY_UNKNOWN_DROP a ray that meets a target voxel 255 before its
+ * target hit is counted in `unknown` and nowhere else but `rays`; with OCCD_RAY_UNKNOWN_PASS 255 is transparent, as it
+ * always is in the prediction.  (2-byte labels above 255 are transparent in both volumes and both modes.)
+ * counts: int64, ADDED to (never zeroed; the caller zeroes it outside a capture or with a fill kernel).  With C =
+ * n_classes and T = n_thresholds, OCCD_RAY_COUNTERS + 2 C + T C + T entries:
+ *   [0] rays       every ray cast, B K N per call
+ *   [1] valid      the target hit a class 1 .. C - 1 (and the ray was not dropped); only these rays are scored
+ *   [2] unknown    rays dropped under OCCD_RAY_UNKNOWN_DROP
+ *   [3] pred_miss  valid rays on which the prediction hit nothing
+ *   [4 + c]                  gt[c]      valid rays whose target hit has class c
+ *   [4 + C + c]              pred[c]    valid rays whose prediction hit has class c < C
+ *   [4 + 2 C + k C + c]      tp[k][c]   valid rays, both hits of class c, fabsf(t_pred - t_target) < thresholds[k]
+ *   [4 + 2 C + T C + k]      tp_geo[k]  valid rays, any prediction hit, fabsf(t_pred - t_target) < thresholds[k]
+ * A hit label >= C (other than 255) reaches no per-class counter: such a target hit leaves the ray out of `valid`, such a
+ * prediction hit on a valid ray is no pred_miss, may count in tp_geo, and counts in no pred[c].  Counters are u32 in LDS
+ * per workgroup, then one integer atomic per non-zero counter: the sums do not depend on the schedule.  No allocation,
+ * no host sync, no memset node (capture-safe).
+ * OCCD_EINVAL before any launch: a NULL argument, NULL pred / target / origins / dirs / counts, non-positive batch,
+ * n_origins, n_rays, X, Y or Z, pred_bytes or target_bytes not 1 or 2, n_thresholds outside 1 .. 4, n_classes outside
+ * 1 .. 32, an unknown_mode other than the two above, X Y Z >= 2^31, batch n_origins n_rays >= 2^31.
+ * ------------------------------------------------------------------------ */
+#define OCCD_RAY_MAX_THRESHOLDS 4
+#define OCCD_RAY_MAX_CLASSES 32
+#define OCCD_RAY_UNKNOWN_DROP 0
+#define OCCD_RAY_UNKNOWN_PASS 1
+#define OCCD_RAY_COUNTERS 4 /* rays, valid, unknown, pred_miss: the scalar counters in front of the per-class ones */
+typedef struct OccdRayMetricArgs {
+    const void* pred;              /* (B, X, Y, Z) predicted labels, pred_bytes each                          */
+    const void* target;            /* (B, X, Y, Z) target labels, target_bytes each                           */
+    const float* origins;          /* (B, K, 3) ray origins, grid-voxel units                                 */
+    const float* dirs;             /* (N, 3) ray directions, shared by every origin and frame                 */
+    int64_t* counts;               /* (OCCD_RAY_COUNTERS + 2 C + T C + T) counters, added to                  */
+    int32_t batch, n_origins, n_rays;
+    int32_t X, Y, Z;
+    int32_t pred_bytes, target_bytes;
+    int32_t n_classes, n_thresholds, unknown_mode;
+    float thresholds[OCCD_RAY_MAX_THRESHOLDS];   /* grid-voxel units: metres / voxel size                    */
+} OccdRayMetricArgs;
+int occd_ray_metric(const OccdRayMetricArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

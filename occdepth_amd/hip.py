@@ -66,6 +66,12 @@ MapMergeArgs = abi.STRUCTS["OccdMapMergeArgs"]
 VisibilityArgs = abi.STRUCTS["OccdVisibilityArgs"]
 MapWeightedArgs = abi.STRUCTS["OccdMapWeightedArgs"]
 MapSampleWeightedArgs = abi.STRUCTS["OccdMapSampleWeightedArgs"]
+RayMetricArgs = abi.STRUCTS["OccdRayMetricArgs"]
+RAY_MAX_THRESHOLDS = abi.CONSTANTS["OCCD_RAY_MAX_THRESHOLDS"]
+RAY_MAX_CLASSES = abi.CONSTANTS["OCCD_RAY_MAX_CLASSES"]
+RAY_UNKNOWN_DROP = abi.CONSTANTS["OCCD_RAY_UNKNOWN_DROP"]
+RAY_UNKNOWN_PASS = abi.CONSTANTS["OCCD_RAY_UNKNOWN_PASS"]
+RAY_COUNTERS = abi.CONSTANTS["OCCD_RAY_COUNTERS"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2258,6 +2264,54 @@ def frame_visibility(labels, view, size, return_hit=False):
     a.X, a.Y, a.Z = (int(d) for d in labels.shape)
     _check(load().occd_frame_visibility(ctypes.byref(a), _stream()), "occd_frame_visibility")
     return (visible, hit) if return_hit else visible
+
+
+def ray_metric_size(n_classes, n_thresholds):
+    """The number of int64 counters occd_ray_metric adds to: rays, valid, unknown, pred_miss, gt[C], pred[C], tp[T][C],
+    tp_geo[T] (the layout is in include/occdepth_amd.h)."""
+    C, T = int(n_classes), int(n_thresholds)
+    return RAY_COUNTERS + 2 * C + T * C + T
+
+
+def ray_metric(pred, target, origins, dirs, counts, thresholds, n_classes, unknown_mode=RAY_UNKNOWN_DROP):
+    """occd_ray_metric (K35): cast rays origins[b, k] + t dirs[r] through pred[b] and target[b] in one walk and add the
+    outcome of every ray to `counts`.  pred, target (B, X, Y, Z) uint8 / int16 / uint16 (the widths may differ); origins
+    (B, K, 3) and dirs (N, 3) float32, grid-voxel units; counts (ray_metric_size(n_classes, len(thresholds)),) int64,
+    added to and never zeroed; thresholds: 1..4 floats in grid-voxel units, by value; unknown_mode RAY_UNKNOWN_DROP /
+    RAY_UNKNOWN_PASS.  All tensors on the GPU and contiguous; no allocation, no host sync.  -> counts.  The contract is
+    in include/occdepth_amd.h."""
+    for t, name in ((pred, "pred"), (target, "target")):
+        if t.dim() != 4 or t.dtype not in _LABEL_BYTES:
+            raise RuntimeError("%s must be a (B, X, Y, Z) uint8 / int16 / uint16 volume, got %s %s" % (name, tuple(t.shape), t.dtype))
+    if target.shape != pred.shape:
+        raise RuntimeError("target %s must have the shape of pred %s" % (tuple(target.shape), tuple(pred.shape)))
+    B, X, Y, Z = (int(d) for d in pred.shape)
+    if origins.dtype != torch.float32 or origins.dim() != 3 or origins.shape[0] != B or origins.shape[2] != 3:
+        raise RuntimeError("origins must be float32 (B, K, 3) with B = %d, got %s %s" % (B, tuple(origins.shape), origins.dtype))
+    if dirs.dtype != torch.float32 or dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise RuntimeError("dirs must be float32 (N, 3), got %s %s" % (tuple(dirs.shape), dirs.dtype))
+    thresholds = [float(t) for t in thresholds]
+    if not 1 <= len(thresholds) <= RAY_MAX_THRESHOLDS:
+        raise RuntimeError("1..%d thresholds, got %d" % (RAY_MAX_THRESHOLDS, len(thresholds)))
+    if not 1 <= int(n_classes) <= RAY_MAX_CLASSES:
+        raise RuntimeError("n_classes must be 1..%d, got %r" % (RAY_MAX_CLASSES, n_classes))
+    size = ray_metric_size(n_classes, len(thresholds))
+    if counts.dtype != torch.int64 or counts.numel() != size:
+        raise RuntimeError("counts must hold %d int64 counters, got %s %s" % (size, tuple(counts.shape), counts.dtype))
+    for t, name in ((target, "target"), (origins, "origins"), (dirs, "dirs"), (counts, "counts")):
+        if t.device != pred.device:
+            raise RuntimeError(f"{name} is on {t.device}, pred on {pred.device}")
+    a = RayMetricArgs()
+    a.pred, a.target = _ptr(pred, "pred"), _ptr(target, "target")
+    a.origins, a.dirs, a.counts = _ptr(origins, "origins"), _ptr(dirs, "dirs"), _ptr(counts, "counts")
+    a.batch, a.n_origins, a.n_rays = B, int(origins.shape[1]), int(dirs.shape[0])
+    a.X, a.Y, a.Z = X, Y, Z
+    a.pred_bytes, a.target_bytes = _LABEL_BYTES[pred.dtype], _LABEL_BYTES[target.dtype]
+    a.n_classes, a.n_thresholds, a.unknown_mode = int(n_classes), len(thresholds), int(unknown_mode)
+    for i, t in enumerate(thresholds):
+        a.thresholds[i] = t
+    _check(load().occd_ray_metric(ctypes.byref(a), _stream()), "occd_ray_metric")
+    return counts
 
 
 # ----------------------------------------------------------------------------- temporal fusion (csrc/fuse.hip)

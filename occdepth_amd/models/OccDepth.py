@@ -186,6 +186,18 @@ class OccDepth(_Base):
                                      exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0",
                                      gather=env("OCCDEPTH_MAP_GATHER", "1") != "0", save_maps=env("OCCDEPTH_MAP_SAVE", "0") == "1",
                                      visibility=tuple(int(w) for w in weights.split(",")) if weights else None)
+        # RayIoU of the test / validation predictions (ray_metric.py, K35), OFF by default: `enable_ray_metrics()` -- or
+        # OCCDEPTH_RAY_METRIC=1 [OCCDEPTH_RAY_ORIGINS=<n>[,<step>]] [OCCDEPTH_RAY_POSES=<.../dataset/sequences>] (falls back
+        # to OCCDEPTH_FUSE_POSES) [OCCDEPTH_RAY_UNKNOWN=pass] in the environment of an unmodified scripts/eval.py.  Off:
+        # nothing is imported, allocated or launched.  Every other method reaches it through getattr(self, "ray_metrics", None).
+        self.ray_metrics = None
+        if env("OCCDEPTH_RAY_METRIC", "0") == "1":
+            spec = env("OCCDEPTH_RAY_ORIGINS", "1").split(",")
+            if len(spec) not in (1, 2) or not all(w.strip().isdigit() for w in spec):
+                raise ValueError("OCCDEPTH_RAY_ORIGINS is <n>[,<step>], got %r" % env("OCCDEPTH_RAY_ORIGINS"))
+            self.enable_ray_metrics(origins=int(spec[0]), origin_step=int(spec[1]) if len(spec) == 2 else 5,
+                                    poses_root=env("OCCDEPTH_RAY_POSES", "") or env("OCCDEPTH_FUSE_POSES", "") or None,
+                                    unknown=env("OCCDEPTH_RAY_UNKNOWN", "drop") or "drop")
         self.init_2d_to_3d_trans(config)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
@@ -786,7 +798,96 @@ class OccDepth(_Base):
         metric = self.fused_metrics.get(step_type)
         if metric is None:
             metric = self.fused_metrics[step_type] = SSCMetrics(self.n_classes)
-        metric.add_batch(torch.stack(labels), target)
+        labels = torch.stack(labels)
+        metric.add_batch(labels, target)
+        return labels
+
+    # ---------------------------------------------------------------- RayIoU along sensor rays (ray_metric.py)
+    def enable_ray_metrics(self, thresholds_m=(1, 2, 4), origins=1, origin_step=5, poses_root=None, unknown="drop",
+                           **direction_kwargs):
+        """Score every test / validation frame along sensor rays as well (ray_metric.RayMetrics, K35: RayIoU of "Fully
+        Sparse 3D Occupancy Prediction", Liu et al., 2024).  The rays of ray_metric.lidar_directions(**direction_kwargs)
+        (a 64-beam stand-in fan, not a sensor's calibration table) are cast from the velodyne origin through the arg-max of
+        the unfused logits and through the target in one launch per step; a ray is a true positive of class c at
+        threshold tau when both hit class c and the depths differ by less than tau.  `val_ray/RayIoU`, `val_ray/RayIoU@<tau>`
+        per threshold and `val_ray/RayIoU_geo` (class-agnostic, mean over the thresholds) are logged and `test_epoch_end`
+        prints a `test_ray======` block with the per-class table and the ray tallies; with temporal fusion on its fused
+        labels are scored into a second metric (`val_fused_ray/*`, `test_fused_ray======`).  The ordinary metrics are
+        untouched.  unknown: "drop" (a ray that meets a target voxel 255 before its target hit is left out) or "pass"
+        (255 is seen through).  origins > 1: the sensor positions of the frames t, t + origin_step, ... (up to `origins`,
+        those inside the grid; ray_metric.trajectory_origins) are ray origins too, which scores surfaces hidden from the
+        current position; that needs the ego-motion, <poses_root>/<sequence>/poses.txt and calib.txt.  With
+        metrics_allreduce the counters are summed over the ranks before the statistics.  No RayIoU of a trained model is
+        measured (no checkpoint and no dataset where this was built)."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("ray metrics cast a lidar's rays from the velodyne origin and are wired for the "
+                                      "SemanticKITTI geometry only; a %s model has no sensor origin to cast from" % self.dataset)
+        if int(origins) < 1 or int(origin_step) < 1:
+            raise ValueError("origins and origin_step must be >= 1, got %r, %r" % (origins, origin_step))
+        if int(origins) > 1 and not poses_root:
+            raise ValueError("ray metrics from more than one origin need the sequences directory (poses_root / "
+                             "OCCDEPTH_RAY_POSES, or OCCDEPTH_FUSE_POSES): <root>/<sequence>/poses.txt and calib.txt")
+        if unknown not in ("drop", "pass"):
+            raise ValueError("unknown is 'drop' or 'pass' (OCCDEPTH_RAY_UNKNOWN), got %r" % (unknown,))
+        thresholds_m = tuple(float(t) for t in thresholds_m)
+        if not 1 <= len(thresholds_m) <= 4 or any(not t > 0.0 for t in thresholds_m):
+            raise ValueError("1..4 positive thresholds in metres, got %r" % (thresholds_m,))
+        self.ray_metrics = {"thresholds_m": thresholds_m, "origins": int(origins), "origin_step": int(origin_step),
+                            "poses_root": str(poses_root) if poses_root else None, "unknown": unknown,
+                            "directions": dict(direction_kwargs), "dirs": None, "poses": {}, "metrics": {}, "fused": {}}
+        return self
+
+    def _ray_step(self, step_type, batch, ssc_pred, target, fused_labels=None):
+        """Cast the rays through every batch item's arg-max labels (and the fused labels, if any) and its target."""
+        from .. import hip, ray_metric
+        st = self.ray_metrics
+        ssc_pred = ssc_pred.detach()
+        B = ssc_pred.shape[0]
+        dims = tuple(int(d) for d in ssc_pred.shape[2:])
+        vs = 0.2 * float(self.full_scene_size[0]) / float(dims[0])
+        origin = self._kitti_origin(batch)
+        if st["dirs"] is None:
+            st["dirs"] = ray_metric.lidar_directions(**st["directions"])
+        if st["origins"] > 1:                                            # every pose first: a refusal launches nothing
+            from .. import fuse
+            origins = []
+            for i in range(B):
+                seq = str(batch["sequence"][i])
+                frame = int(batch["frame_id"][i])
+                poses = st["poses"].get(seq)
+                if poses is None:
+                    poses = st["poses"][seq] = fuse.read_kitti_poses(os.path.join(st["poses_root"], seq))
+                if frame not in poses:
+                    raise KeyError("sequence %s has no pose for frame %d (%s)" % (seq, frame, os.path.join(st["poses_root"], seq, "poses.txt")))
+                origins.append(ray_metric.trajectory_origins(poses, frame, st["origins"], st["origin_step"], origin, vs, dims))
+        else:
+            origins = [ray_metric.sensor_origin(origin, vs)[None]] * B
+        pred = hip.argmax_labels_u16(ssc_pred.float())                   # (B, X, Y, Z) uint16 bits, the unfused logits
+        gt = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).reshape((B,) + dims)
+        for store, labels in ((st["metrics"], pred), (st["fused"], fused_labels)):
+            if labels is None:
+                continue
+            metric = store.get(step_type)
+            if metric is None:
+                metric = store[step_type] = ray_metric.RayMetrics(self.n_classes, vs, st["dirs"], st["thresholds_m"], st["unknown"])
+            if len(set(len(o) for o in origins)) == 1:                   # one launch for the batch
+                metric.add_batch(labels, gt, torch.stack(list(origins)))
+            else:                                                        # frames kept different numbers of origins
+                for i in range(B):
+                    metric.add_batch(labels[i:i + 1], gt[i:i + 1], origins[i][None])
+
+    def _ray_epoch_end(self, step_type):
+        """-> [(prefix, statistics)] of the ray metrics of `step_type` that counted something, reset."""
+        out = []
+        for name, store in (("ray", self.ray_metrics["metrics"]), ("fused_ray", self.ray_metrics["fused"])):
+            metric = store.get(step_type)
+            if metric is None:
+                continue
+            if self.metrics_allreduce:
+                metric.allreduce_()
+            out.append(("%s_%s" % (step_type, name), metric.get_stats()))
+            metric.reset()
+        return out
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
     def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
@@ -1301,8 +1402,11 @@ class OccDepth(_Base):
                 metric.add_batch(ssc_pred.detach().argmax(1).cpu().numpy(), target.cpu().numpy())
         if self.eval_report is not None and step_type in ("test", "val"):
             self._report_count(step_type, batch, ssc_pred, target)
+        fused_labels = None
         if self.temporal_fusion is not None and step_type in ("test", "val"):
-            self._fuse_step(step_type, batch, ssc_pred, target)
+            fused_labels = self._fuse_step(step_type, batch, ssc_pred, target)
+        if getattr(self, "ray_metrics", None) is not None and step_type in ("test", "val"):
+            self._ray_step(step_type, batch, ssc_pred, target, fused_labels)
         if getattr(self, "semantic_map", None) is not None and step_type in ("test", "val"):
             self._map_step(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
@@ -1655,6 +1759,12 @@ class OccDepth(_Base):
             if stats is not None:
                 self.log("val_mapped/mIoU", stats["iou_ssc_mean"], sync_dist=True)
                 self.log("val_mapped/IoU", stats["iou"], sync_dist=True)
+        if getattr(self, "ray_metrics", None) is not None:
+            for prefix, stats in self._ray_epoch_end("val"):
+                self.log(prefix + "/RayIoU", stats["RayIoU"], sync_dist=True)
+                for t, v in zip(stats["thresholds_m"], stats["ray_miou"]):
+                    self.log("%s/RayIoU@%g" % (prefix, t), v, sync_dist=True)
+                self.log(prefix + "/RayIoU_geo", stats["ray_iou_geo"].mean(), sync_dist=True)
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -1685,6 +1795,10 @@ class OccDepth(_Base):
                     print("class IoU: {}, ".format(classes))
                     print(" ".join(["{:.4f}, "] * len(classes)).format(*(stats["iou_ssc"] * 100).tolist()))
                     print("mIoU={:.4f}".format(stats["iou_ssc_mean"] * 100))
+        if getattr(self, "ray_metrics", None) is not None:
+            from ..ray_metric import format_report
+            for prefix, stats in self._ray_epoch_end("test"):
+                print("\n".join(format_report(stats, classes, prefix)))
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

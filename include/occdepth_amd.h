@@ -89,7 +89,9 @@ extern "C" {
  *     occd_map_sample_weighted (votes of a weight per voxel, csrc/semantic_map.hip): three new structs and three new
  *     functions only; likewise OCCD_RAY_MAX_THRESHOLDS, OCCD_RAY_MAX_CLASSES, OCCD_RAY_UNKNOWN_*, OCCD_RAY_COUNTERS,
  *     OccdRayMetricArgs and occd_ray_metric (K35, the ray-wise counters of RayIoU, csrc/ray_metric.hip): one new struct
- *     and one new function only */
+ *     and one new function only; likewise OCCD_RENDER_LOSS_ABS / _REL, OccdRenderLossArgs, occd_render_opacity,
+ *     occd_render_depth_fwd, occd_render_depth_bwd_rays and occd_render_depth_bwd_voxels (K36, the depth-rendering loss,
+ *     csrc/render_loss.hip): one new struct and four new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1680,6 +1682,89 @@ typedef struct OccdRayMetricArgs {
     float thresholds[OCCD_RAY_MAX_THRESHOLDS];   /* grid-voxel units: metres / voxel size                    */
 } OccdRayMetricArgs;
 int occd_ray_metric(const OccdRayMetricArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K36: the depth-rendering loss (csrc/render_loss.hip).  Additive (OCCD_ABI_VERSION note).  The soft occupancy of the
+ * logits is alpha-composited along one camera's pixel rays into an expected depth image d^, which is held to a metric
+ * depth map D; forward and backward in four kernels that share one argument struct (every kernel reads the fields it
+ * names below and ignores the rest).
+ *
+ * Volume: logits z, element (b, c, s) at b*s_b + c*s_c + s*s_v floats, the layouts of occd_ssc_loss_stats_*_strided
+ * ((s_c, s_v) = (S, 1) planes, or (1, cs) channels-last rows with cs % 4 == 0, s_b % 4 == 0 and a 16-byte aligned base,
+ * read with 16-byte loads); S = X Y Z, voxel s = (x*Y + y)*Z + z; class 0 is empty; 2 <= C <= 32.
+ * Opacity: a_v = 1 - softmax(z_v)[0], formed as min(1, sum_{c > 0} p_c) so that it does not cancel when p_0 -> 1.  The
+ * opacity buffer holds it in a SIGNED form that keeps the relative precision of both a and 1 - a in 4 bytes: s = a where
+ * a <= 1/2, s = -p_0 where a > 1/2 (-0.0f where p_0 < 2^-25: a rounds to 1, the voxel is opaque); the ray passes read
+ * a = s or 1 + s and 1 - a = 1 - s or -s by the sign BIT.  (1 - a formed from a float32 a near 1 carries ulp(1) / (1 - a) of
+ * relative error into every transmittance behind the voxel and into the voxel's own gradient: 6e-6 at a = 0.99.)  A
+ * buffer of plain non-negative opacities is read as what it says.
+ * Rays: ray (i, j) of frame b is pixel (u, v) = (off_u + stride*i, off_v + stride*j) of the (H, W) image of view b
+ * (OccdRenderView, 18 floats): origin and direction are formed from (float)u + 0.5f, (float)v + 0.5f exactly as
+ * occd_render_voxels forms them, so a strided pass walks rows off_v::stride and columns off_u::stride of the full
+ * pass's rays bit for bit.  h = ceil((H - off_v) / stride), w = ceil((W - off_u) / stride), h*w <= 2^21.  t along a ray
+ * is whatever the view makes it (camera depth in metres for render.camera_view).
+ * Walk: that of occd_render_voxels (slab entry, clamped first voxel, boundary times ((float)(i + (dir > 0)) - origin) *
+ * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32 without fma).  It visits voxels v_1 .. v_n
+ * with entry depths t_1 <= .. <= t_n (t_1 = the slab entry, 0 when the origin lies inside) and ends when the ray leaves
+ * the grid or the next entry depth is >= max_depth (no voxel at all when t_1 >= max_depth).  t_end = min(t_far,
+ * max_depth), t_far the slab exit; max_depth for a ray that misses the grid (it renders empty).
+ * Compositing, float32: T_1 = 1, w_i = T_i a_i, T_{i+1} = T_i (1 - a_i), d^ = sum_i w_i t_i + T_{n+1} t_end (summed in
+ * walk order); the rendered opacity is 1 - T_{n+1}.  The depth of a voxel is its ENTRY t: with hard logits d^ is the
+ * depth occd_render_voxels reports, bit for bit.  No path-length weighting.  The walk may stop once T is exactly 0:
+ * everything behind is weighted by an exact zero.
+ * Target: gt_depth element (b, v, u) at b*d_b + v*d_h + u*d_w floats (read in place at the ray's pixel, no resampled
+ * copy), 0 = no measurement.  A ray is valid when it passes the slab test, D is finite, 0 < D <= max_depth and D > t_1.
+ * D_r = min(D, t_end).  l_r = omega_r |d^_r - D_r|, omega_r = 1 (OCCD_RENDER_LOSS_ABS) or 1 / max(D_r, 0.25)
+ * (OCCD_RENDER_LOSS_REL; the floor bounds the fixed-point sums below).
+ *   stats[0] = sum over valid rays of l_r (Q24: (u64)(l_r 2^24 + 0.5) each), stats[1] = #valid rays; zeroed by the
+ *   forward with a kernel; L = stats[0] / 2^24 / max(1, stats[1]).  LDS first, one integer atomic per workgroup.
+ * Backward, without a division: with pre_k = sum_{i <= k} w_i t_i,  d d^ / d a_k * (1 - a_k) = T_{k+1} t_k - (d^ - pre_k),
+ * and every d a_v / d z_{v,c} carries the factor p_0 = 1 - a_v.  The ray pass re-walks each valid ray in forward order
+ * with the saved d^ and adds  omega_r sign(d^_r - D_r) [T_{k+1} t_k - (d^_r - pre_k)]  (sign(0) = 0; float32, then
+ * rint(x 2^32)) into hsum (B, S) int64 with one 8-byte integer atomic per visited voxel, zero contributions skipped:
+ * |term| <= 4 * 128 = 2^9 over at most 2^21 rays, |H| < 2^62.  The voxel pass writes
+ *   grad(b, c, s) = gscale[0] * H_v 2^-32 * p_c  (c > 0),   -gscale[0] * H_v 2^-32 * a_v  (c = 0)
+ * to element b*g_b + c*g_c + s*g_v (channels-last rows: channels [C, g_pad) written as zeros, as
+ * occd_ssc_loss_stats_bwd_strided) and stores 0 back into hsum: zero it once at allocation and it is clean after every
+ * backward, in captured replays too.  gscale: device scalar g / max(1, #valid).  Integer sums: loss and gradient do not
+ * depend on the schedule.  No allocation, no host sync, no memset node (capture-safe).
+ *   occd_render_opacity           reads logits (+ strides, C);                         writes opacity (B, S), signed form
+ *   occd_render_depth_fwd         reads opacity, views, gt_depth (NULL: render only, stats NULL too);
+ *                                 writes depth (B, h, w), alpha (B, h, w), stats[2]
+ *   occd_render_depth_bwd_rays    reads opacity, views, gt_depth, depth;                adds into hsum
+ *   occd_render_depth_bwd_voxels  reads logits, hsum, gscale;                           writes grad, zeroes hsum
+ * OCCD_EINVAL before any launch: a NULL argument or a NULL pointer the kernel reads or writes, batch outside 1 .. 256,
+ * non-positive X, Y or Z, X Y Z >= 2^31, C outside 2 .. 32, strides the strided ssc kernels would refuse, non-positive H,
+ * W or stride, an offset outside [0, stride) or outside the image, h or w that are not the two quotients above,
+ * h*w > 2^21, max_depth not in (0, 128], a norm other than the two above, negative depth-map strides, gt_depth without
+ * stats or stats without gt_depth, a g_pad the ssc backward would refuse.
+ * ------------------------------------------------------------------------ */
+#define OCCD_RENDER_LOSS_ABS 0
+#define OCCD_RENDER_LOSS_REL 1
+typedef struct OccdRenderLossArgs {
+    const float* logits;           /* (B, C, S) through (s_b, s_c, s_v)                                       */
+    float* opacity;                /* (B, S), the signed form                                                 */
+    const float* views;            /* (B, 18): one OccdRenderView per frame                                   */
+    const float* gt_depth;         /* (B, H, W) through (d_b, d_h, d_w), or NULL                              */
+    float* depth;                  /* (B, h, w) d^: written by the forward, read by the backward ray pass     */
+    float* alpha;                  /* (B, h, w) rendered opacity 1 - T_{n+1}                                  */
+    int64_t* stats;                /* [sum of l_r (Q24), #valid rays]                                         */
+    int64_t* hsum;                 /* (B, S) H, Q32                                                           */
+    const float* gscale;           /* device scalar g / max(1, #valid)                                        */
+    float* grad;                   /* d L / d logits through (g_b, g_c, g_v)                                  */
+    int64_t s_b, s_c, s_v;
+    int64_t g_b, g_c, g_v;
+    int64_t d_b, d_h, d_w;
+    int32_t batch, C, X, Y, Z;
+    int32_t H, W, h, w;
+    int32_t stride, off_u, off_v;
+    int32_t g_pad, norm;
+    float max_depth;
+} OccdRenderLossArgs;
+int occd_render_opacity(const OccdRenderLossArgs* a, void* stream);
+int occd_render_depth_fwd(const OccdRenderLossArgs* a, void* stream);
+int occd_render_depth_bwd_rays(const OccdRenderLossArgs* a, void* stream);
+int occd_render_depth_bwd_voxels(const OccdRenderLossArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

@@ -72,6 +72,9 @@ RAY_MAX_CLASSES = abi.CONSTANTS["OCCD_RAY_MAX_CLASSES"]
 RAY_UNKNOWN_DROP = abi.CONSTANTS["OCCD_RAY_UNKNOWN_DROP"]
 RAY_UNKNOWN_PASS = abi.CONSTANTS["OCCD_RAY_UNKNOWN_PASS"]
 RAY_COUNTERS = abi.CONSTANTS["OCCD_RAY_COUNTERS"]
+RenderLossArgs = abi.STRUCTS["OccdRenderLossArgs"]
+RENDER_LOSS_ABS = abi.CONSTANTS["OCCD_RENDER_LOSS_ABS"]
+RENDER_LOSS_REL = abi.CONSTANTS["OCCD_RENDER_LOSS_REL"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -3032,6 +3035,188 @@ def depth_bce_grad(prob, gt, cell, d_off, d_step, gscale):
     grad = torch.empty((Bn, D, h, w), dtype=torch.float32, device=prob.device)
     _check(load().occd_depth_bce_grad(prob.data_ptr(), gt.data_ptr(), gscale.data_ptr(), grad.data_ptr(), Bn, D, h, w, sh, sw,
                                       int(cell), pb, float(d_off), float(d_step), _stream()), "occd_depth_bce_grad")
+    return grad
+
+
+# ---- depth-rendering loss (K36, csrc/render_loss.hip) ---------------------------------------------------------------
+RENDER_LOSS_NORMS = {"abs": RENDER_LOSS_ABS, "rel": RENDER_LOSS_REL}
+RENDER_LOSS_MAX_RAYS = 1 << 21           # rays per frame: the bound of the Q32 sums in H
+RENDER_LOSS_MAX_DEPTH = 128.0
+RENDER_LOSS_MAX_BATCH = 256
+RENDER_LOSS_Q32 = 4294967296.0
+
+
+def render_loss_usable(logits, gt_depth=None):
+    """The rendering loss runs on the K36 kernels: float32 GPU logits (B, C, X, Y, Z) with 2 <= C <= 32, and a GPU depth map
+    when there is one (a missing library is an error there, as everywhere).  CPU tensors and other dtypes take the torch
+    formulation of loss/render_loss.py."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32):
+        return False
+    if logits.dim() != 5 or not 2 <= logits.shape[1] <= 32 or logits.shape[0] > RENDER_LOSS_MAX_BATCH:
+        return False
+    return gt_depth is None or gt_depth.is_cuda
+
+
+def render_loss_rays(image_hw, stride=1, offset=(0, 0)):
+    """(h, w) of the ray image: pixel (u, v) = (ou + stride i, ov + stride j), h = ceil((H - ov) / stride), w likewise.
+    Raises on a geometry the kernels refuse (no GPU involved)."""
+    H, W = int(image_hw[0]), int(image_hw[1])
+    s, ou, ov = int(stride), int(offset[0]), int(offset[1])
+    if H < 1 or W < 1:
+        raise RuntimeError("the depth image must be at least 1 x 1, got %r" % (tuple(image_hw),))
+    if s < 1:
+        raise RuntimeError("stride must be >= 1, got %r" % (stride,))
+    if not (0 <= ou < s and 0 <= ov < s):
+        raise RuntimeError("offsets must lie in [0, stride), got %r at stride %d" % (tuple(offset), s))
+    if ou >= W or ov >= H:
+        raise RuntimeError("offset %r lies outside the %d x %d image" % (tuple(offset), H, W))
+    h, w = -(-(H - ov) // s), -(-(W - ou) // s)
+    if h * w > RENDER_LOSS_MAX_RAYS:
+        raise RuntimeError("%d x %d rays per frame: at most 2^21 (raise the stride)" % (h, w))
+    return h, w
+
+
+def _render_loss_volume(a, logits):
+    if not torch.is_tensor(logits) or logits.dtype != torch.float32 or logits.dim() != 5:
+        raise RuntimeError("logits must be float32 (B, C, X, Y, Z)")
+    B, C, X, Y, Z = (int(d) for d in logits.shape)
+    if not 2 <= C <= 32:
+        raise RuntimeError("2 <= C <= 32 classes (class 0 is empty), got %d" % C)
+    if not 1 <= B <= RENDER_LOSS_MAX_BATCH:
+        raise RuntimeError("1 <= B <= %d frames, got %d" % (RENDER_LOSS_MAX_BATCH, B))
+    if X * Y * Z >= 1 << 31:
+        raise RuntimeError("X Y Z must stay below 2^31")
+    a.batch, a.C, a.X, a.Y, a.Z = B, C, X, Y, Z
+    return B, C, X * Y * Z
+
+
+def _render_loss_rays(a, opacity, views, dims, image_hw, stride, offset, max_depth, gt_depth, norm):
+    """Fill and check everything the two ray passes share -> (B, h, w)."""
+    X, Y, Z = (int(d) for d in dims)
+    if min(X, Y, Z) < 1 or X * Y * Z >= 1 << 31:
+        raise RuntimeError("dims must be three positive extents with X Y Z < 2^31, got %r" % (tuple(dims),))
+    if not torch.is_tensor(opacity) or opacity.dtype != torch.float32 or opacity.dim() != 2 or opacity.shape[1] != X * Y * Z:
+        raise RuntimeError("opacity must be float32 (B, X Y Z)")
+    B = int(opacity.shape[0])
+    if not 1 <= B <= RENDER_LOSS_MAX_BATCH:
+        raise RuntimeError("1 <= B <= %d frames, got %d" % (RENDER_LOSS_MAX_BATCH, B))
+    if not torch.is_tensor(views) or views.dtype != torch.float32 or tuple(views.shape) != (B, 18):
+        raise RuntimeError("views must be float32 (B, 18) with B = %d" % B)
+    h, w = render_loss_rays(image_hw, stride, offset)
+    md = float(max_depth)
+    if not 0.0 < md <= RENDER_LOSS_MAX_DEPTH:
+        raise RuntimeError("max_depth must lie in (0, %g], got %r" % (RENDER_LOSS_MAX_DEPTH, max_depth))
+    if norm not in RENDER_LOSS_NORMS:
+        raise RuntimeError("norm must be 'abs' or 'rel', got %r" % (norm,))
+    H, W = int(image_hw[0]), int(image_hw[1])
+    if gt_depth is not None:
+        if gt_depth.dim() == 4 and gt_depth.shape[1] == 1:
+            gt_depth = gt_depth[:, 0]
+        if gt_depth.dtype != torch.float32 or tuple(gt_depth.shape) != (B, H, W):
+            raise RuntimeError("gt_depth must be float32 (B, 1, H, W) or (B, H, W) with (B, H, W) = %r, got %s %s"
+                               % ((B, H, W), tuple(gt_depth.shape), gt_depth.dtype))
+        if min(gt_depth.stride()) < 0:
+            raise RuntimeError("gt_depth needs non-negative strides")
+        if not gt_depth.is_cuda:
+            raise RuntimeError("gt_depth must live on the GPU (the HIP kernels have no CPU path)")
+        a.gt_depth = gt_depth.data_ptr()
+        a.d_b, a.d_h, a.d_w = (int(s) for s in gt_depth.stride())
+    a.opacity, a.views = _ptr(opacity, "opacity"), _ptr(views, "views")
+    a.batch, a.X, a.Y, a.Z = B, X, Y, Z
+    a.H, a.W, a.h, a.w = H, W, h, w
+    a.stride, a.off_u, a.off_v = int(stride), int(offset[0]), int(offset[1])
+    a.max_depth, a.norm = md, RENDER_LOSS_NORMS[norm]
+    return B, h, w
+
+
+def render_opacity_decode(signed):
+    """The opacity a of occd_render_opacity's signed form (a where a <= 1/2, -(1 - a) above, told apart by the sign bit)."""
+    return torch.where(torch.signbit(signed), 1.0 + signed, signed)
+
+
+def render_opacity(logits):
+    """occd_render_opacity: a = 1 - softmax(logits)[0] per voxel -> (B, X Y Z) float32 in the signed form the ray passes read
+    (`render_opacity_decode`; include/occdepth_amd.h says why).  logits (B, C, X, Y, Z) float32, read in place as planes or
+    as channels-last rows (`_logit_layout`); anything else is made contiguous."""
+    a = RenderLossArgs()
+    B, C, S = _render_loss_volume(a, logits)
+    if not logits.is_cuda:
+        raise RuntimeError("logits must live on the GPU (the HIP kernels have no CPU path)")
+    lay = _logit_layout(logits)
+    if lay is None:
+        logits = logits.contiguous()
+        lay = (C * S, S, 1)
+    a.logits = logits.data_ptr()
+    a.s_b, a.s_c, a.s_v = lay
+    out = torch.empty((B, S), dtype=torch.float32, device=logits.device)
+    a.opacity = out.data_ptr()
+    _check(load().occd_render_opacity(ctypes.byref(a), _stream()), "occd_render_opacity")
+    return out
+
+
+def render_depth_fwd(opacity, views, dims, image_hw, stride=1, offset=(0, 0), max_depth=RENDER_LOSS_MAX_DEPTH, gt_depth=None,
+                     norm="abs"):
+    """occd_render_depth_fwd: composite `opacity` (B, X Y Z; `render_opacity`'s signed form or plain values) along the rays of `views` (B, 18) -> (depth (B, h, w), rendered
+    opacity (B, h, w), stats).  With gt_depth ((B, 1, H, W) / (B, H, W) float32, read in place through its strides):
+    stats = int64 [sum of the per-ray loss (Q24), #valid rays]; without: stats is None.  Contract: include/occdepth_amd.h."""
+    a = RenderLossArgs()
+    B, h, w = _render_loss_rays(a, opacity, views, dims, image_hw, stride, offset, max_depth, gt_depth, norm)
+    depth = torch.empty((B, h, w), dtype=torch.float32, device=opacity.device)
+    alpha = torch.empty((B, h, w), dtype=torch.float32, device=opacity.device)
+    stats = torch.empty(2, dtype=torch.int64, device=opacity.device) if gt_depth is not None else None
+    a.depth, a.alpha = depth.data_ptr(), alpha.data_ptr()
+    if stats is not None:
+        a.stats = stats.data_ptr()
+    _check(load().occd_render_depth_fwd(ctypes.byref(a), _stream()), "occd_render_depth_fwd")
+    return depth, alpha, stats
+
+
+def render_depth_bwd_rays(opacity, views, dims, image_hw, stride, offset, max_depth, gt_depth, norm, depth, hsum):
+    """occd_render_depth_bwd_rays: re-walk the valid rays with the forward's `depth` and add every visited voxel's term into
+    hsum (B, X Y Z) int64 (Q32; zeroed once by the caller, cleaned by `render_depth_bwd_voxels`) -> hsum."""
+    a = RenderLossArgs()
+    if gt_depth is None:
+        raise RuntimeError("the backward ray pass needs gt_depth")
+    B, h, w = _render_loss_rays(a, opacity, views, dims, image_hw, stride, offset, max_depth, gt_depth, norm)
+    if not torch.is_tensor(depth) or depth.dtype != torch.float32 or tuple(depth.shape) != (B, h, w):
+        raise RuntimeError("depth must be the forward's float32 (B, h, w) = %r image" % ((B, h, w),))
+    if not torch.is_tensor(hsum) or hsum.dtype != torch.int64 or tuple(hsum.shape) != tuple(opacity.shape):
+        raise RuntimeError("hsum must be int64 of the opacity's shape %r" % (tuple(opacity.shape),))
+    a.depth, a.hsum = _ptr(depth, "depth"), _ptr(hsum, "hsum")
+    _check(load().occd_render_depth_bwd_rays(ctypes.byref(a), _stream()), "occd_render_depth_bwd_rays")
+    return hsum
+
+
+def render_depth_bwd_voxels(logits, hsum, gscale):
+    """occd_render_depth_bwd_voxels: d L / d logits from H, in the logits' layout (channels-last logits get a (B, C, ...) view
+    of zero-padded channels-last rows, as `ssc_loss_grad`); hsum is zero afterwards.  gscale: one-element float32 device
+    tensor g / max(1, #valid rays)."""
+    a = RenderLossArgs()
+    B, C, S = _render_loss_volume(a, logits)
+    if not torch.is_tensor(hsum) or hsum.dtype != torch.int64 or tuple(hsum.shape) != (B, S):
+        raise RuntimeError("hsum must be int64 (B, X Y Z) = %r" % ((B, S),))
+    if not torch.is_tensor(gscale) or gscale.dtype != torch.float32 or gscale.numel() != 1:
+        raise RuntimeError("gscale must be a one-element float32 GPU tensor")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must live on the GPU (the HIP kernels have no CPU path)")
+    lay = _logit_layout(logits)
+    if lay is None:
+        logits = logits.contiguous()
+        lay = (C * S, S, 1)
+    if lay[1] == 1:
+        cs = round_up(C, 8)
+        rows = torch.empty((B,) + tuple(logits.shape[2:]) + (cs,), dtype=torch.float32, device=logits.device)
+        grad = rows[..., :C].permute(0, 4, 1, 2, 3)
+        glay, gpad = (S * cs, 1, cs), cs
+    else:
+        grad = torch.empty_like(logits)
+        glay, gpad = lay, 0
+    a.logits, a.grad = logits.data_ptr(), grad.data_ptr()
+    a.hsum, a.gscale = _ptr(hsum, "hsum"), _ptr(gscale, "gscale")
+    a.s_b, a.s_c, a.s_v = lay
+    a.g_b, a.g_c, a.g_v = glay
+    a.g_pad = gpad
+    _check(load().occd_render_depth_bwd_voxels(ctypes.byref(a), _stream()), "occd_render_depth_bwd_voxels")
     return grad
 
 

@@ -199,6 +199,20 @@ class OccDepth(_Base):
                                     poses_root=env("OCCDEPTH_RAY_POSES", "") or env("OCCDEPTH_FUSE_POSES", "") or None,
                                     unknown=env("OCCDEPTH_RAY_UNKNOWN", "drop") or "drop")
         self.init_2d_to_3d_trans(config)
+        # `enable_render_loss()` -- or OCCDEPTH_RENDER_LOSS=<weight>[,<stride>] in the environment of an unmodified
+        # scripts/train.py: the depth-rendering loss (loss/render_loss.py, K36) -- `ssc_logit` composited along the left
+        # camera's pixel rays into an expected depth image, held to the step's `gt_depth` (the batch's, or the one
+        # `enable_stereo_depth` matches) -- is added to the train / val loss.  Off: nothing is imported, allocated or launched.
+        self.render_loss = None
+        if env("OCCDEPTH_RENDER_LOSS", "0") not in ("", "0"):
+            spec = env("OCCDEPTH_RENDER_LOSS").split(",")
+            try:
+                if len(spec) > 2:
+                    raise ValueError
+                weight, stride = float(spec[0]), int(spec[1]) if len(spec) > 1 else 4
+            except ValueError:
+                raise ValueError("OCCDEPTH_RENDER_LOSS is <weight>[,<stride>], got %r" % env("OCCDEPTH_RENDER_LOSS")) from None
+            self.enable_render_loss(weight=weight, stride=stride)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
         if self.dataset == "kitti":
@@ -1204,6 +1218,70 @@ class OccDepth(_Base):
             ida = (torch.stack([t.to(dev) for t in ida]) if isinstance(ida, (list, tuple)) else ida.to(dev)).to(torch.float32)
         return stereo.stereo_depth(pair, k, E, ida=ida, **self.gpu_stereo)
 
+    # ---------------------------------------------------------------- depth-rendering loss (K36)
+    def enable_render_loss(self, weight=1.0, stride=4, max_depth=None, norm="abs"):
+        """Add `weight` x the depth-rendering loss (loss/render_loss.py: csrc/render_loss.hip on the GPU) to the train and val
+        loss of every step that has a `gt_depth` -- the batch's, or the one `enable_stereo_depth` matches: `ssc_logit`'s
+        soft occupancy is alpha-composited along every `stride`-th pixel ray of the left camera into an expected depth
+        image and held to `gt_depth` (|d^ - D|, or that over D with norm="rel"), over the rays that have a measurement
+        within `max_depth` metres (default: the upper depth bound of the dataset's FLoSP-Depth configuration; at most 128).
+        Logged: <step_type>/loss_render (weighted, like the other terms); in val also <step_type>/render_abs_rel and
+        <step_type>/render_rmse of the rendered depth over the valid rays.  Frames the loader mirrored
+        (ida_mats[b, 0, 0, 0] < 0) are rendered through the mirrored view, chosen on the device: no host read, so the
+        captured fast training step includes the loss.  SemanticKITTI geometry only.  A step without `gt_depth` logs and
+        adds nothing.  The same switch from the environment: OCCDEPTH_RENDER_LOSS=<weight>[,<stride>]."""
+        if self.dataset != "kitti":
+            raise NotImplementedError("the depth-rendering loss is wired for the SemanticKITTI camera geometry only, not "
+                                      "for a %s model" % self.dataset)
+        from ..loss.render_loss import RenderDepthLoss
+        if max_depth is None:
+            max_depth = float(flosp_depth_conf_map[self.dataset]["d_bound"][1])
+        if not float(weight) > 0.0:
+            raise ValueError("enable_render_loss: weight must be > 0, got %r" % (weight,))
+        self.render_loss = {"weight": float(weight), "fn": RenderDepthLoss(stride=stride, max_depth=max_depth, norm=norm)}
+        self._fast_train = None                      # a captured step was captured without the loss
+        return self
+
+    def _render_loss_views(self, batch, ssc_pred, width):
+        """One camera view per frame at the logits' own voxel size, mirrored where the loader mirrored the frame."""
+        from .. import render
+        from ..loss.render_loss import frame_views
+        dev = ssc_pred.device
+        vs = self.RENDER_VOXEL_METRES["kitti"] * float(self.full_scene_size[0]) / float(ssc_pred.shape[2])
+        # the origin as a device tensor, made once per (origin, device) -- in the warm-up steps of a captured step, never inside
+        # the capture: a host tuple would be copied to the device by every call, which a capture forbids
+        origin = self._kitti_origin(batch)
+        cache = self.render_loss.setdefault("origin", {})
+        if (origin, str(dev)) not in cache:
+            cache[(origin, str(dev))] = torch.tensor(origin, dtype=torch.float64, device=dev)
+        k, E, origin = render.batch_camera(batch, self.dataset, cache[(origin, str(dev))], dev)
+        ida = batch.get("ida_mats")
+        flip = None
+        if ida is not None:
+            ida = torch.stack([t.to(dev) for t in ida]) if isinstance(ida, (list, tuple)) else ida.to(dev)
+            flip = ida.reshape(ida.shape[0], -1, 4, 4)[:, 0, 0, 0] < 0
+        return frame_views(k, E, origin, vs, width=width, flip=flip)
+
+    def _render_loss_step(self, step_type, batch, ssc_pred, gt_depth):
+        """-> the weighted loss term (logged), or None when this step has no depth target."""
+        if gt_depth is None or gt_depth.numel() == 0 or step_type not in ("train", "val"):
+            return None
+        st = self.render_loss
+        gt_depth = gt_depth.to(ssc_pred.device).float()
+        gt_depth = gt_depth.reshape(gt_depth.shape[0], -1, *gt_depth.shape[-2:])[:, :1]          # the left camera's map
+        views = self._render_loss_views(batch, ssc_pred, int(gt_depth.shape[-1]))
+        fn = st["fn"]
+        loss = fn(ssc_pred, gt_depth, views) * st["weight"]
+        self._log(step_type + "/loss_render", loss)
+        if step_type == "val":
+            depth = fn.last[0]
+            valid, target = fn.valid_rays(gt_depth, views, ssc_pred.shape[2:])
+            n = valid.sum().clamp(min=1).float()
+            err = (depth - target) * valid
+            self._log(step_type + "/render_abs_rel", (err.abs() / target.clamp(min=1e-3)).sum() / n)
+            self._log(step_type + "/render_rmse", ((err * err).sum() / n).sqrt())
+        return loss
+
     # ---------------------------------------------------------------- whole-forward hipGraph
     @staticmethod
     def _batch_signature(batch):
@@ -1375,6 +1453,11 @@ class OccDepth(_Base):
             loss_depth = self.depth_loss_fn.get_depth_loss(gt_depth.to(dev), depth_pred) * self.depth_loss_w
             loss = loss + loss_depth
             self._log(step_type + "/loss_depth", loss_depth)
+
+        if self.render_loss is not None:
+            loss_render = self._render_loss_step(step_type, batch, ssc_pred, gt_depth)
+            if loss_render is not None:
+                loss = loss + loss_render
 
         if self.sem_scal_loss:
             decay = max(0.1, (1 - self.cur_batch / self.total_batch)) if self.sem_step_decay_loss else 1.0

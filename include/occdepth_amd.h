@@ -91,7 +91,9 @@ extern "C" {
  *     OccdRayMetricArgs and occd_ray_metric (K35, the ray-wise counters of RayIoU, csrc/ray_metric.hip): one new struct
  *     and one new function only; likewise OCCD_RENDER_LOSS_ABS / _REL, OccdRenderLossArgs, occd_render_opacity,
  *     occd_render_depth_fwd, occd_render_depth_bwd_rays and occd_render_depth_bwd_voxels (K36, the depth-rendering loss,
- *     csrc/render_loss.hip): one new struct and four new functions only */
+ *     csrc/render_loss.hip): one new struct and four new functions only; likewise OCCD_EDT_MAX_CLASSES, OCCD_EDT_CHUNK,
+ *     OccdEdtArgs, occd_edt_sq and occd_dist_metric (K37, the exact truncated squared distance transform of label volumes
+ *     and the distance-tolerant score counters made of it, csrc/edt.hip): one new struct and two new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1765,6 +1767,57 @@ int occd_render_opacity(const OccdRenderLossArgs* a, void* stream);
 int occd_render_depth_fwd(const OccdRenderLossArgs* a, void* stream);
 int occd_render_depth_bwd_rays(const OccdRenderLossArgs* a, void* stream);
 int occd_render_depth_bwd_voxels(const OccdRenderLossArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K37: exact truncated squared Euclidean distance transform of label volumes (occd_edt_sq) and the counters of the
+ * distance-tolerant scores -- precision, recall and F-score at a distance, Chamfer distance -- made of it
+ * (occd_dist_metric); csrc/edt.hip.  Additive (OCCD_ABI_VERSION note).
+ *
+ * Definitions.  A label volume is (B, X, Y, Z), z fastest, 1 or 2 bytes per label (uint8, or the uint16 values
+ * occd_argmax_channels writes).  Classes are 0 .. C - 1 with 0 free, C = n_classes <= OCCD_EDT_MAX_CLASSES.
+ *   Slot s of a volume is a seed set: slot 0 = every voxel with 1 <= label < C (occupied), slot c >= 1 = every voxel
+ *   with label == c.  A label >= C (255 included) is never a seed.
+ *   D_s(v) = min(min over the seeds u of slot s of |v - u|^2, T + 1): integer, in voxel units, T = max_d2 the caller's
+ *   truncation, 1 <= T <= 65534.  A volume without a seed of the slot has T + 1 everywhere.  Frames are independent.
+ * Truncation is exact under the separable passes (z, then y, then x, each out[i] = min(min_k in[i + k] + k^2, T + 1)): a
+ * candidate more than floor(sqrt(T)) away along an axis cannot give a value <= T and a saturating add stays saturated, so
+ * no pass looks further than that window.  Integer arithmetic only: nothing depends on the schedule.
+ *
+ * occd_edt_sq: labels -> dist (B, n_slots, X, Y, Z) uint16, dist[b][i] = D_{slots[i]} of labels[b].  scratch: at least
+ *   2 B n_slots X Y Z bytes (one plane set beside `dist`).  target, mask, counts, target_bytes are ignored.
+ * occd_dist_metric: labels = the prediction, target, optional byte mask (B, X, Y, Z) -> counts, int64
+ *   [2][C][T + 2], ADDED to (never zeroed; the caller zeroes it outside a capture).  A voxel v is a QUERY iff
+ *   target(v) != 255 and, with a mask, mask(v) != 0.
+ *     side 0: for every query v and every slot s whose PREDICTION seed set contains v: counts[0][s][D_s^target(v)] += 1
+ *     side 1: for every query v and every slot s whose TARGET seed set contains v:     counts[1][s][D_s^pred(v)] += 1
+ *   Seeds are not masked: only queries are restricted.  Bin T + 1 is "further than T, or no seed at all".
+ *   The x pass feeds the counters directly (u32 LDS histograms of T + 2 bins where T + 2 <= 4096, one 64-bit integer
+ *   atomic per non-zero bin; above that one atomic per counted voxel); D is never written.  The 2 C (side, slot)
+ *   pairs of a frame are processed OCCD_EDT_CHUNK at a time.  scratch: at least 4 OCCD_EDT_CHUNK X Y Z bytes (two sets
+ *   of OCCD_EDT_CHUNK uint16 planes of one frame), whatever B and C.  dist, slots, n_slots are ignored.
+ * No allocation, no host sync, no memset node (capture-safe).
+ * OCCD_EINVAL before any launch: a NULL argument, NULL labels / scratch, NULL dist (edt_sq), NULL target / counts
+ * (dist_metric), non-positive batch, X, Y or Z, label_bytes (target_bytes) not 1 or 2, n_classes outside 1 .. 32, max_d2
+ * outside 1 .. 65534, X^2 + Y^2 + Z^2 >= 2^31, B X Y Z >= 2^31, scratch_bytes below the sizes above, n_slots outside
+ * 1 .. 32, a slot outside 0 .. C - 1, B n_slots > 65535, B n_slots X Y Z >= 2^40.
+ * ------------------------------------------------------------------------ */
+#define OCCD_EDT_MAX_CLASSES 32
+#define OCCD_EDT_CHUNK 8 /* (side, slot) pairs of a frame occd_dist_metric transforms per group of launches */
+typedef struct OccdEdtArgs {
+    const void* labels;            /* (B, X, Y, Z) labels, label_bytes each; dist_metric: the prediction      */
+    const void* target;            /* (B, X, Y, Z) target labels, target_bytes each (dist_metric)             */
+    const uint8_t* mask;           /* (B, X, Y, Z) query mask or NULL (dist_metric)                           */
+    uint16_t* dist;                /* (B, n_slots, X, Y, Z) squared distances (edt_sq)                        */
+    int64_t* counts;               /* [2][C][T + 2] counters, added to (dist_metric)                          */
+    void* scratch;                 /* intermediate planes                                                     */
+    int64_t scratch_bytes;
+    int32_t batch, X, Y, Z;
+    int32_t label_bytes, target_bytes;
+    int32_t n_classes, max_d2, n_slots;
+    int32_t slots[OCCD_EDT_MAX_CLASSES];
+} OccdEdtArgs;
+int occd_edt_sq(const OccdEdtArgs* a, void* stream);
+int occd_dist_metric(const OccdEdtArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

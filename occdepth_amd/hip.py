@@ -75,6 +75,10 @@ RAY_COUNTERS = abi.CONSTANTS["OCCD_RAY_COUNTERS"]
 RenderLossArgs = abi.STRUCTS["OccdRenderLossArgs"]
 RENDER_LOSS_ABS = abi.CONSTANTS["OCCD_RENDER_LOSS_ABS"]
 RENDER_LOSS_REL = abi.CONSTANTS["OCCD_RENDER_LOSS_REL"]
+EdtArgs = abi.STRUCTS["OccdEdtArgs"]
+EDT_MAX_CLASSES = abi.CONSTANTS["OCCD_EDT_MAX_CLASSES"]
+EDT_CHUNK = abi.CONSTANTS["OCCD_EDT_CHUNK"]
+EDT_MAX_D2 = 65534
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -2314,6 +2318,110 @@ def ray_metric(pred, target, origins, dirs, counts, thresholds, n_classes, unkno
     for i, t in enumerate(thresholds):
         a.thresholds[i] = t
     _check(load().occd_ray_metric(ctypes.byref(a), _stream()), "occd_ray_metric")
+    return counts
+
+
+# ---- distance transform and distance-tolerant scores (K37, csrc/edt.hip) --------------------------------------------
+def dist_metric_size(n_classes, max_d2):
+    """The number of int64 counters occd_dist_metric adds to: counts[2][C][T + 2] (side, slot, squared distance; the
+    layout is in include/occdepth_amd.h)."""
+    return 2 * int(n_classes) * (int(max_d2) + 2)
+
+
+def edt_scratch_bytes(batch, n_slots, dims):
+    """Bytes of scratch edt_sq needs: one uint16 plane per frame and slot beside the output."""
+    X, Y, Z = (int(d) for d in dims)
+    return 2 * int(batch) * int(n_slots) * X * Y * Z
+
+
+def dist_metric_scratch_bytes(dims):
+    """Bytes of scratch dist_metric needs: two sets of EDT_CHUNK uint16 planes of ONE frame, whatever B and C
+    (4 * 8 * X Y Z: 64 MiB at 256 x 256 x 32)."""
+    X, Y, Z = (int(d) for d in dims)
+    return 4 * EDT_CHUNK * X * Y * Z
+
+
+def _edt_common(a, labels, n_classes, max_d2, scratch, need, name):
+    if labels.dim() != 4 or labels.dtype not in _LABEL_BYTES:
+        raise RuntimeError("%s must be a (B, X, Y, Z) uint8 / int16 / uint16 volume, got %s %s" % (name, tuple(labels.shape), labels.dtype))
+    if not 1 <= int(n_classes) <= EDT_MAX_CLASSES:
+        raise RuntimeError("n_classes must be 1..%d, got %r" % (EDT_MAX_CLASSES, n_classes))
+    if not 1 <= int(max_d2) <= EDT_MAX_D2:
+        raise RuntimeError("max_d2 must be 1..%d, got %r" % (EDT_MAX_D2, max_d2))
+    if scratch.device != labels.device:
+        raise RuntimeError(f"scratch is on {scratch.device}, {name} on {labels.device}")
+    nbytes = scratch.numel() * scratch.element_size()
+    if nbytes < need:
+        raise RuntimeError("scratch must hold %d bytes, got %d" % (need, nbytes))
+    a.labels, a.label_bytes = _ptr(labels, name), _LABEL_BYTES[labels.dtype]
+    a.scratch, a.scratch_bytes = _ptr(scratch, "scratch"), nbytes
+    a.batch, a.X, a.Y, a.Z = (int(d) for d in labels.shape)
+    a.n_classes, a.max_d2 = int(n_classes), int(max_d2)
+
+
+def edt_sq(labels, slots, n_classes, max_d2, out=None, scratch=None):
+    """occd_edt_sq (K37): the exact truncated squared Euclidean distance transform.  labels (B, X, Y, Z) uint8 / int16 /
+    uint16 on the GPU; slots: 1..32 ints in 0 .. n_classes - 1 (slot 0: the voxels with 1 <= label < n_classes, slot c:
+    label == c) -> (B, len(slots), X, Y, Z) uint16 values in an int16 tensor (`.view(torch.uint16)` where torch has it):
+    min(squared distance in voxels to the nearest seed of the slot, max_d2 + 1).  out / scratch: reusable buffers (scratch
+    of edt_scratch_bytes(B, len(slots), dims) bytes; allocated when absent).  No host sync.  The contract is in
+    include/occdepth_amd.h."""
+    slots = [int(s) for s in slots]
+    if not 1 <= len(slots) <= EDT_MAX_CLASSES:
+        raise RuntimeError("1..%d slots, got %d" % (EDT_MAX_CLASSES, len(slots)))
+    if any(not 0 <= s < int(n_classes) for s in slots):
+        raise RuntimeError("slots must lie in 0..%d, got %r" % (int(n_classes) - 1, slots))
+    if labels.dim() != 4:
+        raise RuntimeError("labels must be a (B, X, Y, Z) uint8 / int16 / uint16 volume, got %s %s" % (tuple(labels.shape), labels.dtype))
+    B, X, Y, Z = (int(d) for d in labels.shape)
+    need = edt_scratch_bytes(B, len(slots), (X, Y, Z))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=labels.device)
+    if out is None:
+        out = torch.empty((B, len(slots), X, Y, Z), dtype=torch.int16, device=labels.device)
+    if out.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or tuple(out.shape) != (B, len(slots), X, Y, Z) \
+            or out.device != labels.device:
+        raise RuntimeError("out must be a 16-bit (B, S, X, Y, Z) = %s tensor beside labels, got %s %s"
+                           % ((B, len(slots), X, Y, Z), tuple(out.shape), out.dtype))
+    a = EdtArgs()
+    _edt_common(a, labels, n_classes, max_d2, scratch, need, "labels")
+    a.dist, a.n_slots = _ptr(out, "out"), len(slots)
+    for i, s in enumerate(slots):
+        a.slots[i] = s
+    _check(load().occd_edt_sq(ctypes.byref(a), _stream()), "occd_edt_sq")
+    return out
+
+
+def dist_metric(pred, target, counts, n_classes, max_d2, scratch, mask=None):
+    """occd_dist_metric (K37): add the distance histograms of a prediction against a target to `counts`.  pred, target
+    (B, X, Y, Z) uint8 / int16 / uint16 (the widths may differ); mask None or (B, X, Y, Z) uint8 / bool: with the target's
+    255 it restricts the QUERIES, never the seeds; counts (dist_metric_size(n_classes, max_d2),) int64 =
+    [2][C][max_d2 + 2], added to and never zeroed: side 0 counts the prediction's voxels of every slot by their squared
+    distance to the target's seeds of that slot, side 1 the target's by their distance to the prediction's; scratch: any
+    tensor of at least dist_metric_scratch_bytes(dims) bytes.  All on the GPU and contiguous; no allocation, no host
+    sync.  -> counts.  The contract is in include/occdepth_amd.h."""
+    if pred.dim() != 4 or pred.dtype not in _LABEL_BYTES:
+        raise RuntimeError("pred must be a (B, X, Y, Z) uint8 / int16 / uint16 volume, got %s %s" % (tuple(pred.shape), pred.dtype))
+    if target.dim() != 4 or target.dtype not in _LABEL_BYTES or target.shape != pred.shape:
+        raise RuntimeError("target must be a uint8 / int16 / uint16 volume with the shape of pred %s, got %s %s"
+                           % (tuple(pred.shape), tuple(target.shape), target.dtype))
+    a = EdtArgs()
+    size = dist_metric_size(n_classes, max_d2)
+    if counts.dtype != torch.int64 or counts.numel() != size:
+        raise RuntimeError("counts must hold %d int64 counters, got %s %s" % (size, tuple(counts.shape), counts.dtype))
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or mask.shape != pred.shape:
+            raise RuntimeError("mask must be uint8 / bool with the shape of pred %s, got %s %s" % (tuple(pred.shape), tuple(mask.shape), mask.dtype))
+    _edt_common(a, pred, n_classes, max_d2, scratch, dist_metric_scratch_bytes(pred.shape[1:]), "pred")
+    if mask is not None:
+        a.mask = _ptr(mask, "mask")
+    for t, name in ((target, "target"), (counts, "counts"), (mask, "mask")):
+        if t is not None and t.device != pred.device:
+            raise RuntimeError(f"{name} is on {t.device}, pred on {pred.device}")
+    a.target, a.target_bytes, a.counts = _ptr(target, "target"), _LABEL_BYTES[target.dtype], _ptr(counts, "counts")
+    _check(load().occd_dist_metric(ctypes.byref(a), _stream()), "occd_dist_metric")
     return counts
 
 

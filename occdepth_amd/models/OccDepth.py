@@ -198,6 +198,18 @@ class OccDepth(_Base):
             self.enable_ray_metrics(origins=int(spec[0]), origin_step=int(spec[1]) if len(spec) == 2 else 5,
                                     poses_root=env("OCCDEPTH_RAY_POSES", "") or env("OCCDEPTH_FUSE_POSES", "") or None,
                                     unknown=env("OCCDEPTH_RAY_UNKNOWN", "drop") or "drop")
+        # Distance-tolerant scores of the test / validation predictions (dist_metric.py, K37), OFF by default:
+        # `enable_distance_metrics()` -- or OCCDEPTH_DIST_METRIC=1 [OCCDEPTH_DIST_THRESHOLDS=<m>[,<m>...]] [OCCDEPTH_DIST_FOV=1]
+        # in the environment of an unmodified scripts/eval.py.  Off: nothing is imported, allocated or launched.  Every
+        # other method reaches it through getattr(self, "dist_metrics", None).
+        self.dist_metrics = None
+        if env("OCCDEPTH_DIST_METRIC", "0") == "1":
+            spec = env("OCCDEPTH_DIST_THRESHOLDS", "") or "0.2,0.4,0.8"
+            try:
+                thresholds = tuple(float(w) for w in spec.split(","))
+            except ValueError:
+                raise ValueError("OCCDEPTH_DIST_THRESHOLDS is <metres>[,<metres>...], got %r" % spec) from None
+            self.enable_distance_metrics(thresholds_m=thresholds, fov_only=env("OCCDEPTH_DIST_FOV", "0") == "1")
         self.init_2d_to_3d_trans(config)
         # `enable_render_loss()` -- or OCCDEPTH_RENDER_LOSS=<weight>[,<stride>] in the environment of an unmodified
         # scripts/train.py: the depth-rendering loss (loss/render_loss.py, K36) -- `ssc_logit` composited along the left
@@ -851,8 +863,9 @@ class OccDepth(_Base):
                             "directions": dict(direction_kwargs), "dirs": None, "poses": {}, "metrics": {}, "fused": {}}
         return self
 
-    def _ray_step(self, step_type, batch, ssc_pred, target, fused_labels=None):
-        """Cast the rays through every batch item's arg-max labels (and the fused labels, if any) and its target."""
+    def _ray_step(self, step_type, batch, ssc_pred, target, fused_labels=None, pred_labels=None):
+        """Cast the rays through every batch item's arg-max labels (and the fused labels, if any) and its target.
+        pred_labels: the arg-max of ssc_pred when the caller already has it."""
         from .. import hip, ray_metric
         st = self.ray_metrics
         ssc_pred = ssc_pred.detach()
@@ -876,7 +889,8 @@ class OccDepth(_Base):
                 origins.append(ray_metric.trajectory_origins(poses, frame, st["origins"], st["origin_step"], origin, vs, dims))
         else:
             origins = [ray_metric.sensor_origin(origin, vs)[None]] * B
-        pred = hip.argmax_labels_u16(ssc_pred.float())                   # (B, X, Y, Z) uint16 bits, the unfused logits
+        # (B, X, Y, Z) uint16 bits, the unfused logits
+        pred = hip.argmax_labels_u16(ssc_pred.float()) if pred_labels is None else pred_labels
         gt = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).reshape((B,) + dims)
         for store, labels in ((st["metrics"], pred), (st["fused"], fused_labels)):
             if labels is None:
@@ -894,6 +908,67 @@ class OccDepth(_Base):
         """-> [(prefix, statistics)] of the ray metrics of `step_type` that counted something, reset."""
         out = []
         for name, store in (("ray", self.ray_metrics["metrics"]), ("fused_ray", self.ray_metrics["fused"])):
+            metric = store.get(step_type)
+            if metric is None:
+                continue
+            if self.metrics_allreduce:
+                metric.allreduce_()
+            out.append(("%s_%s" % (step_type, name), metric.get_stats()))
+            metric.reset()
+        return out
+
+    # ---------------------------------------------------------------- distance-tolerant scores (dist_metric.py)
+    def enable_distance_metrics(self, thresholds_m=(0.2, 0.4, 0.8), max_d2=1024, fov_only=False):
+        """Score every test / validation frame by distance as well (dist_metric.DistanceMetrics, K37): for every predicted
+        occupied voxel the distance to the nearest true one and the other way round, class-agnostic and per class, from
+        the exact distance transform of both label volumes on the GPU.  The arg-max of the unfused logits is scored against
+        the target in one call per step; `val_dist/F_geo@<tau>` and `val_dist/F_sem@<tau>` per threshold (metres),
+        `val_dist/CD_geo` and `val_dist/CD_sem` (the Chamfer distance in metres, truncated at voxel_size * sqrt(max_d2 + 1)
+        per side) are logged and `test_epoch_end` prints a `test_dist======` block with the per-class table; with temporal
+        fusion on its fused labels are scored into a second metric (`val_fused_dist/*`, `test_fused_dist======`).  The
+        ordinary metrics are untouched.  Target voxels 255 are no queries (their neighbours' predictions still serve as
+        seeds); fov_only: only voxels inside the batch's full-scale FOV mask (`fov_mask_1`) are queries.  The metric
+        needs the grid alone, so it works for every dataset; the voxel size is the dataset's.  With metrics_allreduce the
+        counters are summed over the ranks before the statistics.  No score of a trained model is measured (no
+        checkpoint and no dataset where this was built)."""
+        thresholds_m = tuple(float(t) for t in thresholds_m)
+        if not thresholds_m or any(not t > 0.0 for t in thresholds_m):
+            raise ValueError("at least one positive threshold in metres, got %r" % (thresholds_m,))
+        if not 1 <= int(max_d2) <= 65534:
+            raise ValueError("max_d2 must be 1..65534, got %r" % (max_d2,))
+        self.dist_metrics = {"thresholds_m": thresholds_m, "max_d2": int(max_d2), "fov_only": bool(fov_only),
+                             "metrics": {}, "fused": {}}
+        return self
+
+    def _dist_step(self, step_type, batch, ssc_pred, target, fused_labels=None, pred_labels=None):
+        """Add the batch's arg-max labels (and the fused labels, if any) against its target to the distance histograms.
+        pred_labels: the arg-max of ssc_pred when the caller already has it."""
+        from .. import dist_metric, hip
+        st = self.dist_metrics
+        ssc_pred = ssc_pred.detach()
+        B = ssc_pred.shape[0]
+        dims = tuple(int(d) for d in ssc_pred.shape[2:])
+        vs = OccDepth.RENDER_VOXEL_METRES.get(self.dataset, 0.2) * float(self.full_scene_size[0]) / float(dims[0])
+        mask = None
+        if st["fov_only"]:
+            mask = self._report_fov(batch, target) if batch.get("fov_mask_1") is not None else None
+            if not torch.is_tensor(mask):
+                raise ValueError("fov_only distance metrics need the batch's full-scale FOV mask (fov_mask_1)")
+            mask = mask.reshape((B,) + dims)
+        pred = hip.argmax_labels_u16(ssc_pred.float()) if pred_labels is None else pred_labels
+        gt = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).reshape((B,) + dims)
+        for store, labels in ((st["metrics"], pred), (st["fused"], fused_labels)):
+            if labels is None:
+                continue
+            metric = store.get(step_type)
+            if metric is None:
+                metric = store[step_type] = dist_metric.DistanceMetrics(self.n_classes, vs, st["thresholds_m"], st["max_d2"])
+            metric.add_batch(labels, gt, mask)
+
+    def _dist_epoch_end(self, step_type):
+        """-> [(prefix, statistics)] of the distance metrics of `step_type` that counted something, reset."""
+        out = []
+        for name, store in (("dist", self.dist_metrics["metrics"]), ("fused_dist", self.dist_metrics["fused"])):
             metric = store.get(step_type)
             if metric is None:
                 continue
@@ -1488,8 +1563,17 @@ class OccDepth(_Base):
         fused_labels = None
         if self.temporal_fusion is not None and step_type in ("test", "val"):
             fused_labels = self._fuse_step(step_type, batch, ssc_pred, target)
-        if getattr(self, "ray_metrics", None) is not None and step_type in ("test", "val"):
+        ray_on = getattr(self, "ray_metrics", None) is not None and step_type in ("test", "val")
+        dist_on = getattr(self, "dist_metrics", None) is not None and step_type in ("test", "val")
+        if ray_on and dist_on:                                        # one arg-max of the unfused logits for both
+            from .. import hip
+            pred_labels = hip.argmax_labels_u16(ssc_pred.detach().float())
+            self._ray_step(step_type, batch, ssc_pred, target, fused_labels, pred_labels=pred_labels)
+            self._dist_step(step_type, batch, ssc_pred, target, fused_labels, pred_labels=pred_labels)
+        elif ray_on:
             self._ray_step(step_type, batch, ssc_pred, target, fused_labels)
+        elif dist_on:
+            self._dist_step(step_type, batch, ssc_pred, target, fused_labels)
         if getattr(self, "semantic_map", None) is not None and step_type in ("test", "val"):
             self._map_step(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
@@ -1848,6 +1932,13 @@ class OccDepth(_Base):
                 for t, v in zip(stats["thresholds_m"], stats["ray_miou"]):
                     self.log("%s/RayIoU@%g" % (prefix, t), v, sync_dist=True)
                 self.log(prefix + "/RayIoU_geo", stats["ray_iou_geo"].mean(), sync_dist=True)
+        if getattr(self, "dist_metrics", None) is not None:
+            for prefix, stats in self._dist_epoch_end("val"):
+                for i, t in enumerate(stats["thresholds_m"]):
+                    self.log("%s/F_geo@%g" % (prefix, t), stats["F_geo"][i], sync_dist=True)
+                    self.log("%s/F_sem@%g" % (prefix, t), stats["F_sem"][i], sync_dist=True)
+                self.log(prefix + "/CD_geo", stats["CD_geo"], sync_dist=True)
+                self.log(prefix + "/CD_sem", stats["CD_sem"], sync_dist=True)
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -1882,6 +1973,10 @@ class OccDepth(_Base):
             from ..ray_metric import format_report
             for prefix, stats in self._ray_epoch_end("test"):
                 print("\n".join(format_report(stats, classes, prefix)))
+        if getattr(self, "dist_metrics", None) is not None:
+            from ..dist_metric import format_report as format_dist_report
+            for prefix, stats in self._dist_epoch_end("test"):
+                print("\n".join(format_dist_report(stats, classes, prefix)))
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

@@ -93,7 +93,10 @@ extern "C" {
  *     occd_render_depth_fwd, occd_render_depth_bwd_rays and occd_render_depth_bwd_voxels (K36, the depth-rendering loss,
  *     csrc/render_loss.hip): one new struct and four new functions only; likewise OCCD_EDT_MAX_CLASSES, OCCD_EDT_CHUNK,
  *     OccdEdtArgs, occd_edt_sq and occd_dist_metric (K37, the exact truncated squared distance transform of label volumes
- *     and the distance-tolerant score counters made of it, csrc/edt.hip): one new struct and two new functions only */
+ *     and the distance-tolerant score counters made of it, csrc/edt.hip): one new struct and two new functions only;
+ *     likewise OCCD_SORT_TILE, OCCD_SORT_RADIX_BITS, OccdSortArgs and occd_sort_pairs_u32 (K38, the stable segmented
+ *     radix sort, csrc/sort.hip) and OCCD_LOVASZ_*, OccdLovaszArgs, occd_lovasz_errors, occd_lovasz_ranks and
+ *     occd_lovasz_bwd (the Lovasz-softmax loss on top of it, csrc/lovasz.hip): two new structs and four new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1818,6 +1821,90 @@ typedef struct OccdEdtArgs {
 } OccdEdtArgs;
 int occd_edt_sq(const OccdEdtArgs* a, void* stream);
 int occd_dist_metric(const OccdEdtArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K38: stable segmented key/value radix sort (csrc/sort.hip).  Additive (OCCD_ABI_VERSION note).
+ * Sorts `segments` independent rows of n (uint32 key, uint32 value) pairs each, ascending on key bits
+ * [begin_bit, end_bit) (the other bits are carried along and do not take part); pairs whose keys agree on those bits keep
+ * their input order (stable), so the result is numpy.argsort(kind="stable") of the masked keys, exactly.
+ * LSD radix sort, OCCD_SORT_RADIX_BITS bits a pass (the last pass takes what is left), passes =
+ * ceil((end_bit - begin_bit) / OCCD_SORT_RADIX_BITS), ping-pong between buffer 0 (keys, vals: the input, overwritten)
+ * and buffer 1 (keys_alt, vals_alt): THE RESULT IS IN BUFFER passes % 2.  Each pass is three launches: digit histograms
+ * of every tile of OCCD_SORT_TILE pairs, one exclusive scan per segment over the (digit, tile) table, and a scatter that
+ * ranks a tile's pairs (wave-wide match on the digit's bits with ballots, per-wave digit counters in LDS, the tile
+ * reordered through LDS so that a digit's run leaves as one stretch).  No kernel waits for another workgroup; the launch
+ * geometry depends on (segments, n) only; no allocation, no host read, no memset node: capture-safe, and the output does
+ * not depend on the schedule (no floating point, every position is a sum of counts).
+ * hist: workspace of segments * 2^OCCD_SORT_RADIX_BITS * ceil(n / OCCD_SORT_TILE) uint32.
+ * OCCD_EINVAL before any launch: a NULL argument or pointer, n outside 1 .. 2^31 - 1, segments outside 1 .. 65535,
+ * segments * n >= 2^40, a bit range that is not 0 <= begin_bit < end_bit <= 32.
+ * ------------------------------------------------------------------------ */
+#define OCCD_SORT_TILE 4096
+#define OCCD_SORT_RADIX_BITS 8
+typedef struct OccdSortArgs {
+    uint32_t* keys;                /* (segments, n) buffer 0: the input                                       */
+    uint32_t* vals;
+    uint32_t* keys_alt;            /* (segments, n) buffer 1                                                  */
+    uint32_t* vals_alt;
+    uint32_t* hist;                /* workspace, see above                                                    */
+    int64_t n;
+    int32_t segments, begin_bit, end_bit;
+} OccdSortArgs;
+int occd_sort_pairs_u32(const OccdSortArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * The Lovasz-softmax loss (Berman, Triki, Blaschko, CVPR 2018) on top of K38 (csrc/lovasz.hip).  Additive.  Over the whole
+ * batch (per_image = False) and the classes present in the target.  N = batch * S voxels, voxel i = b * S + s; logits
+ * element (b, c, s) at b*s_b + c*s_c + s*s_v floats, the two layouts of occd_ssc_loss_stats_*_strided; target (N,) uint8,
+ * the label `ignore` is unknown.  For class c and valid voxel i: fg = [y_i == c], p = softmax(z_i)[c] in float32 (expf),
+ * e = fg ? sum_{c' != c} p_c' : p, clamped to [0, 1] (1 - p formed without cancellation: a saturated voxel gives an exact
+ * 0).  G_c = #fg.  The valid voxels of class c are ordered by DESCENDING e, ties by ASCENDING voxel index.  For the element
+ * at sorted position k, with F = #fg strictly before it and b = #bg up to and including it, the Jaccard increment is
+ *   g = 1 / (G + b)  (fg),      g = (G - F) / ((G + b - 1)(G + b))  (bg),      g = 0 for every element when G = 0,
+ * evaluated in float64 from the integer counters with IEEE division and rounded once to float32.
+ *   L_c = sum_k e_(k) g_k,  L = (1 / #present) sum_{G_c > 0} L_c,  d L / d p_{i,c} = (fg ? -1 : +1) g / #present.
+ * L_c is accumulated as integers in Q60: every term is rint(e * g64 * 2^60), g64 the float64 g before its rounding to
+ * float32, added with 64-bit integer atomics (LDS, then one per workgroup), so loss_q does not depend on the schedule.  Terms lie in [0, 1] and sum to at most 1 (the Jaccard index),
+ * so the sum stays below 2^61.  WORST-CASE ROUNDING of L_c against exact arithmetic on the same float32 errors:
+ *   N * 2^-61 (half a unit per term)  +  2^-50 (the float64 roundings of g, e g and the scaling, relative, on terms that
+ *   sum to at most 1).
+ *   occd_lovasz_errors  reads logits, target; for classes c0 .. c0 + cc - 1 writes segment c - c0 of keys, vals (cc, N):
+ *                       key = 0x3F800000 - bits(e) (ascending key = descending e; 30 bits), OCCD_LOVASZ_INVALID_KEY for
+ *                       an unknown voxel (behind every valid one; sort bits [0, OCCD_LOVASZ_KEY_BITS)); val = i | fg << 31
+ *   occd_lovasz_ranks   reads the SORTED keys, vals; three launches (fg sums per tile of OCCD_LOVASZ_RANK_TILE, one scan
+ *                       per segment, apply); writes fg_count[c0 + j] = G, loss_q[c0 + j] (zeroed by a kernel first),
+ *                       q[i * C + c0 + j] = (fg ? -g : g) for every valid voxel (voxel-major); tsum: workspace of
+ *                       cc * ceil(N / OCCD_LOVASZ_RANK_TILE) uint32
+ *   occd_lovasz_bwd     reads logits, target, q (N, C), gscale (device scalar: incoming gradient / #present); writes
+ *                       grad(b, j, s) = gscale p_j (q_j - sum_c q_c p_c) through (g_b, g_c, g_v), zeros for an unknown
+ *                       voxel (q is not read there) and for the pad channels [C, g_pad) of channels-last rows
+ * OCCD_EINVAL before any launch: a NULL argument or a pointer the kernel uses, batch or S non-positive, N >= 2^31, C outside
+ * 2 .. 32, c0 / cc outside the classes, strides or a g_pad the strided ssc kernels would refuse.
+ * ------------------------------------------------------------------------ */
+#define OCCD_LOVASZ_Q 60
+#define OCCD_LOVASZ_KEY_BITS 31
+#define OCCD_LOVASZ_INVALID_KEY 0x40000000
+#define OCCD_LOVASZ_RANK_TILE 2048
+typedef struct OccdLovaszArgs {
+    const float* logits;           /* (B, C, S) through (s_b, s_c, s_v)                                       */
+    const uint8_t* target;         /* (B, S)                                                                  */
+    uint32_t* keys;                /* (cc, N)                                                                 */
+    uint32_t* vals;                /* (cc, N)                                                                 */
+    uint32_t* tsum;                /* workspace of the ranks pass                                             */
+    float* q;                      /* (N, C) signed Jaccard increments                                        */
+    int64_t* fg_count;             /* (C) G_c                                                                 */
+    int64_t* loss_q;               /* (C) L_c, Q60                                                            */
+    const float* gscale;           /* device scalar                                                           */
+    float* grad;                   /* d L / d logits through (g_b, g_c, g_v)                                  */
+    int64_t s_b, s_c, s_v;
+    int64_t g_b, g_c, g_v;
+    int64_t S;
+    int32_t batch, C, c0, cc;
+    int32_t g_pad, ignore;
+} OccdLovaszArgs;
+int occd_lovasz_errors(const OccdLovaszArgs* a, void* stream);
+int occd_lovasz_ranks(const OccdLovaszArgs* a, void* stream);
+int occd_lovasz_bwd(const OccdLovaszArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

@@ -79,6 +79,14 @@ EdtArgs = abi.STRUCTS["OccdEdtArgs"]
 EDT_MAX_CLASSES = abi.CONSTANTS["OCCD_EDT_MAX_CLASSES"]
 EDT_CHUNK = abi.CONSTANTS["OCCD_EDT_CHUNK"]
 EDT_MAX_D2 = 65534
+SortArgs = abi.STRUCTS["OccdSortArgs"]
+SORT_TILE = abi.CONSTANTS["OCCD_SORT_TILE"]
+SORT_RADIX_BITS = abi.CONSTANTS["OCCD_SORT_RADIX_BITS"]
+LovaszArgs = abi.STRUCTS["OccdLovaszArgs"]
+LOVASZ_Q = abi.CONSTANTS["OCCD_LOVASZ_Q"]
+LOVASZ_KEY_BITS = abi.CONSTANTS["OCCD_LOVASZ_KEY_BITS"]
+LOVASZ_INVALID_KEY = abi.CONSTANTS["OCCD_LOVASZ_INVALID_KEY"]
+LOVASZ_RANK_TILE = abi.CONSTANTS["OCCD_LOVASZ_RANK_TILE"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -3326,6 +3334,251 @@ def render_depth_bwd_voxels(logits, hsum, gscale):
     a.g_pad = gpad
     _check(load().occd_render_depth_bwd_voxels(ctypes.byref(a), _stream()), "occd_render_depth_bwd_voxels")
     return grad
+
+
+# ---- stable segmented radix sort (K38, csrc/sort.hip) ----------------------------------------------------------------
+def sort_passes(begin_bit=0, end_bit=32):
+    """Passes of `sort_pairs` over key bits [begin_bit, end_bit); the result lands in buffer passes % 2."""
+    if not 0 <= int(begin_bit) < int(end_bit) <= 32:
+        raise ValueError("the bit range must be 0 <= begin_bit < end_bit <= 32, got [%r, %r)" % (begin_bit, end_bit))
+    return -(-(int(end_bit) - int(begin_bit)) // SORT_RADIX_BITS)
+
+
+def sort_hist_words(segments, n):
+    """uint32 words of the histogram workspace `sort_pairs` needs for (segments, n)."""
+    return int(segments) * (1 << SORT_RADIX_BITS) * (-(-int(n) // SORT_TILE))
+
+
+def sort_scratch(segments, n, device):
+    """(keys_alt, vals_alt, hist) for `sort_pairs` of (segments, n) pairs."""
+    alt = torch.empty((2, int(segments), int(n)), dtype=torch.int32, device=device)
+    return alt[0], alt[1], torch.empty(sort_hist_words(segments, n), dtype=torch.int32, device=device)
+
+
+def sort_pairs(keys, vals, begin_bit=0, end_bit=32, scratch=None):
+    """occd_sort_pairs_u32: sort every row of keys (S, n) -- int32 tensors read as uint32 -- ascending on key bits
+    [begin_bit, end_bit), stably, carrying vals (S, n) -> (sorted keys, sorted vals).  `keys` and `vals` are OVERWRITTEN
+    (they are one of the two ping-pong buffers); the returned tensors are either they or the scratch's, whichever the
+    last pass wrote.  scratch: `sort_scratch(S, n, device)`, made here when None.  No host read: capture-safe when the
+    scratch is given."""
+    for t, name in ((keys, "keys"), (vals, "vals")):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2:
+            raise RuntimeError("%s must be int32 (S, n) (the bits of uint32 values)" % name)
+    if keys.shape != vals.shape:
+        raise RuntimeError("keys %s and vals %s differ in shape" % (tuple(keys.shape), tuple(vals.shape)))
+    S, n = (int(d) for d in keys.shape)
+    if n < 1 or n >= 1 << 31 or not 1 <= S <= 65535:
+        raise RuntimeError("sort_pairs needs 1 <= n < 2^31 and 1 <= S <= 65535, got (S, n) = (%d, %d)" % (S, n))
+    passes = sort_passes(begin_bit, end_bit)
+    if scratch is None:
+        scratch = sort_scratch(S, n, keys.device)
+    kalt, valt, hist = scratch
+    if tuple(kalt.shape) != (S, n) or tuple(valt.shape) != (S, n) or kalt.dtype != torch.int32 or valt.dtype != torch.int32:
+        raise RuntimeError("the scratch pair buffers must be int32 (S, n) = %r" % ((S, n),))
+    if hist.dtype != torch.int32 or hist.numel() < sort_hist_words(S, n):
+        raise RuntimeError("the scratch histogram needs %d int32 words" % sort_hist_words(S, n))
+    a = SortArgs()
+    a.keys, a.vals = _ptr(keys, "keys"), _ptr(vals, "vals")
+    a.keys_alt, a.vals_alt, a.hist = _ptr(kalt, "keys_alt"), _ptr(valt, "vals_alt"), _ptr(hist, "hist")
+    a.n, a.segments, a.begin_bit, a.end_bit = n, S, int(begin_bit), int(end_bit)
+    _check(load().occd_sort_pairs_u32(ctypes.byref(a), _stream()), "occd_sort_pairs_u32")
+    return (kalt, valt) if passes & 1 else (keys, vals)
+
+
+# ---- Lovasz-softmax loss (csrc/lovasz.hip, on K38) -------------------------------------------------------------------
+LOVASZ_MAX_VOXELS = (1 << 31) - 1        # the payload keeps the voxel index in 31 bits, the fg flag in bit 31
+LOVASZ_ONE_BITS = 0x3F800000
+
+
+def lovasz_usable(logits, target=None):
+    """The Lovasz-softmax loss runs on the K38 kernels: float32 GPU logits (B, C, ...) with 2 <= C <= 32 and a GPU uint8
+    target (a missing library is an error there, as everywhere).  CPU tensors and other dtypes take the torch formulation
+    of loss/lovasz_loss.py."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32):
+        return False
+    if logits.dim() < 3 or not 2 <= logits.shape[1] <= 32:
+        return False
+    return target is None or (target.is_cuda and target.dtype == torch.uint8)
+
+
+def lovasz_check_voxels(n):
+    """N = B X Y Z voxels must leave bit 31 of the sort payload to the fg flag."""
+    if int(n) < 1 or int(n) > LOVASZ_MAX_VOXELS:
+        raise ValueError("the Lovasz-softmax loss takes 1 <= N < 2^31 voxels per call, got %d" % int(n))
+    return int(n)
+
+
+def lovasz_value_bound(n):
+    """Worst-case rounding of a class loss L_c against exact arithmetic on the same float32 errors
+    (include/occdepth_amd.h): half a Q60 unit per voxel + the float64 roundings of g, e g and the scaling."""
+    return int(n) * 2.0 ** -(LOVASZ_Q + 1) + 2.0 ** -50
+
+
+def lovasz_chunk(n_classes, class_chunk=None):
+    cc = int(n_classes) if class_chunk is None else int(class_chunk)
+    if not 1 <= cc <= int(n_classes):
+        raise ValueError("class_chunk must lie in 1 .. C = %d, got %r" % (n_classes, class_chunk))
+    return cc
+
+
+def lovasz_scratch_bytes(n, n_classes, class_chunk=None):
+    """Bytes of cached scratch the loss holds for N voxels and C classes sorted `class_chunk` at a time: two ping-pong
+    buffers of (key, value) pairs, the sort's histograms and the tile sums of the ranks pass.  (The table q, N C floats,
+    is the forward's saved state, not scratch.)"""
+    n, cc = lovasz_check_voxels(n), lovasz_chunk(n_classes, class_chunk)
+    return 16 * cc * n + 4 * sort_hist_words(cc, n) + 4 * cc * (-(-n // LOVASZ_RANK_TILE))
+
+
+_lovasz_scratch = {}
+
+
+def lovasz_scratch(n, cc, device):
+    """The cached scratch of one (N, classes per group, device): {"pairs": int32 (2, 2, cc, N), "hist", "tsum"}."""
+    key = (int(n), int(cc), str(device))
+    sc = _lovasz_scratch.get(key)
+    if sc is None:
+        sc = _lovasz_scratch[key] = {
+            "pairs": torch.empty((2, 2, cc, n), dtype=torch.int32, device=device),
+            "hist": torch.empty(sort_hist_words(cc, n), dtype=torch.int32, device=device),
+            "tsum": torch.empty(cc * (-(-n // LOVASZ_RANK_TILE)), dtype=torch.int32, device=device)}
+    return sc
+
+
+def _lovasz_logits(a, logits, target, ignore):
+    if not torch.is_tensor(logits) or logits.dtype != torch.float32 or logits.dim() < 3:
+        raise RuntimeError("logits must be float32 (B, C, ...)")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must live on the GPU (the HIP kernels have no CPU path)")
+    B, C = int(logits.shape[0]), int(logits.shape[1])
+    S = logits[0, 0].numel()
+    if not 2 <= C <= 32:
+        raise RuntimeError("2 <= C <= 32 classes, got %d" % C)
+    lovasz_check_voxels(B * S)
+    if target.dtype != torch.uint8 or tuple(target.shape) != (B,) + tuple(logits.shape[2:]):
+        raise RuntimeError("target must be uint8 of shape (B, ...) = %r" % ((B,) + tuple(logits.shape[2:]),))
+    lay = _logit_layout(logits)
+    if lay is None:
+        logits = logits.contiguous()
+        lay = (C * S, S, 1)
+    target = target.contiguous()
+    a.logits, a.target = logits.data_ptr(), _ptr(target, "target")
+    a.s_b, a.s_c, a.s_v = lay
+    a.batch, a.C, a.S, a.ignore = B, C, S, int(ignore)
+    return logits, target, lay, B, C, S
+
+
+def lovasz_errors(logits, target, c0, cc, keys, vals, ignore=255):
+    """occd_lovasz_errors: softmax per voxel; for the classes c0 .. c0 + cc - 1 the sort key (LOVASZ_ONE_BITS - bits(e):
+    ascending key = descending error; LOVASZ_INVALID_KEY where target == ignore) and the payload (voxel | fg << 31) into
+    keys, vals (cc, N) int32."""
+    a = LovaszArgs()
+    keep = _lovasz_logits(a, logits, target, ignore)
+    N = keep[3] * keep[5]
+    for t, name in ((keys, "keys"), (vals, "vals")):
+        if t.dtype != torch.int32 or tuple(t.shape) != (int(cc), N):
+            raise RuntimeError("%s must be int32 (cc, N) = %r" % (name, (int(cc), N)))
+    a.c0, a.cc = int(c0), int(cc)
+    a.keys, a.vals = _ptr(keys, "keys"), _ptr(vals, "vals")
+    _check(load().occd_lovasz_errors(ctypes.byref(a), _stream()), "occd_lovasz_errors")
+    return keys, vals
+
+
+def lovasz_ranks(keys, vals, c0, q, fg_count, loss_q, tsum=None):
+    """occd_lovasz_ranks on SORTED keys, vals (cc, N): writes q[:, c0:c0 + cc] (q is (N, C) float32: the signed Jaccard
+    increment of every valid voxel), fg_count[c0:c0 + cc] (G_c) and loss_q[c0:c0 + cc] (L_c in Q60), both int64 (C,)."""
+    cc, N = (int(d) for d in keys.shape)
+    lovasz_check_voxels(N)
+    if keys.dtype != torch.int32 or vals.dtype != torch.int32 or tuple(vals.shape) != (cc, N):
+        raise RuntimeError("keys and vals must be int32 (cc, N)")
+    if q.dtype != torch.float32 or q.dim() != 2 or q.shape[0] != N or not 2 <= q.shape[1] <= 32:
+        raise RuntimeError("q must be float32 (N, C) with N = %d and 2 <= C <= 32" % N)
+    C = int(q.shape[1])
+    if not (0 <= int(c0) and int(c0) + cc <= C):
+        raise RuntimeError("classes %d .. %d lie outside 0 .. %d" % (c0, int(c0) + cc - 1, C - 1))
+    for t, name in ((fg_count, "fg_count"), (loss_q, "loss_q")):
+        if t.dtype != torch.int64 or tuple(t.shape) != (C,):
+            raise RuntimeError("%s must be int64 (C,) = (%d,)" % (name, C))
+    words = cc * (-(-N // LOVASZ_RANK_TILE))
+    if tsum is None:
+        tsum = torch.empty(words, dtype=torch.int32, device=keys.device)
+    if tsum.dtype != torch.int32 or tsum.numel() < words:
+        raise RuntimeError("tsum needs %d int32 words" % words)
+    a = LovaszArgs()
+    a.keys, a.vals, a.tsum, a.q = _ptr(keys, "keys"), _ptr(vals, "vals"), _ptr(tsum, "tsum"), _ptr(q, "q")
+    a.fg_count, a.loss_q = _ptr(fg_count, "fg_count"), _ptr(loss_q, "loss_q")
+    a.batch, a.S, a.C, a.c0, a.cc = 1, N, C, int(c0), cc
+    _check(load().occd_lovasz_ranks(ctypes.byref(a), _stream()), "occd_lovasz_ranks")
+    return q, fg_count, loss_q
+
+
+def lovasz_bwd(logits, target, q, gscale, ignore=255):
+    """occd_lovasz_bwd: d L / d logits = gscale p_j (q_j - sum_c q_c p_c) per voxel, zeros where target == ignore, in the
+    logits' layout (channels-last logits get a (B, C, ...) view of zero-padded channels-last rows, as `ssc_loss_grad`).
+    gscale: one-element float32 device tensor (incoming gradient / #present)."""
+    a = LovaszArgs()
+    logits, target, lay, B, C, S = _lovasz_logits(a, logits, target, ignore)
+    if q.dtype != torch.float32 or tuple(q.shape) != (B * S, C):
+        raise RuntimeError("q must be float32 (N, C) = %r" % ((B * S, C),))
+    if not torch.is_tensor(gscale) or gscale.dtype != torch.float32 or gscale.numel() != 1:
+        raise RuntimeError("gscale must be a one-element float32 GPU tensor")
+    if lay[1] == 1:
+        cs = round_up(C, 8)
+        rows = torch.empty((B,) + tuple(logits.shape[2:]) + (cs,), dtype=torch.float32, device=logits.device)
+        grad = rows[..., :C].permute(0, rows.dim() - 1, *range(1, rows.dim() - 1))
+        glay, gpad = (S * cs, 1, cs), cs
+    else:
+        grad = torch.empty_like(logits)
+        glay, gpad = lay, 0
+    a.q, a.gscale, a.grad = _ptr(q, "q"), _ptr(gscale, "gscale"), grad.data_ptr()
+    a.g_b, a.g_c, a.g_v = glay
+    a.g_pad = gpad
+    a.c0, a.cc = 0, C
+    _check(load().occd_lovasz_bwd(ctypes.byref(a), _stream()), "occd_lovasz_bwd")
+    return grad
+
+
+def lovasz_forward(logits, target, class_chunk=None, ignore=255):
+    """Errors, sort and ranks for every class, `class_chunk` classes at a time over one cached scratch ->
+    (q (N, C) float32, fg_count (C,) int64, loss_q (C,) int64).  No host read."""
+    B, C = int(logits.shape[0]), int(logits.shape[1])
+    N = lovasz_check_voxels(B * logits[0, 0].numel())
+    cc = lovasz_chunk(C, class_chunk)
+    sc = lovasz_scratch(N, cc, logits.device)
+    q = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+    fg_count = torch.empty(C, dtype=torch.int64, device=logits.device)
+    loss_q = torch.empty(C, dtype=torch.int64, device=logits.device)
+    for c0 in range(0, C, cc):
+        n = min(cc, C - c0)
+        pairs = sc["pairs"][:, :, :n]
+        lovasz_errors(logits, target, c0, n, pairs[0, 0], pairs[0, 1], ignore)
+        keys, vals = sort_pairs(pairs[0, 0], pairs[0, 1], 0, LOVASZ_KEY_BITS, (pairs[1, 0], pairs[1, 1], sc["hist"]))
+        lovasz_ranks(keys, vals, c0, q, fg_count, loss_q, sc["tsum"])
+    return q, fg_count, loss_q
+
+
+def lovasz_from_errors(err, fg, valid, raw=False):
+    """Sort + ranks on ready-made errors: err (C, N) float32 in [0, 1], fg (C, N) uint8, valid (N,) uint8 ->
+    (q (C, N) float32: (fg ? -g : g) of every valid voxel, 0 elsewhere; L_c (C,) float64 = loss_q / 2^60); with raw=True
+    also (fg_count (C,) int64, loss_q (C,) int64: L_c in Q60).  The seam the exact tests go through: the keys are built
+    here with torch, the kernels are those of the loss."""
+    if err.dtype != torch.float32 or err.dim() != 2 or not err.is_cuda:
+        raise RuntimeError("err must be a float32 (C, N) GPU tensor")
+    C, N = (int(d) for d in err.shape)
+    lovasz_check_voxels(N)
+    if fg.dtype != torch.uint8 or tuple(fg.shape) != (C, N) or valid.dtype != torch.uint8 or tuple(valid.shape) != (N,):
+        raise RuntimeError("fg must be uint8 (C, N) and valid uint8 (N,)")
+    ok = valid.bool()[None].expand(C, N)
+    bits = err.clamp(0.0, 1.0).contiguous().view(torch.int32)
+    keys = torch.where(ok, LOVASZ_ONE_BITS - bits, torch.full_like(bits, LOVASZ_INVALID_KEY)).contiguous()
+    idx = torch.arange(N, dtype=torch.int32, device=err.device)[None].expand(C, N)
+    vals = torch.where(ok & fg.bool(), idx | torch.tensor(-(1 << 31), dtype=torch.int32, device=err.device), idx).contiguous()
+    keys, vals = sort_pairs(keys, vals, 0, LOVASZ_KEY_BITS)
+    q = torch.zeros((N, C), dtype=torch.float32, device=err.device)
+    fg_count = torch.empty(C, dtype=torch.int64, device=err.device)
+    loss_q = torch.empty(C, dtype=torch.int64, device=err.device)
+    lovasz_ranks(keys, vals, 0, q, fg_count, loss_q)
+    lc = loss_q.double() / float(1 << LOVASZ_Q)
+    return (q.t(), lc, fg_count, loss_q) if raw else (q.t(), lc)
 
 
 def cascade_tail(part, occ_off, wn, nbr):

@@ -225,6 +225,16 @@ class OccDepth(_Base):
             except ValueError:
                 raise ValueError("OCCDEPTH_RENDER_LOSS is <weight>[,<stride>], got %r" % env("OCCDEPTH_RENDER_LOSS")) from None
             self.enable_render_loss(weight=weight, stride=stride)
+        # `enable_lovasz_loss()` -- or OCCDEPTH_LOVASZ=<weight> in the environment of an unmodified scripts/train.py: the
+        # Lovasz-softmax loss (loss/lovasz_loss.py, on the K38 sort), the surrogate of the per-class Jaccard index, is added
+        # to the train / val loss.  Off: nothing is imported, allocated or launched.
+        self.lovasz_loss = None
+        if env("OCCDEPTH_LOVASZ", "0") not in ("", "0"):
+            try:
+                weight = float(env("OCCDEPTH_LOVASZ"))
+            except ValueError:
+                raise ValueError("OCCDEPTH_LOVASZ is <weight>, got %r" % env("OCCDEPTH_LOVASZ")) from None
+            self.enable_lovasz_loss(weight=weight)
         print("INFO: Use step decay loss: {}".format(self.sem_step_decay_loss))
         batch_size = config.batch_size_per_gpu * config.n_gpus
         if self.dataset == "kitti":
@@ -1357,6 +1367,21 @@ class OccDepth(_Base):
             self._log(step_type + "/render_rmse", ((err * err).sum() / n).sqrt())
         return loss
 
+    # ---------------------------------------------------------------- Lovasz-softmax loss (K38)
+    def enable_lovasz_loss(self, weight=1.0, class_chunk=None):
+        """Add `weight` x the Lovasz-softmax loss of `ssc_logit` against the step's target (loss/lovasz_loss.py: csrc/sort.hip
+        and csrc/lovasz.hip on the GPU) to the train and val loss: the convex surrogate of the per-class Jaccard index, over
+        the whole batch and the classes present, label 255 unknown.  Logged: <step_type>/loss_lovasz (weighted, like the
+        other terms).  It needs logits and target only: every dataset.  No host read, so the captured fast training step
+        includes it.  class_chunk: classes sorted at a time over one scratch (default: all; `hip.lovasz_scratch_bytes`).
+        The same switch from the environment: OCCDEPTH_LOVASZ=<weight>."""
+        if not float(weight) > 0.0:
+            raise ValueError("enable_lovasz_loss: weight must be > 0, got %r" % (weight,))
+        from ..loss.lovasz_loss import LovaszSoftmaxLoss
+        self.lovasz_loss = {"weight": float(weight), "fn": LovaszSoftmaxLoss(class_chunk=class_chunk)}
+        self._fast_train = None                      # a captured step was captured without the loss
+        return self
+
     # ---------------------------------------------------------------- whole-forward hipGraph
     @staticmethod
     def _batch_signature(batch):
@@ -1533,6 +1558,11 @@ class OccDepth(_Base):
             loss_render = self._render_loss_step(step_type, batch, ssc_pred, gt_depth)
             if loss_render is not None:
                 loss = loss + loss_render
+
+        if getattr(self, "lovasz_loss", None) is not None and step_type in ("train", "val"):
+            loss_lovasz = self.lovasz_loss["fn"](ssc_pred, target) * self.lovasz_loss["weight"]
+            loss = loss + loss_lovasz
+            self._log(step_type + "/loss_lovasz", loss_lovasz)
 
         if self.sem_scal_loss:
             decay = max(0.1, (1 - self.cur_batch / self.total_batch)) if self.sem_step_decay_loss else 1.0

@@ -96,7 +96,9 @@ extern "C" {
  *     and the distance-tolerant score counters made of it, csrc/edt.hip): one new struct and two new functions only;
  *     likewise OCCD_SORT_TILE, OCCD_SORT_RADIX_BITS, OccdSortArgs and occd_sort_pairs_u32 (K38, the stable segmented
  *     radix sort, csrc/sort.hip) and OCCD_LOVASZ_*, OccdLovaszArgs, occd_lovasz_errors, occd_lovasz_ranks and
- *     occd_lovasz_bwd (the Lovasz-softmax loss on top of it, csrc/lovasz.hip): two new structs and four new functions only */
+ *     occd_lovasz_bwd (the Lovasz-softmax loss on top of it, csrc/lovasz.hip): two new structs and four new functions only;
+ *     likewise OCCD_MESH_*, OccdMeshArgs, occd_mesh_count, occd_mesh_emit, occd_mesh_heads and occd_mesh_weld (K39, the
+ *     indexed quad mesh of a brick volume, csrc/mesh.hip): one new struct and four new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1905,6 +1907,72 @@ typedef struct OccdLovaszArgs {
 int occd_lovasz_errors(const OccdLovaszArgs* a, void* stream);
 int occd_lovasz_ranks(const OccdLovaszArgs* a, void* stream);
 int occd_lovasz_bwd(const OccdLovaszArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K39: the surface of a brick volume as an indexed quad mesh (csrc/mesh.hip).  Additive (OCCD_ABI_VERSION note).
+ * Input: the volume occd_map_render draws -- labels (n_rows, 4096) uint8, one row per 16^3 brick, voxel (i, j, l) of a
+ * brick at (i*16 + j)*16 + l, and the directory cells (gx, gy, gz) int32, the row of the brick at that cell or negative.
+ * Only rows the directory points to are meshed; a row named by several cells is meshed at the lowest of them.
+ * Solid: label in 1..254.  Free: label 0.  Unknown: label 255, a voxel of an absent brick (cells < 0 or >= n_rows) and a
+ * voxel outside the window.  A solid voxel emits the face towards direction d when the neighbour there is free, or when
+ * it is unknown and cap_unknown != 0; a neighbour that is solid (of any class) gives no face.
+ * Face code d = 2 * axis + side: axis 0 / 1 / 2 = x / y / z is the code of occd_render_voxels' `face` buffer (d >> 1),
+ * side 0 is the face at the voxel's lower coordinate (outward normal -e_axis), side 1 the one at its upper (+e_axis):
+ *   0 = -x, 1 = +x, 2 = -y, 3 = +y, 4 = -z, 5 = +z.
+ * Output, in window lattice units (corner (x, y, z), 0 <= x <= 16 gx ...; voxel (x, y, z) spans [x, x + 1] ...):
+ *   faces, F of them, ascending in (row, brick-local voxel index, face code): face_label (F) the voxel's label, face_dir (F)
+ *   the code, quads (F, 4) the vertex indices of the corners, counter-clockwise seen from outside, starting at the
+ *   lexicographically smallest corner c0: with b = (axis + 1) % 3, c = (axis + 2) % 3 the corners are c0, c0 + e_b,
+ *   c0 + e_b + e_c, c0 + e_c on side 1 and c0, c0 + e_c, c0 + e_c + e_b, c0 + e_b on side 0, so that
+ *   (v1 - v0) x (v3 - v0) is the outward normal;
+ *   vertices (V, 3) int32: every lattice corner some face uses, once, ascending in (x, y, z).
+ * Every array is a function of the input alone (every position is a sum of counts; the one atomic, a minimum, has an
+ * order-free result).  Corner key = x << (by + bz) | y << bz | z, b* = bit_length(16 g*); key_bits = bx + by + bz.
+ * The stages (the caller scans between them and sorts with occd_sort_pairs_u32):
+ *   occd_mesh_count  writes row_cell (n_rows; workspace: the cell of each row or a value outside the directory, read
+ *                    again by occd_mesh_emit) and counts[row] = the faces of that row.  One workgroup per row stages the
+ *                    brick and the facing planes of its six neighbours in LDS.
+ *   occd_mesh_emit   reads row_cell and offsets (the exclusive scan of counts); writes face_label, face_dir and, for
+ *                    corner k of face f, keys_lo[4 f + k] = the key's low 32 bits, keys_hi[4 f + k] = its high bits
+ *                    (only when key_bits > 32), refs[4 f + k] = 4 f + k.  No entry at or past n_faces is written.
+ *   occd_mesh_heads  reads keys_lo (keys_hi) SORTED by key; marks[p] = 1 where p = 0 or key[p] != key[p - 1], else 0.
+ *   occd_mesh_weld   reads the sorted keys_lo (keys_hi), refs and ranks (the inclusive scan of marks): quads[refs[p]] =
+ *                    ranks[p] - 1, and where ranks[p] differs from ranks[p - 1] (or p = 0) vertices[ranks[p] - 1] = the
+ *                    unpacked key.  A ref >= 4 n_faces or a rank outside 1 .. n_vertices writes nothing.
+ * No allocation, no host sync, no memset node (capture-safe).
+ * OCCD_EINVAL before any launch: a NULL argument or a pointer the stage uses (keys_hi only when key_bits > 32), labels,
+ * keys_lo or refs not 16-byte aligned, gx, gy or gz outside 1 .. OCCD_MESH_MAX_GRID, gx gy gz > OCCD_MESH_MAX_CELLS,
+ * n_rows <= 0, key_bits > OCCD_MESH_MAX_KEY_BITS, an entry of cells_host (the directory's host copy, optional) >= n_rows;
+ * emit, heads, weld: n_faces <= 0 or 4 n_faces >= 2^31 (the n of occd_sort_pairs_u32); weld: n_vertices <= 0.
+ * ------------------------------------------------------------------------ */
+#define OCCD_MESH_MAX_GRID 65536       /* bricks along one axis: the limits of occd_map_render's directory */
+#define OCCD_MESH_MAX_CELLS 134217728  /* 2^27 */
+#define OCCD_MESH_MAX_KEY_BITS 63
+typedef struct OccdMeshArgs {
+    const uint8_t* labels;         /* (n_rows, 4096) device                                                   */
+    const int32_t* cells;          /* (gx, gy, gz) device: row of the brick, negative = absent                */
+    const int32_t* cells_host;     /* optional host copy of cells, checked before the launch                  */
+    int32_t* row_cell;             /* (n_rows) workspace: count writes, emit reads                            */
+    int32_t* counts;               /* count: (n_rows)                                                         */
+    const int64_t* offsets;        /* emit: (n_rows) exclusive prefix sum of counts                           */
+    uint8_t* face_label;           /* emit: (F)                                                               */
+    uint8_t* face_dir;             /* emit: (F)                                                               */
+    uint32_t* keys_lo;             /* (4 F) emit writes; heads, weld read them sorted                         */
+    uint32_t* keys_hi;             /* (4 F) likewise, key_bits > 32 only                                      */
+    uint32_t* refs;                /* (4 F) emit writes 4 f + k; weld reads them sorted                       */
+    int32_t* marks;                /* heads: (4 F)                                                            */
+    const int32_t* ranks;          /* weld: (4 F) inclusive prefix sum of marks                               */
+    int32_t* quads;                /* weld: (F, 4)                                                            */
+    int32_t* vertices;             /* weld: (V, 3)                                                            */
+    int64_t n_faces;               /* F = the sum of counts                                                   */
+    int64_t n_vertices;            /* V = ranks[4 F - 1]                                                      */
+    int32_t gx, gy, gz, n_rows;
+    int32_t cap_unknown;
+} OccdMeshArgs;
+int occd_mesh_count(const OccdMeshArgs* a, void* stream);
+int occd_mesh_emit(const OccdMeshArgs* a, void* stream);
+int occd_mesh_heads(const OccdMeshArgs* a, void* stream);
+int occd_mesh_weld(const OccdMeshArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

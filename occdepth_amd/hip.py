@@ -87,6 +87,10 @@ LOVASZ_Q = abi.CONSTANTS["OCCD_LOVASZ_Q"]
 LOVASZ_KEY_BITS = abi.CONSTANTS["OCCD_LOVASZ_KEY_BITS"]
 LOVASZ_INVALID_KEY = abi.CONSTANTS["OCCD_LOVASZ_INVALID_KEY"]
 LOVASZ_RANK_TILE = abi.CONSTANTS["OCCD_LOVASZ_RANK_TILE"]
+MeshArgs = abi.STRUCTS["OccdMeshArgs"]
+MESH_MAX_GRID = abi.CONSTANTS["OCCD_MESH_MAX_GRID"]
+MESH_MAX_CELLS = abi.CONSTANTS["OCCD_MESH_MAX_CELLS"]
+MESH_MAX_KEY_BITS = abi.CONSTANTS["OCCD_MESH_MAX_KEY_BITS"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -3383,6 +3387,149 @@ def sort_pairs(keys, vals, begin_bit=0, end_bit=32, scratch=None):
     a.n, a.segments, a.begin_bit, a.end_bit = n, S, int(begin_bit), int(end_bit)
     _check(load().occd_sort_pairs_u32(ctypes.byref(a), _stream()), "occd_sort_pairs_u32")
     return (kalt, valt) if passes & 1 else (keys, vals)
+
+
+# ---- surface mesh of a brick volume (K39, csrc/mesh.hip, welded on K38) ----------------------------------------------
+MESH_MAX_CORNERS = (1 << 31) - 1         # 4 F corner references are one segment of sort_pairs
+
+
+def mesh_key_bits(grid):
+    """(bx, by, bz): the bits of a lattice corner's coordinates in the key x << (by + bz) | y << bz | z of a window of
+    `grid` = (gx, gy, gz) bricks, b = bit_length(16 g).  ValueError for a window over the directory's limits."""
+    grid = tuple(int(g) for g in grid)
+    if len(grid) != 3 or min(grid) < 1 or max(grid) > MESH_MAX_GRID or grid[0] * grid[1] * grid[2] > MESH_MAX_CELLS:
+        raise ValueError("the window is %s bricks: 1 .. 2^16 along an axis and at most 2^27 cells can be meshed; take a part "
+                         "of the map with key_range" % (grid,))
+    return tuple((MAP_BRICK * g).bit_length() for g in grid)
+
+
+def _mesh_volume_args(labels, cells, cap_unknown=True, cells_host=None):
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 2 or labels.shape[0] < 1 or \
+            labels.shape[1] != _MAP_BRICK_VOX:
+        raise RuntimeError("labels must be uint8 (n, %d) brick rows" % _MAP_BRICK_VOX)
+    if not torch.is_tensor(cells) or cells.dtype != torch.int32 or cells.dim() != 3 or cells.device != labels.device:
+        raise RuntimeError("cells must be an int32 (gx, gy, gz) directory on the device of labels")
+    mesh_key_bits(cells.shape)
+    a = MeshArgs()
+    a.labels, a.cells = _ptr(labels, "labels"), _ptr(cells, "cells")
+    if cells_host is not None:
+        if cells_host.is_cuda or cells_host.dtype != torch.int32 or cells_host.shape != cells.shape or not cells_host.is_contiguous():
+            raise RuntimeError("cells_host must be the directory's contiguous int32 copy in host memory")
+        a.cells_host = cells_host.data_ptr()
+    a.gx, a.gy, a.gz = (int(d) for d in cells.shape)
+    a.n_rows, a.cap_unknown = int(labels.shape[0]), int(bool(cap_unknown))
+    return a
+
+
+def mesh_count(labels, cells, cap_unknown=True, cells_host=None):
+    """occd_mesh_count: -> (counts (n,) int32, the faces of every brick row; row_cell (n,) int32, the workspace
+    `mesh_emit` reads).  labels (n, 4096) uint8 brick rows, cells (gx, gy, gz) int32 directory (semantic_map.MapVolume)."""
+    a = _mesh_volume_args(labels, cells, cap_unknown, cells_host)
+    n = int(labels.shape[0])
+    counts = torch.empty((n,), dtype=torch.int32, device=labels.device)
+    row_cell = torch.empty((n,), dtype=torch.int32, device=labels.device)
+    a.counts, a.row_cell = counts.data_ptr(), row_cell.data_ptr()
+    _check(load().occd_mesh_count(ctypes.byref(a), _stream()), "occd_mesh_count")
+    return counts, row_cell
+
+
+def mesh_emit(labels, cells, row_cell, offsets, n_faces, cap_unknown=True, cells_host=None):
+    """occd_mesh_emit: the faces behind `offsets` (n,) int64, the exclusive scan of mesh_count's counts -> face_label (F,),
+    face_dir (F,) uint8 and the 4 F corner references keys_lo, keys_hi (None for a key of at most 32 bits), refs, int32
+    tensors holding uint32 bits."""
+    a = _mesh_volume_args(labels, cells, cap_unknown, cells_host)
+    F, dev = int(n_faces), labels.device
+    face_label = torch.empty((F,), dtype=torch.uint8, device=dev)
+    face_dir = torch.empty((F,), dtype=torch.uint8, device=dev)
+    keys_lo = torch.empty((4 * F,), dtype=torch.int32, device=dev)
+    keys_hi = torch.empty((4 * F,), dtype=torch.int32, device=dev) if sum(mesh_key_bits(cells.shape)) > 32 else None
+    refs = torch.empty((4 * F,), dtype=torch.int32, device=dev)
+    if offsets.dtype != torch.int64 or offsets.numel() != labels.shape[0] or row_cell.dtype != torch.int32 or \
+            row_cell.numel() != labels.shape[0]:
+        raise RuntimeError("offsets must be int64 (n,) and row_cell int32 (n,)")
+    a.row_cell, a.offsets = _ptr(row_cell, "row_cell"), _ptr(offsets, "offsets")
+    a.face_label, a.face_dir, a.keys_lo, a.refs = face_label.data_ptr(), face_dir.data_ptr(), keys_lo.data_ptr(), refs.data_ptr()
+    a.keys_hi = None if keys_hi is None else keys_hi.data_ptr()
+    a.n_faces = F
+    _check(load().occd_mesh_emit(ctypes.byref(a), _stream()), "occd_mesh_emit")
+    return face_label, face_dir, keys_lo, keys_hi, refs
+
+
+def _mesh_corner_args(keys_lo, keys_hi, grid):
+    n = int(keys_lo.numel())
+    if keys_lo.dtype != torch.int32 or n < 4 or n % 4 or (keys_hi is not None and (keys_hi.dtype != torch.int32 or keys_hi.numel() != n)):
+        raise RuntimeError("the sorted keys must be int32 (4 F,) tensors (the bits of uint32 values)")
+    if sum(mesh_key_bits(grid)) > 32 and keys_hi is None:
+        raise RuntimeError("a window of %s bricks has keys of more than 32 bits: the high words are missing" % (tuple(grid),))
+    a = MeshArgs()
+    a.gx, a.gy, a.gz = (int(g) for g in grid)
+    a.n_rows, a.n_faces = 1, n // 4
+    a.keys_lo, a.keys_hi = _ptr(keys_lo, "keys_lo"), _ptr(keys_hi, "keys_hi")
+    return a, n
+
+
+def mesh_heads(keys_lo, keys_hi, grid):
+    """occd_mesh_heads on the SORTED keys -> marks (4 F,) int32, 1 where a key differs from its predecessor's."""
+    a, n = _mesh_corner_args(keys_lo, keys_hi, grid)
+    marks = torch.empty((n,), dtype=torch.int32, device=keys_lo.device)
+    a.marks = marks.data_ptr()
+    _check(load().occd_mesh_heads(ctypes.byref(a), _stream()), "occd_mesh_heads")
+    return marks
+
+
+def mesh_weld(keys_lo, keys_hi, refs, ranks, n_vertices, grid):
+    """occd_mesh_weld on the sorted (key, ref) pairs and `ranks`, the inclusive int32 scan of mesh_heads' marks ->
+    quads (F, 4) int32, vertices (V, 3) int32."""
+    a, n = _mesh_corner_args(keys_lo, keys_hi, grid)
+    if refs.dtype != torch.int32 or refs.numel() != n or ranks.dtype != torch.int32 or ranks.numel() != n:
+        raise RuntimeError("refs and ranks must be int32 (4 F,) tensors")
+    V = int(n_vertices)
+    quads = torch.empty((n // 4, 4), dtype=torch.int32, device=keys_lo.device)
+    vertices = torch.empty((V, 3), dtype=torch.int32, device=keys_lo.device)
+    a.refs, a.ranks, a.quads, a.vertices, a.n_vertices = _ptr(refs, "refs"), _ptr(ranks, "ranks"), quads.data_ptr(), vertices.data_ptr(), V
+    _check(load().occd_mesh_weld(ctypes.byref(a), _stream()), "occd_mesh_weld")
+    return quads, vertices
+
+
+def mesh_sort_corners(keys_lo, keys_hi, refs, bits):
+    """The (key, ref) pairs ascending in the key, stably, on exactly its `bits` bits: one sort_pairs for a key of at most
+    32 bits; else the low word first, the high words gathered by that permutation and sorted next (K38 is stable, so the two
+    are an LSD sort of the two-word key) -> (keys_lo, keys_hi, refs), sorted."""
+    n = int(keys_lo.numel())
+    if bits <= 32:
+        lo, ref = sort_pairs(keys_lo.view(1, n), refs.view(1, n), 0, bits)
+        return lo.reshape(n), None, ref.reshape(n)
+    lo0 = keys_lo.clone()                                              # sort_pairs overwrites its input
+    _, ref = sort_pairs(keys_lo.view(1, n), refs.view(1, n), 0, 32)
+    hi = keys_hi[ref.reshape(n).long()]
+    hi, ref = sort_pairs(hi.view(1, n), ref.reshape(1, n).contiguous(), 0, bits - 32)
+    ref = ref.reshape(n)
+    return lo0[ref.long()], hi.reshape(n), ref
+
+
+def mesh_faces(labels, cells, cap_unknown=True, cells_host=None):
+    """The indexed quad mesh of a brick volume (K39; the contract is in include/occdepth_amd.h): occd_mesh_count ->
+    exclusive scan -> occd_mesh_emit -> sort_pairs (K38) over the key's bits -> occd_mesh_heads -> inclusive scan ->
+    occd_mesh_weld.  labels (n, 4096) uint8 brick rows, cells (gx, gy, gz) int32 -> vertices (V, 3) int32 lattice corners
+    ascending in (x, y, z), quads (F, 4) int32, face_label (F,) uint8, face_dir (F,) uint8, faces ascending in (row, voxel,
+    face code).  Two host synchronisations, for F and for V; a volume without a face launches nothing after the count."""
+    bits = sum(mesh_key_bits(cells.shape))
+    counts, row_cell = mesh_count(labels, cells, cap_unknown, cells_host)
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    F = int(ends[-1])
+    dev = labels.device
+    if 4 * F > MESH_MAX_CORNERS:
+        raise ValueError("the volume has %d faces: 4 F = %d corner references are more than the 2^31 - 1 one sort takes; "
+                         "mesh a part of the map with key_range" % (F, 4 * F))
+    if F == 0:
+        return (torch.empty((0, 3), dtype=torch.int32, device=dev), torch.empty((0, 4), dtype=torch.int32, device=dev),
+                torch.empty((0,), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=torch.uint8, device=dev))
+    offsets = (ends - counts).contiguous()
+    face_label, face_dir, keys_lo, keys_hi, refs = mesh_emit(labels, cells, row_cell, offsets, F, cap_unknown, cells_host)
+    keys_lo, keys_hi, refs = mesh_sort_corners(keys_lo, keys_hi, refs, bits)
+    ranks = torch.cumsum(mesh_heads(keys_lo, keys_hi, cells.shape), 0, dtype=torch.int32)
+    quads, vertices = mesh_weld(keys_lo, keys_hi, refs, ranks, int(ranks[-1]), cells.shape)
+    return vertices, quads, face_label, face_dir
 
 
 # ---- Lovasz-softmax loss (csrc/lovasz.hip, on K38) -------------------------------------------------------------------

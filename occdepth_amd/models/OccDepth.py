@@ -175,6 +175,7 @@ class OccDepth(_Base):
         # [OCCDEPTH_MAP_SUBMISSION=<dir>]: the map read back into every frame] [OCCDEPTH_MAP_GATHER=0] [OCCDEPTH_MAP_SAVE=1] in the environment of an unmodified scripts/eval.py.  Off: nothing is
         # imported, allocated or launched.  Every other method reaches it through getattr(self, "semantic_map", None).
         # [OCCDEPTH_MAP_VISIBILITY=<w_vis>,<w_hid>]: the prediction map takes occlusion-aware votes (visibility.py, K34).
+        # [OCCDEPTH_MAP_MESH=1]: every sequence's maps also leave as surface meshes (mesh.py, K39).
         self.semantic_map = None
         if env("OCCDEPTH_MAP_DIR", ""):
             weights = env("OCCDEPTH_MAP_VISIBILITY", "")
@@ -185,7 +186,8 @@ class OccDepth(_Base):
                                      submission_dir=env("OCCDEPTH_MAP_SUBMISSION", "") or None,
                                      exclude_self=env("OCCDEPTH_MAP_FRAMES_SELF", "1") == "0",
                                      gather=env("OCCDEPTH_MAP_GATHER", "1") != "0", save_maps=env("OCCDEPTH_MAP_SAVE", "0") == "1",
-                                     visibility=tuple(int(w) for w in weights.split(",")) if weights else None)
+                                     visibility=tuple(int(w) for w in weights.split(",")) if weights else None,
+                                     mesh=env("OCCDEPTH_MAP_MESH", "0") == "1")
         # RayIoU of the test / validation predictions (ray_metric.py, K35), OFF by default: `enable_ray_metrics()` -- or
         # OCCDEPTH_RAY_METRIC=1 [OCCDEPTH_RAY_ORIGINS=<n>[,<step>]] [OCCDEPTH_RAY_POSES=<.../dataset/sequences>] (falls back
         # to OCCDEPTH_FUSE_POSES) [OCCDEPTH_RAY_UNKNOWN=pass] in the environment of an unmodified scripts/eval.py.  Off:
@@ -990,7 +992,7 @@ class OccDepth(_Base):
 
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
     def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
-                            exclude_self=False, max_frames=1024, gather=True, save_maps=False, visibility=None):
+                            exclude_self=False, max_frames=1024, gather=True, save_maps=False, visibility=None, mesh=False):
         """Vote every test / validation frame into a world-frame voxel map of its sequence (semantic_map.SemanticMap:
         ego-motion from <poses_root>/<sequence>/poses.txt and calib.txt): the arg-max of the unfused logits into the
         prediction map and the frame's target into the ground-truth map, both inside the frame's `fov_mask_1` when the
@@ -1032,7 +1034,12 @@ class OccDepth(_Base):
         every other voxel inside the FOV mask with w_hidden, so a frame that only guessed a voxel no longer outvotes one
         that saw it.  The ground-truth map is unchanged.  Kept frames hold that weight volume where they held the mask
         (the same bytes), the read-back retracts it under exclude_self, and min_obs counts vote units.  None (the
-        default): nothing more is imported or launched.  The effect on mIoU is not measured."""
+        default): nothing more is imported or launched.  The effect on mIoU is not measured.
+
+        mesh (OCCDEPTH_MAP_MESH=1): before the maps are released -- after the exchange over the ranks, by rank 0 alone --
+        every sequence's maps are also written as closed surface meshes, <out_dir>/<step>_<sequence>_{pred,gt}_mesh.ply
+        (mesh.mesh_map with min_obs, K39: one quad per exposed voxel face, every lattice corner once; mesh.write_mesh_ply).
+        False (the default): mesh.py is not imported and nothing more is allocated or launched."""
         if visibility is not None:
             if len(tuple(visibility)) != 2:
                 raise ValueError("visibility is (w_visible, w_hidden) (OCCDEPTH_MAP_VISIBILITY=<w_vis>,<w_hid>), got %r" % (visibility,))
@@ -1057,7 +1064,8 @@ class OccDepth(_Base):
                              "maps": {}, "poses": {}, "paths": [], "views": views,
                              "frames": bool(frames) or bool(submission_dir), "submission_dir": str(submission_dir) if submission_dir else None,
                              "exclude_self": bool(exclude_self), "max_frames": int(max_frames), "kept": {}, "mapped_stats": {},
-                             "gather": bool(gather), "save_maps": bool(save_maps), "seen": {}, "visibility": visibility}
+                             "gather": bool(gather), "save_maps": bool(save_maps), "seen": {}, "visibility": visibility,
+                             "mesh": bool(mesh)}
         return self
 
     def _map_step(self, step_type, batch, ssc_pred, target):
@@ -1174,6 +1182,11 @@ class OccDepth(_Base):
                 st["paths"].append(semantic_map.write_ply(path, coords, labels, n_obs, m.voxel_size, colours))
                 if st.get("save_maps"):
                     st["paths"].append(m.save(os.path.join(st["out_dir"], "%s_%s_%s.occmap" % (step_type, key[1], name))))
+            if st.get("mesh") and writer:
+                from .. import mesh as surface
+                for part, name in zip(surface.mesh_map(pair[0], pair[1], st["min_obs"]), ("pred", "gt")):
+                    path = os.path.join(st["out_dir"], "%s_%s_%s_mesh.ply" % (step_type, key[1], name))
+                    st["paths"].append(surface.write_mesh_ply(path, part, colours))
             semantic_map.map_confusion(pair[0], pair[1], metric)
             if st.get("views") and writer:
                 volume = semantic_map.MapVolume(pair[0], pair[1], st["min_obs"])

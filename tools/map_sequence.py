@@ -4,7 +4,7 @@ as a point PLY, and score a prediction map against a ground-truth map.
     python tools/map_sequence.py --poses .../dataset/sequences/08 --pred out/08 --gt .../dataset/sequences/08/voxels \\
         --out maps/08 [--min-obs 2] [--fov] [--every 5] [--views bev oblique] [--png-side 2048] [--camera-every 50 --t-max 80]
         [--frames-out DIR [--exclude-self] [--keep-own]] [--frame-range FIRST LAST] [--save-map PREFIX] [--load-map PREFIX ...]
-        [--visibility W_VIS W_HID]
+        [--visibility W_VIS W_HID] [--mesh [--mesh-open]]
 
 --pred / --gt name a directory; what it holds decides how it is read:
     <frame>.pkl                          the pickles of generate_output.py (occdepth_amd.output.write_outputs): "y_pred"
@@ -29,6 +29,8 @@ run over frames 0..1999 with --save-map and a second over 2000..4070 with --load
 the left colour camera (P2 and Tr of calib.txt, --camera-size) are cast through every --pred frame's own labels; a voxel a ray
 reaches, up to and including the first occupied one, votes with W_VIS, any other (inside the mask with --fov) with W_HID.  The
 ground-truth map votes as before; --frames-out hands each frame's weights back to the read-back.
+--mesh also writes the maps' surfaces, <out>_pred_mesh.ply / <out>_gt_mesh.ply (occdepth_amd/mesh.py, K39): one quad per exposed
+voxel face, every lattice corner once, closed towards unobserved space; --mesh-open keeps only the faces towards observed free space.
 """
 import argparse
 import glob
@@ -212,6 +214,22 @@ def draw(maps, poses, args, colours):
     return paths
 
 
+def write_meshes(maps, args, colours):
+    """--mesh: <out>_pred_mesh.ply / <out>_gt_mesh.ply, the surfaces of the maps (occdepth_amd.mesh, K39) -> the paths."""
+    from occdepth_amd import mesh
+    closed = not args.mesh_open
+    if "pred" in maps and "gt" in maps:
+        parts = dict(zip(("pred", "gt"), mesh.mesh_map(maps["pred"], maps["gt"], args.min_obs, cap_unknown=closed)))
+    else:
+        role = "pred" if "pred" in maps else "gt"
+        parts = {role: mesh.mesh_map(maps[role], None, args.min_obs, cap_unknown=closed)}
+    paths = []
+    for role, part in parts.items():
+        paths.append(mesh.write_mesh_ply("%s_%s_mesh.ply" % (args.out, role), part, colours))
+        print("%s: %d faces, %d vertices (%s surface)" % (paths[-1], part.n_faces, part.n_vertices, "closed" if closed else "open"))
+    return paths
+
+
 def run(args, device=None):
     device = device or torch.device("cuda")
     poses = fuse.read_kitti_poses(args.poses)
@@ -232,6 +250,8 @@ def run(args, device=None):
         raise SystemExit("give --pred, --gt or both")
     if args.views or args.camera_every:
         draw(maps, poses, args, colours)
+    if args.mesh:
+        write_meshes(maps, args, colours)
     stats = None
     if len(maps) == 2:
         from occdepth_amd.loss.sscMetrics import SSCMetrics
@@ -268,6 +288,10 @@ def parser():
                     help="draw the map through the left colour camera (P2, Tr of calib.txt) of every n-th posed frame")
     ap.add_argument("--camera-size", type=int, nargs=2, default=(370, 1220), help="H W of the camera pictures")
     ap.add_argument("--t-max", type=float, default=80.0, help="camera pictures: voxels deeper than this (m) are not drawn")
+    ap.add_argument("--mesh", action="store_true",
+                    help="write the maps' surfaces as indexed quad meshes: <out>_{pred,gt}_mesh.ply (occdepth_amd.mesh)")
+    ap.add_argument("--mesh-open", action="store_true",
+                    help="--mesh: leave out the faces towards unobserved space (only where observed free space meets matter)")
     ap.add_argument("--frames-out", default=None,
                     help="read the prediction map back into every --pred frame: DIR/sequences/<seq>/predictions/<frame>.label")
     ap.add_argument("--exclude-self", action="store_true", help="--frames-out: take the frame's own vote out of the map first")

@@ -3,11 +3,12 @@ a display: the headless replacement for the reference's scripts/visualization/ki
 and NYU_vis_pred.py.
 
     python tools/render_predictions.py <dir of .pkl> [--out DIR] [--dataset kitti|NYU] [--views camera bev oblique]
-                                       [--image-size H W] [--target] [--batch 8]
+                                       [--image-size H W] [--target] [--batch 8] [--mesh]
 
 Every <name>.pkl gives <name>_<view>.png next to it, or under --out with the same sub-directories.  Pickle keys: `y_pred`
 (X, Y, Z), `fov_mask_1` (dims voxels outside are dimmed), `cam_k`, `T_velo_2_cam` (kitti), `cam_pose`, `vox_origin` (NYU);
---target colours the prediction against the pickle's `target` (error mode).  Frames are batched per launch.
+--target colours the prediction against the pickle's `target` (error mode).  Frames are batched per launch.  --mesh also writes <name>_mesh.ply, the frame's surface as an indexed quad
+mesh in world metres (occdepth_amd/mesh.py, K39).
 """
 import argparse
 import os
@@ -72,7 +73,20 @@ def render_group(paths, frames, args, dev):
             os.makedirs(os.path.dirname(stem), exist_ok=True)
         for name, h in zip(args.views, host):
             written.append(render.write_png("%s_%s.png" % (stem, name), h[i]))
+        if args.mesh:
+            written.append(write_frame_mesh(stem, labels[i], frames[i], vs, args.dataset))
     return written
+
+
+def write_frame_mesh(stem, labels, frame, vs, dataset):
+    """--mesh: <stem>_mesh.ply, the closed surface of one frame's prediction (occdepth_amd.mesh.mesh_labels, K39) -> the path."""
+    from occdepth_amd import mesh
+    if dataset == "kitti":
+        origin = (0.0, -0.5 * vs * int(labels.shape[1]), -2.0)
+    else:
+        origin = np.asarray(frame["vox_origin"], dtype=np.float64).reshape(-1)[:3]
+    part = mesh.mesh_labels(labels, vs, origin)
+    return mesh.write_mesh_ply("%s_mesh.ply" % stem, part, render.palette(dataset))
 
 
 def main(argv=None):
@@ -86,6 +100,7 @@ def main(argv=None):
     ap.add_argument("--voxel-size", type=float, default=None, help="metres; default: the dataset's, from the grid's size")
     ap.add_argument("--target", action="store_true")
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--mesh", action="store_true", help="also write every frame's surface as <name>_mesh.ply (occdepth_amd.mesh)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("render_predictions.py renders on the GPU; none is visible")

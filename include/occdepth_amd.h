@@ -98,7 +98,11 @@ extern "C" {
  *     radix sort, csrc/sort.hip) and OCCD_LOVASZ_*, OccdLovaszArgs, occd_lovasz_errors, occd_lovasz_ranks and
  *     occd_lovasz_bwd (the Lovasz-softmax loss on top of it, csrc/lovasz.hip): two new structs and four new functions only;
  *     likewise OCCD_MESH_*, OccdMeshArgs, occd_mesh_count, occd_mesh_emit, occd_mesh_heads and occd_mesh_weld (K39, the
- *     indexed quad mesh of a brick volume, csrc/mesh.hip): one new struct and four new functions only */
+ *     indexed quad mesh of a brick volume, csrc/mesh.hip): one new struct and four new functions only; likewise
+ *     OCCD_CCL_*, OccdCclArgs, occd_ccl_segments, occd_ccl_roots, occd_ccl_compact and occd_ccl_filter (K40, connected
+ *     components of a label volume, csrc/ccl.hip) and OccdCclPairArgs, occd_ccl_pair_marks, occd_ccl_pair_emit,
+ *     occd_ccl_pair_heads and occd_ccl_pair_rows (the exact overlap counts of two segment volumes, sorted with
+ *     occd_sort_pairs_u32): two new structs and eight new functions only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -1973,6 +1977,121 @@ int occd_mesh_count(const OccdMeshArgs* a, void* stream);
 int occd_mesh_emit(const OccdMeshArgs* a, void* stream);
 int occd_mesh_heads(const OccdMeshArgs* a, void* stream);
 int occd_mesh_weld(const OccdMeshArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * K40: connected components of a label volume (csrc/ccl.hip).  Additive (OCCD_ABI_VERSION note).
+ * Input: labels (B, X, Y, Z) uint8, z fastest, N = X Y Z < 2^31 - 1 voxels a frame; the B frames are independent.  Two
+ * class masks of 256 bits (bit l of a mask = word l >> 5, bit l & 31), disjoint, either may be empty:
+ *   things: a segment is a maximal set of voxels of one and the same class that is connected under `connectivity`
+ *           (6: faces; 26: faces, edges and corners).  With `instances` (B, X, Y, Z) int32 given, a segment is instead
+ *           every voxel of the frame with one and the same instance id in 1 .. N - 1 (ids <= 0 or >= N belong to no
+ *           segment); an id that carries more than one class sets OCCD_CCL_STATUS_INSTANCE.
+ *   stuff:  a segment is every voxel of that class in the frame, as one.
+ * A label in neither mask (0 and 255 too, unless a mask names them) belongs to no segment.
+ * seg (B, X, Y, Z) int32: 0 where the voxel belongs to no segment, else 1 + the smallest linear index, within the frame,
+ * of any voxel of its segment.  This canonical form makes seg a function of the input alone, whatever the schedule.
+ *
+ * occd_ccl_segments: labels -> seg, four launches.  (1) fill: stuff_min = INT32_MAX, *status = 0.  (2) tile-local: one
+ *   workgroup per OCCD_CCL_TILE^3 tile stages the tile's labels in LDS and unites every pair of neighbouring things voxels
+ *   of one class inside the tile (union-find in LDS: a root is the smallest index of its tree, links go from the larger
+ *   root to the smaller with an LDS atomic minimum), then writes parent[v] = the frame-linear index of the root of v (-1
+ *   for a voxel outside things) and lowers stuff_min[b][class] with one atomic minimum per class present in the tile.
+ *   (3) seam: one thread per voxel unites it with each of its "earlier" neighbours (3 of 6, 13 of 26) of the same class
+ *   that lies in ANOTHER tile.  parent only ever decreases and every value ever stored in parent[v] is a voxel of v's
+ *   true component, so a stale read can only name an older ancestor: find() reads with agent-scope atomic loads, and a
+ *   link is made only by atomicMin(parent + hi, lo), which took effect as a link iff it returns hi (hi was a root at that
+ *   instant); otherwise the union goes on from the value returned.  A stale read costs a retry, never a wrong merge.
+ *   (4) flatten, a launch of its own (it reads parent only after the launch boundary): seg = 1 + root, or 1 +
+ *   stuff_min[b][class], or 0.  With OCCD_CCL_NO_TILE_PASS in flags (2) is replaced by parent[v] = v and (3) unites
+ *   every pair: the same seg, for measurements.  No kernel waits for another workgroup.  Every loop that depends on the
+ *   data is bounded: a find by N + 1 steps (4097 in LDS), a union by N + 1 retries (parents strictly decrease); a
+ *   kernel that overruns sets OCCD_CCL_STATUS_OVERRUN in *status and goes on to its end without spinning; the caller
+ *   reads *status when it next synchronises.
+ *   Workspace: parent B N int32, stuff_min 256 B int32, status 1 int32.
+ * occd_ccl_roots: seg -> marks (B, N) int32, 1 at the voxel whose index + 1 is its seg (one per segment), else 0.
+ * occd_ccl_compact: seg, ranks (B, N) int32 = the inclusive scan of marks within each frame, offsets (B) int64 = the
+ *   exclusive scan over the frames of count[b] = ranks[b][N - 1], n_segments = the sum of count -> ids (B, N) int32, the
+ *   segments of a frame numbered 1 .. count[b] in ascending order of seg, 0 kept; and, for segment k of frame b at row
+ *   offsets[b] + k - 1 of the tables (n_segments rows): seg_class its class, seg_index its smallest voxel index, seg_size
+ *   its voxels (integer atomic adds on zeroed rows: the order does not matter).  n_segments = 0: ids only.
+ * occd_ccl_filter: labels, seg -> out (B, X, Y, Z) uint8, a copy of labels in which every voxel of a things segment of
+ *   fewer than min_voxels voxels is 0; stuff and every other voxel pass.  Workspace: parent, B N int32 (the sizes).
+ * Integer arithmetic only; no allocation, no host read, no memset node (capture-safe).
+ * OCCD_EINVAL before any launch: a NULL argument or a pointer the stage uses, batch, X, Y or Z < 1, batch > 65535, N >=
+ * 2^31 - 1, B N >= 2^40, connectivity not 6 or 26 (segments), masks that overlap, min_voxels < 1 (filter), n_segments < 0.
+ * ------------------------------------------------------------------------ */
+#define OCCD_CCL_TILE 16
+#define OCCD_CCL_NO_TILE_PASS 1        /* flags: seam pass over every voxel pair */
+#define OCCD_CCL_STATUS_OVERRUN 1      /* *status: a bounded loop ran out (a bug or a corrupted workspace) */
+#define OCCD_CCL_STATUS_INSTANCE 2     /* *status: an instance id carries more than one class */
+typedef struct OccdCclArgs {
+    const uint8_t* labels;         /* (B, X, Y, Z)                                                            */
+    const int32_t* instances;      /* (B, X, Y, Z) or NULL (segments)                                         */
+    int32_t* parent;               /* workspace (B, N): segments, filter                                      */
+    int32_t* stuff_min;            /* workspace (B, 256): segments                                            */
+    int32_t* status;               /* device word: segments                                                   */
+    int32_t* seg;                  /* (B, N): segments writes; roots, compact, filter read                    */
+    int32_t* marks;                /* roots: (B, N)                                                           */
+    const int32_t* ranks;          /* compact: (B, N)                                                         */
+    const int64_t* offsets;        /* compact: (B)                                                            */
+    int32_t* ids;                  /* compact: (B, N)                                                         */
+    uint8_t* seg_class;            /* compact: (n_segments)                                                   */
+    int32_t* seg_size;             /* compact: (n_segments)                                                   */
+    int32_t* seg_index;            /* compact: (n_segments)                                                   */
+    uint8_t* out;                  /* filter: (B, X, Y, Z)                                                    */
+    int64_t n_segments;
+    int32_t batch, X, Y, Z;
+    int32_t connectivity, min_voxels, flags;
+    uint32_t things[8], stuff[8];
+} OccdCclArgs;
+int occd_ccl_segments(const OccdCclArgs* a, void* stream);
+int occd_ccl_roots(const OccdCclArgs* a, void* stream);
+int occd_ccl_compact(const OccdCclArgs* a, void* stream);
+int occd_ccl_filter(const OccdCclArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * The overlaps of two segment-id volumes, counted exactly (csrc/ccl.hip, on K38).  Additive.  g_ids, p_ids (B, N) int32:
+ * the `ids` of occd_ccl_compact for the target and the prediction of the same frames; g_offsets, p_offsets (B) int64 its
+ * `offsets`.  A voxel is valid iff target != 255 and, with a mask, mask != 0.  The GLOBAL id of a segment is offsets[b] +
+ * id (1-based over the batch), 0 = no segment.  For every ordered pair (g, p) of global ids, not both 0, that some valid
+ * voxel carries: one row (g, p, n), n = the number of such voxels; rows ascending in (g, p).  M = B N < 2^31.
+ *   occd_ccl_pair_marks  marks[i] = 1 where voxel i is valid and lies in a segment of either volume, else 0.
+ *   occd_ccl_pair_emit   pos = the inclusive scan of marks over all M voxels, n_pairs = pos[M - 1]: for a marked voxel
+ *                        at q = pos[i] - 1: keys_lo[q] = g << p_bits | p when keys_hi is NULL (g_bits + p_bits <= 32),
+ *                        else keys_lo[q] = p, keys_hi[q] = g; refs[q] = q.
+ *   (the caller sorts by key with occd_sort_pairs_u32: one stage over p_bits + g_bits, or p_bits then g_bits)
+ *   occd_ccl_pair_heads  the SORTED keys -> marks[q] = 1 where q = 0 or key[q] != key[q - 1].
+ *   occd_ccl_pair_rows   the sorted keys and ranks = the inclusive scan of those marks, n_rows = ranks[n_pairs - 1] ->
+ *                        row_g, row_p, row_n (n_rows); row_start (n_rows) is workspace.  Two launches.
+ * No allocation, no host read, no memset node.  OCCD_EINVAL before any launch: a NULL argument or a pointer the stage uses,
+ * batch or n < 1, batch n >= 2^31, p_bits outside 1 .. 32 or > 31 without keys_hi, n_pairs or n_rows < 1 where the stage
+ * reads them.
+ * ------------------------------------------------------------------------ */
+typedef struct OccdCclPairArgs {
+    const int32_t* g_ids;          /* (B, N) marks, emit                                                      */
+    const int32_t* p_ids;          /* (B, N)                                                                  */
+    const uint8_t* target;         /* (B, N) labels: 255 = not valid                                          */
+    const uint8_t* mask;           /* (B, N) or NULL                                                          */
+    const int64_t* g_offsets;      /* (B) emit                                                                */
+    const int64_t* p_offsets;      /* (B) emit                                                                */
+    int32_t* marks;                /* marks: (B N); heads: (n_pairs)                                          */
+    const int32_t* pos;            /* emit: (B N)                                                             */
+    uint32_t* keys_lo;             /* (n_pairs) emit writes; heads, rows read them sorted                     */
+    uint32_t* keys_hi;             /* (n_pairs) or NULL                                                       */
+    uint32_t* refs;                /* (n_pairs) emit                                                          */
+    const int32_t* ranks;          /* rows: (n_pairs)                                                         */
+    int32_t* row_start;            /* rows: workspace (n_rows)                                                */
+    int32_t* row_g;                /* rows: (n_rows)                                                          */
+    int32_t* row_p;
+    int32_t* row_n;
+    int64_t n;                     /* N, voxels a frame                                                       */
+    int64_t n_pairs, n_rows;
+    int32_t batch, p_bits;
+} OccdCclPairArgs;
+int occd_ccl_pair_marks(const OccdCclPairArgs* a, void* stream);
+int occd_ccl_pair_emit(const OccdCclPairArgs* a, void* stream);
+int occd_ccl_pair_heads(const OccdCclPairArgs* a, void* stream);
+int occd_ccl_pair_rows(const OccdCclPairArgs* a, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * In-library kernel timing (HIP events on the launch stream) used by bench.py

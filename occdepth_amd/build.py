@@ -14,7 +14,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["conv3d_igemm.hip", "conv3d_c32p.hip", "lift.hip", "nchw2d.hip", "loss.hip", "conv3d_wgrad.hip", "conv3d_bf16.hip", "bn.hip", "bneck3d.hip", "rows_gemm.hip", "gemm_x3.hip", "wino2d.hip", "wino_conv2d.hip", "pw_gemm.hip", "se2d.hip", "ipc_allreduce.hip", "graph_fix.hip", "targets.hip", "optim.hip", "render.hip", "stereo.hip", "fuse.hip", "semantic_map.hip", "map_render.hip", "visibility.hip", "ray_metric.hip", "render_loss.hip", "edt.hip", "sort.hip", "lovasz.hip", "mesh.hip", "prof.cpp"]
+SOURCES = ["conv3d_igemm.hip", "conv3d_c32p.hip", "lift.hip", "nchw2d.hip", "loss.hip", "conv3d_wgrad.hip", "conv3d_bf16.hip", "bn.hip", "bneck3d.hip", "rows_gemm.hip", "gemm_x3.hip", "wino2d.hip", "wino_conv2d.hip", "pw_gemm.hip", "se2d.hip", "ipc_allreduce.hip", "graph_fix.hip", "targets.hip", "optim.hip", "render.hip", "stereo.hip", "fuse.hip", "semantic_map.hip", "map_render.hip", "visibility.hip", "ray_metric.hip", "render_loss.hip", "edt.hip", "sort.hip", "lovasz.hip", "mesh.hip", "ccl.hip", "prof.cpp"]
 # every header under csrc/ (a new one cannot drop out of source_digest()) + the public C ABI
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "occdepth_amd.h")]
 LIB = os.path.join(HERE, "libocc_hip.so")

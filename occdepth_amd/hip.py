@@ -91,6 +91,12 @@ MeshArgs = abi.STRUCTS["OccdMeshArgs"]
 MESH_MAX_GRID = abi.CONSTANTS["OCCD_MESH_MAX_GRID"]
 MESH_MAX_CELLS = abi.CONSTANTS["OCCD_MESH_MAX_CELLS"]
 MESH_MAX_KEY_BITS = abi.CONSTANTS["OCCD_MESH_MAX_KEY_BITS"]
+CclArgs = abi.STRUCTS["OccdCclArgs"]
+CclPairArgs = abi.STRUCTS["OccdCclPairArgs"]
+CCL_TILE = abi.CONSTANTS["OCCD_CCL_TILE"]
+CCL_NO_TILE_PASS = abi.CONSTANTS["OCCD_CCL_NO_TILE_PASS"]
+CCL_STATUS_OVERRUN = abi.CONSTANTS["OCCD_CCL_STATUS_OVERRUN"]
+CCL_STATUS_INSTANCE = abi.CONSTANTS["OCCD_CCL_STATUS_INSTANCE"]
 ProfRow = abi.STRUCTS["occd_prof_row"]
 
 
@@ -3530,6 +3536,198 @@ def mesh_faces(labels, cells, cap_unknown=True, cells_host=None):
     ranks = torch.cumsum(mesh_heads(keys_lo, keys_hi, cells.shape), 0, dtype=torch.int32)
     quads, vertices = mesh_weld(keys_lo, keys_hi, refs, ranks, int(ranks[-1]), cells.shape)
     return vertices, quads, face_label, face_dir
+
+
+# ---- connected components of a label volume (K40, csrc/ccl.hip; the overlaps are sorted on K38) ----------------------
+def ccl_class_mask(classes):
+    """The 256-bit class mask of the C ABI (8 uint32 words, bit l of word l >> 5) of an iterable of labels 0..255."""
+    words = [0] * 8
+    for c in classes or ():
+        c = int(c)
+        if not 0 <= c <= 255:
+            raise ValueError("a class must be 0..255, got %r" % (c,))
+        words[c >> 5] |= 1 << (c & 31)
+    return tuple(words)
+
+
+def ccl_workspace(batch, dims, device):
+    """(parent (B, N) int32, stuff_min (B, 256) int32, status (1,) int32): the workspace of `ccl_segments` and `ccl_filter`
+    for `batch` frames of `dims` = (X, Y, Z): 4 B N + 1024 B + 4 bytes."""
+    n = int(dims[0]) * int(dims[1]) * int(dims[2])
+    return (torch.empty((int(batch), n), dtype=torch.int32, device=device),
+            torch.empty((int(batch), 256), dtype=torch.int32, device=device), torch.zeros((1,), dtype=torch.int32, device=device))
+
+
+def _ccl_volume_args(labels, things, stuff, name="labels"):
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 4 or labels.numel() == 0:
+        raise RuntimeError("%s must be a non-empty uint8 (B, X, Y, Z) tensor" % name)
+    B, X, Y, Z = (int(d) for d in labels.shape)
+    if X * Y * Z >= (1 << 31) - 1 or B > 65535:
+        raise ValueError("a frame of %d voxels (B = %d): a frame must stay below 2^31 - 1 voxels and B below 65536" % (X * Y * Z, B))
+    a = CclArgs()
+    a.batch, a.X, a.Y, a.Z = B, X, Y, Z
+    t, s = ccl_class_mask(things), ccl_class_mask(stuff)
+    if any(x & y for x, y in zip(t, s)):
+        raise ValueError("things %r and stuff %r overlap" % (sorted(things), sorted(stuff)))
+    a.things[:], a.stuff[:] = t, s
+    a.labels = _ptr(labels, name)
+    return a
+
+
+def _ccl_check_workspace(workspace, labels):
+    B, n = int(labels.shape[0]), int(labels[0].numel())
+    if workspace is None:
+        workspace = ccl_workspace(B, labels.shape[1:], labels.device)
+    parent, stuff_min, status = workspace
+    for t, need, name in ((parent, B * n, "parent"), (stuff_min, B * 256, "stuff_min"), (status, 1, "status")):
+        if t.dtype != torch.int32 or t.numel() < need or t.device != labels.device:
+            raise RuntimeError("the workspace's %s must be int32 of at least %d elements on the device of labels" % (name, need))
+    return workspace
+
+
+def ccl_status(workspace):
+    """Read the status word `ccl_segments` left in its workspace (one host synchronisation) and raise on a set bit."""
+    code = int(workspace[2][0])
+    if code & CCL_STATUS_OVERRUN:
+        raise RuntimeError("occd_ccl_segments: a bounded union-find loop ran out (status %d): a bug or a corrupted workspace" % code)
+    if code & CCL_STATUS_INSTANCE:
+        raise ValueError("occd_ccl_segments: an instance id carries voxels of more than one class (status %d)" % code)
+
+
+def ccl_segments(labels, things, stuff=(), connectivity=26, workspace=None, instances=None, tile_pass=True, check=True):
+    """occd_ccl_segments: labels (B, X, Y, Z) uint8 -> seg (B, X, Y, Z) int32, 0 outside every segment, else 1 + the smallest
+    frame-linear index of the voxel's segment (the contract is in include/occdepth_amd.h).  things / stuff: iterables of
+    classes; instances (B, X, Y, Z) int32: the things segments are the instance ids 1 .. N - 1 instead of the components.
+    workspace: `ccl_workspace(...)`, made here when None.  check: read the status word (one host synchronisation) and
+    raise if a kernel set it; with check=False nothing is read -- call `ccl_status(workspace)` later.
+    tile_pass=False runs the seam pass over every voxel pair (the same result; for measurements)."""
+    if int(connectivity) not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26, got %r" % (connectivity,))
+    a = _ccl_volume_args(labels, things, stuff)
+    workspace = _ccl_check_workspace(workspace, labels)
+    seg = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if instances is not None:
+        if not torch.is_tensor(instances) or instances.dtype != torch.int32 or instances.shape != labels.shape:
+            raise RuntimeError("instances must be an int32 tensor of labels' shape")
+        a.instances = _ptr(instances, "instances")
+    a.parent, a.stuff_min, a.status = (_ptr(t, "workspace") for t in workspace)
+    a.seg, a.connectivity, a.flags = seg.data_ptr(), int(connectivity), 0 if tile_pass else CCL_NO_TILE_PASS
+    _check(load().occd_ccl_segments(ctypes.byref(a), _stream()), "occd_ccl_segments")
+    if check:
+        ccl_status(workspace)
+    return seg
+
+
+def ccl_compact(seg, labels):
+    """Number the segments of every frame 1 .. K_b in ascending order of seg: occd_ccl_roots -> a scan within each frame ->
+    occd_ccl_compact.  -> ids (B, X, Y, Z) int32 (0 kept), count (B,) int64 (a HOST tensor: the one host read), offsets (B,)
+    int64 on the device (the exclusive scan of count) and the tables of sum(count) rows, frame after frame: seg_class
+    uint8, seg_size int32 (voxels), seg_index int32 (the smallest voxel index, seg - 1)."""
+    if not torch.is_tensor(seg) or seg.dtype != torch.int32 or seg.shape != labels.shape:
+        raise RuntimeError("seg must be the int32 tensor ccl_segments made of labels")
+    a = _ccl_volume_args(labels, (), ())
+    B, n, dev = int(labels.shape[0]), int(labels[0].numel()), labels.device
+    marks = torch.empty((B, n), dtype=torch.int32, device=dev)
+    a.seg, a.marks = _ptr(seg, "seg"), marks.data_ptr()
+    _check(load().occd_ccl_roots(ctypes.byref(a), _stream()), "occd_ccl_roots")
+    ranks = torch.cumsum(marks, 1, dtype=torch.int32)
+    count_dev = ranks[:, -1].to(torch.int64)
+    offsets = (torch.cumsum(count_dev, 0) - count_dev).contiguous()
+    count = count_dev.cpu()
+    K = int(count.sum())
+    ids = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    seg_class = torch.empty((K,), dtype=torch.uint8, device=dev)
+    seg_size = torch.empty((K,), dtype=torch.int32, device=dev)
+    seg_index = torch.empty((K,), dtype=torch.int32, device=dev)
+    a.ranks, a.offsets, a.ids, a.n_segments = _ptr(ranks, "ranks"), _ptr(offsets, "offsets"), ids.data_ptr(), K
+    if K:
+        a.seg_class, a.seg_size, a.seg_index = seg_class.data_ptr(), seg_size.data_ptr(), seg_index.data_ptr()
+    _check(load().occd_ccl_compact(ctypes.byref(a), _stream()), "occd_ccl_compact")
+    return ids, count, offsets, (seg_class, seg_size, seg_index)
+
+
+def ccl_filter(labels, things, min_voxels, connectivity=26, stuff=(), workspace=None, seg=None, check=True):
+    """occd_ccl_filter: a copy of labels (B, X, Y, Z) uint8 in which every voxel of a things segment of fewer than
+    min_voxels voxels is 0 (stuff and all other voxels pass).  seg: `ccl_segments(labels, things, stuff, connectivity)`
+    when the caller has it; else it is made here, in the same workspace."""
+    if not 1 <= int(min_voxels) <= (1 << 31) - 1:
+        raise ValueError("min_voxels must be 1 .. 2^31 - 1, got %r" % (min_voxels,))
+    a = _ccl_volume_args(labels, things, stuff)
+    workspace = _ccl_check_workspace(workspace, labels)
+    if seg is None:
+        seg = ccl_segments(labels, things, stuff, connectivity, workspace, check=check)
+    elif seg.dtype != torch.int32 or seg.shape != labels.shape:
+        raise RuntimeError("seg must be the int32 tensor ccl_segments made of labels")
+    out = torch.empty_like(labels)
+    a.seg, a.parent, a.out, a.min_voxels = _ptr(seg, "seg"), _ptr(workspace[0], "workspace"), out.data_ptr(), int(min_voxels)
+    _check(load().occd_ccl_filter(ctypes.byref(a), _stream()), "occd_ccl_filter")
+    return out
+
+
+def ccl_sort_pairs(keys_lo, keys_hi, refs, lo_bits, hi_bits):
+    """The emitted (key, ref) pairs ascending in the key, stably, over exactly its bits: one `sort_pairs` over lo_bits +
+    hi_bits for a one-word key (keys_hi None); else keys_lo over lo_bits first, the high words gathered by that
+    permutation and sorted over hi_bits next (K38 is stable, so the two stages are an LSD sort of the two-word key) ->
+    (keys_lo, keys_hi), sorted."""
+    n = int(keys_lo.numel())
+    if keys_hi is None:
+        lo, _ = sort_pairs(keys_lo.view(1, n), refs.view(1, n), 0, lo_bits + hi_bits)
+        return lo.reshape(n), None
+    lo0 = keys_lo.clone()                                              # sort_pairs overwrites its input
+    _, ref = sort_pairs(keys_lo.view(1, n), refs.view(1, n), 0, lo_bits)
+    hi = keys_hi[ref.reshape(n).long()]
+    hi, ref = sort_pairs(hi.view(1, n), ref.reshape(1, n).contiguous(), 0, hi_bits)
+    return lo0[ref.reshape(n).long()], hi.reshape(n)
+
+
+def ccl_overlaps(g_ids, g_count, g_offsets, p_ids, p_count, p_offsets, target, mask=None):
+    """The exact overlap counts of two compacted segment volumes of the same frames (occd_ccl_pair_*; the contract is in
+    include/occdepth_amd.h): g_ids / p_ids, count (host) and offsets as `ccl_compact` returns them for the target and the
+    prediction; target (B, X, Y, Z) uint8 (255 = not valid), mask None or uint8 / bool of the same shape.  -> rows (R, 3)
+    int32 on the device: (g, p, n) with g, p the GLOBAL ids (offsets[b] + id, 0 = no segment), ascending in (g, p), n the
+    valid voxels that carry the pair.  Two host reads (the pairs, the rows)."""
+    B, n, dev = int(g_ids.shape[0]), int(g_ids[0].numel()), g_ids.device
+    for t, name in ((g_ids, "g_ids"), (p_ids, "p_ids")):
+        if t.dtype != torch.int32 or t.shape != g_ids.shape:
+            raise RuntimeError("%s must be int32 (B, X, Y, Z)" % name)
+    if target.dtype != torch.uint8 or target.numel() != g_ids.numel():
+        raise RuntimeError("target must be uint8 of the ids' size")
+    if B * n >= 1 << 31:
+        raise ValueError("%d voxels in the batch: the overlaps of one call take fewer than 2^31" % (B * n))
+    a = CclPairArgs()
+    a.g_ids, a.p_ids, a.target = _ptr(g_ids, "g_ids"), _ptr(p_ids, "p_ids"), _ptr(target, "target")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        if mask.dtype != torch.uint8 or mask.numel() != g_ids.numel():
+            raise RuntimeError("mask must be bool / uint8 of the ids' size")
+        a.mask = _ptr(mask, "mask")
+    g_bits, p_bits = max(1, int(g_count.sum()).bit_length()), max(1, int(p_count.sum()).bit_length())
+    a.n, a.batch, a.p_bits = n, B, p_bits
+    marks = torch.empty((B * n,), dtype=torch.int32, device=dev)
+    a.marks = marks.data_ptr()
+    _check(load().occd_ccl_pair_marks(ctypes.byref(a), _stream()), "occd_ccl_pair_marks")
+    pos = torch.cumsum(marks, 0, dtype=torch.int32)
+    P = int(pos[-1])
+    if P == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=dev)
+    keys_lo = torch.empty((P,), dtype=torch.int32, device=dev)
+    keys_hi = torch.empty((P,), dtype=torch.int32, device=dev) if g_bits + p_bits > 32 else None
+    refs = torch.empty((P,), dtype=torch.int32, device=dev)
+    a.pos, a.g_offsets, a.p_offsets = _ptr(pos, "pos"), _ptr(g_offsets, "g_offsets"), _ptr(p_offsets, "p_offsets")
+    a.keys_lo, a.keys_hi, a.refs, a.n_pairs = keys_lo.data_ptr(), _ptr(keys_hi, "keys_hi"), refs.data_ptr(), P
+    _check(load().occd_ccl_pair_emit(ctypes.byref(a), _stream()), "occd_ccl_pair_emit")
+    keys_lo, keys_hi = ccl_sort_pairs(keys_lo, keys_hi, refs, p_bits, g_bits)
+    heads = torch.empty((P,), dtype=torch.int32, device=dev)
+    a.keys_lo, a.keys_hi, a.marks = _ptr(keys_lo, "keys_lo"), _ptr(keys_hi, "keys_hi"), heads.data_ptr()
+    _check(load().occd_ccl_pair_heads(ctypes.byref(a), _stream()), "occd_ccl_pair_heads")
+    ranks = torch.cumsum(heads, 0, dtype=torch.int32)
+    R = int(ranks[-1])
+    rows = torch.empty((4, R), dtype=torch.int32, device=dev)
+    a.ranks, a.n_rows = _ptr(ranks, "ranks"), R
+    a.row_start, a.row_g, a.row_p, a.row_n = (rows[i].data_ptr() for i in range(4))
+    _check(load().occd_ccl_pair_rows(ctypes.byref(a), _stream()), "occd_ccl_pair_rows")
+    return rows[1:].t().contiguous()
 
 
 # ---- Lovasz-softmax loss (csrc/lovasz.hip, on K38) -------------------------------------------------------------------

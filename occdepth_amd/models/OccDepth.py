@@ -212,6 +212,18 @@ class OccDepth(_Base):
             except ValueError:
                 raise ValueError("OCCDEPTH_DIST_THRESHOLDS is <metres>[,<metres>...], got %r" % spec) from None
             self.enable_distance_metrics(thresholds_m=thresholds, fov_only=env("OCCDEPTH_DIST_FOV", "0") == "1")
+        # Panoptic quality of the test / validation predictions (panoptic.py, K40), OFF by default:
+        # `enable_panoptic_metrics()` -- or OCCDEPTH_PANOPTIC=1 [OCCDEPTH_PANOPTIC_MIN_VOXELS=<n>]
+        # [OCCDEPTH_PANOPTIC_CONNECTIVITY=6|26] [OCCDEPTH_PANOPTIC_FOV=1] in the environment of an unmodified scripts/eval.py.
+        # Off: nothing is imported, allocated or launched.  Every other method reaches it through
+        # getattr(self, "panoptic_metrics", None).
+        self.panoptic_metrics = None
+        if env("OCCDEPTH_PANOPTIC", "0") == "1":
+            spec = (env("OCCDEPTH_PANOPTIC_MIN_VOXELS", "") or "1", env("OCCDEPTH_PANOPTIC_CONNECTIVITY", "") or "26")
+            if not all(w.strip().isdigit() for w in spec):
+                raise ValueError("OCCDEPTH_PANOPTIC_MIN_VOXELS and OCCDEPTH_PANOPTIC_CONNECTIVITY are integers, got %r, %r" % spec)
+            self.enable_panoptic_metrics(connectivity=int(spec[1]), min_pred_voxels=int(spec[0]),
+                                         fov_only=env("OCCDEPTH_PANOPTIC_FOV", "0") == "1")
         self.init_2d_to_3d_trans(config)
         # `enable_render_loss()` -- or OCCDEPTH_RENDER_LOSS=<weight>[,<stride>] in the environment of an unmodified
         # scripts/train.py: the depth-rendering loss (loss/render_loss.py, K36) -- `ssc_logit` composited along the left
@@ -990,6 +1002,71 @@ class OccDepth(_Base):
             metric.reset()
         return out
 
+    # ---------------------------------------------------------------- panoptic quality (panoptic.py)
+    def enable_panoptic_metrics(self, connectivity=26, min_pred_voxels=1, things=None, stuff=None, fov_only=False):
+        """Score every test / validation frame by objects as well (panoptic.PanopticMetrics, K40): the connected components
+        of the arg-max of the unfused logits -- per `things` class, under `connectivity` 6 or 26, components of fewer than
+        min_pred_voxels voxels removed first -- and one segment per `stuff` class are matched to the segments of the target
+        at IoU > 1/2.  `val_pan/PQ`, `PQ_things`, `PQ_stuff`, `SQ`, `RQ` and `PQ_dagger` are logged and `test_epoch_end`
+        prints a `test_pan======` block with the per-class table; with temporal fusion on its fused labels are scored
+        into a second metric (`val_fused_pan/*`, `test_fused_pan======`).  The ordinary metrics are untouched.  The
+        target's "instances" are the connected components of the target (the completion volumes carry no instance
+        annotation).  things / stuff: None = the dataset's defaults (panoptic.default_classes).  Target voxels 255 do
+        not count; fov_only: only voxels inside the batch's full-scale FOV mask (`fov_mask_1`) count.  With
+        metrics_allreduce the counters are summed over the ranks before the statistics.  No PQ of a trained model is
+        measured (no checkpoint and no dataset where this was built)."""
+        if int(connectivity) not in (6, 26):
+            raise ValueError("connectivity must be 6 or 26, got %r" % (connectivity,))
+        if int(min_pred_voxels) < 1:
+            raise ValueError("min_pred_voxels must be >= 1, got %r" % (min_pred_voxels,))
+        if things is None or stuff is None:
+            from ..panoptic import default_classes
+            d_things, d_stuff = default_classes(self.dataset)
+            things, stuff = (d_things if things is None else things), (d_stuff if stuff is None else stuff)
+        things, stuff = tuple(int(c) for c in things), tuple(int(c) for c in stuff)
+        if set(things) & set(stuff):
+            raise ValueError("things %r and stuff %r overlap" % (things, stuff))
+        self.panoptic_metrics = {"connectivity": int(connectivity), "min_pred_voxels": int(min_pred_voxels), "things": things,
+                                 "stuff": stuff, "fov_only": bool(fov_only), "metrics": {}, "fused": {}}
+        return self
+
+    def _pan_step(self, step_type, batch, ssc_pred, target, fused_labels=None, pred_labels=None):
+        """Add the batch's arg-max labels (and the fused labels, if any) against its target to the panoptic counters."""
+        from .. import hip, panoptic
+        st = self.panoptic_metrics
+        ssc_pred = ssc_pred.detach()
+        B = ssc_pred.shape[0]
+        dims = tuple(int(d) for d in ssc_pred.shape[2:])
+        mask = None
+        if st["fov_only"]:
+            mask = self._report_fov(batch, target) if batch.get("fov_mask_1") is not None else None
+            if not torch.is_tensor(mask):
+                raise ValueError("fov_only panoptic metrics need the batch's full-scale FOV mask (fov_mask_1)")
+            mask = mask.reshape((B,) + dims)
+        pred = hip.argmax_labels_u16(ssc_pred.float()) if pred_labels is None else pred_labels
+        gt = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).reshape((B,) + dims)
+        for store, labels in ((st["metrics"], pred), (st["fused"], fused_labels)):
+            if labels is None:
+                continue
+            metric = store.get(step_type)
+            if metric is None:
+                metric = store[step_type] = panoptic.PanopticMetrics(self.n_classes, st["things"], st["stuff"],
+                                                                     st["connectivity"], st["min_pred_voxels"])
+            metric.add_batch(labels, gt, mask)
+
+    def _pan_epoch_end(self, step_type):
+        """-> [(prefix, statistics)] of the panoptic metrics of `step_type` that counted something, reset."""
+        out = []
+        for name, store in (("pan", self.panoptic_metrics["metrics"]), ("fused_pan", self.panoptic_metrics["fused"])):
+            metric = store.get(step_type)
+            if metric is None:
+                continue
+            if self.metrics_allreduce:
+                metric.allreduce_()
+            out.append(("%s_%s" % (step_type, name), metric.get_stats()))
+            metric.reset()
+        return out
+
     # ---------------------------------------------------------------- sequence-level semantic map (semantic_map.py)
     def enable_semantic_map(self, out_dir, poses_root, min_obs=1, views=(), frames=False, submission_dir=None,
                             exclude_self=False, max_frames=1024, gather=True, save_maps=False, visibility=None, mesh=False):
@@ -1617,6 +1694,8 @@ class OccDepth(_Base):
             self._ray_step(step_type, batch, ssc_pred, target, fused_labels)
         elif dist_on:
             self._dist_step(step_type, batch, ssc_pred, target, fused_labels)
+        if getattr(self, "panoptic_metrics", None) is not None and step_type in ("test", "val"):
+            self._pan_step(step_type, batch, ssc_pred, target, fused_labels)
         if getattr(self, "semantic_map", None) is not None and step_type in ("test", "val"):
             self._map_step(step_type, batch, ssc_pred, target)
         self._log(step_type + "/loss", loss)
@@ -1982,6 +2061,10 @@ class OccDepth(_Base):
                     self.log("%s/F_sem@%g" % (prefix, t), stats["F_sem"][i], sync_dist=True)
                 self.log(prefix + "/CD_geo", stats["CD_geo"], sync_dist=True)
                 self.log(prefix + "/CD_sem", stats["CD_sem"], sync_dist=True)
+        if getattr(self, "panoptic_metrics", None) is not None:
+            for prefix, stats in self._pan_epoch_end("val"):
+                for key in ("PQ", "PQ_things", "PQ_stuff", "SQ", "RQ", "PQ_dagger"):
+                    self.log("%s/%s" % (prefix, key), stats[key], sync_dist=True)
         if self.render is not None:
             self.render["logged"] = False           # the next epoch logs its first rendered frame again
 
@@ -2020,6 +2103,10 @@ class OccDepth(_Base):
             from ..dist_metric import format_report as format_dist_report
             for prefix, stats in self._dist_epoch_end("test"):
                 print("\n".join(format_dist_report(stats, classes, prefix)))
+        if getattr(self, "panoptic_metrics", None) is not None:
+            from ..panoptic import format_report as format_pan_report
+            for prefix, stats in self._pan_epoch_end("test"):
+                print("\n".join(format_pan_report(stats, classes, prefix)))
 
     def configure_optimizers(self):
         """Reference :582-600: AdamW + MultiStepLR, schedule by dataset."""

@@ -117,6 +117,9 @@ def build_map(src, role, poses, args, device):
         if frame not in poses:
             raise KeyError("no pose for frame %d of %s (%s)" % (frame, src, os.path.join(args.poses, "poses.txt")))
         labels, mask = read_frame(kind, frames[frame], role, tuple(args.dims), device, args.fov, lut)
+        if role == "pred" and int(getattr(args, "min_component", 0) or 0) > 1:      # speckle does not vote
+            from occdepth_amd import panoptic
+            labels = panoptic.remove_small_components(labels.contiguous(), args.min_component, panoptic.KITTI_THINGS)
         weight = visibility_weight(labels, mask, args) if role == "pred" else None
         if weight is not None:
             m.integrate(labels, poses[frame], weight=weight)
@@ -275,6 +278,8 @@ def parser():
     ap.add_argument("--out", required=True, help="path prefix of the PLY files")
     ap.add_argument("--min-obs", type=int, default=1)
     ap.add_argument("--every", type=int, default=1, help="use every n-th frame")
+    ap.add_argument("--min-component", type=int, default=0, metavar="N",
+                    help="prediction frames: connected components (26) of the things classes 1-8 of fewer than N voxels do not vote")
     ap.add_argument("--fov", action="store_true", help="pickles: vote inside the frame's fov_mask_1 only")
     ap.add_argument("--dims", type=int, nargs=3, default=(256, 256, 32))
     ap.add_argument("--voxel", type=float, default=0.2)

@@ -3,12 +3,14 @@ a display: the headless replacement for the reference's scripts/visualization/ki
 and NYU_vis_pred.py.
 
     python tools/render_predictions.py <dir of .pkl> [--out DIR] [--dataset kitti|NYU] [--views camera bev oblique]
-                                       [--image-size H W] [--target] [--batch 8] [--mesh]
+                                       [--image-size H W] [--target] [--batch 8] [--mesh] [--min-component N] [--instances]
 
 Every <name>.pkl gives <name>_<view>.png next to it, or under --out with the same sub-directories.  Pickle keys: `y_pred`
 (X, Y, Z), `fov_mask_1` (dims voxels outside are dimmed), `cam_k`, `T_velo_2_cam` (kitti), `cam_pose`, `vox_origin` (NYU);
 --target colours the prediction against the pickle's `target` (error mode).  Frames are batched per launch.  --mesh also writes <name>_mesh.ply, the frame's surface as an indexed quad
-mesh in world metres (occdepth_amd/mesh.py, K39).
+mesh in world metres (occdepth_amd/mesh.py, K39).  --min-component N removes the connected components (26-connectivity) of
+the dataset's things classes that have fewer than N voxels before anything is drawn or meshed; --instances colours the things
+voxels by component instead of by class (occdepth_amd/panoptic.py, K40).
 """
 import argparse
 import os
@@ -37,6 +39,10 @@ def find_pickles(root):
 def render_group(paths, frames, args, dev):
     """One launch for frames of one grid shape -> the written paths."""
     labels = torch.from_numpy(np.stack([np.asarray(f["y_pred"]).astype(np.int16) for f in frames])).to(dev)
+    min_component, instances = int(getattr(args, "min_component", 0) or 0), bool(getattr(args, "instances", False))
+    drawn = labels
+    if min_component > 1 or instances:
+        labels, drawn = component_labels(labels, args.dataset, min_component, instances)
     B = labels.shape[0]
     dims = tuple(int(d) for d in labels.shape[1:])
     vs = args.voxel_size or VOXEL_METRES[args.dataset] * FULL_X[args.dataset] / dims[0]
@@ -62,7 +68,7 @@ def render_group(paths, frames, args, dev):
         if missing:
             raise SystemExit("--target: no `target` in %s" % missing[0])
         target = torch.from_numpy(np.stack([np.asarray(f["target"]).astype(np.int16) for f in frames])).to(dev)
-    images = render.render_labels(labels, views, sizes, fov=fov, target=target, mode="error" if args.target else "class",
+    images = render.render_labels(labels if args.target else drawn, views, sizes, fov=fov, target=target, mode="error" if args.target else "class",
                                   palette=args.dataset)
     host = [t.cpu().numpy() for t in images]
     written = []
@@ -76,6 +82,25 @@ def render_group(paths, frames, args, dev):
         if args.mesh:
             written.append(write_frame_mesh(stem, labels[i], frames[i], vs, args.dataset))
     return written
+
+
+def component_labels(labels, dataset, min_component=0, instances=False, connectivity=26):
+    """--min-component / --instances: labels (B, X, Y, Z) int16 -> (the labels with every component of a things class of
+    fewer than min_component voxels set to 0, the labels to draw).  With instances the drawn label of a things voxel is a
+    palette row chosen by a fixed integer hash of its segment's compact id, 1 + (id * 2654435761 mod 2^32 >> 16) mod
+    (n_classes - 1), instead of its class (occdepth_amd.panoptic, K40)."""
+    from occdepth_amd import hip, panoptic
+    things, _ = panoptic.default_classes(dataset)
+    lab8 = torch.where((labels < 0) | (labels > 255), torch.full_like(labels, 255), labels).to(torch.uint8).contiguous()
+    if min_component > 1:
+        lab8 = hip.ccl_filter(lab8, things, min_component, connectivity)
+    out = lab8.to(torch.int16)
+    if not instances:
+        return out, out
+    ids, _, _, _ = hip.ccl_compact(hip.ccl_segments(lab8, things, (), connectivity), lab8)
+    n = int(render.palette(dataset).shape[0]) - 3
+    colour = 1 + (((ids.long() * 2654435761) & 0xFFFFFFFF) >> 16) % (n - 1)
+    return out, torch.where(ids > 0, colour.to(torch.int16), out)
 
 
 def write_frame_mesh(stem, labels, frame, vs, dataset):
@@ -101,6 +126,9 @@ def main(argv=None):
     ap.add_argument("--target", action="store_true")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--mesh", action="store_true", help="also write every frame's surface as <name>_mesh.ply (occdepth_amd.mesh)")
+    ap.add_argument("--min-component", type=int, default=0, metavar="N",
+                    help="before drawing and meshing, remove every connected component of a things class of fewer than N voxels")
+    ap.add_argument("--instances", action="store_true", help="colour things voxels by connected component instead of by class")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("render_predictions.py renders on the GPU; none is visible")

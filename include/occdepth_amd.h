@@ -747,8 +747,9 @@ int occd_argmax_channels(const float* x, int64_t rows, int32_t cs, int32_t coff,
                          const uint16_t* lut, uint16_t* out, void* stream);
 
 /* ------------------------------------------------------------------------ *
- * Headless voxel renderer (csrc/render.hip): ray-cast label volumes to images, one launch for batch x n_views x H x W
- * pixels, one thread per pixel -- the GPU counterpart of the reference's mayavi / open3d viewers
+ * Headless voxel renderer (csrc/render.hip; csrc/raycast.h holds the same traversal for the other ray-cast kernels):
+ * ray-cast label volumes to images, one launch for batch x n_views x H x W pixels, one thread per pixel -- the GPU
+ * counterpart of the reference's mayavi / open3d viewers
  * (scripts/visualization/kitti_vis_pred.py, NYU_vis_pred.py), which need a display.  Added without an ABI bump: entries
  * and structures only, every older caller stays valid.  No atomics, no allocation, no host sync (capture-safe).
  *
@@ -1567,7 +1568,8 @@ int occd_map_render(const OccdMapRenderArgs* a, void* stream);
  * K34: which voxels of a frame the camera could see (occd_frame_visibility, csrc/visibility.hip).  Additive
  * (OCCD_ABI_VERSION note).  One ray per pixel of ONE view through ONE frame's label volume, one thread per pixel, a wave
  * per 8 x 8 pixel tile.  `view` is one OccdRenderView in grid-voxel units, read exactly as occd_render_voxels reads it,
- * and the walk is that of occd_render_voxels in class mode (same ray set-up, slab entry, clamped first voxel, boundary
+ * and the walk is that of occd_render_voxels in class mode (csrc/raycast.h holds it, expression for expression: same
+ * ray set-up, slab entry, clamped first voxel, boundary
  * times ((float)(i + (dir > 0)) - origin) * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32
  * without fma).  Every voxel n the walk visits, up to and including the first occupied one (0 < label < 255), gets
  * visible[n] = 1; a ray that leaves the grid has marked all it crossed; a ray that misses the box marks nothing.  Every
@@ -1647,7 +1649,7 @@ int occd_map_sample_weighted(const OccdMapSampleWeightedArgs* a, void* stream);
  * origin k, ray r), 64 consecutive rays a wave: ray r of origin k of frame b is origins[b, k] + t dirs[r], in grid-voxel
  * units (voxel (i, j, l) is the cube [i, i + 1) x [j, j + 1) x [l, l + 1)), through pred[b] and target[b], both
  * (X, Y, Z) with z fastest.
- * The walk is that of occd_render_voxels in class mode (slab entry, clamped first voxel, boundary times
+ * The walk is that of occd_render_voxels in class mode (csrc/raycast.h: slab entry, clamped first voxel, boundary times
  * ((float)(i + (dir > 0)) - origin) * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32
  * without fma), ONE walk for both volumes: every visited voxel is tested in whichever volume has not hit yet, and the
  * walk ends when both have hit or the ray leaves the grid -- the voxel sequence depends on the ray alone, so the outcome
@@ -1714,8 +1716,9 @@ int occd_ray_metric(const OccdRayMetricArgs* a, void* stream);
  * occd_render_voxels forms them, so a strided pass walks rows off_v::stride and columns off_u::stride of the full
  * pass's rays bit for bit.  h = ceil((H - off_v) / stride), w = ceil((W - off_u) / stride), h*w <= 2^21.  t along a ray
  * is whatever the view makes it (camera depth in metres for render.camera_view).
- * Walk: that of occd_render_voxels (slab entry, clamped first voxel, boundary times ((float)(i + (dir > 0)) - origin) *
- * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32 without fma).  It visits voxels v_1 .. v_n
+ * Walk: that of occd_render_voxels (csrc/raycast.h: slab entry, clamped first voxel, boundary times
+ * ((float)(i + (dir > 0)) - origin) * (1 / dir), x before y before z on ties, step bound X + Y + Z + 3, float32 without
+ * fma).  It visits voxels v_1 .. v_n
  * with entry depths t_1 <= .. <= t_n (t_1 = the slab entry, 0 when the origin lies inside) and ends when the ray leaves
  * the grid or the next entry depth is >= max_depth (no voxel at all when t_1 >= max_depth).  t_end = min(t_far,
  * max_depth), t_far the slab exit; max_depth for a ray that misses the grid (it renders empty).

@@ -45,6 +45,18 @@ inline int check_launch() {
     return e == hipSuccess ? OCCD_OK : OCCD_ELAUNCH;
 }
 
+// The view rectangles of a render canvas (occd_render_voxels, occd_map_render), 0 = the whole canvas; false when one is
+// larger than the canvas.
+inline bool fill_view_sizes(const int32_t* in_w, const int32_t* in_h, int n_views, int W, int H, int32_t* view_w, int32_t* view_h) {
+    for (int i = 0; i < OCCD_RENDER_MAX_VIEWS; ++i) {
+        const bool used = i < n_views;
+        if (used && (in_w[i] < 0 || in_w[i] > W || in_h[i] < 0 || in_h[i] > H)) return false;
+        view_w[i] = used ? (in_w[i] ? in_w[i] : W) : 0;
+        view_h[i] = used ? (in_h[i] ? in_h[i] : H) : 0;
+    }
+    return true;
+}
+
 // q = n / d for n*d < 2^32 via one mul-hi; d == 1 is encoded as magic 0.  The host fills it, occd_fastdiv (device.h) divides.
 struct FastDiv {
     uint32_t magic;

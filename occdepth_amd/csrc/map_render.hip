@@ -1,19 +1,21 @@
 // K31, occd_map_render: the sequence map (semantic_map.MapVolume) ray-cast to images without densifying it.  Two levels:
 // a directory of 16^3-voxel bricks over the map's window and one 4 KB row of labels per brick.  One ray per pixel, one
 // thread per pixel, a wave = one 8 x 8 pixel tile, as in render.hip: a tile's rays walk the same few bricks, so its
-// label gathers fall into few 4 KB rows and its directory reads into few lines, both served from L2.  Inside a present
-// brick the walk is render.hip's, step for step; an absent brick is left in one step that lands on the very state the
+// label gathers fall into few 4 KB rows and its directory reads into few lines, both served from L2.  Ray set-up and starting
+// state are render.hip's, taken from csrc/raycast.h; the loop is this kernel's own.  Inside a present
+// brick it steps as the loop of raycast.h does (step 6); an absent brick is left in one step that lands on the very state the
 // voxel walk would have reached (contract and proof sketch: include/occdepth_amd.h).  The walk is latency-bound and
 // divergent by nature (a lane is idle once its ray has ended); the loop body is kept short and branch-light, the
 // directory entry is re-read only when the ray changes brick, and the per-ray state stays in about 50 registers, no scratch.
 // Measured (profiles/map_render_ab.txt): the skip pays for rays along a thin window's short axis and loses elsewhere.
 // No atomics, no allocation, no host sync: capture-safe.
 #include "common.h"
+#include "raycast.h"
 
 namespace {
 
-constexpr int kTile = 8;                   // a wave's pixel tile is kTile x kTile
-constexpr int kBlockW = 16, kBlockH = 16;  // 4 waves = 2 x 2 tiles per workgroup
+using occd::kBlockW;
+using occd::kBlockH;
 constexpr int kBrick = OCCD_MAP_BRICK, kBrickVox = kBrick * kBrick * kBrick;
 static_assert(kBrick == 16, "the index arithmetic below shifts by 4");
 
@@ -62,10 +64,9 @@ __device__ __forceinline__ int advance_to(int i, int last, int s, float o, float
 // ERR: error mode (a target row beside every label row)
 template <bool ERR>
 __global__ __launch_bounds__(kBlockW * kBlockH) void map_render_kernel(MapRenderP p) {
-#pragma clang fp contract(off)   // every product and sum rounds once: tests/test_map_render.py restates this arithmetic in numpy
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int u = blockIdx.x * kBlockW + (wave & 1) * kTile + (lane & 7);
-    const int v = blockIdx.y * kBlockH + (wave >> 1) * kTile + (lane >> 3);
+#pragma clang fp contract(off)   // no product-plus-sum here today (raycast.h has them): a later one stays unfused
+    int u, v;
+    occd::tile_pixel(u, v);
     if (u >= p.W || v >= p.H) return;
     const int view = blockIdx.z;
     const int64_t pixel = ((int64_t)view * p.H + v) * p.W + u;
@@ -76,47 +77,22 @@ __global__ __launch_bounds__(kBlockW * kBlockH) void map_render_kernel(MapRender
     float t = 0.f;
     int colour = 0;
     if (u < p.view_w[view] && v < p.view_h[view]) {
-        const float* g = p.views + (int64_t)view * 18;
-        const float fu = (float)u + 0.5f, fv = (float)v + 0.5f;
-        const float ox = g[0] + fu * g[3] + fv * g[6], oy = g[1] + fu * g[4] + fv * g[7], oz = g[2] + fu * g[5] + fv * g[8];
-        const float dx = g[9] + fu * g[12] + fv * g[15], dy = g[10] + fu * g[13] + fv * g[16],
-                    dz = g[11] + fu * g[14] + fv * g[17];
-        const float inf = __builtin_inff();
-        const float fX = (float)X, fY = (float)Y, fZ = (float)Z;
-        bool alive = (ox - ox) + (oy - oy) + (oz - oz) + (dx - dx) + (dy - dy) + (dz - dz) == 0.f;   // all finite
-        float tn = -inf, tf = inf;
-        int axis = 3;
-        const float ix_ = dx != 0.f ? 1.f / dx : 0.f, iy_ = dy != 0.f ? 1.f / dy : 0.f, iz_ = dz != 0.f ? 1.f / dz : 0.f;
-        if (dx != 0.f) {
-            const float a = (0.f - ox) * ix_, c = (fX - ox) * ix_;
-            const float n = fminf(a, c);
-            if (n > tn) { tn = n; axis = 0; }
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(ox >= 0.f && ox < fX)) alive = false;
-        if (dy != 0.f) {
-            const float a = (0.f - oy) * iy_, c = (fY - oy) * iy_;
-            const float n = fminf(a, c);
-            if (n > tn) { tn = n; axis = 1; }
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(oy >= 0.f && oy < fY)) alive = false;
-        if (dz != 0.f) {
-            const float a = (0.f - oz) * iz_, c = (fZ - oz) * iz_;
-            const float n = fminf(a, c);
-            if (n > tn) { tn = n; axis = 2; }
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(oz >= 0.f && oz < fZ)) alive = false;
-        if (tn > 0.f) { t = tn; face = axis; }
-        if (!(tf >= t)) alive = false;
-        if (alive) {
-            int ix = (int)fminf(fmaxf(floorf(ox + dx * t), 0.f), fX - 1.f);
-            int iy = (int)fminf(fmaxf(floorf(oy + dy * t), 0.f), fY - 1.f);
-            int iz = (int)fminf(fmaxf(floorf(oz + dz * t), 0.f), fZ - 1.f);
-            const int sx = dx > 0.f ? 1 : dx < 0.f ? -1 : 0, sy = dy > 0.f ? 1 : dy < 0.f ? -1 : 0,
-                      sz = dz > 0.f ? 1 : dz < 0.f ? -1 : 0;
-            const auto bound_x = [&](int i) { return ((float)(i + (sx > 0)) - ox) * ix_; };
-            const auto bound_y = [&](int i) { return ((float)(i + (sy > 0)) - oy) * iy_; };
-            const auto bound_z = [&](int i) { return ((float)(i + (sz > 0)) - oz) * iz_; };
-            float mx = sx ? bound_x(ix) : inf, my = sy ? bound_y(iy) : inf, mz = sz ? bound_z(iz) : inf;
+        const occd::Ray ray = occd::pixel_ray(p.views + (int64_t)view * 18, u, v);
+        const occd::Entry entry = occd::walk_enter(ray, X, Y, Z);
+        if (entry.alive) {
+            // the state every walk starts from; the two-level loop below is this kernel's own
+            const occd::Start st = occd::walk_start(ray, entry, X, Y, Z);
+            const float ox = ray.ox, oy = ray.oy, oz = ray.oz, dx = ray.dx, dy = ray.dy, dz = ray.dz;
+            const float inf = __builtin_inff();
+            const float ix_ = entry.ix_, iy_ = entry.iy_, iz_ = entry.iz_;
+            const int sx = st.sx, sy = st.sy, sz = st.sz;
+            int ix = st.ix, iy = st.iy, iz = st.iz;
+            float mx = st.mx, my = st.my, mz = st.mz;
+            t = entry.t;
+            face = entry.face;
+            const auto bound_x = [&](int i) { return occd::boundary_t(i, sx, ox, ix_); };
+            const auto bound_y = [&](int i) { return occd::boundary_t(i, sy, oy, iy_); };
+            const auto bound_z = [&](int i) { return occd::boundary_t(i, sz, oz, iz_); };
             const float t_max = p.t_max;
             const int steps = kBrick * (p.gx + p.gy + p.gz) + 3;
             int cell_at = -1, row = -1;                       // the directory entry of the brick the ray is in
@@ -150,7 +126,7 @@ __global__ __launch_bounds__(kBlockW * kBlockH) void map_render_kernel(MapRender
                     }
                 }
                 if (row >= 0 || p.walk_absent) {
-                    // one voxel on: the nearest boundary, x before y before z on ties (render.hip step 6)
+                    // one voxel on: the nearest boundary, x before y before z on ties (raycast.h step 6)
                     const int ax = (mx <= my && mx <= mz) ? 0 : (my <= mz) ? 1 : 2;
                     const float m = ax == 0 ? mx : ax == 1 ? my : mz;
                     if (!(m < inf) || m > t_max) break;       // nothing left to cross, or every later voxel is past t_max
@@ -230,12 +206,7 @@ extern "C" int occd_map_render(const OccdMapRenderArgs* a, void* stream) {
     p.gx = a->gx; p.gy = a->gy; p.gz = a->gz; p.n_rows = a->n_rows; p.H = a->H; p.W = a->W;
     p.n_palette = a->n_palette; p.alpha = a->alpha; p.walk_absent = a->flags & 1;
     p.t_max = a->t_max;
-    for (int i = 0; i < OCCD_RENDER_MAX_VIEWS; ++i) {
-        const bool used = i < a->n_views;
-        if (used && (a->view_w[i] < 0 || a->view_w[i] > a->W || a->view_h[i] < 0 || a->view_h[i] > a->H)) return OCCD_EINVAL;
-        p.view_w[i] = used ? (a->view_w[i] ? a->view_w[i] : a->W) : 0;      // 0 = the whole canvas
-        p.view_h[i] = used ? (a->view_h[i] ? a->view_h[i] : a->H) : 0;
-    }
+    if (!occd::fill_view_sizes(a->view_w, a->view_h, a->n_views, a->W, a->H, p.view_w, p.view_h)) return OCCD_EINVAL;
     for (int i = 0; i < 4; ++i) p.bg[i] = a->bg_colour[i];
     const double pixels = (double)a->n_views * a->H * a->W;
     const double map_bytes = (double)a->n_rows * kBrickVox * (a->target ? 2.0 : 1.0) + (double)n_cells * 4.0;

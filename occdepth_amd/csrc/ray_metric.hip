@@ -7,12 +7,12 @@
 // that they are neighbours (ray_metric.lidar_directions) and their gathers fall into few cache lines.  No allocation, no
 // host sync, no memset node: capture-safe.  Contract: include/occdepth_amd.h.
 //
-// The walk is occd_render_voxels' (csrc/render.hip) restated: the same float32 expressions in the same order, so that the
-// hit of a ray in either volume, and the t it is entered at, are what that kernel reports for the same ray.  It is restated
-// rather than shared through a header for the reason csrc/visibility.hip gives: the sources and code objects of render.hip,
-// map_render.hip and visibility.hip stay what they were.  The voxel sequence depends on the ray alone, so one walk that
-// tests two volumes equals two walks.
+// The walk is occd_render_voxels': csrc/raycast.h holds its set-up and arithmetic, expression for expression, and the loop
+// given there is written out here (the reason is given there), so the hit of a ray in either volume, and the t it is
+// entered at, are what that kernel reports for the same ray.  The voxel sequence depends on the ray alone, so one
+// walk that tests two volumes equals two walks.
 #include "common.h"
+#include "raycast.h"
 
 namespace {
 
@@ -31,16 +31,12 @@ struct RayP {
     float thr[OCCD_RAY_MAX_THRESHOLDS];
 };
 
-template <int BYTES>
-__device__ __forceinline__ int load_label(const void* base, int64_t i) {
-    if (BYTES == 1) return static_cast<const uint8_t*>(base)[i];
-    return static_cast<const uint16_t*>(base)[i];
-}
+using occd::load_label;
 
 // LB: bytes per prediction label; TB: bytes per target label
 template <int LB, int TB>
 __global__ __launch_bounds__(kThreads) void ray_metric_kernel(RayP p) {
-#pragma clang fp contract(off)   // every product and sum rounds once: tests/test_ray_metric.py restates this arithmetic in numpy
+#pragma clang fp contract(off)   // no product-plus-sum here today (raycast.h has them): a later one stays unfused
     __shared__ unsigned int lds[kMaxCounters];
     const int C = p.C, T = p.T;
     const int n_counters = 4 + 2 * C + T * C + T;
@@ -53,52 +49,21 @@ __global__ __launch_bounds__(kThreads) void ray_metric_kernel(RayP p) {
         const int X = p.X, Y = p.Y, Z = p.Z;
         const float* og = p.origins + (int64_t)bk * 3;
         const float* dg = p.dirs + (int64_t)r * 3;
-        const float ox = og[0], oy = og[1], oz = og[2];
-        const float dx = dg[0], dy = dg[1], dz = dg[2];
-        const float inf = __builtin_inff();
-        const float fX = (float)X, fY = (float)Y, fZ = (float)Z;
-        bool alive = (ox - ox) + (oy - oy) + (oz - oz) + (dx - dx) + (dy - dy) + (dz - dz) == 0.f;   // all finite
-        // slab test; a zero component is parallel: inside or outside by the origin, never a division
-        float tn = -inf, tf = inf, t = 0.f;
-        const float ix_ = dx != 0.f ? 1.f / dx : 0.f, iy_ = dy != 0.f ? 1.f / dy : 0.f, iz_ = dz != 0.f ? 1.f / dz : 0.f;
-        if (dx != 0.f) {
-            const float a = (0.f - ox) * ix_, c = (fX - ox) * ix_;
-            const float n = fminf(a, c);
-            if (n > tn) tn = n;
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(ox >= 0.f && ox < fX)) alive = false;
-        if (dy != 0.f) {
-            const float a = (0.f - oy) * iy_, c = (fY - oy) * iy_;
-            const float n = fminf(a, c);
-            if (n > tn) tn = n;
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(oy >= 0.f && oy < fY)) alive = false;
-        if (dz != 0.f) {
-            const float a = (0.f - oz) * iz_, c = (fZ - oz) * iz_;
-            const float n = fminf(a, c);
-            if (n > tn) tn = n;
-            tf = fminf(tf, fmaxf(a, c));
-        } else if (!(oz >= 0.f && oz < fZ)) alive = false;
-        if (tn > 0.f) t = tn;
-        if (!(tf >= t)) alive = false;
+        const occd::Ray ray = {og[0], og[1], og[2], dg[0], dg[1], dg[2]};
+        const occd::Entry entry = occd::walk_enter(ray, X, Y, Z);
         int cls_p = 0, cls_g = 0;                  // 0 = no hit; a hit has 0 < class < 255
         float t_p = 0.f, t_g = 0.f;
         bool unknown = false;
-        if (alive) {
-            // first voxel, clamped as floats so that the conversion is always in range
-            int ix = (int)fminf(fmaxf(floorf(ox + dx * t), 0.f), fX - 1.f);
-            int iy = (int)fminf(fmaxf(floorf(oy + dy * t), 0.f), fY - 1.f);
-            int iz = (int)fminf(fmaxf(floorf(oz + dz * t), 0.f), fZ - 1.f);
-            const int sx = dx > 0.f ? 1 : dx < 0.f ? -1 : 0, sy = dy > 0.f ? 1 : dy < 0.f ? -1 : 0,
-                      sz = dz > 0.f ? 1 : dz < 0.f ? -1 : 0;
-            // t at which the ray leaves the current voxel along each axis, from the boundary itself (no running sum)
-            float mx = sx ? ((float)(ix + (sx > 0)) - ox) * ix_ : inf;
-            float my = sy ? ((float)(iy + (sy > 0)) - oy) * iy_ : inf;
-            float mz = sz ? ((float)(iz + (sz > 0)) - oz) * iz_ : inf;
+        if (entry.alive) {
             const int64_t frame = (int64_t)(bk / p.n_origins) * X * Y * Z;
             const bool drop = p.unknown_mode == 0;
             bool done_p = false, done_g = false;
-            const int steps = X + Y + Z + 3;          // every step moves one index one way: at most X + Y + Z - 2 in range
+            // the loop of csrc/raycast.h (step 6 and the step bound are kept here: see there)
+            const occd::Start s = occd::walk_start(ray, entry, X, Y, Z);
+            int ix = s.ix, iy = s.iy, iz = s.iz;
+            float mx = s.mx, my = s.my, mz = s.mz;
+            float t = entry.t;
+            const int steps = X + Y + Z + 3;
             for (int n = 0; n < steps; ++n) {
                 const int vox = (ix * Y + iy) * Z + iz;               // 0 <= ix < X, ... holds here, always: vox < X Y Z
                 if (!done_p) {
@@ -111,22 +76,21 @@ __global__ __launch_bounds__(kThreads) void ray_metric_kernel(RayP p) {
                     else if (drop && lab == 255) { unknown = true; break; }    // nobody knows what is there: the ray is dropped
                 }
                 if (done_p && done_g) break;
-                // the nearest boundary, x before y before z on ties
                 const int ax = (mx <= my && mx <= mz) ? 0 : (my <= mz) ? 1 : 2;
                 const float m = ax == 0 ? mx : ax == 1 ? my : mz;
-                if (!(m < inf)) break;                                // nothing left to cross (a zero direction)
+                if (!(m < __builtin_inff())) break;
                 if (ax == 0) {
-                    ix += sx;
+                    ix += s.sx;
                     if (ix < 0 || ix >= X) break;
-                    mx = ((float)(ix + (sx > 0)) - ox) * ix_;
+                    mx = occd::boundary_t(ix, s.sx, ray.ox, entry.ix_);
                 } else if (ax == 1) {
-                    iy += sy;
+                    iy += s.sy;
                     if (iy < 0 || iy >= Y) break;
-                    my = ((float)(iy + (sy > 0)) - oy) * iy_;
+                    my = occd::boundary_t(iy, s.sy, ray.oy, entry.iy_);
                 } else {
-                    iz += sz;
+                    iz += s.sz;
                     if (iz < 0 || iz >= Z) break;
-                    mz = ((float)(iz + (sz > 0)) - oz) * iz_;
+                    mz = occd::boundary_t(iz, s.sz, ray.oz, entry.iz_);
                 }
                 t = m;
             }

@@ -2,6 +2,10 @@
 // wins.  One launch for B frames x V views x H x W pixels, one thread per pixel, a wave = one 8 x 8 pixel tile (the rays
 // of a tile walk neighbouring voxels, so the gathers of a wave fall into few cache lines and the volume -- 2-4 MB at
 // config 2 -- is served from L2).  No atomics, no allocation, no host sync: capture-safe.  Contract: include/occdepth_amd.h.
+//
+// This file and csrc/raycast.h hold the same walk, expression for expression: map_render.hip, visibility.hip and
+// ray_metric.hip take it from the header, this kernel keeps its own text because on the header its uint8 instantiation
+// measured 1.5 % slower on long walks (profiles/raycast_refactor.txt).  A change to the walk is made in both.
 #include "common.h"
 
 namespace {
@@ -175,12 +179,7 @@ extern "C" int occd_render_voxels(const OccdRenderArgs* a, void* stream) {
     p.rgb = a->rgb; p.hit = a->hit; p.face = a->face; p.depth = a->depth;
     p.n_views = a->n_views; p.H = a->H; p.W = a->W; p.X = a->X; p.Y = a->Y; p.Z = a->Z;
     p.n_palette = a->n_palette; p.alpha = a->alpha;
-    for (int i = 0; i < OCCD_RENDER_MAX_VIEWS; ++i) {
-        const bool used = i < a->n_views;
-        if (used && (a->view_w[i] < 0 || a->view_w[i] > a->W || a->view_h[i] < 0 || a->view_h[i] > a->H)) return OCCD_EINVAL;
-        p.view_w[i] = used ? (a->view_w[i] ? a->view_w[i] : a->W) : 0;      // 0 = the whole canvas
-        p.view_h[i] = used ? (a->view_h[i] ? a->view_h[i] : a->H) : 0;
-    }
+    if (!occd::fill_view_sizes(a->view_w, a->view_h, a->n_views, a->W, a->H, p.view_w, p.view_h)) return OCCD_EINVAL;
     for (int i = 0; i < 4; ++i) p.bg[i] = a->bg_colour[i];
     const double pixels = (double)bv * a->H * a->W;
     const double volume = (double)a->batch * a->X * a->Y * a->Z * (a->label_bytes + (a->target ? a->target_bytes : 0));

@@ -9,10 +9,10 @@
 // integers added with integer atomics: the loss and the gradient are bitwise reproducible whatever the schedule.  No
 // allocation, no host sync, no memset node: capture-safe.  Contract: include/occdepth_amd.h.
 //
-// The walk is occd_render_voxels' (csrc/render.hip) restated: the same float32 expressions in the same order, so that with
-// hard logits (a = 0 or 1 exactly) d^ is, bit for bit, the depth that kernel reports.  It is restated rather than shared
-// through a header for the reason csrc/visibility.hip gives: the sources and code objects of the existing kernels stay
-// what they were.
+// The walk is occd_render_voxels' (csrc/raycast.h) restated: the same float32 expressions in the same order, so that with
+// hard logits (a = 0 or 1 exactly) d^ is, bit for bit, the depth that kernel reports.  Like render.hip this kernel does
+// not take them from raycast.h: on the header its forward pass measured 1.7 - 1.9 % slower at every stride, with the loop
+// written out as well as through a callback (profiles/raycast_refactor.txt).  A change to the walk is made there and here.
 #include "common.h"
 
 namespace {

@@ -3,10 +3,9 @@
 // per pixel, a wave = one 8 x 8 pixel tile, as in render.hip: the rays of a tile walk neighbouring voxels, so the label
 // gathers and the marks of a wave fall into few cache lines.  Contract: include/occdepth_amd.h.
 //
-// The walk is occd_render_voxels' (csrc/render.hip) restated: the same float32 expressions in the same order, so that the
-// first occupied voxel of a pixel is the one that kernel reports.  It is restated rather than shared through a header, so
-// the sources and code objects of render.hip and map_render.hip stay what they were (that walk is interleaved with the
-// face, depth and colour bookkeeping this kernel has no use for; conv3d_tile.h is the precedent for the choice).
+// The walk is occd_render_voxels': csrc/raycast.h holds its set-up and arithmetic, expression for expression, and the loop
+// given there is written out here (the reason is given there), so the first occupied voxel of a pixel is the one that kernel
+// reports.
 //
 // Marks are plain byte stores of the constant 1 into a volume that this entry point's own fill kernel zeroed first (same
 // stream; no memset node -- captured memset nodes replay wrongly on this runtime).  Many rays
@@ -15,11 +14,12 @@
 // atomics, no allocation, no host sync.
 #include "common.h"
 #include "device.h"
+#include "raycast.h"
 
 namespace {
 
-constexpr int kTile = 8;                   // a wave's pixel tile is kTile x kTile
-constexpr int kBlockW = 16, kBlockH = 16;  // 4 waves = 2 x 2 tiles per workgroup
+using occd::kBlockW;
+using occd::kBlockH;
 constexpr int kFillThreads = 256;
 constexpr int64_t kMaxVox = (int64_t)1 << 28;
 
@@ -30,12 +30,6 @@ struct VisP {
     int32_t* hit;
     int32_t H, W, X, Y, Z;
 };
-
-template <int BYTES>
-__device__ __forceinline__ int load_label(const void* base, int i) {
-    if (BYTES == 1) return static_cast<const uint8_t*>(base)[i];
-    return static_cast<const uint16_t*>(base)[i];
-}
 
 // zeroes out[0, n): 16-byte pieces from the first 16-byte boundary on, the bytes before and after it by thread 0
 __global__ __launch_bounds__(kFillThreads) void zero_bytes_kernel(uint8_t* out, int64_t n, int64_t head, int64_t pieces) {
@@ -53,77 +47,40 @@ __global__ __launch_bounds__(kFillThreads) void zero_bytes_kernel(uint8_t* out, 
 
 template <int LB>
 __global__ __launch_bounds__(kBlockW * kBlockH) void visibility_kernel(VisP p) {
-#pragma clang fp contract(off)   // every product and sum rounds once: tests/test_visibility.py restates this arithmetic in numpy
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int u = blockIdx.x * kBlockW + (wave & 1) * kTile + (lane & 7);
-    const int v = blockIdx.y * kBlockH + (wave >> 1) * kTile + (lane >> 3);
+#pragma clang fp contract(off)   // no product-plus-sum here today (raycast.h has them): a later one stays unfused
+    int u, v;
+    occd::tile_pixel(u, v);
     if (u >= p.W || v >= p.H) return;
     const int X = p.X, Y = p.Y, Z = p.Z;
-    const float* g = p.view;
-    const float fu = (float)u + 0.5f, fv = (float)v + 0.5f;
-    const float ox = g[0] + fu * g[3] + fv * g[6], oy = g[1] + fu * g[4] + fv * g[7], oz = g[2] + fu * g[5] + fv * g[8];
-    const float dx = g[9] + fu * g[12] + fv * g[15], dy = g[10] + fu * g[13] + fv * g[16],
-                dz = g[11] + fu * g[14] + fv * g[17];
-    const float inf = __builtin_inff();
-    const float fX = (float)X, fY = (float)Y, fZ = (float)Z;
-    bool alive = (ox - ox) + (oy - oy) + (oz - oz) + (dx - dx) + (dy - dy) + (dz - dz) == 0.f;   // all finite
-    // slab test; a zero component is parallel: inside or outside by the origin, never a division
-    float tn = -inf, tf = inf, t = 0.f;
-    const float ix_ = dx != 0.f ? 1.f / dx : 0.f, iy_ = dy != 0.f ? 1.f / dy : 0.f, iz_ = dz != 0.f ? 1.f / dz : 0.f;
-    if (dx != 0.f) {
-        const float a = (0.f - ox) * ix_, c = (fX - ox) * ix_;
-        const float n = fminf(a, c);
-        if (n > tn) tn = n;
-        tf = fminf(tf, fmaxf(a, c));
-    } else if (!(ox >= 0.f && ox < fX)) alive = false;
-    if (dy != 0.f) {
-        const float a = (0.f - oy) * iy_, c = (fY - oy) * iy_;
-        const float n = fminf(a, c);
-        if (n > tn) tn = n;
-        tf = fminf(tf, fmaxf(a, c));
-    } else if (!(oy >= 0.f && oy < fY)) alive = false;
-    if (dz != 0.f) {
-        const float a = (0.f - oz) * iz_, c = (fZ - oz) * iz_;
-        const float n = fminf(a, c);
-        if (n > tn) tn = n;
-        tf = fminf(tf, fmaxf(a, c));
-    } else if (!(oz >= 0.f && oz < fZ)) alive = false;
-    if (tn > 0.f) t = tn;
-    if (!(tf >= t)) alive = false;
+    const occd::Ray ray = occd::pixel_ray(p.view, u, v);
+    const occd::Entry entry = occd::walk_enter(ray, X, Y, Z);
     int hit = -1;
-    if (alive) {
-        // first voxel, clamped as floats so that the conversion is always in range
-        int ix = (int)fminf(fmaxf(floorf(ox + dx * t), 0.f), fX - 1.f);
-        int iy = (int)fminf(fmaxf(floorf(oy + dy * t), 0.f), fY - 1.f);
-        int iz = (int)fminf(fmaxf(floorf(oz + dz * t), 0.f), fZ - 1.f);
-        const int sx = dx > 0.f ? 1 : dx < 0.f ? -1 : 0, sy = dy > 0.f ? 1 : dy < 0.f ? -1 : 0,
-                  sz = dz > 0.f ? 1 : dz < 0.f ? -1 : 0;
-        // t at which the ray leaves the current voxel along each axis, from the boundary itself (no running sum)
-        float mx = sx ? ((float)(ix + (sx > 0)) - ox) * ix_ : inf;
-        float my = sy ? ((float)(iy + (sy > 0)) - oy) * iy_ : inf;
-        float mz = sz ? ((float)(iz + (sz > 0)) - oz) * iz_ : inf;
-        const int steps = X + Y + Z + 3;              // every step moves one index one way: at most X + Y + Z - 2 in range
+    if (entry.alive) {
+        // the loop of csrc/raycast.h (step 6 and the step bound are kept here: see there)
+        const occd::Start s = occd::walk_start(ray, entry, X, Y, Z);
+        int ix = s.ix, iy = s.iy, iz = s.iz;
+        float mx = s.mx, my = s.my, mz = s.mz;
+        const int steps = X + Y + Z + 3;
         for (int n = 0; n < steps; ++n) {
             const int vox = (ix * Y + iy) * Z + iz;               // 0 <= ix < X, ... holds here, always: vox < X Y Z
             if (p.visible[vox] == 0) p.visible[vox] = 1;
-            const int lab = load_label<LB>(p.labels, vox);
+            const int lab = occd::load_label<LB>(p.labels, vox);
             if (lab > 0 && lab < 255) { hit = vox; break; }
-            // the nearest boundary, x before y before z on ties
             const int ax = (mx <= my && mx <= mz) ? 0 : (my <= mz) ? 1 : 2;
             const float m = ax == 0 ? mx : ax == 1 ? my : mz;
-            if (!(m < inf)) break;                                // nothing left to cross (a zero direction)
+            if (!(m < __builtin_inff())) break;
             if (ax == 0) {
-                ix += sx;
+                ix += s.sx;
                 if (ix < 0 || ix >= X) break;
-                mx = ((float)(ix + (sx > 0)) - ox) * ix_;
+                mx = occd::boundary_t(ix, s.sx, ray.ox, entry.ix_);
             } else if (ax == 1) {
-                iy += sy;
+                iy += s.sy;
                 if (iy < 0 || iy >= Y) break;
-                my = ((float)(iy + (sy > 0)) - oy) * iy_;
+                my = occd::boundary_t(iy, s.sy, ray.oy, entry.iy_);
             } else {
-                iz += sz;
+                iz += s.sz;
                 if (iz < 0 || iz >= Z) break;
-                mz = ((float)(iz + (sz > 0)) - oz) * iz_;
+                mz = occd::boundary_t(iz, s.sz, ray.oz, entry.iz_);
             }
         }
     }

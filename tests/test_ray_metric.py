@@ -1,7 +1,7 @@
 """CPU: RayIoU along sensor rays (K35, occd_ray_metric; occdepth_amd/ray_metric.py).
 
 `ray_metric_ref` restates the kernel's counters: two independent `cast_ref` calls (tests/test_render.py, the walk of
-csrc/render.hip in float32) per origin, one through the prediction and one through the target, then plain numpy counting
+csrc/raycast.h in float32) per origin, one through the prediction and one through the target, then plain numpy counting
 with the depth test in float32.  tests/test_ray_metric_gpu.py holds the kernel to it with exact equality.  Here: the
 restatement against analytic cases and edge rays, the direction fan and the trajectory origins, RayMetrics on a Python
 stand-in for the kernel, the model hook, the environment switches and the offline tool on that stand-in, and the entry

@@ -1,7 +1,7 @@
 """CPU: the headless voxel renderer's host side (occdepth_amd/render.py) and the numpy restatement of its kernel.
 
-`cast_ref` restates the traversal of csrc/render.hip (contract: include/occdepth_amd.h) step for step, in the dtype it is
-given; `colour_ref` restates the integer colour rule.  tests/test_render_gpu.py compares the kernel with both.  Here the
+`cast_ref` restates the traversal of csrc/render.hip and csrc/raycast.h (contract: include/occdepth_amd.h) step for step,
+in the dtype it is given; `colour_ref` restates the integer colour rule.  tests/test_render_gpu.py compares the kernel with both.  Here the
 restatement in float32 is compared with itself in float64, which pins how much float32 alone moves an image."""
 import os
 import struct

@@ -1,6 +1,6 @@
 """CPU: per-frame visibility (K34, occd_frame_visibility) and the weighted votes of the sequence map.
 
-`carve_ref` restates the kernel's walk (csrc/visibility.hip, the walk of csrc/render.hip) in numpy, in the dtype it is
+`carve_ref` restates the kernel's walk (csrc/visibility.hip on the walk of csrc/raycast.h) in numpy, in the dtype it is
 given, and returns the marked volume and the hits; tests/test_visibility_gpu.py holds the kernel to its float32 run byte for
 byte.  `WeightedMapRef` / `sample_ref_weighted` extend the integer restatements of tests/test_map.py and
 tests/test_map_sample.py by a weight per voxel; tests/test_map_weighted_gpu.py holds the weighted entry points to them.

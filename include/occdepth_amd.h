@@ -102,7 +102,8 @@ extern "C" {
  *     OCCD_CCL_*, OccdCclArgs, occd_ccl_segments, occd_ccl_roots, occd_ccl_compact and occd_ccl_filter (K40, connected
  *     components of a label volume, csrc/ccl.hip) and OccdCclPairArgs, occd_ccl_pair_marks, occd_ccl_pair_emit,
  *     occd_ccl_pair_heads and occd_ccl_pair_rows (the exact overlap counts of two segment volumes, sorted with
- *     occd_sort_pairs_u32): two new structs and eight new functions only */
+ *     occd_sort_pairs_u32): two new structs and eight new functions only; likewise
+ *     occd_wino_conv3x3_f16x2_fwd_form (K10h with two cout blocks per work item, csrc/wino_conv2d.hip): one new function only */
 #define OCCD_ABI_VERSION 22
 int occd_abi_version(void);
 const char* occd_strerror(int code);
@@ -639,6 +640,14 @@ int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream);
  * The ABI number stays 22 although this export is new: no struct changed, and tests/test_metric_regions.py pins 22.  A
  * library without it fails at symbol lookup (hip.load() binds every export), not at the version check.                   */
 int occd_wino_conv3x3_f16x2_fwd_ex(const occd_wino_args* a, int32_t max_workgroups, void* stream);
+/* K10h with the work item chosen by the caller as well.  cout_blocks:
+ *    1  an item is one block of 32 output channels and 128 tiles: occd_wino_conv3x3_f16x2_fwd_ex(a, max_workgroups, stream);
+ *    2  the cout-pair form: an item is two neighbouring blocks of 32 output channels and 64 tiles, so the input patch of a
+ *       tile block is fetched, transformed and split once for both (with an odd number of blocks the last pair computes
+ *       one).  One workgroup per item only: max_workgroups must be -1, anything else is OCCD_EINVAL;
+ * anything else: OCCD_EINVAL.  Same arguments, checks, weight image and profiler row; both forms give the same bits
+ * (tests/test_wino_cout_pair.py).  Additive (OCCD_ABI_VERSION note).                                                     */
+int occd_wino_conv3x3_f16x2_fwd_form(const occd_wino_args* a, int32_t max_workgroups, int32_t cout_blocks, void* stream);
 
 /* Backward of the depthwise convolution (autograd of the geffnet conv_dw layers in training_step):
  *   data  : dx (B, C, H, W) from gy (B, C, Ho, Wo) and w (C, 1, k, k), same geometry arguments as the forward;

@@ -518,6 +518,42 @@ __device__ __forceinline__ void split2_f16x2(float a, float b, uint32_t& hi, uin
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, f16x2));
 }
 
+// One ROW of the Winograd domain for the lane's 8 cins, shared by wino3x3_f16x2_kernel (row i of the wave's half h: xi = 8 h +
+// 4 i + j) and wino3x3_f16x2_pair_kernel (row 2 h + i).  Row 2h + i of B^T d needs two patch rows (B^T = [1 0 -1 0; 0 1 1 0;
+// 0 -1 1 0; 0 1 0 -1]; rows counted from patch row h, where `pl` points):
+//   h = 0: i = 0: d0 - d2, i = 1: d1 + d2        h = 1: i = 0: d1 - d0, i = 1: d0 - d2
+// then (.) B with the staging factor 2^kWinoStageExp riding on it: 2 t_a -+ 2 t_b is one fma of t_a against the doubled
+// t_b, exactly 2 (t_a -+ t_b).  Two cins at a time: a pair is one packed fp16 register per position and term.
+// PLANE, RS: floats of one staged cin plane and of one of its rows.  vh, vl: [position of the row][cin pair].
+static_assert(kWinoStageExp == 1, "the transform below stages 2 V");
+template <int H, int I, int PLANE, int RS>
+__device__ __forceinline__ void wino_row_v(const float* pl, uint32_t (&vh)[4][4], uint32_t (&vl)[4][4]) {
+    constexpr int RA = H == 0 ? I : 1 - I, RB = H == 1 && I == 0 ? 0 : 2;
+    constexpr bool ADD = H == 0 && I == 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        float v[2][4];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float* pq = pl + (2 * m + e) * PLANE;
+            const f32x2 a0 = *(const f32x2*)(pq + RA * RS), a1 = *(const f32x2*)(pq + RA * RS + 2);
+            const f32x2 b0 = *(const f32x2*)(pq + RB * RS), b1 = *(const f32x2*)(pq + RB * RS + 2);
+            float ra[4] = {a0.x, a0.y, a1.x, a1.y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) asm("" : "+v"(ra[j]));          // (scalar adds: see split2_f16x2)
+            const float t0 = ADD ? ra[0] + b0.x : ra[0] - b0.x, t1 = ADD ? ra[1] + b0.y : ra[1] - b0.y;
+            const float t2 = ADD ? ra[2] + b1.x : ra[2] - b1.x, t3 = ADD ? ra[3] + b1.y : ra[3] - b1.y;
+            const float u1 = 2.f * t1, u2 = 2.f * t2;
+            v[e][0] = __builtin_fmaf(2.f, t0, -u2);
+            v[e][1] = u1 + u2;
+            v[e][2] = u2 - u1;
+            v[e][3] = __builtin_fmaf(-2.f, t3, u1);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) split2_f16x2(v[0][j], v[1][j], vh[j][m], vl[j][m]);
+    }
+}
+
 // PERSIST: a workgroup walks the items v = blockIdx.x, blockIdx.x + gridDim.x, ... < nwg (a static assignment: no queue, no
 // flags, nothing shared between workgroups, any grid size is correct) and hands over inside the epilogue:
 //     last barrier of the K loop | shifts, factors, first residual requested | next item: DMA offsets, descriptor, patch DMA
@@ -600,39 +636,6 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
     asm volatile("" ::"a"(0.f));                          // AGPR accumulators (see wino3x3_kernel)
     f32x16 acc[8];                                        // xi = 8 h + k
 
-    // One ROW i of this wave's half of the domain (xi = 8 h + 4 i + j) for the lane's 8 cins: row 2h + i of B^T d needs two
-    // patch rows (B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]; rows counted from patch row h):
-    //   h = 0: i = 0: d0 - d2, i = 1: d1 + d2        h = 1: i = 0: d1 - d0, i = 1: d0 - d2
-    // then (.) B with the staging factor 2^kWinoStageExp riding on it: 2 t_a -+ 2 t_b is one fma of t_a against the doubled
-    // t_b, exactly 2 (t_a -+ t_b).  Two cins at a time: a pair is one packed fp16 register per position and term.
-    static_assert(kWinoStageExp == 1, "the transform below stages 2 V");
-    auto row_v = [&](auto hc, auto ic, const float* pl, uint32_t (&vh)[4][4], uint32_t (&vl)[4][4]) {
-        constexpr int H = decltype(hc)::value, I = decltype(ic)::value;
-        constexpr int RA = H == 0 ? I : 1 - I, RB = H == 1 && I == 0 ? 0 : 2;
-        constexpr bool ADD = H == 0 && I == 1;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            float v[2][4];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float* pq = pl + (2 * m + e) * PLANE;
-                const f32x2 a0 = *(const f32x2*)(pq + RA * RS), a1 = *(const f32x2*)(pq + RA * RS + 2);
-                const f32x2 b0 = *(const f32x2*)(pq + RB * RS), b1 = *(const f32x2*)(pq + RB * RS + 2);
-                float ra[4] = {a0.x, a0.y, a1.x, a1.y};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) asm("" : "+v"(ra[j]));      // (scalar adds: see split2_f16x2)
-                const float t0 = ADD ? ra[0] + b0.x : ra[0] - b0.x, t1 = ADD ? ra[1] + b0.y : ra[1] - b0.y;
-                const float t2 = ADD ? ra[2] + b1.x : ra[2] - b1.x, t3 = ADD ? ra[3] + b1.y : ra[3] - b1.y;
-                const float u1 = 2.f * t1, u2 = 2.f * t2;
-                v[e][0] = __builtin_fmaf(2.f, t0, -u2);
-                v[e][1] = u1 + u2;
-                v[e][2] = u2 - u1;
-                v[e][3] = __builtin_fmaf(-2.f, t3, u1);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) split2_f16x2(v[0][j], v[1][j], vh[j][m], vl[j][m]);
-        }
-    };
     // the 12 MFMAs of row i against the U records r = 2 xi + image of this chunk; positions in two interleaved pairs so
     // that no MFMA waits on its predecessor
     auto row_m = [&](auto ic, const u32x4* ul, const uint32_t (&vh)[4][4], const uint32_t (&vl)[4][4]) {
@@ -689,12 +692,12 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
             if (c + 1 < p.chunks) issue_patch(c + 1);
             const float* pl = lds + (c & 1) * 2 * PBUF + pbase;
             uint32_t ah[4][4], al[4][4], bh[4][4], bl[4][4];   // [position of the row][cin pair]: B fragments, hi and lo' terms
-            if (h0) row_v(I0{}, I0{}, pl, ah, al);
-            else row_v(I1{}, I0{}, pl, ah, al);
+            if (h0) wino_row_v<0, 0, PLANE, RS>(pl, ah, al);
+            else wino_row_v<1, 0, PLANE, RS>(pl, ah, al);
             __syncthreads();                               // U of chunk c has landed (vmcnt(0): so has the patch of chunk c + 1)
             row_m(I0{}, ul, ah, al);                       // ... and run under the transform of the second row
-            if (h0) row_v(I0{}, I1{}, pl, bh, bl);
-            else row_v(I1{}, I1{}, pl, bh, bl);
+            if (h0) wino_row_v<0, 1, PLANE, RS>(pl, bh, bl);
+            else wino_row_v<1, 1, PLANE, RS>(pl, bh, bl);
             row_m(I1{}, ul, bh, bl);
             __syncthreads();                               // every wave is done with U and the patch of chunk c; patch c + 1 has landed
         }
@@ -720,6 +723,304 @@ __global__ void __launch_bounds__(512, 2) wino3x3_f16x2_kernel(const WinoHP p) {
         }
         v = vn;
     }
+}
+
+// K10h, cout-pair form: a work item is (cout blocks 2q and 2q + 1, image, block of 64 tiles), so that the patch DMA, the LDS
+// reads, the transform and the split of a tile block are done once for two cout blocks, not once for each.
+//   * a QUAD of waves (g = wave >> 2) owns 32 tiles x 64 couts; wave `row` = wave & 3 of it owns row `row` of the 4 x 4 domain
+//     (xi = 4 row + j) for BOTH blocks: acc[4 blk + j], 128 AGPRs as before, 24 MFMAs per wave and chunk as before, but one
+//     row transform per chunk where wino3x3_f16x2_kernel runs two.  A workgroup is 2 x 32 (TWV = 32) or 4 x 16 tiles;
+//   * per accumulator the MFMAs come in the order of wino3x3_f16x2_kernel (lo_u hi_v, hs_u lo'_v, hi_u hi_v; chunks ascending)
+//     and the epilogue adds in the order of wino_exchange_store's finish(), so every output has the bits of that kernel;
+//   * U of one chunk is 64 records (64 KB, single-buffered as before): record 32 blk + 2 xi + image, 8 per wave.  With an odd
+//     number of cout blocks the last pair has no second block (`live1`, uniform over the workgroup): its U is not requested,
+//     its MFMAs and its half of the epilogue are skipped, nothing is read or written for it;
+//   * one item per workgroup only (no persistent grid).
+// Measured (profiles/wino_cout_pair_ab.txt): 0.17 ms per frame of a 0.32 - 0.50 ms bound.  The likeliest reason, NOT measured:
+// a chunk's U (twice K10h's request) is asked for and waited for inside the chunk behind ONE row transform, half of K10h's
+// window; staging block 1's records under block 0's MFMAs is the untried remedy.
+// The transform is wino_row_v, shared with wino3x3_f16x2_kernel (the reference for bit equality); the MFMA block is that
+// kernel's with the cout block added to the accumulator and U record indices.
+// The quad exchange and the epilogue of the cout-pair form.  Wave `row` finishes the cout registers 4 row .. 4 row + 3 of both
+// blocks (r8 = 4 blk + t: cout 32 (nb0 + blk) + 8 row + 4 (lane >> 5) + t) and needs the 12 positions of the three other waves
+// of its quad for them: the RAW accumulators go through xchg[quad][reader][writer slot][j][t][lane], one block per exchange
+// (96 KB each, over the staging buffers, which are dead behind the caller's last barrier).  The arithmetic, the descriptors
+// and the order of the memory traffic are those of wino_exchange_store, REPEATED here, not shared: with the offsets, the
+// descriptor, the residual load and the store tail taken from common helpers hipcc schedules the epilogues of K10 and K10h
+// differently (every kernel of this file changed), and those two stay instruction for instruction what was measured.  A change
+// to the float operations there must be made here too; tests/test_wino_cout_pair.py compares the two bit for bit.
+// Writing and finishing are instantiated once per row,
+// every barrier is one instruction that all waves of the workgroup reach on one path (`live1` is uniform over the workgroup).
+template <int TWV, bool WE>
+__device__ __forceinline__ void wino_quad_exchange_store(const WinoHP& p, f32x16 (&acc)[8], float* xchg, int row, int g, int lane,
+                                                         int nb0, bool live1, int b, int ty0, int tx0) {
+    wino_acc_settle(acc);
+    constexpr int RW = 32 / TWV;
+    const int li = lane & 31, kk = lane >> 5;
+    const int lr = g * RW + li / TWV, lc = li % TWV;
+    const int oy0 = 2 * (ty0 + lr), ox = 2 * (tx0 + lc);
+    const size_t hw = (size_t)p.H * p.W;
+    const int cb = nb0 * 32 + 8 * row;                     // cout of register r8 = 0 in lane half 0 (uniform)
+    auto cout_of = [](int r8) { return 32 * (r8 >> 2) + (r8 & 3); };
+    uint32_t vo[2][2];                                     // (as in wino_exchange_store)
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const bool ok = ox < p.W && oy0 + a < p.H;
+        const uint32_t o = (uint32_t)(((size_t)(4 * kk) * hw + (size_t)(oy0 + a) * p.W + ox) * 4);
+        vo[a][0] = ok ? o : kWinoOutside;
+        vo[a][1] = ok && ox + 1 < p.W ? o + 4 : kWinoOutside;
+    }
+    const size_t plane0 = ((size_t)b * p.Cout + cb) * hw;
+    // descriptor over the planes of register r8 that exist; none do for a second block that does not
+    auto desc = [&](const float* base, int r8) {
+        const int rem = p.Cout - cb - cout_of(r8);
+        const uint32_t n = base == nullptr || rem <= 0 ? 0u : (uint32_t)((size_t)(rem < 5 ? rem : 5) * hw * 4);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((base == nullptr ? p.y : base) + plane0 + (size_t)cout_of(r8) * hw), 0, n,
+                                                 0x00020000);
+    };
+    float sh[8], fc[8], rn[4];
+    {
+        const auto ss = __builtin_amdgcn_make_buffer_rsrc((void*)(p.shift != nullptr ? p.shift : p.y), 0,
+                                                          p.shift != nullptr ? (uint32_t)p.Cout * 4u : 0u, 0x00020000);
+        const auto fs = __builtin_amdgcn_make_buffer_rsrc((void*)p.fac, 0, (uint32_t)p.Cout * 4u, 0x00020000);
+        const uint32_t co4 = (uint32_t)(cb + 4 * kk) * 4;
+#pragma unroll
+        for (int r8 = 0; r8 < 8; ++r8) {
+            sh[r8] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ss, co4 + cout_of(r8) * 4, 0, 0));
+            fc[r8] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(fs, co4 + cout_of(r8) * 4, 0, 0));
+        }
+    }
+    auto res_issue = [&](int r8) {
+        const auto rs = desc(p.res, r8);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            if (WE) {
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo[a][0], 0, 0);
+                const uint32_t v0 = v[0], v1 = v[1];
+                rn[2 * a] = __builtin_bit_cast(float, v0);
+                rn[2 * a + 1] = __builtin_bit_cast(float, v1);
+            } else {
+                rn[2 * a] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo[a][0], 0, 0));
+                rn[2 * a + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo[a][1], 0, 0));
+            }
+        }
+    };
+    res_issue(0);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // writer row I -> slot of the three a reader keeps for the other rows
+    auto xwrite = [&](auto ic, int blk) {
+        constexpr int I = decltype(ic)::value;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int rd = 0; rd < 4; ++rd) {
+                if (rd == I) continue;
+                float* dst = xchg + (((g * 4 + rd) * 3 + (I < rd ? I : I - 1)) * 16 + j * 4) * 64 + lane;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) dst[t * 64] = wino_acc_read(acc[blk * 4 + j][4 * rd + t]);
+            }
+            __builtin_amdgcn_sched_barrier(0);             // (one accumulator tile at a time: few registers in flight)
+        }
+    };
+    auto finish = [&](auto ic, int blk) {
+        constexpr int I = decltype(ic)::value;
+        const float* theirs = xchg + ((g * 4 + I) * 3 * 16) * 64 + lane;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            __builtin_amdgcn_sched_barrier(0);             // (one cout register per iteration: see wino_exchange_store)
+            const int r8 = blk * 4 + t;
+            const float rc[4] = {rn[0], rn[1], rn[2], rn[3]};
+            if (r8 + 1 < 8) res_issue(r8 + 1);            // one register ahead (a dead second block: zero records)
+            float m[4][4];                                 // m[i][j], xi = 4 i + j; row I is this wave's
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    m[i][j] = i == I ? wino_acc_read(acc[blk * 4 + j][4 * I + t]) : theirs[(((i < I ? i : i - 1) * 16) + j * 4 + t) * 64];
+            float s[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[0][j] = m[0][j] + m[1][j] + m[2][j];
+                s[1][j] = m[1][j] - m[2][j] - m[3][j];
+            }
+            const auto ws = desc(p.y, r8);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                float y0 = __builtin_fmaf(s[a][0] + s[a][1] + s[a][2], fc[r8], sh[r8]);
+                float y1 = __builtin_fmaf(s[a][1] - s[a][2] - s[a][3], fc[r8], sh[r8]);
+                const float r0 = rc[2 * a], r1 = rc[2 * a + 1];
+                if (p.res_first) { y0 += r0; y1 += r1; }
+                y0 = act2d_exact(y0, p.act, p.slope);
+                y1 = act2d_exact(y1, p.act, p.slope);
+                if (!p.res_first) { y0 += r0; y1 += r1; }
+                if (WE) {
+                    __builtin_amdgcn_raw_buffer_store_b64((u32x2){__builtin_bit_cast(uint32_t, y0), __builtin_bit_cast(uint32_t, y1)},
+                                                          ws, vo[a][0], 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y0), ws, vo[a][0], 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, y1), ws, vo[a][1], 0, 0);
+                }
+            }
+        }
+    };
+    auto by_row = [&](auto f, int blk) {                   // (wave-uniform)
+        if (row == 0) f(std::integral_constant<int, 0>{}, blk);
+        else if (row == 1) f(std::integral_constant<int, 1>{}, blk);
+        else if (row == 2) f(std::integral_constant<int, 2>{}, blk);
+        else f(std::integral_constant<int, 3>{}, blk);
+    };
+    by_row(xwrite, 0);
+    wino_lds_barrier();
+    by_row(finish, 0);
+    if (live1) {
+        wino_lds_barrier();                                // the quad has read block 0
+        by_row(xwrite, 1);
+        wino_lds_barrier();
+        by_row(finish, 1);
+    }
+}
+
+template <int TWV, bool WE>
+__global__ void __launch_bounds__(512, 2) wino3x3_f16x2_pair_kernel(const WinoHP p) {
+    constexpr int RW = 32 / TWV;                 // tile rows of a quad; a workgroup is two quads
+    constexpr int WGR = 2 * RW;
+    constexpr int PR = 2 * WGR + 2;
+    constexpr int PC = 2 * TWV + 2;
+    constexpr int RS = TWV == 16 ? 48 : 68;
+    constexpr int PLANE = PR * RS;
+    constexpr int NEL = 8 * PLANE;               // floats of one staged 8-cin image
+    constexpr int NDMA = (NEL + 511) / 512;
+    constexpr int PBUF = NDMA * 512;
+    constexpr int UOFF = 4 * PBUF;               // [2 buffers][2 x 8 cins][PBUF] patches, then 64 records of U (64 KB)
+    constexpr int XFLOATS = 2 * 4 * 3 * 16 * 64; // one block's exchange
+    static_assert((UOFF + 64 * 256) * 4 <= 160 * 1024 && XFLOATS * 4 <= 160 * 1024, "LDS of a CU");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+
+    const size_t plane_hw = (size_t)p.H * p.W;
+    const size_t u_rec = (size_t)p.nblk * 512;           // halves per (chunk, xi, image) record
+    const int npair = (p.nblk + 1) >> 1;
+    uint32_t voff[NDMA];                          // as in wino3x3_kernel: 0xFFFFFFF0 = outside, the DMA writes 0.0f
+    auto fresh_tid = [] {                         // (see wino3x3_f16x2_kernel)
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int row = wave & 3, g = wave >> 2;
+
+    // the item: pair of cout blocks, image, first tile; the pairs of one tile block are neighbours in the remapped order
+    const uint32_t bid = xcd_remap(blockIdx.x, p.nwg);
+    const int nb0 = 2 * (int)(bid % npair);
+    const bool live1 = nb0 + 1 < p.nblk;
+    uint32_t t = bid / npair;
+    const int bx = t % p.wg_tx;
+    t /= p.wg_tx;
+    const int by = t % p.wg_ty;
+    const int b = t / p.wg_ty;
+    const int ty0 = by * WGR, tx0 = bx * TWV;
+    {
+        const int gy0 = 2 * ty0 - 1, gx0 = 2 * tx0 - 1;
+        const int lane = fresh_tid() & 63;
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) {
+            const int e = (wave * NDMA + i) * 64 + lane;
+            const int cin = e / PLANE, rem = e - cin * PLANE;
+            const int prow = rem / RS, col = rem - prow * RS;
+            const int gy = gy0 + prow, gx = gx0 + col;
+            const bool ok = e < NEL && col < PC && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            voff[i] = ok ? (uint32_t)((cin * plane_hw + (size_t)gy * p.W + gx) * 4) : 0xFFFFFFF0u;
+        }
+    }
+    auto issue_patch = [&](int c) {
+        const float* const xb = p.x + (size_t)b * p.Cin * plane_hw;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            // descriptor over channels [16 c + 8 s, Cin) of image b; none left: zero records, every lane reads 0.0f
+            const int ch0 = c * 16 + s * 8, left = p.Cin - ch0;
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (size_t)(left > 0 ? ch0 : 0) * plane_hw), 0,
+                                                                left > 0 ? (uint32_t)((size_t)left * plane_hw * 4) : 0u, 0x00020000);
+            float* pdst = lds + ((c & 1) * 2 + s) * PBUF + wave * NDMA * 64;
+#pragma unroll
+            for (int i = 0; i < NDMA; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, pdst + i * 64, 4, voff[i], 0, 0, 0);
+        }
+    };
+
+    asm volatile("" ::"a"(0.f));                          // AGPR accumulators (see wino3x3_kernel)
+    f32x16 acc[8];                                        // [4 blk + j]: position xi = 4 row + j of cout block nb0 + blk
+
+    // the 12 MFMAs of cout block `blk` against its U records 2 (4 row + j) + image; positions in two interleaved pairs so
+    // that no MFMA waits on its predecessor
+    auto row_m = [&](auto bc, const u32x4* ul, const uint32_t (&vh)[4][4], const uint32_t (&vl)[4][4]) {
+        constexpr int BLK = decltype(bc)::value;
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            f16x8 uh[2], ulo[2], us[2], bh[2], bl[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                uh[e] = __builtin_bit_cast(f16x8, ul[(BLK * 32 + 2 * (j + e)) * 64]);
+                ulo[e] = __builtin_bit_cast(f16x8, ul[(BLK * 32 + 2 * (j + e) + 1) * 64]);
+                us[e] = uh[e] * (_Float16)(1.f / 2048.f);
+                bh[e] = __builtin_bit_cast(f16x8, (u32x4){vh[j + e][0], vh[j + e][1], vh[j + e][2], vh[j + e][3]});
+                bl[e] = __builtin_bit_cast(f16x8, (u32x4){vl[j + e][0], vl[j + e][1], vl[j + e][2], vl[j + e][3]});
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * BLK + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ulo[e], bh[e], acc[4 * BLK + j + e], 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * BLK + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(us[e], bl[e], acc[4 * BLK + j + e], 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                acc[4 * BLK + j + e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[e], bh[e], acc[4 * BLK + j + e], 0, 0, 0);
+        }
+    };
+
+    issue_patch(0);
+    const int lane = fresh_tid() & 63;
+    const int li = lane & 31, kk = lane >> 5;
+    const int lr = g * RW + li / TWV, lc = li % TWV;
+    const int pbase = kk * PBUF + (2 * lr + (row >> 1)) * RS + 2 * lc;
+    const u32x4* const ul = (const u32x4*)(lds + UOFF) + (row * 8 * 64 + lane);
+    // 64 records of 1 KB, 8 per wave: waves 0-3 bring block nb0, waves 4-7 block nb0 + 1 (if there is one)
+    const bool u_live = wave < 4 || live1;
+    const uint16_t* const ubase = p.upk + (size_t)(nb0 + (wave >> 2)) * 512 + lane * 8 + (size_t)((wave & 3) * 8) * u_rec;
+    auto issue_u = [&](int c) {
+        float* udst = lds + UOFF + wave * 8 * 256;
+        const uint16_t* usrc = ubase + (size_t)c * 32 * u_rec;
+        if (u_live) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) __builtin_amdgcn_global_load_lds(usrc + (size_t)j * u_rec, udst + j * 256, 16, 0, 0);
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
+
+    __syncthreads();                                       // (vmcnt(0) + barrier: patch 0 has landed)
+    // One loop per value of live1 (uniform over the workgroup: all its waves meet the same barriers).  With a branch around
+    // the second block's MFMAs inside one loop, hipcc carries that block's 64 accumulator registers through VGPR copies.
+    auto k_loop = [&](auto l1) {
+        for (int c = 0; c < p.chunks; ++c) {
+            issue_u(c);
+            if (c + 1 < p.chunks) issue_patch(c + 1);
+            const float* pl = lds + (c & 1) * 2 * PBUF + pbase;
+            uint32_t vh[4][4], vl[4][4];                   // [position of the row][cin pair]: B fragments, hi and lo' terms
+            if (row == 0) wino_row_v<0, 0, PLANE, RS>(pl, vh, vl);
+            else if (row == 1) wino_row_v<0, 1, PLANE, RS>(pl, vh, vl);
+            else if (row == 2) wino_row_v<1, 0, PLANE, RS>(pl, vh, vl);
+            else wino_row_v<1, 1, PLANE, RS>(pl, vh, vl);
+            __syncthreads();                               // U of chunk c has landed (vmcnt(0): so has the patch of chunk c + 1)
+            row_m(std::integral_constant<int, 0>{}, ul, vh, vl);
+            if (decltype(l1)::value) row_m(std::integral_constant<int, 1>{}, ul, vh, vl);
+            __syncthreads();                               // every wave is done with U and the patch of chunk c
+        }
+    };
+    if (live1) k_loop(std::true_type{});
+    else k_loop(std::false_type{});
+    wino_quad_exchange_store<TWV, WE>(p, acc, lds, row, g, fresh_tid() & 63, nb0, live1, b, ty0, tx0);
 }
 
 // K10h weight image: fp16 halves [chunk of 16 cins][xi 16][image: 0 hi, 1 lo][cout/32][lane][8], then (cout/32) * 32 floats
@@ -809,6 +1110,24 @@ int launch_wino_f16x2_we(const WinoHP& p, int grid, hipStream_t st) {
     if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_kernel<TWV, false, WE>)) != OCCD_OK) return OCCD_ELAUNCH;
     hipLaunchKernelGGL((wino3x3_f16x2_kernel<TWV, false, WE>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
     return occd::check_launch();
+}
+
+// the cout-pair form: one workgroup per (pair of cout blocks, image, block of 64 tiles)
+template <int TWV, bool WE>
+int launch_wino_f16x2_pair_we(const WinoHP& p, hipStream_t st) {
+    constexpr int RW = 32 / TWV, PR = 2 * 2 * RW + 2, RS = TWV == 16 ? 48 : 68;
+    constexpr int PBUF = (8 * PR * RS + 511) / 512 * 512;
+    size_t lds = ((size_t)4 * PBUF + 64 * 256) * sizeof(float);
+    const size_t xchg = (size_t)2 * 4 * 3 * 16 * 64 * sizeof(float);      // one block's exchange (96 KB)
+    if (lds < xchg) lds = xchg;
+    if (occd::ensure_big_lds(reinterpret_cast<const void*>(wino3x3_f16x2_pair_kernel<TWV, WE>)) != OCCD_OK) return OCCD_ELAUNCH;
+    hipLaunchKernelGGL((wino3x3_f16x2_pair_kernel<TWV, WE>), dim3((unsigned)p.nwg), dim3(512), lds, st, p);
+    return occd::check_launch();
+}
+
+template <int TWV>
+int launch_wino_f16x2_pair(const WinoHP& p, hipStream_t st) {
+    return (p.W & 1) == 0 ? launch_wino_f16x2_pair_we<TWV, true>(p, st) : launch_wino_f16x2_pair_we<TWV, false>(p, st);
 }
 
 // (even W: the epilogue's 2-pixel accesses, see wino_exchange_store)
@@ -956,6 +1275,29 @@ int occd_wino_conv3x3_f16x2_fwd_ex(const occd_wino_args* a, int32_t max_workgrou
     occd::ProfScope prof("wino_conv3x3_f16x2", (hipStream_t)stream, 2.0 * 16 * tiles * ((a->cin + 7) / 8) * 8 * p.nblk * 32,
                          4.0 * p.B * ((double)p.Cin + p.Cout) * p.H * p.W);
     return twv == 16 ? launch_wino_f16x2<16>(p, grid, (hipStream_t)stream) : launch_wino_f16x2<32>(p, grid, (hipStream_t)stream);
+}
+
+int occd_wino_conv3x3_f16x2_fwd_form(const occd_wino_args* a, int32_t max_workgroups, int32_t cout_blocks, void* stream) {
+    if (cout_blocks != 1 && cout_blocks != 2) return OCCD_EINVAL;
+    if (cout_blocks == 1) return occd_wino_conv3x3_f16x2_fwd_ex(a, max_workgroups, stream);
+    if (max_workgroups != -1) return OCCD_EINVAL;            // the cout-pair form has no persistent grid
+    WinoHP p{};
+    const int twv = wino_geometry(a, 16, p);
+    if (twv < 0) return twv;
+    p.upk = reinterpret_cast<const uint16_t*>(a->upk);
+    p.fac = reinterpret_cast<const float*>(p.upk + (size_t)p.chunks * 32 * p.nblk * 512);
+    // items of 64 tiles (2 x 32 or 4 x 16) and two cout blocks.  The tile width is still wino_geometry's, which minimises the
+    // padding of K10h's 4 x 32 / 8 x 16 workgroups, not of these: correct for any shape, possibly not the faster width (unmeasured)
+    const int th = (a->H + 1) / 2, wgr = twv == 16 ? 4 : 2;
+    p.wg_ty = (th + wgr - 1) / wgr;
+    const long nwg = (long)((p.nblk + 1) / 2) * p.wg_tx * p.wg_ty * p.B;
+    if (nwg > 0x7fffffffL) return OCCD_EINVAL;
+    p.nwg = (int)nwg;
+    const double tiles = (double)p.B * th * ((a->W + 1) / 2);
+    // (the tag, flops and bytes of occd_wino_conv3x3_f16x2_fwd_ex: one row of the profile for both forms)
+    occd::ProfScope prof("wino_conv3x3_f16x2", (hipStream_t)stream, 2.0 * 16 * tiles * ((a->cin + 7) / 8) * 8 * p.nblk * 32,
+                         4.0 * p.B * ((double)p.Cin + p.Cout) * p.H * p.W);
+    return twv == 16 ? launch_wino_f16x2_pair<16>(p, (hipStream_t)stream) : launch_wino_f16x2_pair<32>(p, (hipStream_t)stream);
 }
 
 int occd_wino_conv3x3_f16x2_fwd(const occd_wino_args* a, void* stream) {

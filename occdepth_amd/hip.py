@@ -1594,13 +1594,41 @@ def _parse_wino_persist(value):
 WINO_PERSIST = _parse_wino_persist(os.environ.get("OCCDEPTH_WINO_PERSIST", "0"))
 
 
+def _parse_wino_cout_pair(value):
+    if value not in ("auto", "0", "1"):
+        raise ValueError("OCCDEPTH_WINO_COUT_PAIR must be auto, 0 or 1, not %r" % (value,))
+    return None if value == "auto" else value == "1"
+
+
+# K10h's work item: 1 = the cout-pair form (two blocks of 32 couts share one patch fetch, transform and split; bit-identical,
+# tests/test_wino_cout_pair.py) on every K10h launch, 0 = one cout block per item on every launch, auto (default) = the pair
+# form where wino_cout_pair_wins says so
+WINO_COUT_PAIR = _parse_wino_cout_pair(os.environ.get("OCCDEPTH_WINO_COUT_PAIR", "auto"))
+
+# (cin, cout, H, W) at batch 2 of the config-2 frame's K10h launches whose pair form's WORST round beat the one-block form's
+# BEST round in tools/bench_wino_pair.py (profiles/wino_cout_pair_ab.txt).  An exact-geometry table: any other resolution or
+# batch size keeps the one-block form unless OCCDEPTH_WINO_COUT_PAIR=1.  (128, 128, 47, 153) and (64, 128, 47, 153) are DepthNet's
+# launches, which wino_f16x2_wins keeps on K10: the two entries take effect only where K10h is forced on them.
+WINO_COUT_PAIR_TABLE = frozenset({(160, 160, 185, 610), (320, 320, 93, 305), (128, 128, 47, 153), (32, 160, 185, 610),
+                                  (48, 320, 93, 305), (224, 1280, 24, 77), (80, 640, 47, 153), (64, 128, 47, 153)})
+
+
+def wino_cout_pair_wins(B, cin, cout, H, W):
+    """Whether a K10h launch takes the cout-pair form by default: only the measured launch geometries of the table above;
+    everything else is unmeasured and stays on the one-block form."""
+    return B == 2 and (cin, cout, H, W) in WINO_COUT_PAIR_TABLE
+
+
 def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, res_first=False, tile_hint=0, out=None,
-                     max_workgroups=None):
+                     max_workgroups=None, cout_blocks=None):
     """K10: act(conv3x3(x, g * scale, pad 1) + shift) (+ res) in one launch (upk = wino_pack_weights(g, scale)); K10h, the
     same on the two-term fp16 split, when upk is the WinoF16x2 of wino_pack_weights_f16x2(g, scale).  max_workgroups (K10h
     only; RuntimeError with a K10 operand; without effect on a launch that wino_f16x2_wins sends to the K10 image of a WinoF16x2):
     0 = persistent workgroups, one per CU (the one-item form when the launch has no more items than that); k > 0 = at most k
-    persistent workgroups; -1 = one workgroup per tile block; None = WINO_PERSIST's choice between 0 and -1."""
+    persistent workgroups; -1 = one workgroup per tile block; None = WINO_PERSIST's choice between 0 and -1.  cout_blocks (K10h
+    only): 1 = one block of 32 couts per work item; 2 = the cout-pair form, which has one workgroup per item only (it takes
+    max_workgroups None as -1 and refuses max_workgroups >= 0); None = WINO_COUT_PAIR's choice (auto: wino_cout_pair_wins),
+    where a persistent grid, asked for by max_workgroups or by WINO_PERSIST, keeps the one-block form.  Same bits either way."""
     if not x.is_contiguous():
         x = x.contiguous()
     B, cin, H, W = x.shape
@@ -1609,6 +1637,8 @@ def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, r
         res = res.contiguous()
     if max_workgroups is not None and not isinstance(upk, WinoF16x2):
         raise RuntimeError("max_workgroups is K10h's grid: the operand of this launch is K10's float32 image")
+    if cout_blocks is not None and not isinstance(upk, WinoF16x2):
+        raise RuntimeError("cout_blocks is K10h's work item: the operand of this launch is K10's float32 image")
     if isinstance(upk, WinoF16x2) and upk.f32 is not None and not wino_f16x2_wins(B, cin, cout, H, W, x.device):
         upk = upk.f32
     split = isinstance(upk, WinoF16x2)
@@ -1625,9 +1655,12 @@ def conv2d_3x3_fused(x, upk, cout, shift=None, act=None, slope=0.01, res=None, r
         set_tag("%d>%d @%dx%dx%d" % (cin, cout, B, H, W))
     if split:
         if max_workgroups is None:
-            max_workgroups = 0 if WINO_PERSIST else -1
-        _check(load().occd_wino_conv3x3_f16x2_fwd_ex(ctypes.byref(a), int(max_workgroups), _stream()),
-               "occd_wino_conv3x3_f16x2_fwd_ex")
+            max_workgroups = 0 if WINO_PERSIST and cout_blocks != 2 else -1
+        if cout_blocks is None:
+            pair = wino_cout_pair_wins(B, cin, cout, H, W) if WINO_COUT_PAIR is None else WINO_COUT_PAIR
+            cout_blocks = 2 if pair and max_workgroups == -1 else 1
+        _check(load().occd_wino_conv3x3_f16x2_fwd_form(ctypes.byref(a), int(max_workgroups), int(cout_blocks), _stream()),
+               "occd_wino_conv3x3_f16x2_fwd_form")
     else:
         _check(load().occd_wino_conv3x3_fwd(ctypes.byref(a), _stream()), "occd_wino_conv3x3_fwd")
     return y
